@@ -2,7 +2,7 @@
 """
 bench.py -- throughput of the recognition hot path on MI355X.
 
-    python bench.py --gpus N --steps K --warmup W [--config cfg2|cfg4]
+    python bench.py --gpus N --steps K --warmup W [--config cfg2|cfg4] [--dump-outputs DIR] [--full]
 
 A "step" is one pass of the hot path over one batch, through the C ABI of libcocr_hip.so:
 line batch resident in HBM -> conformer encoder (bf16 operands) -> decoder -> CTC greedy label records.
@@ -17,15 +17,26 @@ With N > 1 every rank owns one GPU, receives the packed weights by one RCCL broa
 batches (no data-path collective): weak scaling.  Launched either by `python -m torch.distributed.run --nproc-per-node N bench.py
 --gpus N ...` (RANK set by the launcher) or plainly as `python bench.py --gpus N ...`: without RANK in the environment this
 process starts the N rank processes itself (`launch_ranks`, before anything has touched the GPU) and forwards rank 0's line.
-Rank 0 prints ONE JSON line:
+Rank 0 prints ONE JSON line.  A plain run sets up, warms up, times the `--steps` steps, writes the last step's outputs when
+`--dump-outputs DIR` is given and prints the line:
 
   value                 whole-job lines/s, `--streams` (4) batches in flight per GPU, inputs resident in HBM
+  ms_per_step           milliseconds one timed step took (the timed region / `--steps`)
+
+Everything else the bench measures or checks runs only with `--full` (without it these fields are null or absent):
+
   value_streams1        the same loop with ONE batch in flight (what a single caller thread without its own streams sees; 48-row workgroups)
   predict_string        `PytorchRecognitionModel.predict_string` (the drop-in surface) called with a FRESH input tensor per call
   ingest                u8 lines from pinned host memory, double-buffered host->device copies inside the loop (PCIe-inclusive)
   cer_vs_reference      CER of the bf16 strings against the reference's fp32 greedy strings (fixture), cer_vs_truth: against the text
   roofline              the dominant kernel: algorithmic FLOP per launch / HIP-event duration measured live on the forward's stream
   cpu_baseline          the CPU oracle (fp32 restatement of the reference) on the host cores, bounded sample
+  latency, other_configs, kernels   small-batch latency (cfg2 / cfg1), the bounded cfg4 / cfg1 legs, per-kernel roofline figures
+
+`--dump-outputs DIR` (after the timed steps, outside the timed region): what the timed path handed its caller in its last step, as
+DIR/logits.npy (float32 (N,T,classes); a fixed, seeded sample of it when the batch's logits exceed 56 MB), DIR/out_lens.npy and
+DIR/records.npy (float64; one row (line, label, start frame, end frame, confidence) per label record of the greedy decode).
+The inputs are seeded: the same arguments give the same batch on every run.
 """
 import argparse
 import json
@@ -142,6 +153,8 @@ METRIC = 'text lines/sec (whole node) + CER vs reference, 96×1200 bf16 batch'  
 MFMA_PEAK_TFLOPS = {'bf16': 2500.0, 'fp32': 157.3}     # dense, MI355X_MICROARCH.md
 HBM_PEAK_GBS = 8000.0
 GOLDEN = os.path.join(ROOT, 'tests', 'golden')
+DUMP_MAX_BYTES = 64 << 20                                 # --dump-outputs: all files together
+DUMP_LOGITS_MAX_BYTES = 56 << 20                          # larger logits are written as a fixed, seeded sample
 
 
 def kernel_table(hp, n, w, dtype):
@@ -294,6 +307,28 @@ def strings_of(records):
     return [[int(r[0]) for r in line] for line in records]
 
 
+def dump_outputs(d, logits, out_lens, recs):
+    """--dump-outputs: the arrays the caller of the timed path received in its last step -- the logits (float32), the output lengths
+    and the greedy decode's label records (float64) -- as d/<name>.npy.  Logits larger than DUMP_LOGITS_MAX_BYTES are written as a
+    sample at fixed, seeded flat indices (d/logits_sample.npy + d/logits_sample_index.npy) so that two runs write the same entries."""
+    os.makedirs(d, exist_ok=True)
+    lg = logits.detach().float().cpu().numpy()
+    rows = [(n, lab, st, en, cf) for n, line in enumerate(recs) for (lab, st, en, cf) in line]
+    arrays = {'out_lens': np.asarray(out_lens, dtype=np.float64),
+              'records': np.asarray(rows, dtype=np.float64).reshape(-1, 5)}
+    if lg.nbytes <= DUMP_LOGITS_MAX_BYTES:
+        arrays['logits'] = np.ascontiguousarray(lg, dtype=np.float32)
+    else:
+        k = DUMP_LOGITS_MAX_BYTES // 12                       # float32 value + float64 index per sampled entry
+        sel = np.sort(np.random.Generator(np.random.PCG64(0)).choice(lg.size, size=k, replace=False))
+        arrays['logits_sample'] = lg.reshape(-1)[sel].astype(np.float32)
+        arrays['logits_sample_index'] = sel.astype(np.float64)
+    if sum(a.nbytes for a in arrays.values()) > DUMP_MAX_BYTES:
+        raise RuntimeError(f'--dump-outputs: {sum(a.nbytes for a in arrays.values())} bytes exceed {DUMP_MAX_BYTES}')
+    for name, a in arrays.items():
+        np.save(os.path.join(d, name + '.npy'), a)
+
+
 def dry_run(args, json_fd):
     """The launcher's rehearsal (tests/test_bench_launcher.py): every rank joins a gloo group, the ranks count themselves by an
     all-reduce of ones, rank 0 prints one line that says it measured nothing."""
@@ -352,7 +387,16 @@ def main():
     ap.add_argument('--launch-timeout', type=float, default=600.0, help='(launcher) seconds after which ranks that are still running are named on stderr and ended by PID, exit code 124; 0 = never')
     ap.add_argument('--profile-batch-only', action='store_true', help='(rocprofv3 runs of a mixed-width queue) the queue is reduced to its heaviest batch, the one the roofline leg prices: the profile\'s per-kernel averages are then that shape\'s')
     ap.add_argument('--no-latency-leg', action='store_true', help='skip the bounded small-batch latency leg (BASELINE configs[4])')
+    ap.add_argument('--full', action='store_true', help='also run every leg beside the timed steps: CER against the reference\'s strings, '
+                    'streams1 / predict_string / ingest, latency, the cfg4 / cfg1 legs, the roofline, the CPU baseline (each still subject to its --no-* flag)')
+    ap.add_argument('--dump-outputs', metavar='DIR', default=None, help='after the timed steps, write the last step\'s logits, output lengths '
+                    'and label records to DIR/<name>.npy (float32 / float64, at most 64 MB)')
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error('--steps must be at least 1')
+    if not args.full:              # a plain run: set-up, warm-up, the timed steps, --dump-outputs, the line -- nothing else
+        args.no_cpu_baseline = args.no_extra_legs = args.no_latency_leg = args.no_other_configs = True
+        args.profile_steps = 0
     # stdout carries exactly ONE JSON line: libraries that print banners to fd 1 (RCCL / gloo at communicator creation) go to stderr
     sys.stdout.flush()
     json_fd = os.dup(1)
@@ -443,7 +487,7 @@ def main():
     for e in engines:
         e.set_graph(use_graph)
 
-    _times = []
+    _times, _last = [], {}
     def run_steps(n, nstreams, first=0, depth=None):
         """n steps; step i runs batch (first + i) % NB on stream i % nstreams (forward + greedy decode; the label records land in
         pinned host memory) and is collected nstreams steps later, so nstreams independent batches overlap on the GPU.
@@ -455,6 +499,7 @@ def main():
             with torch.cuda.stream(streams[k]):
                 logits, out_lens = e.forward(batches[b]['x'], batches[b]['lens'], out=outs[k][b])
                 pending.append((e, e.ctc_greedy_async(logits, out_lens), b))
+                _last['step'] = (logits, out_lens)
             if i < nstreams - 1 and args.stagger_us > 0:
                 t_end = time.perf_counter() + args.stagger_us * 1e-6
                 while time.perf_counter() < t_end:
@@ -508,6 +553,8 @@ def main():
     else:
         lines_total = float(done)
     value = lines_total / dt
+    if rank == 0 and args.dump_outputs:      # before any other leg reuses the logits buffers
+        dump_outputs(args.dump_outputs, *_last['step'], recs)
 
     extra = {}
     if rank == 0 and not args.no_extra_legs:
@@ -620,7 +667,7 @@ def main():
     # ---- CER (outside the timed region): the compute dtype's greedy strings on the fixture against the reference's fp32 greedy
     # strings of the same padded batches (tests/golden) and against the ground-truth text
     cer = None
-    if rank == 0 and fix:
+    if rank == 0 and fix and args.full:
         fb = [(max(fix['meta']['widths']), list(range(len(fix['lines']))))] if not fix['meta']['edge'] else \
             make_batches(fix['meta']['widths'], fix['meta']['batch_size'], fix['meta']['edge'])
         got = {}
@@ -708,7 +755,7 @@ def main():
         torch.cuda.synchronize(dev)
         others = {}
         for cfg, extra_args in (('cfg4', ['--steps', '50', '--warmup', '5', '--lines', '320']), ('cfg1', ['--steps', '100', '--warmup', '5'])):
-            cmd = [sys.executable, os.path.abspath(__file__), '--config', cfg, '--gpus', '1', '--no-cpu-baseline', '--no-extra-legs', '--no-other-configs',
+            cmd = [sys.executable, os.path.abspath(__file__), '--config', cfg, '--gpus', '1', '--full', '--no-cpu-baseline', '--no-extra-legs', '--no-other-configs',
                    '--profile-steps', '2', '--prewarm-ms', '200', '--dtype', args.dtype] + extra_args
             t_c = time.perf_counter()
             try:

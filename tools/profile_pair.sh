@@ -8,7 +8,7 @@ TAG=$1
 export TMPDIR=/tmp
 OUT=gpurun_out/prof_pair_$TAG
 rm -rf $OUT; mkdir -p $OUT profiles
-ARGS="--batch 80 --streams 1 --steps 10 --warmup 2 --no-cpu-baseline --no-extra-legs --no-other-configs --no-latency-leg"
+ARGS="--full --batch 80 --streams 1 --steps 10 --warmup 2 --no-cpu-baseline --no-extra-legs --no-other-configs --no-latency-leg"
 for form in rows96 pair48; do
   if [ $form = pair48 ]; then export COCR_LIB_PATH=$PWD/conformer_ocr_amd/lib/libcocr_pair.so COCR_CHAIN_ROWS=48; else unset COCR_LIB_PATH; export COCR_CHAIN_ROWS=0; fi
   rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/${form}_stats -- python3 bench.py $ARGS > $OUT/${form}_bench.json 2> $OUT/${form}_stats.err

@@ -9,7 +9,7 @@ rm -rf $OUT; mkdir -p $OUT profiles
 # a mixed-width queue (cfg4) is reduced to its heaviest batch -- the shape bench.py's roofline leg prices -- so that the per-kernel
 # averages of the summaries (duration, traffic, counters) are that shape's and not a mean over every bucket width
 case "$*" in *cfg4*) ONLY="--profile-batch-only";; *) ONLY="";; esac
-CMD="python3 bench.py --steps 10 --warmup 2 --no-cpu-baseline --no-extra-legs --streams 1 $ONLY $*"
+CMD="python3 bench.py --full --steps 10 --warmup 2 --no-cpu-baseline --no-extra-legs --streams 1 $ONLY $*"
 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/stats -- $CMD > $OUT/bench_under_rocprof.json 2> $OUT/stats.err
 rocprofv3 --kernel-trace --pmc FETCH_SIZE --output-format csv -d $OUT/fetch -- $CMD > /dev/null 2> $OUT/fetch.err
 rocprofv3 --kernel-trace --pmc WRITE_SIZE --output-format csv -d $OUT/write -- $CMD > /dev/null 2> $OUT/write.err

@@ -1,5 +1,5 @@
 #!/usr/bin/env python3
-"""Pretty-prints a bench.py JSON line: python tools/show_bench.py gpurun_out/bench.json"""
+"""Pretty-prints a bench.py JSON line: python bench.py --full > bench.json; python tools/show_bench.py bench.json"""
 import json
 import sys
 r = json.load(open(sys.argv[1]))
