@@ -32,6 +32,7 @@
 #include "frontend.hip.h"
 #include "norm.hip.h"
 #include "preproc.hip.h"
+#include "page.hip.h"
 
 // ------------------------------------------------------------------------------------ errors
 static thread_local char g_err[512] = "";
@@ -125,6 +126,8 @@ struct cocr_model {
     int pos_maxlen = COCR_POS_MAXLEN;                  // relative positions the P tables cover: -(max_len - 1) .. max_len - 1
     unsigned char *pre_buf = nullptr;      // line pre-processing: descriptors, tap tables, intermediates
     size_t pre_cap = 0;
+    unsigned char *page_buf = nullptr;     // line extraction: descriptors, column frames, polygons, span table
+    size_t page_cap = 0;
     int32_t *d_lens = nullptr, *h_lens = nullptr, *d_lens_cur = nullptr;      // device / pinned-host rings of per-line lengths (upload_lens)
     int lens_slot = 0;
     int32_t *ctc_lab = nullptr;
@@ -305,6 +308,7 @@ extern "C" void cocr_destroy(cocr_model *m) {
         if (m->fpack) (void)hipFree(m->fpack);
     }
     if (m->pre_buf) (void)hipFree(m->pre_buf);
+    if (m->page_buf) (void)hipFree(m->page_buf);
     if (m->stamps) {
         (void)hipDeviceSynchronize();
         if (m->stamps[1024]) {                          // row-chain kernel (dominant form), workgroup 7: per wave, cycles between stamps
@@ -1852,6 +1856,96 @@ extern "C" int cocr_preproc_lines(cocr_model *m, const uint8_t *pixels, const in
     HIP_TRY(hipStreamSynchronize(s));                      // the host tables go out of scope; also orders reuse of pre_buf by the next call
     hipLaunchKernelGGL(preproc_h_kernel, dim3(ceil_div(max_ow, 256), max_h, N), dim3(256), 0, s, pixels, d_lines, d_tab, d_tmp);
     hipLaunchKernelGGL(preproc_v_kernel, dim3(ceil_div(out_w, 256), out_h, N), dim3(256), 0, s, d_tmp, d_lines, d_tab, out, out_h, out_w, pad);
+    LAUNCH_CHECK();
+    return COCR_OK;
+}
+
+// ------------------------------------------------------------------------------------ baseline line extraction (page.hip.h)
+extern "C" int cocr_extract_lines(cocr_model *m, const uint8_t *const *pages, const int32_t *page_dims, int P, const int32_t *line_page,
+                                  const int32_t *line_dims, const int64_t *cols, const int32_t *verts, const int32_t *nverts, int N, int fill,
+                                  uint8_t *out, const int64_t *out_offsets, void *stream) {
+    if (!m || !pages || !page_dims || !line_page || !line_dims || !cols || !verts || !nverts || !out || !out_offsets)
+        return fail(COCR_EINVAL, "null argument");
+    if (N < 1 || P < 1) return fail(COCR_EINVAL, "empty problem: %d lines on %d pages", N, P);
+    if (N > 65535) return fail(COCR_EINVAL, "%d lines in one call (at most 65535)", N);
+    if (fill < 0 || fill > 255) return fail(COCR_EINVAL, "fill %d is not a byte value", fill);
+    for (int p = 0; p < P; ++p) {
+        const int h = page_dims[3 * p], w = page_dims[3 * p + 1], c = page_dims[3 * p + 2];
+        if (!pages[p] || h < 1 || w < 1 || (c != 1 && c != 3)) return fail(COCR_EINVAL, "page %d: %d x %d pixels, %d channels", p, h, w, c);
+    }
+    const long long kCoord = 1ll << 24;                    // |coordinate| bound: every product of the kernels stays inside int64 / int32
+    std::vector<PageLine> lines((size_t)N);
+    std::vector<long long> row_start;
+    std::vector<long long> cnt;
+    long long ncols = 0, nthr = 0, nv = 0;
+    int max_ws = 0, max_hs = 0, max_rows = 0;
+    for (int i = 0; i < N; ++i) {
+        PageLine &L = lines[(size_t)i];
+        const int p = line_page[i], hs = line_dims[3 * i], ws = line_dims[3 * i + 1], t = line_dims[3 * i + 2], V = nverts[i];
+        if (p < 0 || p >= P) return fail(COCR_EINVAL, "line %d: page %d of %d", i, p, P);
+        if (hs < 1 || hs > 4096 || ws < 1 || ws > 65535 || t < 0 || t >= hs)
+            return fail(COCR_EINVAL, "line %d: strip %d x %d with the baseline on row %d (limits 4096 x 65535)", i, hs, ws, t);
+        if (V < 3 || V > 4096) return fail(COCR_EINVAL, "line %d: %d boundary vertices (3 .. 4096)", i, V);
+        if (out_offsets[i] < 0) return fail(COCR_EINVAL, "line %d: negative output offset", i);
+        const int64_t *cr = cols + 4 * ncols;
+        for (int c = 0; c < ws; ++c) {
+            const int64_t *q = cr + 4 * c;
+            if (llabs(q[0]) > (kCoord << 16) || llabs(q[1]) > (kCoord << 16) || llabs(q[2]) > 65536 || llabs(q[3]) > 65536)
+                return fail(COCR_EINVAL, "line %d: column %d frame out of range", i, c);
+        }
+        const int32_t *v = verts + 2 * nv;
+        int ymin = v[1], ymax = v[1];
+        for (int k = 0; k < V; ++k) {
+            if (llabs(v[2 * k]) > kCoord || llabs(v[2 * k + 1]) > kCoord) return fail(COCR_EINVAL, "line %d: boundary vertex %d out of range", i, k);
+            ymin = std::min(ymin, (int)v[2 * k + 1]); ymax = std::max(ymax, (int)v[2 * k + 1]);
+        }
+        const int nrows = ymax - ymin;
+        if (nrows > (1 << 17)) return fail(COCR_EINVAL, "line %d: the boundary spans %d rows (at most %d)", i, nrows, 1 << 17);
+        cnt.assign((size_t)nrows + 1, 0);                  // thresholds per source row: each edge straddles the rows [min y, max y)
+        for (int k = 0; k < V; ++k) {
+            const int ay = v[2 * k + 1], by = v[2 * ((k + 1) % V) + 1];
+            if (ay == by) continue;
+            ++cnt[(size_t)(std::min(ay, by) - ymin)];
+            --cnt[(size_t)(std::max(ay, by) - ymin)];
+        }
+        L.page = pages[p]; L.ph = page_dims[3 * p]; L.pw = page_dims[3 * p + 1]; L.cpp = page_dims[3 * p + 2];
+        L.out_off = out_offsets[i]; L.col_off = ncols; L.row_off = (long long)row_start.size();
+        L.hs = hs; L.ws = ws; L.t = t; L.vert_off = (int)nv; L.nverts = V; L.ymin = ymin; L.nrows = nrows; L.fill = fill;
+        long long run = 0;
+        for (int r = 0; r <= nrows; ++r) {
+            row_start.push_back(nthr);
+            if (r < nrows) { run += cnt[(size_t)r]; nthr += run; }
+        }
+        ncols += ws; nv += V;
+        max_ws = std::max(max_ws, ws); max_hs = std::max(max_hs, hs); max_rows = std::max(max_rows, nrows);
+    }
+    HIP_TRY(hipSetDevice(m->device));
+    hipStream_t s = (hipStream_t)stream;
+    auto al = [](size_t b) { return (b + 255) / 256 * 256; };
+    const size_t lines_b = al(lines.size() * sizeof(PageLine)), cols_b = al((size_t)ncols * 32), verts_b = al((size_t)nv * 8),
+                 rows_b = al(row_start.size() * 8), thr_b = al((size_t)std::max(nthr, 1ll) * 4);
+    const size_t need = lines_b + cols_b + verts_b + rows_b + thr_b;
+    if (need > m->page_cap) {
+        HIP_TRY(hipStreamSynchronize(s));                  // an earlier call on this stream may still read the old buffer
+        if (m->page_buf) (void)hipFree(m->page_buf);
+        m->page_buf = nullptr; m->page_cap = 0;
+        HIP_TRY(hipMalloc((void **)&m->page_buf, need + need / 4));
+        m->page_cap = need + need / 4;
+    }
+    unsigned char *b = m->page_buf;
+    PageLine *d_lines = reinterpret_cast<PageLine *>(b);
+    long long *d_cols = reinterpret_cast<long long *>(b + lines_b);
+    int *d_verts = reinterpret_cast<int *>(b + lines_b + cols_b);
+    long long *d_rows = reinterpret_cast<long long *>(b + lines_b + cols_b + verts_b);
+    int *d_thr = reinterpret_cast<int *>(b + lines_b + cols_b + verts_b + rows_b);
+    HIP_TRY(hipMemcpyAsync(d_lines, lines.data(), lines.size() * sizeof(PageLine), hipMemcpyHostToDevice, s));
+    HIP_TRY(hipMemcpyAsync(d_cols, cols, (size_t)ncols * 32, hipMemcpyHostToDevice, s));
+    HIP_TRY(hipMemcpyAsync(d_verts, verts, (size_t)nv * 8, hipMemcpyHostToDevice, s));
+    HIP_TRY(hipMemcpyAsync(d_rows, row_start.data(), row_start.size() * 8, hipMemcpyHostToDevice, s));
+    HIP_TRY(hipStreamSynchronize(s));                      // the host tables go out of scope; also orders reuse of page_buf by the next call
+    if (max_rows > 0) hipLaunchKernelGGL(page_spans_kernel, dim3(ceil_div(max_rows, 256), N), dim3(256), 0, s, d_lines, d_verts, d_rows, d_thr);
+    hipLaunchKernelGGL(page_sample_kernel, dim3(ceil_div(max_ws, 256), N, ceil_div(max_hs, PAGE_ROWS_PER_THREAD)), dim3(256), 0, s,
+                       d_lines, d_cols, d_rows, d_thr, out);
     LAUNCH_CHECK();
     return COCR_OK;
 }

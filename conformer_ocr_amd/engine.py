@@ -414,6 +414,74 @@ class HipRecognizer:
         self._keep = px            # the kernels read it asynchronously on the current stream
         return out, lens
 
+    def preprocess_device(self, pixels: torch.Tensor, offsets, heights, widths, channels=None, height: Optional[int] = None,
+                          pad: int = 16, width: int = 0, bucket_edge: int = 0) -> Tuple[torch.Tensor, np.ndarray]:
+        """`preprocess` on lines already in device memory: `pixels` a uint8 device buffer holding line i at byte offsets[i] as
+        heights[i] x widths[i] pixels of channels[i] (None: all 1) bytes -- e.g. the strips of `extract_lines`.  Same output."""
+        height = int(height or self.hp.height)
+        if pixels.device != self.device or pixels.dtype != torch.uint8 or not pixels.is_contiguous():
+            raise ValueError('pixels must be a contiguous uint8 buffer on the model device')
+        offs = np.ascontiguousarray(np.asarray(offsets, dtype=np.int64).reshape(-1))
+        hs = np.ascontiguousarray(np.asarray(heights, dtype=np.int32).reshape(-1))
+        ws = np.ascontiguousarray(np.asarray(widths, dtype=np.int32).reshape(-1))
+        n = offs.shape[0]
+        ch = np.ones(n, dtype=np.int32) if channels is None else np.ascontiguousarray(np.asarray(channels, dtype=np.int32).reshape(-1))
+        if n < 1:
+            raise ValueError('empty batch')
+        if hs.shape[0] != n or ws.shape[0] != n or ch.shape[0] != n:
+            raise ValueError('offsets, heights, widths and channels need one entry per line')
+        ends = offs + hs.astype(np.int64) * ws * ch
+        if offs.min() < 0 or ends.max() > pixels.numel():
+            raise ValueError('a line reaches outside the pixel buffer')
+        wl = [int(self.lib.cocr_preproc_width(int(h), int(w), height, int(pad))) for h, w in zip(hs, ws)]
+        wb = int(width) if width else max(wl)
+        if not width and bucket_edge:
+            wb = -(-wb // int(bucket_edge)) * int(bucket_edge)
+        out = torch.empty((n, height, wb), dtype=torch.uint8, device=self.device)
+        lens = np.zeros(n, dtype=np.int32)
+        _lib.check(self.lib.cocr_preproc_lines(self._h, C.c_void_p(pixels.data_ptr()), offs.ctypes.data_as(C.POINTER(C.c_int64)),
+                                               hs.ctypes.data_as(C.POINTER(C.c_int32)), ws.ctypes.data_as(C.POINTER(C.c_int32)),
+                                               ch.ctypes.data_as(C.POINTER(C.c_int32)), n, height, int(pad), wb,
+                                               C.c_void_p(out.data_ptr()), lens.ctypes.data_as(C.POINTER(C.c_int32)),
+                                               _stream_ptr(self.device)))
+        return out, lens
+
+    # ---- baseline line extraction (include/cocr.h: cocr_extract_lines) -------------------------------------------------------
+    def extract_lines(self, pages: Sequence['np.ndarray | torch.Tensor'], geoms: Sequence, fill: int = 0
+                      ) -> Tuple[torch.Tensor, np.ndarray, np.ndarray, np.ndarray]:
+        """Cuts and straightens text lines out of page images on the GPU.  `pages`: (H, W) or (H, W, 3) uint8
+        images, numpy (uploaded here) or tensors on this device; `geoms`: (page index, `page.LineGeometry`) pairs.  Returns the packed
+        uint8 strip buffer (device) and per line its byte offset, rows H_s and columns W_s: the input of `preprocess_device`."""
+        if len(geoms) < 1:
+            raise ValueError('no lines to extract')
+        dp = []
+        for a in pages:
+            t = a if isinstance(a, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(a))
+            if t.dtype != torch.uint8 or not (t.dim() == 2 or (t.dim() == 3 and t.shape[2] == 3)) or t.numel() == 0:
+                raise ValueError('a page is a non-empty (H, W) or (H, W, 3) uint8 image')
+            dp.append(t.to(self.device).contiguous())
+        P = len(dp)
+        page_dims = np.array([[t.shape[0], t.shape[1], 1 if t.dim() == 2 else 3] for t in dp], dtype=np.int32)
+        page_ptrs = (C.c_void_p * P)(*[t.data_ptr() for t in dp])
+        lp = np.array([int(p) for p, _ in geoms], dtype=np.int32)
+        gs = [g for _, g in geoms]
+        dims = np.ascontiguousarray(np.array([[g.H_s, g.W_s, g.T] for g in gs], dtype=np.int32))
+        cols = np.ascontiguousarray(np.concatenate([g.cols for g in gs]).astype(np.int64))
+        verts = np.ascontiguousarray(np.concatenate([g.verts for g in gs]).astype(np.int32))
+        nv = np.array([g.verts.shape[0] for g in gs], dtype=np.int32)
+        hs, ws = dims[:, 0].copy(), dims[:, 1].copy()
+        sizes = hs.astype(np.int64) * ws
+        offs = np.concatenate([[0], np.cumsum(sizes)[:-1]]).astype(np.int64)
+        out = torch.empty((int(sizes.sum()),), dtype=torch.uint8, device=self.device)
+        with torch.cuda.device(self.device):
+            _lib.check(self.lib.cocr_extract_lines(self._h, page_ptrs, page_dims.ctypes.data_as(C.POINTER(C.c_int32)), P,
+                                                   lp.ctypes.data_as(C.POINTER(C.c_int32)), dims.ctypes.data_as(C.POINTER(C.c_int32)),
+                                                   cols.ctypes.data_as(C.POINTER(C.c_int64)), verts.ctypes.data_as(C.POINTER(C.c_int32)),
+                                                   nv.ctypes.data_as(C.POINTER(C.c_int32)), len(gs), int(fill), C.c_void_p(out.data_ptr()),
+                                                   offs.ctypes.data_as(C.POINTER(C.c_int64)), _stream_ptr(self.device)))
+        self._keep_pages = dp          # the sampler reads them asynchronously on the current stream
+        return out, offs, hs, ws
+
     # ---- test / measurement hooks ---------------------------------------------------------------
     def set_debug(self, on: bool) -> None:
         _lib.check(self.lib.cocr_set_debug(self._h, int(on)))

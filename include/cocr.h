@@ -190,6 +190,22 @@ int32_t cocr_preproc_width(int32_t h, int32_t w, int32_t out_h, int32_t pad);
 int cocr_preproc_lines(cocr_model *m, const uint8_t *pixels, const int64_t *offsets, const int32_t *heights, const int32_t *widths,
                        const int32_t *channels, int N, int out_h, int pad, int out_w, uint8_t *out, int32_t *out_widths, void *stream);
 
+/* Baseline line extraction in front of cocr_preproc_lines -- the step kraken's `extract_polygons` performs for the reference's
+ * `cocr ocr` (README.rst:32-39), with this library's own definition (not pinned against kraken): every text line
+ * of a page is masked by its boundary polygon and resampled along its baseline into a straight grayscale strip.
+ * Pages: P 8-bit images in DEVICE memory, page p at pages[p] (a HOST array of device pointers), page_dims[3p..3p+2] = rows, columns,
+ * channels (1 = L, 3 = RGB, converted like Pillow).  Lines (all arrays HOST): line i lies on page line_page[i];
+ * line_dims[3i..3i+2] = strip rows H_s (<= 4096), columns W_s (<= 65535), baseline row T; its W_s column frames follow the previous
+ * lines' in `cols` as (Bx, By, Nx, Ny) int64 in 1/65536 px; its nverts[i] (3 .. 4096) integer boundary vertices follow theirs in
+ * `verts` as (x, y) pairs.  Strip pixel (r, c) = bilinear sample (1/256 px, integer blend) of the page at B(c) + (r - T) N(c);
+ * neighbours outside the page or the polygon (even-odd rule, half-open spans) count as `fill` (0 .. 255).  Output: strip i as
+ * H_s rows of W_s bytes at byte out_offsets[i] of the DEVICE buffer `out` -- the packed input of cocr_preproc_lines (channels 1).
+ * Errors: COCR_EINVAL naming the line index for a line over a limit or with coordinates beyond +-2^24 px.  Synchronises `stream`
+ * once (the tables are uploaded from host memory). */
+int cocr_extract_lines(cocr_model *m, const uint8_t *const *pages, const int32_t *page_dims, int P, const int32_t *line_page,
+                       const int32_t *line_dims, const int64_t *cols, const int32_t *verts, const int32_t *nverts, int N, int fill,
+                       uint8_t *out, const int64_t *out_offsets, void *stream);
+
 /* Launch-overhead control: with graph replay on, cocr_forward captures its ~40 kernel launches into a hipGraph and
  * replays it.  A caller that reuses (lines, logits, N, W, dtype, stream) gets a graph on its own buffers (second
  * identical call captures, later ones replay; contents may change, addresses not).  A caller with fresh buffers per
