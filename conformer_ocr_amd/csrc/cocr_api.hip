@@ -33,6 +33,7 @@
 #include "norm.hip.h"
 #include "preproc.hip.h"
 #include "page.hip.h"
+#include "augment.hip.h"
 
 // ------------------------------------------------------------------------------------ errors
 static thread_local char g_err[512] = "";
@@ -1946,6 +1947,25 @@ extern "C" int cocr_extract_lines(cocr_model *m, const uint8_t *const *pages, co
     if (max_rows > 0) hipLaunchKernelGGL(page_spans_kernel, dim3(ceil_div(max_rows, 256), N), dim3(256), 0, s, d_lines, d_verts, d_rows, d_thr);
     hipLaunchKernelGGL(page_sample_kernel, dim3(ceil_div(max_ws, 256), N, ceil_div(max_hs, PAGE_ROWS_PER_THREAD)), dim3(256), 0, s,
                        d_lines, d_cols, d_rows, d_thr, out);
+    LAUNCH_CHECK();
+    return COCR_OK;
+}
+
+// ------------------------------------------------------------------------------------ training augmentation
+extern "C" int cocr_augment_lines(cocr_model *m, const uint8_t *in, uint8_t *out, int N, int H, int W, const int32_t *seq_lens,
+                                  const int64_t *params, const int32_t *grid, int grid_cols, void *stream) {
+    if (!m || !in || !out || !seq_lens || !params || !grid) return fail(COCR_EINVAL, "null argument");
+    if (in == out) return fail(COCR_EINVAL, "the output must be a buffer of its own");
+    if (N < 1 || N > 65535) return fail(COCR_EINVAL, "%d lines in one call (1 .. 65535)", N);
+    if (H < 1 || H > 4096 || W < 1 || W > 65535) return fail(COCR_EINVAL, "batch of %d x %d px (limits 4096 x 65535)", H, W);
+    const int need_cols = (W - 1) / AUG_GRID_STEP + 2;
+    if (grid_cols < need_cols) return fail(COCR_EINVAL, "control grid of %d columns, a batch %d px wide needs %d", grid_cols, W, need_cols);
+    for (int i = 0; i < N; ++i)
+        if (seq_lens[i] < 0 || seq_lens[i] > W) return fail(COCR_EINVAL, "line %d: seq_len %d outside the batch width %d", i, seq_lens[i], W);
+    HIP_TRY(hipSetDevice(m->device));
+    hipStream_t s = (hipStream_t)stream;
+    hipLaunchKernelGGL(augment_kernel, dim3(ceil_div(W, AUG_TW), ceil_div(H, AUG_TH), N), dim3(256), 0, s, (const unsigned char *)in,
+                       (unsigned char *)out, (const long long *)params, (const int *)grid, grid_cols, H, W);
     LAUNCH_CHECK();
     return COCR_OK;
 }

@@ -446,6 +446,37 @@ class HipRecognizer:
                                                _stream_ptr(self.device)))
         return out, lens
 
+    # ---- training augmentation (include/cocr.h: cocr_augment_lines) -----------------------------------------------------------
+    def augment(self, lines: torch.Tensor, seq_lens, params: np.ndarray, grid: np.ndarray, out: Optional[torch.Tensor] = None
+                ) -> torch.Tensor:
+        """Augmented copy of the (N, H, W) uint8 device batch `lines` with the host tables of `augment.draw`.
+        The tables are checked here (ValueError before any launch), staged in pinned memory and uploaded with non-blocking copies;
+        nothing synchronises the stream."""
+        from . import augment as _aug
+        if lines.device != self.device or lines.dtype != torch.uint8 or lines.dim() != 3 or not lines.is_contiguous():
+            raise ValueError('expected a contiguous (N, H, W) uint8 batch on the model device')
+        N, H, W = lines.shape
+        sl = np.ascontiguousarray(np.asarray(seq_lens, dtype=np.int32).reshape(-1))
+        if sl.shape[0] != N:
+            raise ValueError('one seq_len per line')
+        if H > _aug.MAX_H or W > _aug.MAX_W or sl.min() < 0 or sl.max() > W:
+            raise ValueError(f'batch of {H} x {W} px with seq_lens in [{sl.min()}, {sl.max()}] (limits {_aug.MAX_H} x {_aug.MAX_W}, 0 <= seq_len <= W)')
+        params, grid = np.asarray(params), np.asarray(grid)
+        _aug.check_tables(params, grid, sl, H, W)
+        if out is None:
+            out = torch.empty_like(lines)
+        elif out.shape != lines.shape or out.dtype != torch.uint8 or out.device != self.device or not out.is_contiguous() \
+                or out.data_ptr() == lines.data_ptr():
+            raise ValueError('out must be a separate contiguous uint8 buffer of the batch\'s shape on the model device')
+        # torch's pinned-memory allocator keeps the staging blocks alive until the copies that read them have run
+        d_params = torch.from_numpy(np.ascontiguousarray(params)).pin_memory().to(self.device, non_blocking=True)
+        d_grid = torch.from_numpy(np.ascontiguousarray(grid)).pin_memory().to(self.device, non_blocking=True)
+        with torch.cuda.device(self.device):
+            _lib.check(self.lib.cocr_augment_lines(self._h, C.c_void_p(lines.data_ptr()), C.c_void_p(out.data_ptr()), N, H, W,
+                                                   sl.ctypes.data_as(C.POINTER(C.c_int32)), C.c_void_p(d_params.data_ptr()),
+                                                   C.c_void_p(d_grid.data_ptr()), int(grid.shape[1]), _stream_ptr(self.device)))
+        return out
+
     # ---- baseline line extraction (include/cocr.h: cocr_extract_lines) -------------------------------------------------------
     def extract_lines(self, pages: Sequence['np.ndarray | torch.Tensor'], geoms: Sequence, fill: int = 0
                       ) -> Tuple[torch.Tensor, np.ndarray, np.ndarray, np.ndarray]:

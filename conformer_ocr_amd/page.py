@@ -24,10 +24,12 @@ FIX = 65536.0                    # column frames are int64 in 1/65536 px
 
 @dataclass
 class Line:
-    """One text line of a segmentation: `baseline` (n, 2) polyline in reading order, `boundary` (V, 2) closed polygon, page pixels."""
+    """One text line of a segmentation: `baseline` (n, 2) polyline in reading order, `boundary` (V, 2) closed polygon, page pixels;
+    `text` its ground truth as the document gives it (None if it has none)."""
     id: str
     baseline: np.ndarray
     boundary: np.ndarray
+    text: Optional[str] = None
 
 
 @dataclass
@@ -179,9 +181,40 @@ def _warn_skipped(path, skipped):
         warnings.warn(f'{path}: skipped {len(skipped)} line(s) without a baseline or boundary polygon: {", ".join(skipped)}')
 
 
+def _page_text(line_el) -> Optional[str]:
+    """TextLine/TextEquiv/Unicode of the line's DIRECT TextEquiv children (Word / Glyph level ones are not read): the one of smallest
+    `index` if any carries an index, else the first; None without a TextEquiv or Unicode element."""
+    eqs = [c for c in line_el if _local(c.tag) == 'TextEquiv']
+    if not eqs:
+        return None
+
+    def index(e):
+        try:
+            return int(e.get('index'))
+        except (TypeError, ValueError):
+            return None
+    indexed = [e for e in eqs if index(e) is not None]
+    eq = min(indexed, key=index) if indexed else eqs[0]
+    uni = _child(eq, 'Unicode')
+    return None if uni is None else (uni.text or '')
+
+
+def _alto_text(line_el) -> Optional[str]:
+    """The TextLine's String@CONTENT, SP (one space) and HYP@CONTENT children in document order; None if it has none."""
+    parts = []
+    for c in line_el:
+        tag = _local(c.tag)
+        if tag in ('String', 'HYP'):
+            parts.append(c.get('CONTENT', ''))
+        elif tag == 'SP':
+            parts.append(' ')
+    return ''.join(parts) if parts else None
+
+
 def read_page_xml(path) -> Page:
     """PAGE XML (any schema version: namespaces are ignored): Page@imageFilename, TextLine@id, TextLine/Coords@points,
-    TextLine/Baseline@points.  Lines without a baseline or polygon are skipped with a warning naming them."""
+    TextLine/Baseline@points, TextLine/TextEquiv/Unicode (`_page_text`).  Lines without a baseline or polygon are skipped with a
+    warning naming them."""
     import xml.etree.ElementTree as ET
     root = ET.parse(path).getroot()
     image = ''
@@ -200,14 +233,15 @@ def read_page_xml(path) -> Page:
         if bl is None or bd is None:
             skipped.append(lid)
             continue
-        lines.append(Line(lid, bl, bd))
+        lines.append(Line(lid, bl, bd, _page_text(el)))
     _warn_skipped(path, skipped)
     return Page(image, lines)
 
 
 def read_alto(path) -> Page:
     """ALTO (any version: namespaces are ignored): sourceImageInformation/fileName, TextLine@ID, TextLine@BASELINE ('x,y x,y' or
-    'x y x y'), TextLine/Shape/Polygon@POINTS.  Lines without a baseline or polygon are skipped with a warning naming them."""
+    'x y x y'), TextLine/Shape/Polygon@POINTS, the line's text (`_alto_text`).  Lines without a baseline or polygon are skipped with
+    a warning naming them."""
     import xml.etree.ElementTree as ET
     root = ET.parse(path).getroot()
     image = ''
@@ -228,9 +262,27 @@ def read_alto(path) -> Page:
         if bl is None or bd is None:
             skipped.append(lid)
             continue
-        lines.append(Line(lid, bl, bd))
+        lines.append(Line(lid, bl, bd, _alto_text(el)))
     _warn_skipped(path, skipped)
     return Page(image, lines)
+
+
+def read_xml(path) -> Page:
+    """PAGE or ALTO, told apart by the root element (PcGts / alto, namespaces ignored)."""
+    import xml.etree.ElementTree as ET
+    for _, el in ET.iterparse(path, events=('start',)):
+        root = _local(el.tag)
+        break
+    else:
+        root = ''
+    if root == 'PcGts':
+        return read_page_xml(path)
+    if root.lower() == 'alto':
+        return read_alto(path)
+    raise ValueError(f'{path}: root element <{root}> is neither PAGE (PcGts) nor ALTO (alto)')
+
+
+READERS = {'page': read_page_xml, 'alto': read_alto, 'xml': read_xml}
 
 
 # ---- recognition ------------------------------------------------------------------------------------------------------------

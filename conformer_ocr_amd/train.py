@@ -184,3 +184,143 @@ class Trainer:
                     v.add_(self.global_step - int(v))
                     continue
                 v.copy_(torch.from_numpy(self.engine.train_value(k)).to(v.device).reshape(v.shape))
+
+
+# ---- the fit loop and `python -m conformer_ocr_amd.train` (the reference's `cocr train`, cli/train.py:100-380) ----------------------
+def fit(net: PytorchRecognitionModel, data, trainer: Optional[Trainer] = None, epochs: int = 100, quit: str = 'fixed', min_epochs: int = 0,
+        lag: int = 10, output: Optional[str] = 'model', log=print, **trainer_kw) -> Dict:
+    """Trains `net` on `data` (a `dataset.GroundTruthDataset`).  Per epoch: `training_step` on every batch of `data.batches(epoch)`,
+    `sync_module`, validation CER (`data.validate`), `end_epoch(1 - CER)`, `{output}_{epoch}.safetensors` and, when the CER is the best
+    so far, `{output}_best.safetensors` (no files with output=None); one log line with the summed loss, lines/s and the CER.
+    quit 'fixed': `epochs` epochs; 'early': stops once `lag` epochs in a row did not improve the best CER and at least `min_epochs`
+    ran (`epochs` still bounds the run).  Returns {'best_epoch', 'best_cer', 'history': [(loss, lines/s, cer), ...]}."""
+    import shutil
+    import time
+    from .pred import save_safetensors
+    if quit not in ('fixed', 'early'):
+        raise ValueError("quit must be 'fixed' or 'early'")
+    trainer = trainer or Trainer(net, **trainer_kw)
+    best_epoch, best_cer, bad, history = -1, None, 0, []
+    dev = trainer.engine.device
+    for epoch in range(int(epochs)):
+        t0, loss, lines = time.perf_counter(), 0.0, 0
+        for batch in data.batches(epoch):
+            loss += trainer.training_step(batch)
+            lines += int(batch['image'].shape[0])
+        torch.cuda.synchronize(dev)
+        rate = lines / max(time.perf_counter() - t0, 1e-9)
+        trainer.sync_module()
+        cer = float(data.validate(net))
+        trainer.end_epoch(1.0 - cer)
+        improved = best_cer is None or cer < best_cer
+        if improved:
+            best_epoch, best_cer, bad = epoch, cer, 0
+        else:
+            bad += 1
+        if output is not None:
+            path = f'{output}_{epoch}.safetensors'
+            save_safetensors(net, path)
+            if improved:
+                shutil.copyfile(path, f'{output}_best.safetensors')
+        history.append((loss, rate, cer))
+        if log is not None:
+            log(f'epoch {epoch}: loss {loss:.4f}  {rate:.1f} lines/s  val CER {cer:.4f}{"  (best)" if improved else ""}')
+        if quit == 'early' and bad >= int(lag) and epoch + 1 >= int(min_epochs):
+            break
+    return {'best_epoch': best_epoch, 'best_cer': best_cer, 'history': history}
+
+
+# the reference's RECOGNITION_HYPER_PARAMS (default_specs.py): model shape and the training defaults the command exposes
+MODEL_DEFAULTS = dict(encoder_dim=144, num_encoder_layers=16, num_attention_heads=4, feed_forward_expansion_factor=4, conv_expansion_factor=2,
+                      input_dropout_p=0.1, feed_forward_dropout_p=0.1, attention_dropout_p=0.1, conv_dropout_p=0.1, conv_kernel_size=31,
+                      half_step_residual=True, subsampling_conv_channels=32, subsampling_factor=4)
+
+
+def main(argv=None) -> int:
+    import argparse
+    import glob
+    import json
+    import os
+    import numpy as np
+    ap = argparse.ArgumentParser(prog='python -m conformer_ocr_amd.train',
+                                 description='Trains a recognition model from PAGE / ALTO / line-image ground truth on the GPU.')
+    ap.add_argument('ground_truth', nargs='*', help='training files (added to -t)')
+    ap.add_argument('-t', '--training-files', action='append', default=[], help='file of training file names, one per line, or a glob')
+    ap.add_argument('-e', '--evaluation-files', action='append', default=[], help='file of evaluation file names, one per line, or a glob')
+    ap.add_argument('-f', '--format-type', choices=('path', 'page', 'alto', 'xml'), default='path')
+    ap.add_argument('-p', '--partition', type=float, default=0.9, help='training share of the lines without -e')
+    ap.add_argument('-B', '--batch-size', type=int, default=32)
+    ap.add_argument('--pad', type=int, default=16)
+    ap.add_argument('--line-height', type=int, default=96)
+    ap.add_argument('--edge', type=int, default=200, help='width bucket edge of the batches')
+    ap.add_argument('-r', '--lrate', type=float, default=3e-4)
+    ap.add_argument('-w', '--weight-decay', type=float, default=1e-5)
+    ap.add_argument('--warmup', type=int, default=35000)
+    ap.add_argument('--schedule', choices=Trainer.SCHEDULES, default='cosine')
+    ap.add_argument('--cos-max', type=int, default=100)
+    ap.add_argument('--cos-min-lr', type=float, default=3e-5)
+    ap.add_argument('-q', '--quit', choices=('fixed', 'early'), default='fixed')
+    ap.add_argument('-N', '--epochs', type=int, default=100)
+    ap.add_argument('--min-epochs', type=int, default=10)
+    ap.add_argument('--lag', type=int, default=10)
+    ap.add_argument('-u', '--normalization', choices=('NFD', 'NFKD', 'NFC', 'NFKC'), default='NFD')
+    ap.add_argument('--normalize-whitespace', dest='normalize_whitespace', action='store_true', default=True)
+    ap.add_argument('--no-normalize-whitespace', dest='normalize_whitespace', action='store_false')
+    ap.add_argument('--augment', dest='augment', action='store_true', default=True)
+    ap.add_argument('--no-augment', dest='augment', action='store_false')
+    ap.add_argument('-i', '--load', default=None, help='safetensors archive or checkpoint to continue training')
+    ap.add_argument('-o', '--output', default='model', help='prefix of the written models')
+    ap.add_argument('--device', default='cuda:0')
+    ap.add_argument('--seed', type=int, default=0)
+    ap.add_argument('--precision', choices=('medium', 'highest'), default='medium', help='matmul precision of the training step')
+    ap.add_argument('--hyper-params', default=None, help='JSON object overriding the model hyper-parameters of a new model')
+    args = ap.parse_args(argv)
+
+    def expand(entries):
+        out = []
+        for e in entries:
+            if os.path.isfile(e) and not e.lower().endswith(('.xml', '.png', '.jpg', '.jpeg', '.tif', '.tiff')):
+                with open(e, encoding='utf-8') as fp:
+                    out.extend(l.strip() for l in fp if l.strip())
+            else:
+                out.extend(sorted(glob.glob(e)) or [e])
+        return out
+    from .dataset import GroundTruthDataset
+    from .ocr import load_model
+    from .synth import make_state_dict
+    from .spec import HParams
+    train_files = expand(args.training_files) + list(args.ground_truth)
+    if not train_files:
+        ap.error('no training data: give files or -t')
+    codec, net = None, None
+    if args.load:
+        net = load_model(args.load, device=args.device)
+        codec = net.codec
+    data = GroundTruthDataset(train_files, expand(args.evaluation_files) or None, format_type=args.format_type, partition=args.partition,
+                              normalization=args.normalization, normalize_whitespace=args.normalize_whitespace, height=args.line_height,
+                              pad=args.pad, batch_size=args.batch_size, edge=args.edge, seed=args.seed, augment=args.augment, codec=codec,
+                              device=args.device)
+    if net is None:
+        from .pred import PytorchRecognitionModel
+        hp = dict(MODEL_DEFAULTS, **json.loads(args.hyper_params or '{}'))
+        hp.update(height=args.line_height, num_classes=data.codec.max_label + 1)
+        net = PytorchRecognitionModel(**hp, codec=data.codec)
+        shape = HParams.from_kwargs(**{k: v for k, v in hp.items() if not k.endswith('dropout_p')})
+        state = make_state_dict(shape, seed=args.seed)
+        net.nn.load_state_dict({k: torch.from_numpy(np.asarray(v)) for k, v in state.items()})
+        net = net.to(args.device).eval()
+    elif net.height != args.line_height:
+        ap.error(f'the loaded model takes lines of {net.height} rows, not {args.line_height}')
+    trainer = Trainer(net, lr=args.lrate, weight_decay=args.weight_decay, warmup=args.warmup, schedule=args.schedule,
+                      cos_t_max=args.cos_max, cos_min_lr=args.cos_min_lr, seed=args.seed, matmul_precision=args.precision)
+    res = fit(net, data, trainer, epochs=args.epochs, quit=args.quit, min_epochs=args.min_epochs, lag=args.lag, output=args.output)
+    if res['best_epoch'] < 0:
+        print('Model did not improve during training.')
+        return 1
+    print(f'Best model {args.output}_best.safetensors (epoch {res["best_epoch"]}, val CER {res["best_cer"]:.4f})')
+    return 0
+
+
+if __name__ == '__main__':
+    import sys
+    sys.exit(main())

@@ -206,6 +206,19 @@ int cocr_extract_lines(cocr_model *m, const uint8_t *const *pages, const int32_t
                        const int32_t *line_dims, const int64_t *cols, const int32_t *verts, const int32_t *nverts, int N, int fill,
                        uint8_t *out, const int64_t *out_offsets, void *stream);
 
+/* Training-time augmentation of a pre-processed line batch -- the step the reference hands to kraken's default augmenter
+ * (albumentations, on the host, after scaling each line; reference dataset.py), with this library's own definition (DESIGN.md
+ * section 7b; not pinned against kraken): `in` (N, H, W) uint8 DEVICE, the batch cocr_preproc_lines wrote, seq_lens HOST int32 (N) its
+ * line widths; `out` a DEVICE buffer of the same shape (not `in`).  params DEVICE int64 (N, 16): per line seq_len, stage flags
+ * (1 geometry, 2 control-grid displacement, 4 blur, 8 pixel dropout), the inverse affine map (a0 .. a5, 1/65536 px), blur kind
+ * (1 box 3x3, 2 median 3x3, 3 motion), motion length and direction, dropout threshold (of 65536) and hash key; the table's seq_len must
+ * equal seq_lens[i] (the kernel clamps it to [0, W]).  grid DEVICE int32 (N, grid_cols, 3): (dx, dy, shear) in 1/65536 px at columns
+ * 0, 32, 64, ...; grid_cols >= (W - 1) / 32 + 2.  Pixels of a line read only [0, H) x [0, seq_len) of `in` (anything else is 0);
+ * columns >= seq_len are copied unchanged.  Integer arithmetic throughout.  Errors: COCR_EINVAL before any launch for a shape over
+ * the limits (H <= 4096, W <= 65535), seq_lens[i] > W, or a grid too small for W.  Never synchronises `stream`. */
+int cocr_augment_lines(cocr_model *m, const uint8_t *in, uint8_t *out, int N, int H, int W, const int32_t *seq_lens, const int64_t *params,
+                       const int32_t *grid, int grid_cols, void *stream);
+
 /* Launch-overhead control: with graph replay on, cocr_forward captures its ~40 kernel launches into a hipGraph and
  * replays it.  A caller that reuses (lines, logits, N, W, dtype, stream) gets a graph on its own buffers (second
  * identical call captures, later ones replay; contents may change, addresses not).  A caller with fresh buffers per
