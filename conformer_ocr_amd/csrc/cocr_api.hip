@@ -80,7 +80,40 @@ struct BlobPlan {
     size_t total = 0;
 };
 
-struct DevBuf { void *p = nullptr; size_t bytes = 0; };
+// A grow-only scratch buffer of E: device memory, or pinned host memory.  grow() releases the old memory and records capacity 0
+// before it allocates, so a failed allocation leaves an empty buffer, never a stale capacity.  Work still in flight that reads the
+// old memory is the caller's to finish first.  The destructor releases the buffer.
+template <typename E> struct DevBuf {
+    E *p = nullptr;
+    size_t n = 0;                       // capacity in elements
+    const bool pinned;
+    explicit DevBuf(bool pinned_ = false) : pinned(pinned_) {}
+    DevBuf(const DevBuf &) = delete;
+    DevBuf &operator=(const DevBuf &) = delete;
+    ~DevBuf() { release(); }
+    void release() {
+        if (p) (void)(pinned ? hipHostFree(p) : hipFree(p));
+        p = nullptr; n = 0;
+    }
+    hipError_t grow(size_t need, size_t alloc = 0) {     // at least `need` elements; a growth allocates max(need, alloc)
+        if (need <= n) return hipSuccess;
+        release();
+        alloc = std::max(need, alloc);
+        void *q = nullptr;
+        const hipError_t e = pinned ? hipHostMalloc(&q, alloc * sizeof(E)) : hipMalloc(&q, alloc * sizeof(E));
+        if (e != hipSuccess) return e;
+        p = static_cast<E *>(q); n = alloc;
+        return hipSuccess;
+    }
+};
+// a device buffer and its pinned host staging, grown together to one capacity: both or neither
+template <typename E> static hipError_t grow_pair(DevBuf<E> &dev, DevBuf<E> &host, size_t need, size_t alloc = 0) {
+    if (need <= dev.n && need <= host.n) return hipSuccess;
+    dev.release(); host.release();
+    hipError_t e = dev.grow(need, alloc);
+    if (e == hipSuccess && (e = host.grow(need, alloc)) != hipSuccess) dev.release();
+    return e;
+}
 
 struct ProfRec { int fam; hipEvent_t a, b; };
 struct TrainState;
@@ -125,31 +158,23 @@ struct cocr_model {
     size_t qkv_bytes = 0;
     int vtN = -1, vtT = -1;    // shape the q/k/vt buffers were last zeroed for
     int pos_maxlen = COCR_POS_MAXLEN;                  // relative positions the P tables cover: -(max_len - 1) .. max_len - 1
-    unsigned char *pre_buf = nullptr;      // line pre-processing: descriptors, tap tables, intermediates
-    size_t pre_cap = 0;
-    unsigned char *page_buf = nullptr;     // line extraction: descriptors, column frames, polygons, span table
-    size_t page_cap = 0;
-    int32_t *d_lens = nullptr, *h_lens = nullptr, *d_lens_cur = nullptr;      // device / pinned-host rings of per-line lengths (upload_lens)
+    DevBuf<unsigned char> pre_buf;         // line pre-processing: descriptors, tap tables, intermediates
+    DevBuf<unsigned char> page_buf;        // line extraction: descriptors, column frames, polygons, span table
+    DevBuf<int32_t> d_lens, h_lens{true};  // device / pinned-host rings of per-line lengths (upload_lens)
+    int32_t *d_lens_cur = nullptr;
     int lens_slot = 0;
-    int32_t *ctc_lab = nullptr;
+    DevBuf<int32_t> ctc_lab;                // per-frame argmax / maximum of the greedy decoder (ensure_ctc_scratch)
+    DevBuf<float> ctc_val;
     const float *amax_logits = nullptr;     // the logits buffer whose per-frame argmax / maximum the last forward left in ctc_lab / ctc_val (decoder epilogue)
     int amax_rows = 0;
     bool amax_ok = false;                   // the forward's launch sequence (plain or captured) ends with the argmax epilogue
-    float *ctc_val = nullptr;
-    size_t ctc_cap = 0;
-    float *tr_pad = nullptr;            // padded models: engine-layout staging of the output layer's gradient tensors
-    size_t tr_pad_cap = 0;
-    int32_t *beam_bp = nullptr;
-    size_t beam_cap = 0;
-    int lens_cap = 0;
-    int32_t *loss_d = nullptr, *loss_h = nullptr;      // cocr_ctc_loss: device / pinned-host rings of [lens | label lens | label offsets | labels]
-    size_t loss_ints = 0;
+    DevBuf<float> tr_pad;                   // padded models: engine-layout staging of the output layer's gradient tensors
+    DevBuf<unsigned char> beam_bp;          // cocr_ctc_beam: back-pointers, then log Z or the frame records
+    DevBuf<int32_t> loss_d, loss_h{true};   // cocr_ctc_loss: device / pinned-host rings of [lens | label lens | label offsets | labels]
     int loss_slot = 0;
-    float *loss_ws = nullptr;                          // log-softmax + alpha / beta tables
-    size_t loss_ws_cap = 0;
+    DevBuf<float> loss_ws;                  // log-softmax + alpha / beta tables
     int lastN = 0, lastT = 0;                          // shape of the last forward: its encoder output is still in `xn`
-    float *tr_part = nullptr;                          // decoder backward: per-chunk partial sums of dW | db
-    size_t tr_part_cap = 0;
+    DevBuf<float> tr_part;                  // decoder backward: per-chunk partial sums of dW | db
     float *tr_state = nullptr;                         // decoder AdamW: fp32 master [W | b], then exp_avg, then exp_avg_sq
     long tr_step = 0;
     // debug / profile
@@ -163,7 +188,6 @@ struct cocr_model {
     bool beam_ref = false;       // COCR_BEAM_REF=1: the exhaustive beam kernel (all beam x C candidates per frame) also for <= 256 classes
     bool no_front96 = false;     // COCR_NO_FRONT96=1: frontend conv stages as separate kernels (A/B)
     bool no_front32 = false;     // COCR_NO_FRONT32=1: 32 conv channels: the pointwise conv as a GEMM launch of its own (A/B)
-    bool no_conv_mfma = false;   // COCR_NO_CONV_MFMA=1: the all-VALU fp32 frontend conv kernel also in bf16 mode (A/B)
     bool no_dw_fuse = false;     // COCR_NO_DW_FUSE=1: depthwise conv as its own launch (A/B)
     int chain_rows = 0;          // rows per workgroup of the row-chain kernels (cocr_set_chain_rows / COCR_CHAIN_ROWS); 0 = by the number of rows
     bool no_front_chain = false; // COCR_NO_FRONT_CHAIN=1: the frontend's output linear as a split-K GEMM + reduction in front of the first chain launch (A/B)
@@ -174,10 +198,8 @@ struct cocr_model {
     bool no_kskip = false;       // COCR_NO_KSKIP=1: zero-padded narrow models multiply their zero k-steps too (A/B)
     bool chain_xcd = true;       // COCR_CHAIN_XCD=0: row blocks in plain workgroup order (A/B)
     bool no_chain = false;       // COCR_NO_CHAIN=1: one kernel per GEMM / FFN instead of the row-local chains (A/B measurements)
-    bool no_fused_ffn = false;   // COCR_NO_FUSED_FFN=1: keep the two-GEMM feed-forward (A/B measurements)
     std::map<std::string, std::pair<float *, int64_t>> taps;
-    float *tapbuf = nullptr;     // debug: 4 fp32 (M, D) tap targets of the chain kernels' TAPS instantiation + one bf16 (M, D)
-    size_t tapbuf_rows = 0;
+    DevBuf<float> tapbuf;        // debug: 4 fp32 (M, D) tap targets of the chain kernels' TAPS instantiation + one bf16 (M, D)
     TrainState *train = nullptr;   // cocr_train_begin .. cocr_train_end (train_api.hip.h)
     bool profile = false;
     std::vector<ProfRec> prof;
@@ -190,6 +212,13 @@ static const char *FAMILIES[] = {"frontend_fused", "frontend_conv12", "frontend_
 enum { FAM_FRONT96, FAM_CONV12, FAM_FDW, FAM_FPW, FAM_FOUT, FAM_LN, FAM_FFN_UP, FAM_FFN_DOWN, FAM_FFN_FUSED, FAM_CH_FIRST, FAM_CH_FRONT, FAM_CH_A, FAM_CH_B, FAM_CH_LAST, FAM_QKV, FAM_ATTN, FAM_AOUT, FAM_GLU,
        FAM_DW, FAM_PW2, FAM_DEC, FAM_GREEDY, FAM_BEAM, FAM_LOSS, FAM_FFN_PROBE, FAM_EMPTY, FAM_COUNT };
 
+// captured launch sequences point at the model's buffers, tables and launch shapes: dropped whenever one of them changes
+static void drop_graphs(cocr_model *m) {
+    for (auto &g : m->graphs) (void)hipGraphExecDestroy(g.exec);
+    m->graphs.clear();
+    m->graph_seen.clear();
+}
+
 static int out_len1(int l) { return l >= 1 ? (l - 1) / 2 + 1 : 0; }
 
 extern "C" int32_t cocr_out_len(int32_t in_len, int32_t subsampling_factor) {
@@ -200,6 +229,26 @@ extern "C" int32_t cocr_out_len(int32_t in_len, int32_t subsampling_factor) {
 }
 
 static void add_name(cocr_model *m, const std::string &n) { m->names.push_back(n); m->host[n]; }
+
+// The COCR_* environment switches, read when a model is created.  A flag switch flips its default: '1' turns a
+// default-off flag on, '0' turns a default-on one off.  A count takes the value's integer.
+struct Switch { const char *name; bool cocr_model::*flag; int cocr_model::*count; };
+static const Switch SWITCHES[] = {
+    {"COCR_NO_PAD", &cocr_model::no_pad, nullptr},
+    {"COCR_NO_CHAIN", &cocr_model::no_chain, nullptr},
+    {"COCR_NO_FRONT_CHAIN", &cocr_model::no_front_chain, nullptr},
+    {"COCR_FFN_PROBE", &cocr_model::ffn_probe, nullptr},
+    {"COCR_ATT_TILED", &cocr_model::att_tiled, nullptr},
+    {"COCR_ATT_RESIDENT_LONG", &cocr_model::att_resident_long, nullptr},
+    {"COCR_CHAIN_XCD", &cocr_model::chain_xcd, nullptr},
+    {"COCR_NO_KSKIP", &cocr_model::no_kskip, nullptr},
+    {"COCR_NO_DW_FUSE", &cocr_model::no_dw_fuse, nullptr},
+    {"COCR_NO_FRONT96", &cocr_model::no_front96, nullptr},
+    {"COCR_NO_FRONT32", &cocr_model::no_front32, nullptr},
+    {"COCR_BEAM_REF", &cocr_model::beam_ref, nullptr},
+    {"COCR_ATT_RESIDENT_MIN", nullptr, &cocr_model::att_resident_min},
+    {"COCR_CHAIN_ROWS", nullptr, &cocr_model::chain_rows},
+};
 
 extern "C" int cocr_create(const cocr_hparams *hp, int device, cocr_model **out) {
     if (!hp || !out) return fail(COCR_EINVAL, "null argument");
@@ -225,22 +274,12 @@ extern "C" int cocr_create(const cocr_hparams *hp, int device, cocr_model **out)
     m->ff = hp->feed_forward_expansion_factor * hp->encoder_dim; m->ksz = hp->conv_kernel_size;
     m->rD = m->D; m->rff = m->ff; m->rdh = m->dh;
     m->ncls = hp->num_classes; m->H = hp->height; m->snum = snum;
-    { const char *e = getenv("COCR_NO_PAD"); m->no_pad = e && e[0] == '1'; }
-    { const char *e = getenv("COCR_NO_FUSED_FFN"); m->no_fused_ffn = e && e[0] == '1'; }
-    { const char *e = getenv("COCR_NO_CHAIN"); m->no_chain = e && e[0] == '1'; }
-    { const char *e = getenv("COCR_NO_FRONT_CHAIN"); m->no_front_chain = e && e[0] == '1'; }
-    { const char *e = getenv("COCR_FFN_PROBE"); m->ffn_probe = e && e[0] == '1'; }
-    { const char *e = getenv("COCR_ATT_TILED"); m->att_tiled = e && e[0] == '1'; }
-    { const char *e = getenv("COCR_ATT_RESIDENT_LONG"); m->att_resident_long = e && e[0] == '1'; }
-    { const char *e = getenv("COCR_CHAIN_XCD"); if (e) m->chain_xcd = e[0] != '0'; }
-    { const char *e = getenv("COCR_NO_KSKIP"); m->no_kskip = e && e[0] == '1'; }
-    { const char *e = getenv("COCR_ATT_RESIDENT_MIN"); if (e) m->att_resident_min = atoi(e); }
-    { const char *e = getenv("COCR_CHAIN_ROWS"); m->chain_rows = e ? atoi(e) : 0; }
-    { const char *e = getenv("COCR_NO_DW_FUSE"); m->no_dw_fuse = e && e[0] == '1'; }
-    { const char *e = getenv("COCR_NO_CONV_MFMA"); m->no_conv_mfma = e && e[0] == '1'; }
-    { const char *e = getenv("COCR_NO_FRONT96"); m->no_front96 = e && e[0] == '1'; }
-    { const char *e = getenv("COCR_NO_FRONT32"); m->no_front32 = e && e[0] == '1'; }
-    { const char *e = getenv("COCR_BEAM_REF"); m->beam_ref = e && e[0] == '1'; }
+    for (const Switch &w : SWITCHES) {
+        const char *e = getenv(w.name);
+        if (!e) continue;
+        if (w.count) m->*w.count = atoi(e);
+        else m->*w.flag = m->*w.flag ? e[0] != '0' : e[0] == '1';
+    }
     { const char *e = getenv("COCR_CHAIN_STAMPS"); if (e && e[0] == '1') { (void)hipHostMalloc((void **)&m->stamps, 4096 * 8); memset(m->stamps, 0, 4096 * 8); } }
     int f = hp->height;
     for (int i = 0; i < snum; ++i) { f = out_len1(f); m->feats.push_back(f); }
@@ -292,7 +331,17 @@ static void free_workspace(cocr_model *m) {
 static void clear_taps(cocr_model *m) {
     for (auto &kv : m->taps) (void)hipFree(kv.second.first);
     m->taps.clear();
-    if (m->tapbuf) { (void)hipFree(m->tapbuf); m->tapbuf = nullptr; m->tapbuf_rows = 0; }
+    m->tapbuf.release();
+}
+
+// the weights and their derived copies: released when they are the model's own, forgotten when they are an owner's (cocr_share_weights)
+static void drop_weights(cocr_model *m) {
+    if (!m->owner)
+        for (void *p : {(void *)m->blob, (void *)m->packed, (void *)m->ptab, (void *)m->fpack})
+            if (p) (void)hipFree(p);
+    m->owner = nullptr;
+    m->blob = m->packed = m->ptab = nullptr;
+    m->fpack = nullptr;
 }
 
 static void train_free(cocr_model *m);
@@ -302,14 +351,7 @@ extern "C" void cocr_destroy(cocr_model *m) {
     train_free(m);
     free_workspace(m);
     clear_taps(m);
-    if (!m->owner) {
-        if (m->blob) (void)hipFree(m->blob);
-        if (m->packed) (void)hipFree(m->packed);
-        if (m->ptab) (void)hipFree(m->ptab);
-        if (m->fpack) (void)hipFree(m->fpack);
-    }
-    if (m->pre_buf) (void)hipFree(m->pre_buf);
-    if (m->page_buf) (void)hipFree(m->page_buf);
+    drop_weights(m);
     if (m->stamps) {
         (void)hipDeviceSynchronize();
         if (m->stamps[1024]) {                          // row-chain kernel (dominant form), workgroup 7: per wave, cycles between stamps
@@ -355,21 +397,11 @@ extern "C" void cocr_destroy(cocr_model *m) {
         }
         (void)hipHostFree(m->stamps);
     }
-    if (m->d_lens) (void)hipFree(m->d_lens);
-    if (m->h_lens) (void)hipHostFree(m->h_lens);
-    if (m->ctc_lab) (void)hipFree(m->ctc_lab);
-    if (m->ctc_val) (void)hipFree(m->ctc_val);
-    if (m->beam_bp) (void)hipFree(m->beam_bp);
-    if (m->tr_pad) (void)hipFree(m->tr_pad);
-    if (m->loss_d) (void)hipFree(m->loss_d);
-    if (m->loss_h) (void)hipHostFree(m->loss_h);
-    if (m->loss_ws) (void)hipFree(m->loss_ws);
-    if (m->tr_part) (void)hipFree(m->tr_part);
     if (m->tr_state) (void)hipFree(m->tr_state);
-    for (auto &g : m->graphs) (void)hipGraphExecDestroy(g.exec);
+    drop_graphs(m);
     for (auto &r : m->prof) { (void)hipEventDestroy(r.a); (void)hipEventDestroy(r.b); }
     for (auto e : m->ev_pool) (void)hipEventDestroy(e);
-    delete m;
+    delete m;                                           // (its scratch buffers release themselves)
 }
 
 extern "C" int cocr_set_tensor(cocr_model *m, const char *name, const void *host, int dtype, int ndim, const int64_t *shape) {
@@ -491,8 +523,7 @@ static int set_engine_dims(cocr_model *m, int dtype) {
     const int D = pad ? wide : m->rD, ff = pad ? round_up(m->rff, 256) : m->rff, dh = pad ? slot : m->rdh, dhp = pad ? slot : round_up(m->rdh, 32);
     if (D != m->D || ff != m->ff || dh != m->dh || dhp != m->dhp) {      // workspace and captured launches belong to the old layout
         HIP_TRY(hipDeviceSynchronize());
-        for (auto &g : m->graphs) (void)hipGraphExecDestroy(g.exec);
-        m->graphs.clear(); m->graph_seen.clear();
+        drop_graphs(m);
         free_workspace(m);
         m->capN = m->capW = 0;
     }
@@ -504,13 +535,9 @@ static int alloc_blob(cocr_model *m, int dtype) {
     if (dtype != COCR_BF16 && dtype != COCR_F32) return fail(COCR_EINVAL, "compute dtype must be COCR_BF16 or COCR_F32");
     HIP_TRY(hipSetDevice(m->device));
     { const int rc = set_engine_dims(m, dtype); if (rc) return rc; }
-    if (m->owner) { m->owner = nullptr; m->blob = m->packed = m->ptab = nullptr; m->fpack = nullptr; }      // weights of its own again
+    drop_weights(m);                                  // (weights of its own again)
     m->wgen++;
-    if (m->blob) { (void)hipFree(m->blob); m->blob = nullptr; }
-    if (m->packed) { (void)hipFree(m->packed); m->packed = nullptr; }
-    if (m->ptab) { (void)hipFree(m->ptab); m->ptab = nullptr; }
     m->ptab_stale = true;
-    if (m->fpack) { (void)hipFree(m->fpack); m->fpack = nullptr; }
     if (m->tr_state) { (void)hipFree(m->tr_state); m->tr_state = nullptr; m->tr_step = 0; }      // optimizer state belongs to the old weights
     m->packed_stale = true;
     m->plan = make_plan(m, dtype);
@@ -537,16 +564,11 @@ extern "C" int cocr_share_weights(cocr_model *m, cocr_model *owner) {
     HIP_TRY(hipSetDevice(m->device));
     HIP_TRY(hipDeviceSynchronize());
     if (m->dtype != owner->dtype || !m->blob || m->owner) { const int rc = alloc_blob(m, owner->dtype); if (rc) return rc; }     // dims, plan
-    (void)hipFree(m->blob);
-    if (m->packed) (void)hipFree(m->packed);
-    if (m->ptab) (void)hipFree(m->ptab);
-    if (m->fpack) (void)hipFree(m->fpack);
-    m->blob = m->packed = m->ptab = nullptr; m->fpack = nullptr;
+    drop_weights(m);
     m->owner = owner;
     m->seen_wgen = 0;                               // the next forward adopts the owner's pointers
     m->blob = owner->blob;                          // ("finalized" tests look at it)
-    for (auto &g : m->graphs) (void)hipGraphExecDestroy(g.exec);
-    m->graphs.clear(); m->graph_seen.clear();
+    drop_graphs(m);
     return COCR_OK;
 }
 
@@ -751,8 +773,7 @@ extern "C" int cocr_reserve(cocr_model *m, int N, int W) {
     HIP_TRY(hipSetDevice(m->device));
     HIP_TRY(hipDeviceSynchronize());
     N = std::max(N, m->capN); W = std::max(W, m->capW);
-    for (auto &g : m->graphs) (void)hipGraphExecDestroy(g.exec);     // captured launches point into the old workspace
-    m->graphs.clear(); m->graph_seen.clear();
+    drop_graphs(m);     // captured launches point into the old workspace
     free_workspace(m);
     const size_t es = esize(m->dtype);
     int T = W;
@@ -918,395 +939,444 @@ static hipError_t launch_attention(hipStream_t s, int N, const T *q, const T *k,
     return hipGetLastError();
 }
 
-static bool uses_chain96(const cocr_model *m);
-static bool uses_frontend96(const cocr_model *m);
 static int ensure_ctc_scratch(cocr_model *m, size_t rows);
 
-template <typename T, typename TIn>
-static int forward_impl(cocr_model *m, const TIn *lines, int N, int H, int W, float *logits, hipStream_t s) {
-    const BlobPlan &P = m->plan;
-    const unsigned char *B = m->blob;
-    auto F32 = [&](size_t off) { return (const float *)(B + off); };
-    auto WT = [&](size_t off) { return (const T *)(B + off); };
-    const int D = m->D, C = m->C, ff = m->ff, heads = m->heads, dh = m->dh, dhp = m->dhp;
-    const bool f2only = m->snum == 1;                    // subsampling_factor 2: conv.0 + ReLU, then the output linear
-    const int T1 = out_len1(W), T2 = f2only ? T1 : out_len1(T1), F1 = m->feats[0], F2 = f2only ? F1 : m->feats[1];
-    int rc;
-    // profiling: one EMPTY event pair per forward = the fixed cost of a bracket (record -> record with nothing between), which
-    // bench.py subtracts from every family's average so that the event timings line up with rocprofv3's dispatch durations
-    { ProfScope ps(m, s, FAM_EMPTY); }
+// ------------------------------------------------------------------------------------ forward: its form
+// How each stage of a forward runs, decided in one place (forward_form) from the model, the compute type, the batch shape, the
+// debug-tap state and the switches.  forward_impl launches that form; ensure_packed packs the weights it reads.
+enum FrontForm {
+    FRONT_96,      // bf16, two stages, frontend96_supported: conv.0 + ReLU + depthwise conv.2 + pointwise conv.3 + ReLU in one kernel (frontend.hip.h)
+    FRONT_CONV0,   // subsampling factor 2: conv.0 + ReLU, then the output linear
+    FRONT_PW32,    // bf16, 32 conv channels, no taps: conv.0 .. conv.3 in one launch (conv.hip.h: frontend_conv12pw32_kernel; Z2 stays on chip)
+    FRONT_MFMA,    // bf16, conv channels a multiple of 64: conv.0 on the matrix cores + depthwise conv.2 (conv.hip.h), pointwise conv.3 as a GEMM
+    FRONT_VALU,    // conv.0 + depthwise conv.2 on the vector units, pointwise conv.3 as a GEMM
+};
+enum OutForm {     // the frontend's output linear (K = F C) and the first block's first LayerNorm
+    OUT_IN_CHAIN,  // the first stage of the first row-chain launch (rowchain.hip.h: FRONT stage)
+    OUT_SPLITK,    // split-K GEMM into the idle frontend buffer, then one pass sums the parts, adds the bias and applies the LayerNorm
+    OUT_GEMM,      // one GEMM, the LayerNorm in its epilogue (rowln) or as a launch of its own
+};
+struct Form {
+    FrontForm front;
+    OutForm out;
+    bool rowln;        // N == D products own whole rows: residual + LayerNorm in their epilogue
+    bool chain;        // encoder as row-local chains (rowchain.hip.h), else one kernel per product
+    bool ffn_fused;    // per product: the feed-forward module in one kernel, its hidden tensor on chip (ffn.hip.h)
+    bool dw_fused;     // chains: the depthwise conv as the prologue of chain B, else a launch of its own
+    bool taps;         // debug taps (cocr_set_debug): the chains run their TAPS instantiation; per product, the second feed-forward module
+                       // runs as two GEMMs with its closing LayerNorm apart (the stream is tapped before and after it)
+    bool argmax;       // the decoder product's epilogue also leaves the per-frame argmax / maximum for cocr_ctc_greedy
+};
 
-    // ---- frontend: conv.0 + ReLU + depthwise conv.2 fused, then pointwise conv.3 + ReLU as a GEMM over channels
-    T *za = (T *)m->z_a, *zb = (T *)m->z_b;
-    bool front_fused = false;
-    if constexpr (sizeof(T) == 2) {
-        if (uses_frontend96(m)) {                        // conv.0 + ReLU + depthwise conv.2 + pointwise conv.3 + ReLU in one kernel (frontend.hip.h)
-            ProfScope ps(m, s, FAM_FRONT96);
-            const size_t n0 = (size_t)(C / 16) * 64 * 4;
-            GEMM_TRY(launch_frontend96<TIn>(s, lines, N, H, W, T1, F1, T2, m->fpack, F32(P.b0), m->fpack + n0, F32(P.stages[0].dw_b),
-                                            (const bf16_t *)(m->packed + P.stages[0].pw_w), F32(P.stages[0].pw_b), (bf16_t *)zb, m->stamps ? m->stamps + 128 : nullptr));
-            front_fused = true;
-            if ((rc = tap<T>(m, s, "front.z3", zb, (size_t)N * T2 * F2 * C))) return rc;      // (Z2 does not exist on this path)
-        }
+// split-K over 2 workgroup groups (2 measured best of 2, 4, 8: 63 vs 74 vs 91 us for product + reduction)
+#ifndef COCR_FO_SPLITS
+#define COCR_FO_SPLITS 2
+#endif
+static Form forward_form(const cocr_model *m, int N, int W) {
+    const bool bf16 = m->dtype == COCR_BF16, f2only = m->snum == 1;
+    const int es = bf16 ? 2 : 4, D = m->D, C = m->C, H = m->H;
+    const int T1 = out_len1(W), T2 = f2only ? T1 : out_len1(T1), F2 = m->feats[f2only ? 0 : 1];
+    const int Kf = m->feats.back() * C, M = N * cocr_out_len(W, m->hp.subsampling_factor);
+    const size_t lds32 = (size_t)(4 * 16 + 3) * ((H + 11) & ~3) * 4 + (size_t)16 * F2 * 80;      // FRONT_PW32: line tile + Z2 rows of 16 frames
+    Form f{};
+    f.taps = m->debug;
+    f.rowln = bf16 ? gemm_rowln_supported<bf16_t>(D) : gemm_rowln_supported<float>(D);
+    f.chain = bf16 && rowchain_supported(D, m->ff, m->dh) && !m->no_chain;
+    if (bf16 && m->snum == 2 && frontend96_supported(C, m->feats[0], m->feats[1], H) && !m->no_front96) f.front = FRONT_96;
+    else if (f2only) f.front = FRONT_CONV0;
+    else if (bf16 && C == 32 && F2 <= 32 && lds32 <= 160 * 1024 && !f.taps && !m->no_front32) f.front = FRONT_PW32;
+    else f.front = bf16 && C % 64 == 0 ? FRONT_MFMA : FRONT_VALU;
+    if (f.chain && Kf % 256 == 0 && !m->no_front_chain) f.out = OUT_IN_CHAIN;
+    else if (f.rowln && Kf % (COCR_FO_SPLITS * (128 / es)) == 0 && D <= 256 && (size_t)COCR_FO_SPLITS * M * D * 4 <= (size_t)N * T2 * F2 * C * es)
+        f.out = OUT_SPLITK;     // (the parts fit the idle frontend buffer)
+    else f.out = OUT_GEMM;
+    f.ffn_fused = bf16 && f.rowln && ffn_fused_supported<int>(D, m->ff);
+    f.dw_fused = m->ksz == 31 && (!m->no_dw_fuse || f.taps);
+    f.argmax = m->ncls <= 128 && D % (128 / es) == 0;       // (whole k-steps of the decoder product)
+    return f;
+}
+
+// ------------------------------------------------------------------------------------ forward
+// What every stage of one forward reads: the model, its form, the stream, the plan, the dimensions and the workspace
+template <typename T> struct Fwd {
+    cocr_model *m;
+    const Form &f;
+    hipStream_t s;
+    const BlobPlan &P;
+    const int N, W, D, T1, T2, F1, F2, Tn, M, Tp;        // T1 / F1, T2 / F2: frames / height after the first, second stride-2 stage
+    const float ffr, scale;     // feed-forward residual factor; 1/sqrt(d_head) of the model (a padded model's engine d_head is its 64-wide slot)
+    T *const za, *const zb;     // frontend: each stage's output in zb, its intermediate in za
+    float *const x;             // the fp32 residual stream
+    T *const xn, *const hid, *const q, *const k, *const v, *const ctx, *const glu, *const dwo;
+    Fwd(cocr_model *m_, const Form &f_, int N_, int W_, hipStream_t s_)
+        : m(m_), f(f_), s(s_), P(m_->plan), N(N_), W(W_), D(m_->D), T1(out_len1(W_)), T2(m_->snum == 1 ? T1 : out_len1(T1)), F1(m_->feats[0]),
+          F2(m_->feats[m_->snum == 1 ? 0 : 1]), Tn(cocr_out_len(W_, m_->hp.subsampling_factor)), M(N_ * Tn), Tp(round_up(Tn, 64)),
+          ffr(m_->hp.half_step_residual ? 0.5f : 1.0f), scale(1.0f / sqrtf((float)m_->rdh)), za((T *)m_->z_a), zb((T *)m_->z_b), x(m_->x),
+          xn((T *)m_->xn), hid((T *)m_->hid), q((T *)m_->q), k((T *)m_->k), v((T *)m_->vt), ctx((T *)m_->ctx), glu((T *)m_->glu), dwo((T *)m_->dwo) {}
+    const float *F32(size_t off) const { return (const float *)(m->blob + off); }
+    const T *WT(size_t off) const { return (const T *)(m->blob + off); }
+    template <typename S> int tap(int l, const char *what, const S *src, size_t n) const {      // debug tap "what" (l < 0) or "l<l>.what"
+        if (!f.taps) return COCR_OK;
+        char nm[64];
+        if (l < 0) snprintf(nm, sizeof nm, "%s", what);
+        else snprintf(nm, sizeof nm, "l%d.%s", l, what);
+        return ::tap<S>(m, s, nm, src, n);
     }
-    if (f2only) {
+    int tap_x(int l, const char *what, const float *src) const { return tap<float>(l, what, src, (size_t)M * D); }
+    int tap_qkv(int l) const {
+        const size_t n = m->qkv_bytes / sizeof(T);
+        int rc;
+        if ((rc = tap<T>(l, "q", q, n)) || (rc = tap<T>(l, "k", k, n)) || (rc = tap<T>(l, "v", v, n))) return rc;
+        return COCR_OK;
+    }
+};
+
+// ---- frontend: conv.0 + ReLU [+ depthwise conv.2 + pointwise conv.3 + ReLU] in the form's kernels, then the further (depthwise s2,
+// pointwise, ReLU) stages.  The output is channel-last in zb: the flatten (b, t, (f, c)) of the output linear is a view of it.
+template <typename T, typename TIn> static int frontend(const Fwd<T> &c, const TIn *lines) {
+    cocr_model *m = c.m;
+    const BlobPlan &P = c.P;
+    const hipStream_t s = c.s;
+    const int N = c.N, H = m->H, W = c.W, C = m->C, T1 = c.T1, F1 = c.F1, T2 = c.T2, F2 = c.F2;
+    const FrontForm form = c.f.front;
+    T *za = c.za, *zb = c.zb;
+    int rc;
+    if (form == FRONT_CONV0) {
         ProfScope ps(m, s, FAM_CONV12);
         const size_t npos = (size_t)N * T1 * F1;
         hipLaunchKernelGGL((frontend_conv0_kernel<T, TIn>), dim3((unsigned)((npos * (size_t)(C / 2) + 255) / 256)), dim3(256), 0, s, lines, H, W, T1, F1, C, npos,
-                           F32(P.w0), F32(P.b0), zb);
+                           c.F32(P.w0), c.F32(P.b0), zb);
         LAUNCH_CHECK();
-    } else if (!front_fused) {
-    bool pw_fused = false;
-    if constexpr (sizeof(T) == 2) {
-        // 32 conv channels (the reference's default model): conv.0 + ReLU + depthwise conv.2 + pointwise conv.3 + ReLU in one launch
-        // (conv.hip.h: frontend_conv12pw32_kernel); with debug taps the separate kernels run (Z2 exists there; same arithmetic)
-        const size_t lds32 = (size_t)(4 * 16 + 3) * ((H + 11) & ~3) * 4 + (size_t)16 * F2 * 80;      // line tile + Z2 rows of 16 frames
-        if (C == 32 && F2 <= 32 && lds32 <= 160 * 1024 && !m->debug && !m->no_front32) {
-            ProfScope ps(m, s, FAM_CONV12);
-            const size_t lds = lds32;
-            auto kern = frontend_conv12pw32_kernel<TIn>;
-            GEMM_TRY(raise_lds_limit((const void *)kern, lds));
-            hipLaunchKernelGGL(kern, dim3(ceil_div(T2, 16), N), dim3(256), lds, s, lines, H, W, T1, F1, T2, F2, F32(P.w0), F32(P.b0),
-                               F32(P.stages[0].dw_w), F32(P.stages[0].dw_b), (const bf16_t *)WT(P.stages[0].pw_w), F32(P.stages[0].pw_b), (bf16_t *)zb);
-            LAUNCH_CHECK();
-            pw_fused = true;
-        }
+        return COCR_OK;
     }
-    if (!pw_fused) {
-    {
+    if (form == FRONT_96) {
+        ProfScope ps(m, s, FAM_FRONT96);
+        const size_t n0 = (size_t)(C / 16) * 64 * 4;
+        GEMM_TRY(launch_frontend96<TIn>(s, lines, N, H, W, T1, F1, T2, m->fpack, c.F32(P.b0), m->fpack + n0, c.F32(P.stages[0].dw_b),
+                                        (const bf16_t *)(m->packed + P.stages[0].pw_w), c.F32(P.stages[0].pw_b), (bf16_t *)zb, m->stamps ? m->stamps + 128 : nullptr));
+    } else if (form == FRONT_PW32) {
         ProfScope ps(m, s, FAM_CONV12);
-        bool done = false;
-        if constexpr (sizeof(T) == 2) {
-            if (C % 64 == 0 && !m->no_conv_mfma) {               // conv.0 on the matrix cores (conv.hip.h)
-                GEMM_TRY(launch_conv12_mfma<TIn>(s, lines, N, H, W, T1, F1, T2, F2, C, F32(P.w0), F32(P.b0), F32(P.stages[0].dw_w), F32(P.stages[0].dw_b),
+        const size_t lds = (size_t)(4 * 16 + 3) * ((H + 11) & ~3) * 4 + (size_t)16 * F2 * 80;      // line tile + Z2 rows of 16 frames
+        auto kern = frontend_conv12pw32_kernel<TIn>;
+        GEMM_TRY(raise_lds_limit((const void *)kern, lds));
+        hipLaunchKernelGGL(kern, dim3(ceil_div(T2, 16), N), dim3(256), lds, s, lines, H, W, T1, F1, T2, F2, c.F32(P.w0), c.F32(P.b0),
+                           c.F32(P.stages[0].dw_w), c.F32(P.stages[0].dw_b), (const bf16_t *)c.WT(P.stages[0].pw_w), c.F32(P.stages[0].pw_b), (bf16_t *)zb);
+        LAUNCH_CHECK();
+    } else {
+        {
+            ProfScope ps(m, s, FAM_CONV12);
+            if (form == FRONT_MFMA) {
+                GEMM_TRY(launch_conv12_mfma<TIn>(s, lines, N, H, W, T1, F1, T2, F2, C, c.F32(P.w0), c.F32(P.b0), c.F32(P.stages[0].dw_w), c.F32(P.stages[0].dw_b),
                                                  (bf16_t *)za));
-                done = true;
+            } else {
+                const int TB = std::max(1, 512 / C);                 // 256 threads = TB time steps x C/2 channel pairs
+                const size_t lds = (size_t)(4 * TB + 3) * ((H + 11) & ~3) * 4;
+                hipLaunchKernelGGL((frontend_conv12_kernel<T, TIn>), dim3(ceil_div(T2, TB), N), dim3(256), lds, s, lines, H, W, T1, F1, T2, F2, C,
+                                   c.F32(P.w0), c.F32(P.b0), c.F32(P.stages[0].dw_w), c.F32(P.stages[0].dw_b), za, TB);
+                LAUNCH_CHECK();
             }
         }
-        if (!done) {
-            const int TB = std::max(1, 512 / C);                 // 256 threads = TB time steps x C/2 channel pairs
-            const size_t lds = (size_t)(4 * TB + 3) * ((H + 11) & ~3) * 4;
-            hipLaunchKernelGGL((frontend_conv12_kernel<T, TIn>), dim3(ceil_div(T2, TB), N), dim3(256), lds, s, lines, H, W, T1, F1, T2, F2, C,
-                               F32(P.w0), F32(P.b0), F32(P.stages[0].dw_w), F32(P.stages[0].dw_b), za, TB);
-            LAUNCH_CHECK();
-        }
-    }
-    if ((rc = tap<T>(m, s, "front.z2", za, (size_t)N * T2 * F2 * C))) return rc;
-    {
+        if ((rc = c.tap(-1, "front.z2", za, (size_t)N * T2 * F2 * C))) return rc;
         ProfScope ps(m, s, FAM_FPW);
-        EpiBiasAct<T, ACT_RELU> epi{zb, C, F32(P.stages[0].pw_b), C};
-        GEMM_TRY(launch_gemm<T>(s, za, C, WT(P.stages[0].pw_w), C, N * T2 * F2, C, C, epi));
+        EpiBiasAct<T, ACT_RELU> epi{zb, C, c.F32(P.stages[0].pw_b), C};
+        GEMM_TRY(launch_gemm<T>(s, za, C, c.WT(P.stages[0].pw_w), C, N * T2 * F2, C, C, epi));
     }
-    }
-    }
-    if (!f2only && (rc = tap<T>(m, s, "front.z3", zb, (size_t)N * T2 * F2 * C))) return rc;
+    if ((rc = c.tap(-1, "front.z3", zb, (size_t)N * T2 * F2 * C))) return rc;      // (FRONT_96: Z2 does not exist)
     int Tc = T2, Fc = F2;
-    T *zcur = zb, *zoth = za;
-    for (int st = 1; st < m->snum - 1; ++st) {           // further (depthwise s2, pointwise, ReLU) stages
+    for (int st = 1; st < m->snum - 1; ++st) {
         const int To = out_len1(Tc), Fo = m->feats[st + 1];
         {
             ProfScope ps(m, s, FAM_FDW);
-            hipLaunchKernelGGL((dw3x3s2_kernel<T>), dim3(1024), dim3(256), 0, s, zcur, N, Tc, Fc, To, Fo, C, F32(P.stages[st].dw_w),
-                               F32(P.stages[st].dw_b), zoth);
+            hipLaunchKernelGGL((dw3x3s2_kernel<T>), dim3(1024), dim3(256), 0, s, zb, N, Tc, Fc, To, Fo, C, c.F32(P.stages[st].dw_w),
+                               c.F32(P.stages[st].dw_b), za);
             LAUNCH_CHECK();
         }
         {
             ProfScope ps(m, s, FAM_FPW);
-            EpiBiasAct<T, ACT_RELU> epi{zcur, C, F32(P.stages[st].pw_b), C};
-            GEMM_TRY(launch_gemm<T>(s, zoth, C, WT(P.stages[st].pw_w), C, N * To * Fo, C, C, epi));
+            EpiBiasAct<T, ACT_RELU> epi{zb, C, c.F32(P.stages[st].pw_b), C};
+            GEMM_TRY(launch_gemm<T>(s, za, C, c.WT(P.stages[st].pw_w), C, N * To * Fo, C, C, epi));
         }
         Tc = To; Fc = Fo;
     }
-    const int Tn = Tc, F = Fc, M = N * Tn, Tp = round_up(Tn, 64);
-    float *x = m->x;
-    T *xn = (T *)m->xn, *hid = (T *)m->hid, *q = (T *)m->q, *k = (T *)m->k, *v = (T *)m->vt, *ctx = (T *)m->ctx, *glu = (T *)m->glu,
-      *dwo = (T *)m->dwo;
-    const float ffr = m->hp.half_step_residual ? 0.5f : 1.0f;
-    const float scale = 1.0f / sqrtf((float)m->rdh);    // (the model's d_head: a padded model's engine d_head is its 64-wide slot)
-    const bool rowln = gemm_rowln_supported<T>(D);       // N == D products own whole rows: residual + LayerNorm in their epilogue
-    // bf16 row chains: the output linear (K = F C) is the first stage of the first chain launch
-    const bool front_in_chain = sizeof(T) == 2 && uses_chain96(m) && (F * C) % 256 == 0 && !m->no_front_chain;
-    auto ln = [&](size_t g1, size_t b1, bool write_f32, long g2, long b2) -> int {
-        ProfScope ps(m, s, FAM_LN);
-        launch_layernorm<T>(s, x, M, D, F32(g1), F32(b1), write_f32 ? x : nullptr, g2 >= 0 ? F32((size_t)g2) : nullptr,
-                            b2 >= 0 ? F32((size_t)b2) : nullptr, xn, m->rD);
-        LAUNCH_CHECK();
-        return COCR_OK;
-    };
-    // x <- [x +] alpha (A W^T + bias); then the LayerNorm(s) that follow in the reference: xn <- LN1(x), or
-    // x <- LN1(x), xn <- LN2(x) (g2 >= 0: block-final LayerNorm chained with the next block's first)
-    auto gemm_to_stream = [&](int fam, const T *A, int K, size_t w, size_t bias, float alpha, bool resid, size_t g1, size_t b1, long g2,
-                              long b2) -> int {
-        if (rowln) {
-            ProfScope ps(m, s, fam);
-            EpiResidualLN<T, 1> e{x, D, F32(bias), alpha, D, resid ? 1 : 0, F32(g1), F32(b1), g2 >= 0 ? F32((size_t)g2) : nullptr,
-                                  b2 >= 0 ? F32((size_t)b2) : nullptr, xn};
-            e.Dn = m->rD;
-            GEMM_TRY(launch_gemm_rowln<T>(s, A, K, WT(w), K, M, D, K, e));
-            return COCR_OK;
-        }
-        {
-            ProfScope ps(m, s, fam);
-            if (resid) { EpiResidual e{x, D, F32(bias), alpha, D}; GEMM_TRY(launch_gemm<T>(s, A, K, WT(w), K, M, D, K, e)); }
-            else { EpiStoreF32 e{x, D, F32(bias), D}; GEMM_TRY(launch_gemm<T>(s, A, K, WT(w), K, M, D, K, e)); }
-        }
-        return ln(g1, b1, g2 >= 0, g2, b2);
-    };
-    // feed-forward module + the LayerNorm(s) that follow it.  bf16, D == 256: one fused kernel (hidden stays on chip)
-    auto ffn = [&](const FfnW &fw, size_t g1, size_t b1, long g2, long b2) -> int {
-        if constexpr (sizeof(T) == 2) {
-            if (rowln && ffn_fused_supported<int>(D, ff) && !m->no_fused_ffn) {
-                ProfScope ps(m, s, FAM_FFN_FUSED);
-                EpiResidualLN<T, 1> e{x, D, F32(fw.b2), ffr, D, 1, F32(g1), F32(b1), g2 >= 0 ? F32((size_t)g2) : nullptr,
-                                      b2 >= 0 ? F32((size_t)b2) : nullptr, xn};
-                GEMM_TRY(launch_ffn_fused(s, (const bf16_t *)xn, (const bf16_t *)WT(fw.w1), F32(fw.b1), (const bf16_t *)WT(fw.w2), M, D, ff, e));
-                return COCR_OK;
-            }
-        }
-        { ProfScope ps(m, s, FAM_FFN_UP); EpiBiasAct<T, ACT_SILU> e{hid, ff, F32(fw.b1), ff}; GEMM_TRY(launch_gemm<T>(s, xn, D, WT(fw.w1), D, M, ff, D, e)); }
-        return gemm_to_stream(FAM_FFN_DOWN, hid, ff, fw.w2, fw.b2, ffr, true, g1, b1, g2, b2);
-    };
-    // flatten (b,t,(f,c)) is a view of the channel-last tensor; the output linear writes the fp32 residual stream.
-    // K = F*C (6144) against N = D: split-K over 2 workgroup groups (2 measured best of 2, 4, 8: 63 vs 74 vs 91 us for product + reduction) (partials in the idle frontend buffer), then one pass
-    // sums them, adds the bias and applies the first block's LayerNorm.
-    {
-#ifndef COCR_FO_SPLITS
-#define COCR_FO_SPLITS 2
-#endif
-        constexpr int SPLITS = COCR_FO_SPLITS;
-        const int Kf = F * C;
-        if (front_in_chain) {
-            // the first row-chain launch multiplies the frontend output by the output linear itself (rowchain.hip.h: FRONT stage)
-        } else {
-        const bool splitk = rowln && (Kf % (SPLITS * (128 / (int)sizeof(T))) == 0) && D <= 256 &&
-                            (size_t)SPLITS * M * D * 4 <= (size_t)N * T2 * F2 * C * sizeof(T);
-        if (splitk) {
-            float *partial = reinterpret_cast<float *>(zcur == zb ? za : zb);          // the other frontend buffer is free now
-            { ProfScope ps(m, s, FAM_FOUT); GEMM_TRY(launch_gemm_splitk<T>(s, zcur, Kf, WT(P.wout), Kf, M, D, Kf, SPLITS, partial)); }
-            ProfScope ps(m, s, FAM_LN);
-            hipLaunchKernelGGL((splitk_reduce_ln_kernel<T>), dim3(ceil_div(M, 16)), dim3(256), 0, s, partial, SPLITS, (size_t)M * D, F32(P.bout), M, D, m->rD,
-                               F32(P.layers[0].ffn[0].ln_g), F32(P.layers[0].ffn[0].ln_b), x, xn);
-            LAUNCH_CHECK();
-        } else if ((rc = gemm_to_stream(FAM_FOUT, zcur, Kf, P.wout, P.bout, 1.0f, false, P.layers[0].ffn[0].ln_g, P.layers[0].ffn[0].ln_b, -1, -1))) {
-            return rc;
-        }
-        }
-    }
-    if (!front_in_chain && (rc = tap<float>(m, s, "front.y", x, (size_t)M * D))) return rc;
+    return COCR_OK;
+}
 
-    if (m->vtN != N || m->vtT != Tn) {   // pad dims of q, k, v must read as zero for this shape
-        HIP_TRY(hipMemsetAsync(q, 0, m->qkv_bytes, s));
-        HIP_TRY(hipMemsetAsync(k, 0, m->qkv_bytes, s));
-        HIP_TRY(hipMemsetAsync(v, 0, m->qkv_bytes, s));
-        m->vtN = N; m->vtT = Tn;
-    }
-    char nm[64];
-    // decoder nn.Linear (pred.py:90,121): logits fp32.  Up to 128 classes the product's epilogue also leaves the greedy decoder's per-frame
-    // argmax / maximum (ctc_lab / ctc_val): cocr_ctc_greedy on these logits then only merges runs.
-    auto decoder = [&](const T *xin) -> int {
-        ProfScope ps(m, s, FAM_DEC);
-        constexpr int BK = 128 / (int)sizeof(T);
-        if (m->ncls <= 128 && D % BK == 0 && (rc = ensure_ctc_scratch(m, (size_t)M)) == COCR_OK) {
-            EpiLogitsArgmax e{logits, m->ncls, F32(P.bdec), m->ncls, m->ctc_lab, m->ctc_val};
-            GemmArgs<T> a{xin, D, WT(P.wdec), D, M, m->ncls, D, 0};
-            GEMM_TRY((launch_ring_cfg<T, 64, 128, 3, EpiLogitsArgmax>(s, a, e)));
-            m->amax_ok = true; m->amax_rows = M;
+// xn <- LN1(x); g2 >= 0: x <- LN1(x), xn <- LN2(x) (a block-final LayerNorm chained with the next block's first); write_f32: x <- LN1(x)
+template <typename T> static int layernorm(const Fwd<T> &c, size_t g1, size_t b1, bool write_f32, long g2, long b2) {
+    ProfScope ps(c.m, c.s, FAM_LN);
+    launch_layernorm<T>(c.s, c.x, c.M, c.D, c.F32(g1), c.F32(b1), write_f32 ? c.x : nullptr, g2 >= 0 ? c.F32((size_t)g2) : nullptr,
+                        b2 >= 0 ? c.F32((size_t)b2) : nullptr, c.xn, c.m->rD);
+    LAUNCH_CHECK();
+    return COCR_OK;
+}
+
+// x <- [x +] alpha (A W^T + bias); then the LayerNorm(s) that follow in the reference (layernorm)
+template <typename T> static int gemm_to_stream(const Fwd<T> &c, int fam, const T *A, int K, size_t w, size_t bias, float alpha, bool resid,
+                                                size_t g1, size_t b1, long g2, long b2) {
+    const int M = c.M, D = c.D;
+    {
+        ProfScope ps(c.m, c.s, fam);
+        if (c.f.rowln) {
+            EpiResidualLN<T, 1> e{c.x, D, c.F32(bias), alpha, D, resid ? 1 : 0, c.F32(g1), c.F32(b1), g2 >= 0 ? c.F32((size_t)g2) : nullptr,
+                                  b2 >= 0 ? c.F32((size_t)b2) : nullptr, c.xn};
+            e.Dn = c.m->rD;
+            GEMM_TRY(launch_gemm_rowln<T>(c.s, A, K, c.WT(w), K, M, D, K, e));
             return COCR_OK;
         }
+        if (resid) { EpiResidual e{c.x, D, c.F32(bias), alpha, D}; GEMM_TRY(launch_gemm<T>(c.s, A, K, c.WT(w), K, M, D, K, e)); }
+        else { EpiStoreF32 e{c.x, D, c.F32(bias), D}; GEMM_TRY(launch_gemm<T>(c.s, A, K, c.WT(w), K, M, D, K, e)); }
+    }
+    return layernorm(c, g1, b1, g2 >= 0, g2, b2);
+}
+
+// ---- the frontend's output linear into the fp32 residual stream, and the first block's first LayerNorm
+template <typename T> static int front_out(const Fwd<T> &c) {
+    cocr_model *m = c.m;
+    const BlobPlan &P = c.P;
+    const FfnW &f0 = P.layers[0].ffn[0];
+    const int Kf = m->feats.back() * m->C, M = c.M, D = c.D;
+    if (c.f.out == OUT_IN_CHAIN) return COCR_OK;                  // (encoder_chains; front.y is tapped there)
+    if (c.f.out == OUT_SPLITK) {
+        float *partial = reinterpret_cast<float *>(c.za);          // the other frontend buffer is free now
+        { ProfScope ps(m, c.s, FAM_FOUT); GEMM_TRY(launch_gemm_splitk<T>(c.s, c.zb, Kf, c.WT(P.wout), Kf, M, D, Kf, COCR_FO_SPLITS, partial)); }
+        ProfScope ps(m, c.s, FAM_LN);
+        hipLaunchKernelGGL((splitk_reduce_ln_kernel<T>), dim3(ceil_div(M, 16)), dim3(256), 0, c.s, partial, COCR_FO_SPLITS, (size_t)M * D, c.F32(P.bout), M, D,
+                           m->rD, c.F32(f0.ln_g), c.F32(f0.ln_b), c.x, c.xn);
+        LAUNCH_CHECK();
+    } else {
+        const int rc = gemm_to_stream(c, FAM_FOUT, c.zb, Kf, P.wout, P.bout, 1.0f, false, f0.ln_g, f0.ln_b, -1, -1);
         if (rc) return rc;
-        EpiStoreF32 e{logits, m->ncls, F32(P.bdec), m->ncls};
-        GEMM_TRY(launch_gemm<T>(s, xin, D, WT(P.wdec), D, M, m->ncls, D, e));
-        m->amax_ok = false;
+    }
+    return c.tap_x(-1, "front.y", c.x);
+}
+
+template <typename T> static int ffn_up(const Fwd<T> &c, const FfnW &fw) {
+    ProfScope ps(c.m, c.s, FAM_FFN_UP);
+    EpiBiasAct<T, ACT_SILU> e{c.hid, c.m->ff, c.F32(fw.b1), c.m->ff};
+    GEMM_TRY(launch_gemm<T>(c.s, c.xn, c.D, c.WT(fw.w1), c.D, c.M, c.m->ff, c.D, e));
+    return COCR_OK;
+}
+// feed-forward module + the LayerNorm(s) that follow it (layernorm)
+template <typename T> static int ffn(const Fwd<T> &c, const FfnW &fw, size_t g1, size_t b1, long g2, long b2) {
+    if constexpr (sizeof(T) == 2) {
+        if (c.f.ffn_fused) {
+            ProfScope ps(c.m, c.s, FAM_FFN_FUSED);
+            EpiResidualLN<T, 1> e{c.x, c.D, c.F32(fw.b2), c.ffr, c.D, 1, c.F32(g1), c.F32(b1), g2 >= 0 ? c.F32((size_t)g2) : nullptr,
+                                  b2 >= 0 ? c.F32((size_t)b2) : nullptr, c.xn};
+            GEMM_TRY(launch_ffn_fused(c.s, (const bf16_t *)c.xn, (const bf16_t *)c.WT(fw.w1), c.F32(fw.b1), (const bf16_t *)c.WT(fw.w2), c.M, c.D, c.m->ff, e));
+            return COCR_OK;
+        }
+    }
+    const int rc = ffn_up(c, fw);
+    return rc ? rc : gemm_to_stream(c, FAM_FFN_DOWN, c.hid, c.m->ff, fw.w2, fw.b2, c.ffr, true, g1, b1, g2, b2);
+}
+
+template <typename T, int DHP> static hipError_t attention_dhp(const Fwd<T> &c, int l, unsigned long long *stamps) {
+    const cocr_model *m = c.m;
+    const LayerW &w = c.P.layers[l];
+    return launch_attention<T, DHP>(c.s, c.N, c.q, c.k, c.v, (const T *)(m->ptab + (size_t)l * m->ptab_stride), c.F32(w.ub), c.F32(w.vb), c.ctx, c.Tn,
+                                    c.Tp, m->heads, m->dh, c.scale, m->pos_maxlen - 1, stamps, m->att_tiled, m->att_resident_min, m->att_resident_long);
+}
+// block l's attention core: ctx <- attention(q, k, v) (launch_attention chooses the kernel)
+template <typename T> static int attention(const Fwd<T> &c, int l, unsigned long long *stamps) {
+    ProfScope ps(c.m, c.s, FAM_ATTN);
+    const int dhp = c.m->dhp;
+    GEMM_TRY((dhp == 32   ? attention_dhp<T, 32>(c, l, stamps)
+              : dhp == 64 ? attention_dhp<T, 64>(c, l, stamps)
+              : dhp == 96 ? attention_dhp<T, 96>(c, l, stamps)
+                          : attention_dhp<T, 128>(c, l, stamps)));
+    return COCR_OK;
+}
+
+template <typename T> static int dwconv(const Fwd<T> &c, const LayerW &w) {
+    ProfScope ps(c.m, c.s, FAM_DW);
+    launch_dwconv<T>(c.s, c.glu, c.N, c.Tn, c.D, c.m->ksz, c.F32(w.dww), c.F32(w.dwb), c.dwo);
+    LAUNCH_CHECK();
+    return COCR_OK;
+}
+
+// ---- encoder, one kernel per product
+template <typename T> static int encoder_products(const Fwd<T> &c) {
+    cocr_model *m = c.m;
+    const hipStream_t s = c.s;
+    const int M = c.M, D = c.D;
+    const size_t MD = (size_t)M * D;
+    int rc;
+    for (int l = 0; l < m->L; ++l) {
+        const LayerW &w = c.P.layers[l];
+        const bool last = l + 1 == m->L;
+        const long g_next = last ? -1 : (long)c.P.layers[l + 1].ffn[0].ln_g, b_next = last ? -1 : (long)c.P.layers[l + 1].ffn[0].ln_b;
+        // FFN, half-step residual (feed_forward.py:45-52, encoder.py:68-75); epilogue: LayerNorm of the attention module
+        if ((rc = ffn(c, w.ffn[0], w.a_ln_g, w.a_ln_b, -1, -1)) || (rc = c.tap_x(l, "ffn1", c.x))) return rc;
+        // MHSA (attention.py:143-151)
+        { ProfScope ps(m, s, FAM_QKV); EpiQKV<T> e{c.q, c.k, c.v, c.F32(w.bqkv), D, m->dh, m->dhp, m->heads, c.Tn, c.Tp, 3 * D}; GEMM_TRY(launch_gemm<T>(s, c.xn, D, c.WT(w.wqkv), D, M, 3 * D, D, e)); }
+        if ((rc = attention(c, l, nullptr)) || (rc = c.tap_qkv(l)) || (rc = c.tap(l, "ctx", c.ctx, MD))) return rc;
+        if ((rc = gemm_to_stream(c, FAM_AOUT, c.ctx, D, w.wo, w.bo, 1.0f, true, w.c_ln_g, w.c_ln_b, -1, -1)) || (rc = c.tap_x(l, "mhsa", c.x))) return rc;
+        // conv module (convolution.py:135-148)
+        { ProfScope ps(m, s, FAM_GLU); EpiGLU<T> e{c.glu, D, c.F32(w.bpw1), 2 * D}; GEMM_TRY(launch_gemm<T>(s, c.xn, D, c.WT(w.wpw1), D, M, 2 * D, D, e)); }
+        if ((rc = dwconv(c, w)) || (rc = c.tap(l, "glu", c.glu, MD)) || (rc = c.tap(l, "dw", c.dwo, MD))) return rc;
+        if ((rc = gemm_to_stream(c, FAM_PW2, c.dwo, D, w.wpw2, w.bpw2, 1.0f, true, w.ffn[1].ln_g, w.ffn[1].ln_b, -1, -1)) || (rc = c.tap_x(l, "conv", c.x))) return rc;
+        // second FFN; its epilogue applies the block-final LayerNorm (encoder.py:99) chained with the next block's first
+        if (!c.f.taps) {
+            if ((rc = ffn(c, w.ffn[1], w.f_ln_g, w.f_ln_b, g_next, b_next))) return rc;
+            continue;
+        }
+        if ((rc = ffn_up(c, w.ffn[1]))) return rc;
+        { ProfScope ps(m, s, FAM_FFN_DOWN); EpiResidual e{c.x, D, c.F32(w.ffn[1].b2), c.ffr, D}; GEMM_TRY(launch_gemm<T>(s, c.hid, m->ff, c.WT(w.ffn[1].w2), m->ff, M, D, m->ff, e)); }
+        if ((rc = c.tap_x(l, "ffn2", c.x)) || (rc = layernorm(c, w.f_ln_g, w.f_ln_b, true, g_next, b_next)) || (rc = c.tap_x(l, "out", c.x))) return rc;
+    }
+    return COCR_OK;
+}
+
+// ---- encoder as row-local chains (rowchain.hip.h, bf16): 3 launches per block (attention core, chain A, chain B).  Debug taps: the
+// TAPS instantiation of the SAME kernels copies what never leaves the chip (or is overwritten inside the launch) into tapbuf; everything
+// else is read from the buffers the launches leave behind.
+template <typename T> static int encoder_chains(const Fwd<T> &c) {
+    cocr_model *m = c.m;
+    const BlobPlan &P = c.P;
+    const int D = c.D, M = c.M;
+    const size_t MD = (size_t)M * D;
+    const bool taps = c.f.taps;
+    int rc;
+    float *tp[4] = {nullptr, nullptr, nullptr, nullptr};
+    bf16_t *tap_dw = nullptr;
+    if (taps) {
+        HIP_TRY(m->tapbuf.grow(MD * 4 + MD / 2));
+        for (int i = 0; i < 4; ++i) tp[i] = m->tapbuf.p + (size_t)i * MD;
+        tap_dw = reinterpret_cast<bf16_t *>(m->tapbuf.p + 4 * MD);
+    }
+    auto CW = [&](size_t off) { return (const bf16_t *)(m->packed + off); };      // chain weights: fragment-major copies (ensure_packed)
+    auto launch = [&](const ChainArgs &a, int fam) -> int {
+        ProfScope ps(m, c.s, fam);
+        GEMM_TRY(D == 256 ? launch_rowchain_256(c.s, a, taps, m->chain_rows) : launch_rowchain_512(c.s, a, taps, m->chain_rows));
         return COCR_OK;
     };
-    if constexpr (sizeof(T) == 2) {
-        if (rowchain_supported(D, ff, dh) && !m->no_chain) {      // (debug taps: the TAPS instantiation of every chain shape)
-            // ---- row-local chains (rowchain.hip.h): 3 launches per block (attention core, chain A, chain B)
-            const unsigned char *CW = m->packed;                 // chain weights: fragment-major copies
-            auto CWT = [&](size_t off) { return (const bf16_t *)(CW + off); };
-            // debug taps: the TAPS instantiation of the SAME kernels copies what never leaves the chip (or is overwritten inside the
-            // launch) into tapbuf; everything else is read from the buffers the launches leave behind
-            const bool taps = m->debug;
-            float *tp[4] = {nullptr, nullptr, nullptr, nullptr};
-            bf16_t *tap_dw = nullptr;
-            if (taps) {
-                if (m->tapbuf_rows < (size_t)M) {
-                    if (m->tapbuf) (void)hipFree(m->tapbuf);
-                    HIP_TRY(hipMalloc((void **)&m->tapbuf, (size_t)M * D * (4 * 4 + 2)));
-                    m->tapbuf_rows = (size_t)M;
-                }
-                for (int i = 0; i < 4; ++i) tp[i] = m->tapbuf + (size_t)i * M * D;
-                tap_dw = reinterpret_cast<bf16_t *>(m->tapbuf + (size_t)4 * M * D);
-            }
-            auto tapx = [&](int l, const char *what, const float *src) -> int { if (l < 0) snprintf(nm, sizeof nm, "%s", what); else snprintf(nm, sizeof nm, "l%d.%s", l, what); return tap<float>(m, s, nm, src, (size_t)M * D); };
-            auto tapb = [&](int l, const char *what, const T *src, size_t n) -> int { snprintf(nm, sizeof nm, "l%d.%s", l, what); return tap<T>(m, s, nm, src, n); };
-            auto tap_qkv = [&](int l) -> int {
-                if (!taps) return COCR_OK;
-                int r;
-                if ((r = tapb(l, "q", q, m->qkv_bytes / sizeof(T))) || (r = tapb(l, "k", k, m->qkv_bytes / sizeof(T))) || (r = tapb(l, "v", v, m->qkv_bytes / sizeof(T)))) return r;
-                return COCR_OK;
-            };
-            auto launch = [&](const ChainArgs &a) { return D == 256 ? launch_rowchain_256(s, a, taps, m->chain_rows) : launch_rowchain_512(s, a, taps, m->chain_rows); };
-            // the fp32 stream between the chain launches: in the kernels' register order (ChainArgs::x_in_blocked); the first launch reads
-            // the row-major stream the frontend's reduction wrote
-            auto base = [&]() { ChainArgs a{}; a.x = x; a.x_in_blocked = 1; a.x_out_blocked = 1; a.xn = (bf16_t *)xn; a.M = M; a.dh = dh; a.dhp = dhp; a.heads = heads; a.T_ = Tn; a.Tp = Tp; a.inv_d = 1.0f / (float)m->rD; a.xcd_order = m->chain_xcd ? 1 : 0;
-                                 a.kd = (m->padded && !m->no_kskip) ? ceil_div(m->rD, 32) : 8; a.kl = (m->padded && !m->no_kskip) ? ((m->rff - 1) % 256) / 32 + 1 : 8; return a; };
-            auto st_rowln = [&](size_t wgt, size_t bias, float alpha, size_t g1, size_t b1) {
-                ChainStage st{}; st.kind = ST_ROWLN; st.W = CWT(wgt); st.bias = F32(bias); st.N = D; st.alpha = alpha;
-                st.g1 = F32(g1); st.b1 = F32(b1); return st; };
-            auto st_ffn = [&](const FfnW &fw, size_t g1, size_t b1, long g2, long b2) {
-                ChainStage st{}; st.kind = ST_FFN; st.W = CWT(fw.w1); st.W2 = CWT(fw.w2); st.bias = F32(fw.b1); st.bias2 = F32(fw.b2);
-                st.N = ff; st.alpha = ffr; st.g1 = F32(g1); st.b1 = F32(b1);      // (W2's fragment-major copy is pre-scaled by ffr: ensure_packed)
-                st.g2 = g2 >= 0 ? F32((size_t)g2) : nullptr; st.b2 = b2 >= 0 ? F32((size_t)b2) : nullptr; return st; };
-            auto st_qkv = [&](const LayerW &lw) {
-                ChainStage st{}; st.kind = ST_QKV; st.W = CWT(lw.wqkv); st.bias = F32(lw.bqkv); st.N = 3 * D;
-                st.q = (bf16_t *)q; st.k = (bf16_t *)k; st.v = (bf16_t *)v; return st; };
-            if (front_in_chain) {   // frontend output linear + first LayerNorm -> first block's FFN -> its q/k/v projection
-                ChainArgs a = base(); a.A0 = (const bf16_t *)zcur; a.nstages = 3; a.x_in_blocked = 0;
-                ChainStage f{}; f.kind = ST_FRONT; f.W = CWT(P.wout); f.bias = F32(P.bout); f.N = D; f.K = F * C; f.alpha = 1.0f;
-                f.g1 = F32(P.layers[0].ffn[0].ln_g); f.b1 = F32(P.layers[0].ffn[0].ln_b);
-                a.st[0] = f;
-                a.st[1] = st_ffn(P.layers[0].ffn[0], P.layers[0].a_ln_g, P.layers[0].a_ln_b, -1, -1); a.st[1].store_x = 1;
-                a.st[2] = st_qkv(P.layers[0]);
-                a.st[0].tap_pre = tp[1]; a.st[1].tap_pre = tp[0];
-                { ProfScope ps(m, s, FAM_CH_FRONT); GEMM_TRY(launch(a)); }
-                if (taps && ((rc = tapx(-1, "front.y", tp[1])) || (rc = tapx(0, "ffn1", tp[0])) || (rc = tap_qkv(0)))) return rc;
-            } else {   // first block's FFN + q/k/v projection on the frontend output
-                ChainArgs a = base(); a.A0 = (const bf16_t *)xn; a.nstages = 2; a.x_in_blocked = 0;
-                a.st[0] = st_ffn(P.layers[0].ffn[0], P.layers[0].a_ln_g, P.layers[0].a_ln_b, -1, -1); a.st[0].store_x = 1;
-                a.st[1] = st_qkv(P.layers[0]);
-                a.st[0].tap_pre = tp[0];
-                { ProfScope ps(m, s, FAM_CH_FIRST); GEMM_TRY(launch(a)); }
-                if (taps && ((rc = tapx(0, "ffn1", tp[0])) || (rc = tap_qkv(0)))) return rc;
-            }
-            if (m->ffn_probe) {
-                // measurement only (COCR_FFN_PROBE=1): block 0's first feed-forward module as a launch of its own on real operands (the
-                // frontend output's first M x D values, the stream the launch above left), results discarded (no store flags) -- so that
-                // rocprofv3's matrix-pipe counters can be read for the FFN products alone (tools/ffn_probe.py, profiles/r03_ffn_probe_*)
-                ChainArgs a = base(); a.A0 = (const bf16_t *)zcur; a.nstages = 1;
-                a.st[0] = st_ffn(P.layers[0].ffn[0], P.layers[0].a_ln_g, P.layers[0].a_ln_b, -1, -1);
-                { ProfScope ps(m, s, FAM_FFN_PROBE); GEMM_TRY(launch(a)); }
-            }
-            for (int l = 0; l < m->L; ++l) {
-                const LayerW &w = P.layers[l];
-                {
-                    ProfScope ps(m, s, FAM_ATTN);
-#define ATTN(DHP) GEMM_TRY((launch_attention<T, DHP>(s, N, q, k, v, (const T *)(m->ptab + (size_t)l * m->ptab_stride), F32(w.ub), F32(w.vb), ctx, Tn, Tp, heads, dh, scale, m->pos_maxlen - 1, (m->stamps && l == 5) ? m->stamps + 192 : nullptr, m->att_tiled, m->att_resident_min, m->att_resident_long)))
-                    if (dhp == 32) ATTN(32); else if (dhp == 64) ATTN(64); else if (dhp == 96) ATTN(96); else ATTN(128);
-#undef ATTN
-                }
-                {   // out-proj + residual + conv-module LayerNorm -> pointwise conv 1 + GLU
-                    ChainArgs a = base(); a.A0 = (const bf16_t *)ctx; a.nstages = 2;
-                    a.st[0] = st_rowln(w.wo, w.bo, 1.0f, w.c_ln_g, w.c_ln_b); a.st[0].store_x = 1;
-                    ChainStage g{}; g.kind = ST_GLU; g.W = CWT(w.wpw1); g.bias = F32(w.bpw1); g.N = 2 * D; g.out = (bf16_t *)glu;
-                    a.st[1] = g;
-                    if (taps && (rc = tapb(l, "ctx", ctx, (size_t)M * D))) return rc;
-                    a.st[0].tap_pre = tp[0];
-                    { ProfScope ps(m, s, FAM_CH_A); GEMM_TRY(launch(a)); }
-                    if (taps && ((rc = tapx(l, "mhsa", tp[0])) || (rc = tapb(l, "glu", glu, (size_t)M * D)))) return rc;
-                }
-                const bool dw_fused = m->ksz == 31 && (!m->no_dw_fuse || taps);      // depthwise conv as the chain's prologue
-                if (!dw_fused) {
-                    ProfScope ps(m, s, FAM_DW);
-                    launch_dwconv<T>(s, glu, N, Tn, D, m->ksz, F32(w.dww), F32(w.dwb), dwo);
-                    LAUNCH_CHECK();
-                }
-                {   // [depthwise conv + BN + SiLU ->] pointwise conv 2 + residual + LayerNorm -> FFN 2 (+ closing LayerNorm [+ next block's]) [-> next block's FFN 1 -> its q/k/v]
-                    ChainArgs a = base(); a.A0 = (const bf16_t *)dwo;
-                    if (dw_fused) { a.dw_in = (const bf16_t *)glu; a.dw_w = F32(w.dww); a.dw_b = F32(w.dwb); a.tap_dw = tap_dw; }
-                    a.st[0] = st_rowln(w.wpw2, w.bpw2, 1.0f, w.ffn[1].ln_g, w.ffn[1].ln_b);
-                    a.st[0].tap_pre = tp[0];
-                    auto tap_common = [&]() -> int {          // the stages every chain B has: depthwise output, stream after the conv module and after FFN 2
-                        int r;
-                        if ((r = tapb(l, "dw", dw_fused ? (const T *)tap_dw : (const T *)dwo, (size_t)M * D)) || (r = tapx(l, "conv", tp[0])) || (r = tapx(l, "ffn2", tp[1]))) return r;
-                        return COCR_OK;
-                    };
-                    if (l + 1 < m->L) {
-                        const LayerW &nx = P.layers[l + 1];
-                        a.st[1] = st_ffn(w.ffn[1], w.f_ln_g, w.f_ln_b, (long)nx.ffn[0].ln_g, (long)nx.ffn[0].ln_b);
-                        a.st[2] = st_ffn(nx.ffn[0], nx.a_ln_g, nx.a_ln_b, -1, -1); a.st[2].store_x = 1;
-                        a.st[3] = st_qkv(nx);
-                        a.nstages = 4;
-                        a.st[1].tap_pre = tp[1]; a.st[1].tap_post = tp[2]; a.st[2].tap_pre = tp[3];
-                        a.stamps = (m->stamps && l == 5) ? m->stamps + 1024 : nullptr;
-                        { ProfScope ps(m, s, FAM_CH_B); GEMM_TRY(launch(a)); }
-                        if (taps && ((rc = tap_common()) || (rc = tapx(l, "out", tp[2])) || (rc = tapx(l + 1, "ffn1", tp[3])) || (rc = tap_qkv(l + 1)))) return rc;
-                    } else {
-                        a.st[1] = st_ffn(w.ffn[1], w.f_ln_g, w.f_ln_b, -1, -1); a.st[1].store_x = 1; a.st[1].store_xn = 1;
-                        a.nstages = 2;
-                        a.st[1].tap_pre = tp[1];
-                        { ProfScope ps(m, s, FAM_CH_LAST); GEMM_TRY(launch(a)); }
-                        // the closing LayerNorm's output exists only as the bf16 decoder operand xn on this path
-                        if (taps && ((rc = tap_common()) || (rc = tapb(l, "out", xn, (size_t)M * D)))) return rc;
-                    }
-                }
-            }
-            return decoder(xn);
-        }
+    // the fp32 stream between the chain launches: in the kernels' register order (ChainArgs::x_in_blocked); the first launch reads
+    // the row-major stream the frontend's reduction wrote
+    auto base = [&](const T *A0, int nstages) {
+        ChainArgs a{}; a.x = c.x; a.x_in_blocked = 1; a.x_out_blocked = 1; a.xn = (bf16_t *)c.xn; a.M = M; a.dh = m->dh; a.dhp = m->dhp; a.heads = m->heads; a.T_ = c.Tn; a.Tp = c.Tp; a.inv_d = 1.0f / (float)m->rD; a.xcd_order = m->chain_xcd ? 1 : 0;
+        a.kd = (m->padded && !m->no_kskip) ? ceil_div(m->rD, 32) : 8; a.kl = (m->padded && !m->no_kskip) ? ((m->rff - 1) % 256) / 32 + 1 : 8;
+        a.A0 = (const bf16_t *)A0; a.nstages = nstages; return a; };
+    auto st_rowln = [&](size_t wgt, size_t bias, float alpha, size_t g1, size_t b1) {
+        ChainStage st{}; st.kind = ST_ROWLN; st.W = CW(wgt); st.bias = c.F32(bias); st.N = D; st.alpha = alpha;
+        st.g1 = c.F32(g1); st.b1 = c.F32(b1); return st; };
+    auto st_ffn = [&](const FfnW &fw, size_t g1, size_t b1, long g2, long b2) {
+        ChainStage st{}; st.kind = ST_FFN; st.W = CW(fw.w1); st.W2 = CW(fw.w2); st.bias = c.F32(fw.b1); st.bias2 = c.F32(fw.b2);
+        st.N = m->ff; st.alpha = c.ffr; st.g1 = c.F32(g1); st.b1 = c.F32(b1);      // (W2's fragment-major copy is pre-scaled by ffr: ensure_packed)
+        st.g2 = g2 >= 0 ? c.F32((size_t)g2) : nullptr; st.b2 = b2 >= 0 ? c.F32((size_t)b2) : nullptr; return st; };
+    auto st_qkv = [&](const LayerW &lw) {
+        ChainStage st{}; st.kind = ST_QKV; st.W = CW(lw.wqkv); st.bias = c.F32(lw.bqkv); st.N = 3 * D;
+        st.q = (bf16_t *)c.q; st.k = (bf16_t *)c.k; st.v = (bf16_t *)c.v; return st; };
+    const LayerW &w0 = P.layers[0];
+    if (c.f.out == OUT_IN_CHAIN) {   // frontend output linear + first LayerNorm -> first block's FFN -> its q/k/v projection
+        ChainArgs a = base(c.zb, 3); a.x_in_blocked = 0;
+        ChainStage f{}; f.kind = ST_FRONT; f.W = CW(P.wout); f.bias = c.F32(P.bout); f.N = D; f.K = m->feats.back() * m->C; f.alpha = 1.0f;
+        f.g1 = c.F32(w0.ffn[0].ln_g); f.b1 = c.F32(w0.ffn[0].ln_b);
+        a.st[0] = f;
+        a.st[1] = st_ffn(w0.ffn[0], w0.a_ln_g, w0.a_ln_b, -1, -1); a.st[1].store_x = 1;
+        a.st[2] = st_qkv(w0);
+        a.st[0].tap_pre = tp[1]; a.st[1].tap_pre = tp[0];
+        if ((rc = launch(a, FAM_CH_FRONT)) || (rc = c.tap_x(-1, "front.y", tp[1])) || (rc = c.tap_x(0, "ffn1", tp[0])) || (rc = c.tap_qkv(0))) return rc;
+    } else {   // first block's FFN + q/k/v projection on the frontend output
+        ChainArgs a = base(c.xn, 2); a.x_in_blocked = 0;
+        a.st[0] = st_ffn(w0.ffn[0], w0.a_ln_g, w0.a_ln_b, -1, -1); a.st[0].store_x = 1;
+        a.st[1] = st_qkv(w0);
+        a.st[0].tap_pre = tp[0];
+        if ((rc = launch(a, FAM_CH_FIRST)) || (rc = c.tap_x(0, "ffn1", tp[0])) || (rc = c.tap_qkv(0))) return rc;
+    }
+    if (m->ffn_probe) {
+        // measurement only (COCR_FFN_PROBE=1): block 0's first feed-forward module as a launch of its own on real operands (the
+        // frontend output's first M x D values, the stream the launch above left), results discarded (no store flags) -- so that
+        // rocprofv3's matrix-pipe counters can be read for the FFN products alone (tools/ffn_probe.py, profiles/r03_ffn_probe_*)
+        ChainArgs a = base(c.zb, 1);
+        a.st[0] = st_ffn(w0.ffn[0], w0.a_ln_g, w0.a_ln_b, -1, -1);
+        if ((rc = launch(a, FAM_FFN_PROBE))) return rc;
     }
     for (int l = 0; l < m->L; ++l) {
         const LayerW &w = P.layers[l];
-        // FFN, half-step residual (feed_forward.py:45-52, encoder.py:68-75); epilogue: LayerNorm of the attention module
-        if ((rc = ffn(w.ffn[0], w.a_ln_g, w.a_ln_b, -1, -1))) return rc;
-        snprintf(nm, sizeof nm, "l%d.ffn1", l); if ((rc = tap<float>(m, s, nm, x, (size_t)M * D))) return rc;
-        // MHSA (attention.py:143-151)
-        { ProfScope ps(m, s, FAM_QKV); EpiQKV<T> e{q, k, v, F32(w.bqkv), D, dh, dhp, heads, Tn, Tp, 3 * D}; GEMM_TRY(launch_gemm<T>(s, xn, D, WT(w.wqkv), D, M, 3 * D, D, e)); }
-        {
-            ProfScope ps(m, s, FAM_ATTN);
-#define ATTN(DHP) GEMM_TRY((launch_attention<T, DHP>(s, N, q, k, v, (const T *)(m->ptab + (size_t)l * m->ptab_stride), F32(w.ub), F32(w.vb), ctx, Tn, Tp, heads, dh, scale, m->pos_maxlen - 1, nullptr, m->att_tiled, m->att_resident_min, m->att_resident_long)))
-            if (dhp == 32) ATTN(32); else if (dhp == 64) ATTN(64); else if (dhp == 96) ATTN(96); else ATTN(128);
-#undef ATTN
+        const bool last = l + 1 == m->L;
+        if ((rc = attention(c, l, (m->stamps && l == 5) ? m->stamps + 192 : nullptr))) return rc;
+        {   // out-proj + residual + conv-module LayerNorm -> pointwise conv 1 + GLU
+            ChainArgs a = base(c.ctx, 2);
+            a.st[0] = st_rowln(w.wo, w.bo, 1.0f, w.c_ln_g, w.c_ln_b); a.st[0].store_x = 1;
+            ChainStage g{}; g.kind = ST_GLU; g.W = CW(w.wpw1); g.bias = c.F32(w.bpw1); g.N = 2 * D; g.out = (bf16_t *)c.glu;
+            a.st[1] = g;
+            a.st[0].tap_pre = tp[0];
+            if ((rc = c.tap(l, "ctx", c.ctx, MD)) || (rc = launch(a, FAM_CH_A)) || (rc = c.tap_x(l, "mhsa", tp[0])) || (rc = c.tap(l, "glu", c.glu, MD))) return rc;
         }
-        if (m->debug) {
-            snprintf(nm, sizeof nm, "l%d.q", l); if ((rc = tap<T>(m, s, nm, q, m->qkv_bytes / sizeof(T)))) return rc;
-            snprintf(nm, sizeof nm, "l%d.k", l); if ((rc = tap<T>(m, s, nm, k, m->qkv_bytes / sizeof(T)))) return rc;
-            snprintf(nm, sizeof nm, "l%d.v", l); if ((rc = tap<T>(m, s, nm, v, m->qkv_bytes / sizeof(T)))) return rc;
-            snprintf(nm, sizeof nm, "l%d.ctx", l); if ((rc = tap<T>(m, s, nm, ctx, (size_t)M * D))) return rc;
-        }
-        if ((rc = gemm_to_stream(FAM_AOUT, ctx, D, w.wo, w.bo, 1.0f, true, w.c_ln_g, w.c_ln_b, -1, -1))) return rc;
-        snprintf(nm, sizeof nm, "l%d.mhsa", l); if ((rc = tap<float>(m, s, nm, x, (size_t)M * D))) return rc;
-        // conv module (convolution.py:135-148)
-        { ProfScope ps(m, s, FAM_GLU); EpiGLU<T> e{glu, D, F32(w.bpw1), 2 * D}; GEMM_TRY(launch_gemm<T>(s, xn, D, WT(w.wpw1), D, M, 2 * D, D, e)); }
-        {
-            ProfScope ps(m, s, FAM_DW);
-            launch_dwconv<T>(s, glu, N, Tn, D, m->ksz, F32(w.dww), F32(w.dwb), dwo);
-            LAUNCH_CHECK();
-        }
-        if (m->debug) {
-            snprintf(nm, sizeof nm, "l%d.glu", l); if ((rc = tap<T>(m, s, nm, glu, (size_t)M * D))) return rc;
-            snprintf(nm, sizeof nm, "l%d.dw", l); if ((rc = tap<T>(m, s, nm, dwo, (size_t)M * D))) return rc;
-        }
-        if ((rc = gemm_to_stream(FAM_PW2, dwo, D, w.wpw2, w.bpw2, 1.0f, true, w.ffn[1].ln_g, w.ffn[1].ln_b, -1, -1))) return rc;
-        snprintf(nm, sizeof nm, "l%d.conv", l); if ((rc = tap<float>(m, s, nm, x, (size_t)M * D))) return rc;
-        // second FFN; its epilogue applies the block-final LayerNorm (encoder.py:99) chained with the next block's first
-        if (m->debug) {
-            // taps want the stream before and after the closing LayerNorm separately: unfused in debug mode
-            { ProfScope ps(m, s, FAM_FFN_UP); EpiBiasAct<T, ACT_SILU> e{hid, ff, F32(w.ffn[1].b1), ff}; GEMM_TRY(launch_gemm<T>(s, xn, D, WT(w.ffn[1].w1), D, M, ff, D, e)); }
-            { ProfScope ps(m, s, FAM_FFN_DOWN); EpiResidual e{x, D, F32(w.ffn[1].b2), ffr, D}; GEMM_TRY(launch_gemm<T>(s, hid, ff, WT(w.ffn[1].w2), ff, M, D, ff, e)); }
-            snprintf(nm, sizeof nm, "l%d.ffn2", l); if ((rc = tap<float>(m, s, nm, x, (size_t)M * D))) return rc;
-            if (l + 1 < m->L) { if ((rc = ln(w.f_ln_g, w.f_ln_b, true, (long)P.layers[l + 1].ffn[0].ln_g, (long)P.layers[l + 1].ffn[0].ln_b))) return rc; }
-            else if ((rc = ln(w.f_ln_g, w.f_ln_b, true, -1, -1))) return rc;
-            snprintf(nm, sizeof nm, "l%d.out", l); if ((rc = tap<float>(m, s, nm, x, (size_t)M * D))) return rc;
-        } else if (l + 1 < m->L) {
+        if (!c.f.dw_fused && (rc = dwconv(c, w))) return rc;
+        // [depthwise conv + BN + SiLU ->] pointwise conv 2 + residual + LayerNorm -> FFN 2 (+ closing LayerNorm [+ next block's]) [-> next block's FFN 1 -> its q/k/v]
+        ChainArgs a = base(c.dwo, 2);
+        if (c.f.dw_fused) { a.dw_in = (const bf16_t *)c.glu; a.dw_w = c.F32(w.dww); a.dw_b = c.F32(w.dwb); a.tap_dw = tap_dw; }
+        a.st[0] = st_rowln(w.wpw2, w.bpw2, 1.0f, w.ffn[1].ln_g, w.ffn[1].ln_b);
+        a.st[0].tap_pre = tp[0];
+        if (!last) {
             const LayerW &nx = P.layers[l + 1];
-            if ((rc = ffn(w.ffn[1], w.f_ln_g, w.f_ln_b, (long)nx.ffn[0].ln_g, (long)nx.ffn[0].ln_b))) return rc;
+            a.st[1] = st_ffn(w.ffn[1], w.f_ln_g, w.f_ln_b, (long)nx.ffn[0].ln_g, (long)nx.ffn[0].ln_b);
+            a.st[2] = st_ffn(nx.ffn[0], nx.a_ln_g, nx.a_ln_b, -1, -1); a.st[2].store_x = 1;
+            a.st[3] = st_qkv(nx);
+            a.nstages = 4;
+            a.st[1].tap_pre = tp[1]; a.st[1].tap_post = tp[2]; a.st[2].tap_pre = tp[3];
+            a.stamps = (m->stamps && l == 5) ? m->stamps + 1024 : nullptr;
+            if ((rc = launch(a, FAM_CH_B))) return rc;
         } else {
-            if ((rc = ffn(w.ffn[1], w.f_ln_g, w.f_ln_b, -1, -1))) return rc;
+            a.st[1] = st_ffn(w.ffn[1], w.f_ln_g, w.f_ln_b, -1, -1); a.st[1].store_x = 1; a.st[1].store_xn = 1;
+            a.st[1].tap_pre = tp[1];
+            if ((rc = launch(a, FAM_CH_LAST))) return rc;
         }
+        // every chain B: the depthwise output, the stream after the conv module and after FFN 2
+        if ((rc = c.tap(l, "dw", c.f.dw_fused ? (const T *)tap_dw : (const T *)c.dwo, MD)) || (rc = c.tap_x(l, "conv", tp[0])) || (rc = c.tap_x(l, "ffn2", tp[1])))
+            return rc;
+        if (!last && ((rc = c.tap_x(l, "out", tp[2])) || (rc = c.tap_x(l + 1, "ffn1", tp[3])) || (rc = c.tap_qkv(l + 1)))) return rc;
+        if (last && (rc = c.tap(l, "out", c.xn, MD))) return rc;     // (the closing LayerNorm's output exists only as the bf16 decoder operand xn here)
     }
-    return decoder(xn);
+    return COCR_OK;
 }
 
-// (Re)builds the fragment-major weight copies the 96-row chain kernels read.  Runs on `s` ahead of the forward's launches
-// (stream order covers a blob import issued on the same stream), never inside a graph capture.
-static bool uses_chain96(const cocr_model *m) {
-    return m->dtype == COCR_BF16 && rowchain_supported(m->D, m->ff, m->dh) && !m->no_chain;
+// ---- decoder nn.Linear (pred.py:90,121): logits fp32.  The argmax form's epilogue also leaves the greedy decoder's per-frame argmax /
+// maximum (ctc_lab / ctc_val): cocr_ctc_greedy on these logits then only merges runs.
+template <typename T> static int decoder(const Fwd<T> &c, float *logits) {
+    cocr_model *m = c.m;
+    const int M = c.M, D = c.D;
+    ProfScope ps(m, c.s, FAM_DEC);
+    if (c.f.argmax) {
+        const int rc = ensure_ctc_scratch(m, (size_t)M);
+        if (rc) return rc;
+        EpiLogitsArgmax e{logits, m->ncls, c.F32(c.P.bdec), m->ncls, m->ctc_lab.p, m->ctc_val.p};
+        GemmArgs<T> a{c.xn, D, c.WT(c.P.wdec), D, M, m->ncls, D, 0};
+        GEMM_TRY((launch_ring_cfg<T, 64, 128, 3, EpiLogitsArgmax>(c.s, a, e)));
+        m->amax_ok = true; m->amax_rows = M;
+        return COCR_OK;
+    }
+    EpiStoreF32 e{logits, m->ncls, c.F32(c.P.bdec), m->ncls};
+    GEMM_TRY(launch_gemm<T>(c.s, c.xn, D, c.WT(c.P.wdec), D, M, m->ncls, D, e));
+    m->amax_ok = false;
+    return COCR_OK;
 }
-static bool uses_frontend96(const cocr_model *m) {
-    return m->dtype == COCR_BF16 && m->snum == 2 && frontend96_supported(m->C, m->feats[0], m->feats[1], m->H) && !m->no_front96;
+
+// frontend -> output linear -> encoder -> decoder, in the form `f`
+template <typename T, typename TIn>
+static int forward_impl(cocr_model *m, const Form &f, const TIn *lines, int N, int W, float *logits, hipStream_t s) {
+    const Fwd<T> c(m, f, N, W, s);
+    // profiling: one EMPTY event pair per forward = the fixed cost of a bracket (record -> record with nothing between), which
+    // bench.py subtracts from every family's average so that the event timings line up with rocprofv3's dispatch durations
+    { ProfScope ps(m, s, FAM_EMPTY); }
+    int rc;
+    if ((rc = frontend<T, TIn>(c, lines)) || (rc = front_out(c))) return rc;
+    if (m->vtN != N || m->vtT != c.Tn) {   // pad dims of q, k, v must read as zero for this shape
+        for (T *p : {c.q, c.k, c.v}) HIP_TRY(hipMemsetAsync(p, 0, m->qkv_bytes, s));
+        m->vtN = N; m->vtT = c.Tn;
+    }
+    if constexpr (sizeof(T) == 2) rc = f.chain ? encoder_chains(c) : encoder_products(c);
+    else rc = encoder_products(c);
+    return rc ? rc : decoder(c, logits);
 }
-static int ensure_packed(cocr_model *m, hipStream_t s) {
-    if ((!uses_chain96(m) && !uses_frontend96(m)) || !m->packed_stale) return COCR_OK;
+
+// (Re)builds the fragment-major weight copies that the form's row chains and fused frontend read.  Runs on `s` ahead of the forward's
+// launches (stream order covers a blob import issued on the same stream), never inside a graph capture.  What it packs does not depend
+// on the batch shape (forward_form).
+static int ensure_packed(cocr_model *m, const Form &f, hipStream_t s) {
+    if ((!f.chain && f.front != FRONT_96) || !m->packed_stale) return COCR_OK;
     if (!m->packed) HIP_TRY(hipMalloc((void **)&m->packed, m->plan.total));
     const int D = m->D, ff = m->ff, C = m->C;
     auto pack = [&](size_t off, int N, int K, float scale = 1.0f) {
@@ -1314,13 +1384,13 @@ static int ensure_packed(cocr_model *m, hipStream_t s) {
                            (bf16_t *)(m->packed + off), N, K, scale);
     };
     const float ffr = m->hp.half_step_residual ? 0.5f : 1.0f;       // the FFN's residual factor rides on the packed copy of its second matrix (exact)
-    if (uses_chain96(m))
+    if (f.chain)
         for (const LayerW &w : m->plan.layers) {
             for (int i = 0; i < 2; ++i) { pack(w.ffn[i].w1, ff, D); pack(w.ffn[i].w2, D, ff, ffr); }
             pack(w.wqkv, 3 * D, D); pack(w.wo, D, D); pack(w.wpw1, 2 * D, D); pack(w.wpw2, D, D);
         }
-    if (uses_chain96(m) && (m->feats[m->snum - 1] * C) % 256 == 0) pack(m->plan.wout, D, m->feats[m->snum - 1] * C);      // the FRONT stage's matrix
-    if (uses_frontend96(m)) {
+    if (f.out == OUT_IN_CHAIN) pack(m->plan.wout, D, m->feats.back() * C);      // the FRONT stage's matrix
+    if (f.front == FRONT_96) {
         pack(m->plan.stages[0].pw_w, C, C);
         const size_t n0 = (size_t)(C / 16) * 64 * 4, n2 = (size_t)(C / 16) * 5 * 64 * 8;
         if (!m->fpack) HIP_TRY(hipMalloc((void **)&m->fpack, (n0 + n2) * sizeof(bf16_t)));
@@ -1329,8 +1399,7 @@ static int ensure_packed(cocr_model *m, hipStream_t s) {
     }
     LAUNCH_CHECK();
     m->packed_stale = false;
-    for (auto &g : m->graphs) (void)hipGraphExecDestroy(g.exec);     // (pointers unchanged, but keep replay and rebuild ordered simply)
-    m->graphs.clear(); m->graph_seen.clear();
+    drop_graphs(m);     // (pointers unchanged, but keep replay and rebuild ordered simply)
     return COCR_OK;
 }
 
@@ -1363,8 +1432,7 @@ static int forward_entry(cocr_model *m, const void *lines, int line_dtype, int N
         cocr_model *root = m->owner ? m->owner : m;      // whose tables these are
         if (Tp64 + 64 > root->pos_maxlen) {
             HIP_TRY(hipDeviceSynchronize());
-            for (auto &g : m->graphs) (void)hipGraphExecDestroy(g.exec);      // captured launches point at the old tables
-            m->graphs.clear(); m->graph_seen.clear();
+            drop_graphs(m);      // captured launches point at the old tables
             if (root->ptab) { (void)hipFree(root->ptab); root->ptab = nullptr; }
             root->pos_maxlen = round_up(Tp64 + 64, 1024);
             root->ptab_stale = true;
@@ -1379,8 +1447,7 @@ static int forward_entry(cocr_model *m, const void *lines, int line_dtype, int N
         if (o->dtype < 0 || !o->blob) return fail(COCR_ESTATE, "the model whose weights this one shares is not finalized");
         HIP_TRY(hipDeviceSynchronize());
         if ((rc = set_engine_dims(m, o->dtype))) return rc;
-        for (auto &g : m->graphs) (void)hipGraphExecDestroy(g.exec);
-        m->graphs.clear(); m->graph_seen.clear();
+        drop_graphs(m);
         free_workspace(m);
         m->plan = make_plan(m, o->dtype);
         m->dtype = o->dtype;
@@ -1393,13 +1460,15 @@ static int forward_entry(cocr_model *m, const void *lines, int line_dtype, int N
     if (in_lens && out_lens)
         for (int i = 0; i < N; ++i) out_lens[i] = cocr_out_len(in_lens[i], m->hp.subsampling_factor);
     hipStream_t s = (hipStream_t)stream;
+    const Form form = forward_form(m, N, W);
     if (m->owner) {
         // shared weights: the derived copies are the owner's; rebuilt (rarely: new weights, longer tables) with the device idle, because
-        // other models that share them run on other streams; then this model's view of the pointers is refreshed
+        // other models that share them run on other streams; then this model's view of the pointers is refreshed.  (The owner packs
+        // what this model's form reads: models that share weights share the switches.)
         cocr_model *o = m->owner;
         if (o->packed_stale || o->ptab_stale) {
             HIP_TRY(hipDeviceSynchronize());
-            if ((rc = ensure_packed(o, s)) || (rc = ensure_ptab(o, s))) return rc;
+            if ((rc = ensure_packed(o, form, s)) || (rc = ensure_ptab(o, s))) return rc;
             HIP_TRY(hipDeviceSynchronize());
             o->wgen++;
         }
@@ -1407,16 +1476,15 @@ static int forward_entry(cocr_model *m, const void *lines, int line_dtype, int N
             m->blob = o->blob; m->packed = o->packed; m->fpack = o->fpack; m->ptab = o->ptab; m->ptab_stride = o->ptab_stride; m->pos_maxlen = o->pos_maxlen;
             m->packed_stale = m->ptab_stale = false;
             m->seen_wgen = o->wgen;
-            for (auto &g : m->graphs) (void)hipGraphExecDestroy(g.exec);      // captured launches may point at moved buffers
-            m->graphs.clear(); m->graph_seen.clear();
+            drop_graphs(m);      // captured launches may point at moved buffers
         }
     } else {
         const bool rebuilt = m->packed_stale || m->ptab_stale;
         if (rebuilt && m->wgen > 1) HIP_TRY(hipDeviceSynchronize());       // (models may share these buffers: cocr_share_weights)
-        if ((rc = ensure_packed(m, s)) || (rc = ensure_ptab(m, s))) return rc;
+        if ((rc = ensure_packed(m, form, s)) || (rc = ensure_ptab(m, s))) return rc;
         if (rebuilt) { m->wgen++; HIP_TRY(hipStreamSynchronize(s)); }
         if (m->seen_wgen != m->wgen) {                  // (a model that shares these buffers may have regrown the tables)
-            if (m->seen_wgen) { for (auto &g : m->graphs) (void)hipGraphExecDestroy(g.exec); m->graphs.clear(); m->graph_seen.clear(); }
+            if (m->seen_wgen) drop_graphs(m);
             m->seen_wgen = m->wgen;
         }
     }
@@ -1424,11 +1492,11 @@ static int forward_entry(cocr_model *m, const void *lines, int line_dtype, int N
     m->lastT = cocr_out_len(W, m->hp.subsampling_factor);
     auto run_on = [&](const void *in, float *out) -> int {
         if (m->dtype == COCR_BF16) {
-            if (line_dtype == COCR_F32) return forward_impl<bf16_t, float>(m, (const float *)in, N, H, W, out, s);
-            if (line_dtype == COCR_U8) return forward_impl<bf16_t, uint8_t>(m, (const uint8_t *)in, N, H, W, out, s);
+            if (line_dtype == COCR_F32) return forward_impl<bf16_t, float>(m, form, (const float *)in, N, W, out, s);
+            if (line_dtype == COCR_U8) return forward_impl<bf16_t, uint8_t>(m, form, (const uint8_t *)in, N, W, out, s);
         } else {
-            if (line_dtype == COCR_F32) return forward_impl<float, float>(m, (const float *)in, N, H, W, out, s);
-            if (line_dtype == COCR_U8) return forward_impl<float, uint8_t>(m, (const uint8_t *)in, N, H, W, out, s);
+            if (line_dtype == COCR_F32) return forward_impl<float, float>(m, form, (const float *)in, N, W, out, s);
+            if (line_dtype == COCR_U8) return forward_impl<float, uint8_t>(m, form, (const uint8_t *)in, N, W, out, s);
         }
         return fail(COCR_EINVAL, "line dtype must be COCR_F32 or COCR_U8");
     };
@@ -1525,35 +1593,24 @@ extern "C" int cocr_collate_lines(const void *const *lines, const int32_t *width
 // COCR_LENS_SLOTS further decode calls of this model (one model = one stream = a handful of calls in flight at most).
 #define COCR_LENS_SLOTS 16
 static int upload_lens(cocr_model *m, const int32_t *lens, int N, hipStream_t s) {
-    if (N > m->lens_cap) {
-        if (m->d_lens) (void)hipFree(m->d_lens);
-        if (m->h_lens) (void)hipHostFree(m->h_lens);
-        HIP_TRY(hipMalloc((void **)&m->d_lens, (size_t)N * 4 * COCR_LENS_SLOTS));
-        HIP_TRY(hipHostMalloc((void **)&m->h_lens, (size_t)N * 4 * COCR_LENS_SLOTS));
-        m->lens_cap = N;
-        m->lens_slot = 0;
-    }
+    HIP_TRY(grow_pair(m->d_lens, m->h_lens, (size_t)N * COCR_LENS_SLOTS));
+    const size_t per = m->d_lens.n / COCR_LENS_SLOTS;          // lengths per slot
     const int slot = m->lens_slot;
     m->lens_slot = (slot + 1) % COCR_LENS_SLOTS;
-    int32_t *h = m->h_lens + (size_t)slot * m->lens_cap;
+    int32_t *h = m->h_lens.p + (size_t)slot * per;
     memcpy(h, lens, (size_t)N * 4);
-    m->d_lens_cur = m->d_lens + (size_t)slot * m->lens_cap;
+    m->d_lens_cur = m->d_lens.p + (size_t)slot * per;
     HIP_TRY(hipMemcpyAsync(m->d_lens_cur, h, (size_t)N * 4, hipMemcpyHostToDevice, s));
     return COCR_OK;
 }
 
 static int ensure_ctc_scratch(cocr_model *m, size_t rows) {
-    if (rows > m->ctc_cap) {
-        HIP_TRY(hipDeviceSynchronize());                      // (captured launches that point at the old scratch are dropped with it)
-        for (auto &g : m->graphs) (void)hipGraphExecDestroy(g.exec);
-        m->graphs.clear(); m->graph_seen.clear();
-        if (m->ctc_lab) (void)hipFree(m->ctc_lab);
-        if (m->ctc_val) (void)hipFree(m->ctc_val);
-        HIP_TRY(hipMalloc((void **)&m->ctc_lab, rows * 4));
-        HIP_TRY(hipMalloc((void **)&m->ctc_val, rows * 4));
-        m->ctc_cap = rows;
-        m->amax_logits = nullptr;
-    }
+    if (rows <= m->ctc_lab.n && rows <= m->ctc_val.n) return COCR_OK;
+    HIP_TRY(hipDeviceSynchronize());                          // (captured launches that point at the old scratch are dropped with it)
+    drop_graphs(m);
+    m->amax_logits = nullptr;
+    HIP_TRY(m->ctc_lab.grow(rows));
+    HIP_TRY(m->ctc_val.grow(rows));
     return COCR_OK;
 }
 
@@ -1571,10 +1628,10 @@ extern "C" int cocr_ctc_greedy(cocr_model *m, const float *logits, int N, int T,
     ProfScope ps(m, s, FAM_GREEDY);
     if (!have_argmax) {
         m->amax_logits = nullptr;                             // the scratch no longer belongs to the last forward's logits
-        hipLaunchKernelGGL(ctc_argmax_kernel, dim3(ceil_div(N * T, 4)), dim3(256), 0, s, logits, T, ncls, N * T, m->d_lens_cur, m->ctc_lab, m->ctc_val);
+        hipLaunchKernelGGL(ctc_argmax_kernel, dim3(ceil_div(N * T, 4)), dim3(256), 0, s, logits, T, ncls, N * T, m->d_lens_cur, m->ctc_lab.p, m->ctc_val.p);
         LAUNCH_CHECK();
     }
-    hipLaunchKernelGGL(ctc_collapse_kernel, dim3(N), dim3(64), (size_t)T * 8, s, T, m->d_lens_cur, m->ctc_lab, m->ctc_val, labels, starts, ends, conf, counts,
+    hipLaunchKernelGGL(ctc_collapse_kernel, dim3(N), dim3(64), (size_t)T * 8, s, T, m->d_lens_cur, m->ctc_lab.p, m->ctc_val.p, labels, starts, ends, conf, counts,
                        max_per_line);
     LAUNCH_CHECK();
     return COCR_OK;
@@ -1594,13 +1651,8 @@ extern "C" int cocr_ctc_beam(cocr_model *m, const float *logits, int N, int T, i
     const int K = std::min(beam + 1, ncls - 1);
     // scratch: back-pointers [N][T][COCR_BEAM_MAX] i32, then log Z [N][T] (exhaustive kernel) or the frame records (fast)
     const size_t need = (size_t)N * T * ((size_t)COCR_BEAM_MAX * 4 + (fast ? (size_t)COCR_BEAM_REC : 4));
-    if (need > m->beam_cap) {
-        if (m->beam_bp) (void)hipFree(m->beam_bp);
-        m->beam_bp = nullptr; m->beam_cap = 0;
-        HIP_TRY(hipMalloc((void **)&m->beam_bp, need));
-        m->beam_cap = need;
-    }
-    int32_t *bp = m->beam_bp;
+    HIP_TRY(m->beam_bp.grow(need));
+    int32_t *bp = reinterpret_cast<int32_t *>(m->beam_bp.p);
     ProfScope ps(m, s, FAM_BEAM);
     if (fast) {
         unsigned char *rec = reinterpret_cast<unsigned char *>(bp + (size_t)N * T * COCR_BEAM_MAX);
@@ -1651,20 +1703,11 @@ extern "C" int cocr_ctc_loss(cocr_model *m, const float *probits, int N, int T, 
     HIP_TRY(hipSetDevice(m->device));
     hipStream_t s = (hipStream_t)stream;
     const size_t ints = (size_t)3 * N + total;
-    if (ints > m->loss_ints) {
-        if (m->loss_d) (void)hipFree(m->loss_d);
-        if (m->loss_h) (void)hipHostFree(m->loss_h);
-        m->loss_d = m->loss_h = nullptr;
-        m->loss_ints = 0;
-        const size_t cap = ints + ints / 2;
-        HIP_TRY(hipMalloc((void **)&m->loss_d, cap * 4 * COCR_LENS_SLOTS));
-        HIP_TRY(hipHostMalloc((void **)&m->loss_h, cap * 4 * COCR_LENS_SLOTS));
-        m->loss_ints = cap;
-        m->loss_slot = 0;
-    }
+    HIP_TRY(grow_pair(m->loss_d, m->loss_h, ints * COCR_LENS_SLOTS, (ints + ints / 2) * COCR_LENS_SLOTS));
+    const size_t per = m->loss_d.n / COCR_LENS_SLOTS;          // ints per slot
     const int slot = m->loss_slot;
     m->loss_slot = (slot + 1) % COCR_LENS_SLOTS;
-    int32_t *h = m->loss_h + (size_t)slot * m->loss_ints, *d = m->loss_d + (size_t)slot * m->loss_ints;
+    int32_t *h = m->loss_h.p + (size_t)slot * per, *d = m->loss_d.p + (size_t)slot * per;
     int32_t off = 0;
     for (int n = 0; n < N; ++n) { h[n] = out_lens[n]; h[N + n] = label_lens[n]; h[2 * N + n] = off; off += label_lens[n]; }
     if (total) memcpy(h + 3 * N, targets, total * 4);
@@ -1672,15 +1715,9 @@ extern "C" int cocr_ctc_loss(cocr_model *m, const float *probits, int N, int T, 
     const int states = 2 * max_l + 1;
     const int sj = states <= 64 ? 1 : states <= 128 ? 2 : states <= 256 ? 4 : 8;
     const size_t need = (size_t)N * T * ((size_t)ncls + 2 * 64 * sj);
-    if (need > m->loss_ws_cap) {
-        if (m->loss_ws) (void)hipFree(m->loss_ws);
-        m->loss_ws = nullptr;
-        m->loss_ws_cap = 0;
-        HIP_TRY(hipMalloc((void **)&m->loss_ws, need * 4));
-        m->loss_ws_cap = need;
-    }
+    HIP_TRY(m->loss_ws.grow(need));
     ProfScope ps(m, s, FAM_LOSS);
-    launch_ctc_loss(s, sj, (size_t)ncls * 4, probits, N, T, ncls, d, d + N, d + 2 * N, d + 3 * N, nll, grad, m->loss_ws, m->loss_ws + (size_t)N * T * ncls);
+    launch_ctc_loss(s, sj, (size_t)ncls * 4, probits, N, T, ncls, d, d + N, d + 2 * N, d + 3 * N, nll, grad, m->loss_ws.p, m->loss_ws.p + (size_t)N * T * ncls);
     LAUNCH_CHECK();
     return COCR_OK;
 }
@@ -1695,28 +1732,17 @@ extern "C" int cocr_decoder_backward(cocr_model *m, const float *grad_probits, i
     hipStream_t s = (hipStream_t)stream;
     const int M = N * T, C = m->ncls, D = m->D, chunks = ceil_div(M, COCR_TR_ROWS);
     const size_t per = (size_t)C * D + C, need = per * chunks;
-    if (need > m->tr_part_cap) {
-        if (m->tr_part) (void)hipFree(m->tr_part);
-        m->tr_part = nullptr;
-        m->tr_part_cap = 0;
-        HIP_TRY(hipMalloc((void **)&m->tr_part, need * 4));
-        m->tr_part_cap = need;
-    }
-    float *part_w = m->tr_part, *part_b = m->tr_part + (size_t)chunks * C * D;
+    HIP_TRY(m->tr_part.grow(need));
+    float *part_w = m->tr_part.p, *part_b = m->tr_part.p + (size_t)chunks * C * D;
     // A padded model (set_engine_dims): the kernels work on the engine's D-wide rows (the padded columns of the encoder output and of
     // the weight are zero, so are their gradients); the caller's tensors have the model's own width rD: strided copies at the boundary.
     const int rD = m->rD;
     float *gw_dst = grad_weight, *go_dst = grad_output;
     if (m->padded) {
         const size_t need_pad = (size_t)C * D + (grad_output ? (size_t)M * D : 0);
-        if (need_pad > m->tr_pad_cap) {
-            if (m->tr_pad) (void)hipFree(m->tr_pad);
-            m->tr_pad = nullptr; m->tr_pad_cap = 0;
-            HIP_TRY(hipMalloc((void **)&m->tr_pad, need_pad * 4));
-            m->tr_pad_cap = need_pad;
-        }
-        gw_dst = m->tr_pad;
-        if (grad_output) go_dst = m->tr_pad + (size_t)C * D;
+        HIP_TRY(m->tr_pad.grow(need_pad));
+        gw_dst = m->tr_pad.p;
+        if (grad_output) go_dst = m->tr_pad.p + (size_t)C * D;
     }
     const dim3 grid(chunks, ceil_div(C, COCR_TR_CT));
     if (m->dtype == COCR_BF16) hipLaunchKernelGGL((decoder_wgrad_kernel<bf16_t>), grid, dim3(256), 0, s, grad_probits, (const bf16_t *)m->xn, M, C, D, part_w, part_b);
@@ -1749,15 +1775,10 @@ extern "C" int cocr_decoder_adamw(cocr_model *m, const float *grad_weight, const
     const size_t nw = (size_t)m->ncls * m->D, nb = (size_t)m->ncls, n = nw + nb, nw_model = (size_t)m->ncls * m->rD;
     const size_t row_e = (size_t)m->D * 4, row_m = (size_t)m->rD * 4;      // engine / model row bytes of the decoder weight (equal unless padded)
     if (m->padded) {    // the caller's (ncls, rD) gradient embedded in the engine's zero-padded rows
-        if (nw > m->tr_pad_cap) {
-            if (m->tr_pad) (void)hipFree(m->tr_pad);
-            m->tr_pad = nullptr; m->tr_pad_cap = 0;
-            HIP_TRY(hipMalloc((void **)&m->tr_pad, nw * 4));
-            m->tr_pad_cap = nw;
-        }
-        HIP_TRY(hipMemsetAsync(m->tr_pad, 0, nw * 4, s));
-        HIP_TRY(hipMemcpy2DAsync(m->tr_pad, row_e, grad_weight, row_m, row_m, m->ncls, hipMemcpyDeviceToDevice, s));
-        grad_weight = m->tr_pad;
+        HIP_TRY(m->tr_pad.grow(nw));
+        HIP_TRY(hipMemsetAsync(m->tr_pad.p, 0, nw * 4, s));
+        HIP_TRY(hipMemcpy2DAsync(m->tr_pad.p, row_e, grad_weight, row_m, row_m, m->ncls, hipMemcpyDeviceToDevice, s));
+        grad_weight = m->tr_pad.p;
     }
     if (!m->tr_state) {
         // fp32 master copy: the state-dict tensors when this rank has them, else (weights received by broadcast) the blob's values
@@ -1843,15 +1864,11 @@ extern "C" int cocr_preproc_lines(cocr_model *m, const uint8_t *pixels, const in
     hipStream_t s = (hipStream_t)stream;
     const size_t lines_b = round_up((int)(lines.size() * sizeof(PreLine)), 256), tab_b = (size_t)round_up((int)(tab.size() * 4), 256);
     const size_t need = lines_b + tab_b + tmp_bytes;
-    if (need > m->pre_cap) {
-        HIP_TRY(hipStreamSynchronize(s));                  // an earlier call on this stream may still read the old buffer
-        if (m->pre_buf) (void)hipFree(m->pre_buf);
-        HIP_TRY(hipMalloc((void **)&m->pre_buf, need + need / 4));
-        m->pre_cap = need + need / 4;
-    }
-    PreLine *d_lines = reinterpret_cast<PreLine *>(m->pre_buf);
-    int *d_tab = reinterpret_cast<int *>(m->pre_buf + lines_b);
-    unsigned char *d_tmp = m->pre_buf + lines_b + tab_b;
+    if (need > m->pre_buf.n) HIP_TRY(hipStreamSynchronize(s));      // an earlier call on this stream may still read the old buffer
+    HIP_TRY(m->pre_buf.grow(need, need + need / 4));
+    PreLine *d_lines = reinterpret_cast<PreLine *>(m->pre_buf.p);
+    int *d_tab = reinterpret_cast<int *>(m->pre_buf.p + lines_b);
+    unsigned char *d_tmp = m->pre_buf.p + lines_b + tab_b;
     HIP_TRY(hipMemcpyAsync(d_lines, lines.data(), lines.size() * sizeof(PreLine), hipMemcpyHostToDevice, s));
     HIP_TRY(hipMemcpyAsync(d_tab, tab.data(), tab.size() * 4, hipMemcpyHostToDevice, s));
     HIP_TRY(hipStreamSynchronize(s));                      // the host tables go out of scope; also orders reuse of pre_buf by the next call
@@ -1926,14 +1943,9 @@ extern "C" int cocr_extract_lines(cocr_model *m, const uint8_t *const *pages, co
     const size_t lines_b = al(lines.size() * sizeof(PageLine)), cols_b = al((size_t)ncols * 32), verts_b = al((size_t)nv * 8),
                  rows_b = al(row_start.size() * 8), thr_b = al((size_t)std::max(nthr, 1ll) * 4);
     const size_t need = lines_b + cols_b + verts_b + rows_b + thr_b;
-    if (need > m->page_cap) {
-        HIP_TRY(hipStreamSynchronize(s));                  // an earlier call on this stream may still read the old buffer
-        if (m->page_buf) (void)hipFree(m->page_buf);
-        m->page_buf = nullptr; m->page_cap = 0;
-        HIP_TRY(hipMalloc((void **)&m->page_buf, need + need / 4));
-        m->page_cap = need + need / 4;
-    }
-    unsigned char *b = m->page_buf;
+    if (need > m->page_buf.n) HIP_TRY(hipStreamSynchronize(s));     // an earlier call on this stream may still read the old buffer
+    HIP_TRY(m->page_buf.grow(need, need + need / 4));
+    unsigned char *b = m->page_buf.p;
     PageLine *d_lines = reinterpret_cast<PageLine *>(b);
     long long *d_cols = reinterpret_cast<long long *>(b + lines_b);
     int *d_verts = reinterpret_cast<int *>(b + lines_b + cols_b);
@@ -2051,8 +2063,7 @@ extern "C" int cocr_set_chain_rows(cocr_model *m, int rows) {
     if (!m) return fail(COCR_EINVAL, "null argument");
     if (rows < 0 || rows > 96) return fail(COCR_EINVAL, "rows per workgroup must be in 0..96");
     if (rows != m->chain_rows) {          // captured launch sequences use the old grid
-        for (auto &g : m->graphs) (void)hipGraphExecDestroy(g.exec);
-        m->graphs.clear(); m->graph_seen.clear();
+        drop_graphs(m);
     }
     m->chain_rows = rows;
     return COCR_OK;

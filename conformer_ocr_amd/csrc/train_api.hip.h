@@ -19,31 +19,28 @@ struct TrainState {
     size_t nparam = 0, ntotal = 0;            // floats: parameters first (the optimizer's range), then buffers (BatchNorm running statistics)
     float *P = nullptr, *G = nullptr, *Mo = nullptr, *Vo = nullptr;
     long step = 0;
-    unsigned char *ws = nullptr;              // activations + scratch of one step
-    size_t ws_bytes = 0;
-    float *pe = nullptr;                      // sinusoid rows for relative positions T-1 ... -(T-1), (2T-1, D)
+    DevBuf<unsigned char> ws;                 // activations + scratch of one step
+    DevBuf<float> pe;                         // sinusoid rows for relative positions T-1 ... -(T-1), (2T-1, D)
     int peT = 0;
     bool matmul_bf16 = false;                 // cocr_train_set_matmul: the Linear / pointwise-conv products on bf16-rounded operands (fp32 accumulate)
-    float *parts = nullptr;                        // partial column sums of the step's deferred finals (k_colsum_final_jobs), bump-allocated per step
-    size_t parts_floats = 0, parts_used = 0;
+    DevBuf<float> parts;                           // partial column sums of the step's deferred finals (k_colsum_final_jobs), bump-allocated per step
+    size_t parts_used = 0;
     std::vector<ColsumJob> jobs;
-    ColsumJob *jobs_host = nullptr, *jobs_dev = nullptr;      // pinned staging + device copy of the job table (COCR_MAX_COLSUM_JOBS entries)
+    DevBuf<ColsumJob> jobs_dev, jobs_host{true};   // device copy + pinned staging of the job table (COCR_MAX_COLSUM_JOBS entries)
     bool no_tn = false;                            // COCR_TRAIN_NO_TN=1 (read at cocr_train_set_matmul): weight gradients on transposed copies (A/B)
-    unsigned char *Xb = nullptr;                   // 'medium': the bf16 copy of every Linear's input (rows zero-padded to the weight-gradient product's depth), written by the
-    size_t Xb_bytes = 0, Xb_used = 0;              // forward, read by the backward as a K-major operand (gemm_tn_kernel): bump-allocated per step, offsets by weight name
+    DevBuf<unsigned char> Xb;                      // 'medium': the bf16 copy of every Linear's input (rows zero-padded to the weight-gradient product's depth), written by the
+    size_t Xb_used = 0;                            // forward, read by the backward as a K-major operand (gemm_tn_kernel): bump-allocated per step, offsets by weight name
     std::map<std::string, size_t> Xb_off;
-    unsigned char *Wb = nullptr, *WTb = nullptr;   // 'medium': bf16 copies of every Linear weight (N, K) and of its transpose (K, N), written by the forward, read by the
+    DevBuf<unsigned char> Wb, WTb;                 // 'medium': bf16 copies of every Linear weight (N, K) and of its transpose (K, N), written by the forward, read by the
                                               // backward (byte offset of a tensor = its float offset x 4: 16-byte aligned like the fp32 tensors)
 };
 
 static void train_free(cocr_model *m) {
     TrainState *t = m->train;
     if (!t) return;
-    for (void *p : {(void *)t->P, (void *)t->G, (void *)t->Mo, (void *)t->Vo, (void *)t->ws, (void *)t->pe, (void *)t->Wb, (void *)t->WTb, (void *)t->Xb, (void *)t->parts,
-                    (void *)t->jobs_dev})
+    for (void *p : {(void *)t->P, (void *)t->G, (void *)t->Mo, (void *)t->Vo})
         if (p) (void)hipFree(p);
-    if (t->jobs_host) (void)hipHostFree(t->jobs_host);
-    delete t;
+    delete t;                                     // (its scratch buffers release themselves)
     m->train = nullptr;
 }
 
@@ -55,10 +52,10 @@ extern "C" int cocr_train_set_matmul(cocr_model *m, int bf16_operands) {
     TrainState *t = m->train;
     t->matmul_bf16 = bf16_operands != 0;
     { const char *e = getenv("COCR_TRAIN_NO_TN"); t->no_tn = e && e[0] == '1'; }
-    if (t->matmul_bf16 && !t->Wb) {
+    if (t->matmul_bf16) {
         HIP_TRY(hipSetDevice(m->device));
-        HIP_TRY(hipMalloc((void **)&t->Wb, t->nparam * 4 + 256));
-        HIP_TRY(hipMalloc((void **)&t->WTb, t->nparam * 4 + 256));
+        HIP_TRY(t->Wb.grow(t->nparam * 4 + 256));
+        HIP_TRY(t->WTb.grow(t->nparam * 4 + 256));
     }
     return COCR_OK;
 }
@@ -251,17 +248,9 @@ extern "C" int cocr_train_step(cocr_model *m, const void *lines, int line_dtype,
     const size_t oSplit = rsv(split_floats), oLinePart = rsv((size_t)N * std::max((size_t)R * D, (size_t)ceil_div(T, COCR_DW_WC) * D * K));
     {   // deferred column-sum finals: at most 12 jobs per block + the frontend's and the decoder's, each up to ceil(M / 32) x (widest matrix) partial sums
         const size_t pf = (size_t)(12 * L + 16) * (size_t)ceil_div(M, 32) * (size_t)std::max(wide, 2 * D) + 4096;
-        if (pf > t->parts_floats) {
-            HIP_TRY(hipDeviceSynchronize());
-            if (t->parts) (void)hipFree(t->parts);
-            t->parts = nullptr; t->parts_floats = 0;
-            HIP_TRY(hipMalloc((void **)&t->parts, pf * 4));
-            t->parts_floats = pf;
-        }
-        if (!t->jobs_host) {
-            HIP_TRY(hipHostMalloc((void **)&t->jobs_host, COCR_MAX_COLSUM_JOBS * sizeof(ColsumJob)));
-            HIP_TRY(hipMalloc((void **)&t->jobs_dev, COCR_MAX_COLSUM_JOBS * sizeof(ColsumJob)));
-        }
+        if (pf > t->parts.n) HIP_TRY(hipDeviceSynchronize());
+        HIP_TRY(t->parts.grow(pf));
+        HIP_TRY(grow_pair(t->jobs_dev, t->jobs_host, COCR_MAX_COLSUM_JOBS));
         t->parts_used = 0;
         t->jobs.clear();
     }
@@ -270,24 +259,14 @@ extern "C" int cocr_train_step(cocr_model *m, const void *lines, int line_dtype,
         const size_t pad = 2048;
         size_t elems = (size_t)L * ((M + pad) * (size_t)(2 * (D + ff) + 6 * D) + (R + pad) * (size_t)D) + (size_t)snum * (big_rows + pad) * C + (M + pad) * ((size_t)C * F + D);
         const size_t bytes = elems * 2 + (size_t)(8 * L + 16) * 256;
-        if (bytes > t->Xb_bytes) {
-            HIP_TRY(hipDeviceSynchronize());
-            if (t->Xb) (void)hipFree(t->Xb);
-            t->Xb = nullptr; t->Xb_bytes = 0;
-            HIP_TRY(hipMalloc((void **)&t->Xb, bytes));
-            t->Xb_bytes = bytes;
-        }
+        if (bytes > t->Xb.n) HIP_TRY(hipDeviceSynchronize());
+        HIP_TRY(t->Xb.grow(bytes));
         t->Xb_used = 0;
         t->Xb_off.clear();
     }
-    if (need > t->ws_bytes) {
-        HIP_TRY(hipDeviceSynchronize());
-        if (t->ws) (void)hipFree(t->ws);
-        t->ws = nullptr; t->ws_bytes = 0;
-        HIP_TRY(hipMalloc((void **)&t->ws, need));
-        t->ws_bytes = need;
-    }
-    auto WS = [&](size_t off) { return reinterpret_cast<float *>(t->ws + off); };
+    if (need > t->ws.n) HIP_TRY(hipDeviceSynchronize());
+    HIP_TRY(t->ws.grow(need));
+    auto WS = [&](size_t off) { return reinterpret_cast<float *>(t->ws.p + off); };
     auto Pp = [&](const std::string &n) -> float * { return t->P + t->idx.at(n).off; };
     auto Gp = [&](const std::string &n) -> float * { return t->G + t->idx.at(n).off; };
     auto grid1 = [](size_t n) { return dim3((unsigned)std::min<size_t>((n + 255) / 256, 8192)); };
@@ -298,7 +277,7 @@ extern "C" int cocr_train_step(cocr_model *m, const void *lines, int line_dtype,
     // 'medium' matmul precision (cocr_train_set_matmul; the reference trains under torch.set_float32_matmul_precision('medium'),
     // cli/train.py:252): both operands rounded to bf16, products on the bf16 matrix cores, fp32 accumulation and output
     auto to_bf16 = [&](const float *in, size_t off, size_t n) -> const bf16_t * {
-        bf16_t *dst = reinterpret_cast<bf16_t *>(t->ws + off);
+        bf16_t *dst = reinterpret_cast<bf16_t *>(t->ws.p + off);
         hipLaunchKernelGGL(k_f32_to_bf16, grid1((n + 3) / 4), dim3(256), 0, s, in, dst, (n + 3) / 4);
         return dst;
     };
@@ -339,8 +318,8 @@ extern "C" int cocr_train_step(cocr_model *m, const void *lines, int line_dtype,
     // backward pass) runs them all in one launch.
     auto part_alloc = [&](size_t n) -> float * {
         n = (n + 63) / 64 * 64;
-        if (t->parts_used + n > t->parts_floats || t->jobs.size() + 2 > COCR_MAX_COLSUM_JOBS) return nullptr;
-        float *p0 = t->parts + t->parts_used;
+        if (t->parts_used + n > t->parts.n || t->jobs.size() + 2 > COCR_MAX_COLSUM_JOBS) return nullptr;
+        float *p0 = t->parts.p + t->parts_used;
         t->parts_used += n;
         return p0;
     };
@@ -348,13 +327,14 @@ extern "C" int cocr_train_step(cocr_model *m, const void *lines, int line_dtype,
         const int fb = t->jobs.empty() ? 0 : t->jobs.back().first_block + ceil_div(t->jobs.back().N, 64);
         t->jobs.push_back(ColsumJob{part, out, stride, chunks, Nc, fb});
     };
-    auto flush_finals = [&]() {
-        if (t->jobs.empty()) return;
+    auto flush_finals = [&]() -> int {
+        if (t->jobs.empty()) return COCR_OK;
         const int total = t->jobs.back().first_block + ceil_div(t->jobs.back().N, 64);
-        memcpy(t->jobs_host, t->jobs.data(), t->jobs.size() * sizeof(ColsumJob));
-        (void)hipMemcpyAsync(t->jobs_dev, t->jobs_host, t->jobs.size() * sizeof(ColsumJob), hipMemcpyHostToDevice, s);
-        hipLaunchKernelGGL(k_colsum_final_jobs, dim3(total), dim3(256), 0, s, t->jobs_dev, (int)t->jobs.size());
+        memcpy(t->jobs_host.p, t->jobs.data(), t->jobs.size() * sizeof(ColsumJob));
+        HIP_TRY(hipMemcpyAsync(t->jobs_dev.p, t->jobs_host.p, t->jobs.size() * sizeof(ColsumJob), hipMemcpyHostToDevice, s));
+        hipLaunchKernelGGL(k_colsum_final_jobs, dim3(total), dim3(256), 0, s, t->jobs_dev.p, (int)t->jobs.size());
         t->jobs.clear();
+        return COCR_OK;
     };
     auto colsum = [&](const float *a, const float *b, int Mr, int Nc, float *out, int accumulate) {
         const int rows = colsum_chunk_rows(Mr), chunks = ceil_div(Mr, rows);
@@ -377,10 +357,10 @@ extern "C" int cocr_train_step(cocr_model *m, const void *lines, int line_dtype,
     size_t last_xo = 0;
     // Y (rows, Nc) = X (rows, Kr) W(Nc, Kr)^T + b
     auto lin_fwd = [&](const float *X, const std::string &w, const std::string &b, int rows, int Nc, int Kr, float *Y) -> int {
-        if (t->matmul_bf16 && t->Wb && Nc % 8 == 0 && Kr % 8 == 0) {
+        if (t->matmul_bf16 && t->Wb.p && t->WTb.p && Nc % 8 == 0 && Kr % 8 == 0) {
             // 'medium': the weight's bf16 copy AND its bf16 transpose (the input-gradient product's operand) in one pass, kept for the backward
             const size_t wo = t->idx.at(w).off * 4;
-            bf16_t *Wb = reinterpret_cast<bf16_t *>(t->Wb + wo), *WT = reinterpret_cast<bf16_t *>(t->WTb + wo);
+            bf16_t *Wb = reinterpret_cast<bf16_t *>(t->Wb.p + wo), *WT = reinterpret_cast<bf16_t *>(t->WTb.p + wo);
             hipLaunchKernelGGL(k_transpose_bf16, dim3(ceil_div(Kr, 32), ceil_div(Nc, 32)), dim3(256), 0, s, Pp(w), WT, Wb, nullptr, Nc, Kr, Nc);
             // the input's bf16 copy is kept for the backward (K-major operand of dW = dY^T X: rows zero-padded to that product's depth)
             const int rp = round_up(rows, 64 * wg_splits(Nc, Kr));
@@ -388,10 +368,10 @@ extern "C" int cocr_train_step(cocr_model *m, const void *lines, int line_dtype,
             if (X == last_x && rows == last_rows && Kr == last_k && rp <= last_rp) {
                 // the same input as the Linear just before (the query / key / value projections read one LayerNorm output): one copy serves both
                 t->Xb_off[w] = last_xo;
-                Ab = reinterpret_cast<bf16_t *>(t->Xb + last_xo);
+                Ab = reinterpret_cast<bf16_t *>(t->Xb.p + last_xo);
             } else {
                 const size_t xo = t->Xb_used, xbytes = ((size_t)rp * Kr * 2 + 255) / 256 * 256;
-                if (xo + xbytes > t->Xb_bytes) {
+                if (xo + xbytes > t->Xb.n) {
                     // (the arena's size is an estimate over the model's Linears: a shape it did not foresee keeps no copy -- the backward
                     // of this Linear then converts and transposes its operands itself, as before gemm_tn_kernel)
                     t->Xb_off.erase(w);
@@ -403,7 +383,7 @@ extern "C" int cocr_train_step(cocr_model *m, const void *lines, int line_dtype,
                 }
                 t->Xb_used += xbytes;
                 t->Xb_off[w] = xo;
-                Ab = reinterpret_cast<bf16_t *>(t->Xb + xo);
+                Ab = reinterpret_cast<bf16_t *>(t->Xb.p + xo);
                 hipLaunchKernelGGL(k_rows_bf16, dim3(ceil_div(Kr, 256), ceil_div(rp, 32)), dim3(256), 0, s, X, Ab, nullptr, rows, Kr, rp);
                 last_x = X; last_rows = rows; last_k = Kr; last_rp = rp; last_xo = xo;
             }
@@ -417,20 +397,20 @@ extern "C" int cocr_train_step(cocr_model *m, const void *lines, int line_dtype,
     auto lin_bwd = [&](const float *dY, const float *X, const std::string &w, const std::string &b, int rows, int Nc, int Kr, float *dX) -> int {
         const int splits = wg_splits(Nc, Kr), rp = round_up(rows, (t->matmul_bf16 ? 64 : 32) * splits);
         int r;
-        if (t->matmul_bf16 && t->Wb && Nc % 8 == 0 && Kr % 8 == 0) {
+        if (t->matmul_bf16 && t->Wb.p && t->WTb.p && Nc % 8 == 0 && Kr % 8 == 0) {
             // 'medium': dY is read ONCE in fp32 and leaves as the bf16 row-major copy both products take (k_rows_bf16: rows zero-padded to the
             // weight-gradient product's depth, the bias gradient's partial sums on the way); X's copy is the forward's; the weight gradient
             // dW = dY^T X reads both K-major (gemm_tn_kernel: no transposed copies), the input gradient takes the forward's W^T.
             bf16_t *dYR = reinterpret_cast<bf16_t *>(WS(oTA));
             const auto xit = t->Xb_off.find(w);
             const bool have_x = xit != t->Xb_off.end();          // (no copy kept: the forward's arena was full)
-            const bf16_t *XR = have_x ? reinterpret_cast<const bf16_t *>(t->Xb + xit->second) : nullptr;
-            const bf16_t *WT = reinterpret_cast<const bf16_t *>(t->WTb + t->idx.at(w).off * 4);          // written by lin_fwd of this step
+            const bf16_t *XR = have_x ? reinterpret_cast<const bf16_t *>(t->Xb.p + xit->second) : nullptr;
+            const bf16_t *WT = reinterpret_cast<const bf16_t *>(t->WTb.p + t->idx.at(w).off * 4);          // written by lin_fwd of this step
             float *bpart = (!b.empty() && colsum_chunk_rows(rows) == 32 && ((uintptr_t)Gp(b) & 15) == 0) ? part_alloc((size_t)ceil_div(rows, 32) * Nc) : nullptr;
             const bool fuse_bias = bpart != nullptr;
             if (t->no_tn || !have_x) {
                 // COCR_TRAIN_NO_TN=1 (A/B of the test): the weight-gradient product on transposed bf16 copies, as before gemm_tn_kernel existed
-                bf16_t *dYT = reinterpret_cast<bf16_t *>(t->ws + oBfA), *XT = reinterpret_cast<bf16_t *>(t->ws + oBfW);
+                bf16_t *dYT = reinterpret_cast<bf16_t *>(t->ws.p + oBfA), *XT = reinterpret_cast<bf16_t *>(t->ws.p + oBfW);
                 hipLaunchKernelGGL(k_transpose_bf16, dim3(ceil_div(Nc, 32), ceil_div(rp, 32)), dim3(256), 0, s, dY, dYT, dX ? dYR : nullptr, bpart, rows, Nc, rp);
                 hipLaunchKernelGGL(k_transpose_bf16, dim3(ceil_div(Kr, 32), ceil_div(rp, 32)), dim3(256), 0, s, X, XT, nullptr, nullptr, rows, Kr, rp);
                 if (splits == 1) {
@@ -500,8 +480,8 @@ extern "C" int cocr_train_step(cocr_model *m, const void *lines, int line_dtype,
 
     // ---- positional rows PE(p), p = T-1 ... -(T-1) (embedding.py:35-56,66), cached per T
     if (t->peT != T) {
-        if (t->pe) (void)hipFree(t->pe);
-        t->pe = nullptr;
+        t->peT = 0;                                   // (until the new rows are in place)
+        t->pe.release();
         std::vector<float> pe((size_t)R * D);
         for (int r = 0; r < R; ++r) {
             const float pos = (float)(T - 1 - r);
@@ -511,8 +491,8 @@ extern "C" int cocr_train_step(cocr_model *m, const void *lines, int line_dtype,
                 if (i + 1 < D) pe[(size_t)r * D + i + 1] = cosf(pos * div);
             }
         }
-        HIP_TRY(hipMalloc((void **)&t->pe, pe.size() * 4));
-        HIP_TRY(hipMemcpy(t->pe, pe.data(), pe.size() * 4, hipMemcpyHostToDevice));
+        HIP_TRY(t->pe.grow(pe.size()));
+        HIP_TRY(hipMemcpy(t->pe.p, pe.data(), pe.size() * 4, hipMemcpyHostToDevice));
         t->peT = T;
     }
     HIP_TRY(hipMemsetAsync(t->G, 0, t->nparam * 4, s));
@@ -564,7 +544,7 @@ extern "C" int cocr_train_step(cocr_model *m, const void *lines, int line_dtype,
         if ((rc = lin_fwd(WS(a.xn2), key(l, "1.module.attention.query_proj.linear.weight"), key(l, "1.module.attention.query_proj.linear.bias"), M, D, D, WS(a.q)))) return rc;
         if ((rc = lin_fwd(WS(a.xn2), key(l, "1.module.attention.key_proj.linear.weight"), key(l, "1.module.attention.key_proj.linear.bias"), M, D, D, WS(a.k)))) return rc;
         if ((rc = lin_fwd(WS(a.xn2), key(l, "1.module.attention.value_proj.linear.weight"), key(l, "1.module.attention.value_proj.linear.bias"), M, D, D, WS(a.v)))) return rc;
-        if ((rc = lin_fwd(t->pe, key(l, "1.module.attention.pos_proj.linear.weight"), "", R, D, D, WS(a.P)))) return rc;
+        if ((rc = lin_fwd(t->pe.p, key(l, "1.module.attention.pos_proj.linear.weight"), "", R, D, D, WS(a.P)))) return rc;
         if (attn_gemm) {
             hipLaunchKernelGGL(k_attn_qu_qv, grid1(MD), dim3(256), 0, s, WS(a.q), Pp(key(l, "1.module.attention.u_bias")), Pp(key(l, "1.module.attention.v_bias")),
                                WS(oQu), WS(oQv), MD, D);
@@ -731,7 +711,7 @@ extern "C" int cocr_train_step(cocr_model *m, const void *lines, int line_dtype,
             colsum_grad(dvb_part, M, D, Gp(key(l, "1.module.attention.v_bias")));
             hipLaunchKernelGGL(k_axpy, grid1(MD), dim3(256), 0, s, du_part, dvb_part, 1.0f, MD);                 // d q
             // pos_proj weight: P = PE Wpos^T  ->  d Wpos = dP^T PE
-            if ((rc = lin_bwd(WS(oDP), t->pe, key(l, "1.module.attention.pos_proj.linear.weight"), "", R, D, D, nullptr))) return rc;
+            if ((rc = lin_bwd(WS(oDP), t->pe.p, key(l, "1.module.attention.pos_proj.linear.weight"), "", R, D, D, nullptr))) return rc;
             float *dxn = WS(oDc);
             if ((rc = lin_bwd(du_part, WS(a.xn2), key(l, "1.module.attention.query_proj.linear.weight"), key(l, "1.module.attention.query_proj.linear.bias"), M, D, D, dxn))) return rc;
             if ((rc = lin_bwd(WS(oDe), WS(a.xn2), key(l, "1.module.attention.key_proj.linear.weight"), key(l, "1.module.attention.key_proj.linear.bias"), M, D, D, WS(oDwide2)))) return rc;
@@ -770,7 +750,7 @@ extern "C" int cocr_train_step(cocr_model *m, const void *lines, int line_dtype,
         hipLaunchKernelGGL(k_conv_w_final, dim3(ceil_div(C * 10, 64)), dim3(256), 0, s, WS(oPart), chunks, C, Gp("encoder.conv_subsample.conv.0.weight"),
                            Gp("encoder.conv_subsample.conv.0.bias"));
     }
-    flush_finals();
+    if ((rc = flush_finals())) return rc;
     LAUNCH_CHECK();
     return COCR_OK;
 }
