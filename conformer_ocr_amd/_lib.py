@@ -63,6 +63,8 @@ SYMBOLS = {
     'cocr_extract_lines': (_I, [_P, C.POINTER(_P), _I32P, _I, _I32P, _I32P, C.POINTER(C.c_int64), _I32P, _I32P, _I, _I, _P,
                                 C.POINTER(C.c_int64), _P]),
     'cocr_augment_lines': (_I, [_P, _P, _P, _I, _I, _I, _I32P, _P, _P, _I, _P]),
+    'cocr_edit_align': (_I, [_P, _P, C.POINTER(C.c_int64), _P, C.POINTER(C.c_int64), _I, _P, _P, _P, _P]),
+    'cocr_edit_align_lds': (C.c_int64, [_P, _I, _I]),
     'cocr_set_graph': (_I, [_P, _I]),
     'cocr_set_chain_rows': (_I, [_P, _I]),
     'cocr_set_debug': (_I, [_P, _I]),

@@ -220,14 +220,25 @@ class GroundTruthDataset:
                    'target_lens': torch.tensor([len(t) for t in labels], dtype=torch.int64)}
 
     # ---- validation ---------------------------------------------------------------------------------------------------------
-    def validate(self, net) -> float:
-        """CER of `net.predict_string` on the validation lines (cached strips, no augmentation) against their normalised text."""
+    def validate(self, net, scorer: Optional[str] = None) -> float:
+        """CER of `net.predict_string` on the validation lines (cached strips, no augmentation) against their normalised text; the
+        strings are scored in one call at the end (`scorer`: see `evaluate.score_strings`)."""
         import torch
+        from . import score as _score
         from .evaluate import ErrorRate
         vi = np.arange(self.n_train, len(self.lines))
-        er = ErrorRate()
+        preds: List[str] = []
+        refs: List[str] = []
         for width, idx in make_batches([int(self.widths[i]) for i in vi], self.batch_size, self.edge):
             lines = vi[idx]
             im, lens = self._images(lines, width)
-            er.update(net.predict_string(im.unsqueeze(1), torch.from_numpy(lens.astype(np.int64))), [self.lines[i].text for i in lines])
+            preds.extend(net.predict_string(im.unsqueeze(1), torch.from_numpy(lens.astype(np.int64))))
+            refs.extend(self.lines[i].text for i in lines)
+        if _score.use_device(scorer, getattr(net, '_engine', None)):
+            a, a_offs = _score.pack(refs)
+            b, b_offs = _score.pack(preds)
+            counts, _, _ = _score.align_pairs(net._engine, a, a_offs, b, b_offs)
+            return int(counts[:, 0].sum()) / max(int(a_offs[-1]), 1)
+        er = ErrorRate()
+        er.update(preds, refs)
         return er.compute()

@@ -477,6 +477,67 @@ class HipRecognizer:
                                                    C.c_void_p(d_grid.data_ptr()), int(grid.shape[1]), _stream_ptr(self.device)))
         return out
 
+    # ---- scoring (include/cocr.h: cocr_edit_align) ---------------------------------------------------------------------------
+    def edit_align_lds(self, len_a: int, len_b: int) -> int:
+        """Bytes of LDS a pair of these lengths takes when its op-code table lives in LDS; 0: the table goes to the global workspace."""
+        return int(_lib.check(self.lib.cocr_edit_align_lds(self._h, int(len_a), int(len_b))))
+
+    def _score_pinned(self, name: str, nbytes: int) -> torch.Tensor:
+        buf = self._pinned.get(name)
+        if buf is None or buf.numel() < nbytes:
+            buf = self._pinned[name] = torch.empty(max(1 << 16, nbytes + nbytes // 2), dtype=torch.uint8).pin_memory()
+        return buf
+
+    def edit_align(self, a: np.ndarray, a_offs: np.ndarray, b: np.ndarray, b_offs: np.ndarray, want_ops: bool = False
+                   ) -> Tuple[np.ndarray, Optional[np.ndarray], Optional[np.ndarray]]:
+        """Edit-distance alignment of P packed pairs of int32 symbol sequences (a = ground truth, b = prediction; `*_offs` P + 1 int64
+        offsets starting at 0) with `evaluate.global_align`'s definition.  Returns counts (P, 4) int32 = (distance, insertions,
+        deletions, substitutions) and, with `want_ops`, the raw op buffer (sum of len_a + len_b bytes) and ops_len (P): pair p's
+        alignment (0 equal, 1 substitution, 2 deletion, 3 insertion, forward order) is the LAST ops_len[p] bytes of its slot
+        [a_offs[p] + b_offs[p], a_offs[p+1] + b_offs[p+1]).  The packed sequences go up through pinned staging with non-blocking
+        copies, the results come back the same way; the call returns when they have arrived.  ValueError before any launch for a
+        sequence of more than 4096 symbols or malformed offsets."""
+        ao = np.ascontiguousarray(np.asarray(a_offs, dtype=np.int64).reshape(-1))
+        bo = np.ascontiguousarray(np.asarray(b_offs, dtype=np.int64).reshape(-1))
+        if ao.shape[0] < 1 or ao.shape != bo.shape or ao[0] != 0 or bo[0] != 0:
+            raise ValueError('a_offs and b_offs hold P + 1 offsets each, starting at 0')
+        P = ao.shape[0] - 1
+        a = np.ascontiguousarray(np.asarray(a, dtype=np.int32).reshape(-1))
+        b = np.ascontiguousarray(np.asarray(b, dtype=np.int32).reshape(-1))
+        if a.shape[0] != ao[-1] or b.shape[0] != bo[-1]:
+            raise ValueError('the last offsets must equal the lengths of a and b')
+        if P == 0:
+            return np.zeros((0, 4), dtype=np.int32), (np.zeros(0, dtype=np.uint8) if want_ops else None), \
+                (np.zeros(0, dtype=np.int32) if want_ops else None)
+        na, nb = a.shape[0], b.shape[0]
+        nops = (na + nb) if want_ops else 0
+        i64p = C.POINTER(C.c_int64)
+        with torch.cuda.device(self.device):
+            stream = torch.cuda.current_stream(self.device)
+            h_in = self._score_pinned('score_in', (na + nb) * 4 + 16)
+            sym = h_in[:(na + nb) * 4].view(torch.int32).numpy()
+            sym[:na] = a
+            sym[na:] = b
+            d_in = h_in[:(na + nb) * 4 + 16].to(self.device, non_blocking=True)
+            # [counts (P, 4) | ops_len (P) | ops]: one buffer, one copy back
+            out_bytes = 20 * P + nops
+            d_out = torch.empty(out_bytes + 16, dtype=torch.uint8, device=self.device)
+            base = d_out.data_ptr()
+            _lib.check(self.lib.cocr_edit_align(self._h, C.c_void_p(d_in.data_ptr()), ao.ctypes.data_as(i64p),
+                                                C.c_void_p(d_in.data_ptr() + 4 * na), bo.ctypes.data_as(i64p), P, C.c_void_p(base),
+                                                C.c_void_p(base + 20 * P) if want_ops else None,
+                                                C.c_void_p(base + 16 * P) if want_ops else None, C.c_void_p(stream.cuda_stream)))
+            h_out = self._score_pinned('score_out', out_bytes)
+            h_out[:out_bytes].copy_(d_out[:out_bytes], non_blocking=True)
+            ev = torch.cuda.Event()
+            ev.record(stream)
+            ev.synchronize()
+        res = h_out[:out_bytes].numpy()
+        counts = res[:16 * P].view(np.int32).reshape(P, 4).copy()
+        if not want_ops:
+            return counts, None, None
+        return counts, res[20 * P:].copy(), res[16 * P:20 * P].view(np.int32).copy()
+
     # ---- baseline line extraction (include/cocr.h: cocr_extract_lines) -------------------------------------------------------
     def extract_lines(self, pages: Sequence['np.ndarray | torch.Tensor'], geoms: Sequence, fill: int = 0
                       ) -> Tuple[torch.Tensor, np.ndarray, np.ndarray, np.ndarray]:

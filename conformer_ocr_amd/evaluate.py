@@ -8,7 +8,7 @@ ranks take batches round-robin with no collective in the loop.  torchmetrics is 
 edit-distance ratios (errors / reference length) it computes."""
 from __future__ import annotations
 
-from typing import Dict, Iterable, List, Sequence, Tuple
+from typing import Dict, Iterable, List, Optional, Sequence, Tuple
 
 import os
 
@@ -389,12 +389,38 @@ def recognize_crops(net, crops: Sequence[np.ndarray], batch_size: int = 32, edge
     return out
 
 
-def evaluate(net, lines: Sequence[np.ndarray], truths: Sequence[str], report: bool = False, model_name: str = 'model', **kw) -> Dict[str, float]:
+def score_strings(net, preds: Sequence[str], truths: Sequence[str], report: bool = False, model_name: str = 'model',
+                  scorer: Optional[str] = None) -> Dict[str, float]:
+    """The scores of `evaluate` for strings already recognized.  scorer: None / 'device' -- the alignments run on the GPU through the
+    model's engine (conformer_ocr_amd/score.py); 'host' (or COCR_HOST_SCORE=1) -- the Python functions of this
+    module, which are the definition.  Same values either way: they are integers and ratios of integers."""
+    from . import score as _score
+    if _score.use_device(scorer, getattr(net, '_engine', None)):
+        s = _score.score(net._engine, preds, truths, report)
+        out = {'cer': s['char_errors'] / max(s['chars'], 1), 'wer': s['word_errors'] / max(s['words'], 1), 'chars': s['chars'],
+               'lines': len(preds)}
+        if report:
+            confusions, scripts, ins, dels, subs = s['tallies']
+            out.update(errors=s['char_errors'], confusions=confusions, insertions=ins, deletions=dels, substitutions=subs,
+                       report=render_report(model_name, s['chars'], s['char_errors'], 1.0 - out['cer'], 1.0 - out['wer'], confusions, scripts,
+                                            ins, dels, subs))
+        return out
+    return _score_strings_host(preds, truths, report, model_name)
+
+
+def evaluate(net, lines: Sequence[np.ndarray], truths: Sequence[str], report: bool = False, model_name: str = 'model',
+             scorer: Optional[str] = None, **kw) -> Dict[str, float]:
     """CER / WER of `net` on (lines, truths): the numbers of cli/test.py:211-212; with `report` also the alignment-based tallies and the
-    rendered text of cli/test.py:194-224 (`confusions`, `insertions`, `deletions`, `substitutions`, `report`)."""
+    rendered text of cli/test.py:194-224 (`confusions`, `insertions`, `deletions`, `substitutions`, `report`).  `scorer`: see
+    `score_strings`."""
     pred = recognize(net, lines, **kw)
-    cer, wer = ErrorRate(False), ErrorRate(True)
     idx = sorted(pred)
+    return score_strings(net, [pred[i] for i in idx], [truths[i] for i in idx], report, model_name, scorer)
+
+
+def _score_strings_host(pred: Sequence[str], truths: Sequence[str], report: bool, model_name: str) -> Dict[str, float]:
+    cer, wer = ErrorRate(False), ErrorRate(True)
+    idx = range(len(pred))
     cer.update([pred[i] for i in idx], [truths[i] for i in idx])
     wer.update([pred[i] for i in idx], [truths[i] for i in idx])
     out = {'cer': cer.compute(), 'wer': wer.compute(), 'chars': cer.total, 'lines': len(idx)}
@@ -412,12 +438,14 @@ def evaluate(net, lines: Sequence[np.ndarray], truths: Sequence[str], report: bo
 
 
 def validate(net, lines: Sequence[np.ndarray], truths: Sequence[str], batch_size: int = 32, edge: int = 200, rank: int = 0, world: int = 1,
-             device: str = 'cuda:0') -> Dict[str, float]:
+             device: str = 'cuda:0', scorer: Optional[str] = None) -> Dict[str, float]:
     """The reference's validation epoch (model.py:154-193): per batch `_step` (forward + CTC loss), greedy decode of the same
     probits, CER / WER against the targets decoded back through the codec, `val_loss` = mean over batches of the summed loss
     (torchmetrics MeanMetric over `o['loss']`).  The loss, the argmax and the run merging all stay on the device; only label
     records and one float per line come back.  Lines whose text the codec cannot encode completely contribute what it encodes
-    (kraken's non-strict codec drops unknown characters)."""
+    (kraken's non-strict codec drops unknown characters).  The strings are gathered per batch and scored in one call at the end
+    (`scorer`: see `score_strings`)."""
+    from . import score as _score
     from .ctc_decoder import GreedyDecoder
     if not isinstance(net.ctc_decoder, GreedyDecoder):
         raise ValueError('validation decodes greedily (model.py:163)')
@@ -431,9 +459,11 @@ def validate(net, lines: Sequence[np.ndarray], truths: Sequence[str], batch_size
         idx, handle, labels = p
         preds = [''.join(x[0] for x in net.codec.decode(locs)) for locs in net._engine.collect(handle)]
         refs = [''.join(x[0] for x in net.codec.decode([(l, 0, 0, 0) for l in lab])) for lab in labels]       # model.py:166-171
-        cer.update(preds, refs)
-        wer.update(preds, refs)
+        all_preds.extend(preds)
+        all_refs.extend(refs)
 
+    all_preds: List[str] = []
+    all_refs: List[str] = []
     for b in shard_batches(len(batches), rank, world):
         width, idx = batches[b]
         im, lens = collate(lines, idx, width)
@@ -447,6 +477,12 @@ def validate(net, lines: Sequence[np.ndarray], truths: Sequence[str], batch_size
         pending = (idx, handle, labels)
     if pending is not None:
         finish(pending)
+    if _score.use_device(scorer, getattr(net, '_engine', None)):
+        sc = _score.score(net._engine, all_preds, all_refs)
+        cer.errors, cer.total, wer.errors, wer.total = sc['char_errors'], sc['chars'], sc['word_errors'], sc['words']
+    else:
+        cer.update(all_preds, all_refs)
+        wer.update(all_preds, all_refs)
     loss_sum = float(torch.stack(losses).sum().item()) if losses else 0.0
     counts = reduce_counts([cer.errors, cer.total, wer.errors, wer.total, loss_sum, len(losses)], dev if world > 1 else None)
     cer.errors, cer.total, wer.errors, wer.total = int(counts[0]), int(counts[1]), int(counts[2]), int(counts[3])

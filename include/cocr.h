@@ -219,6 +219,24 @@ int cocr_extract_lines(cocr_model *m, const uint8_t *const *pages, const int32_t
 int cocr_augment_lines(cocr_model *m, const uint8_t *in, uint8_t *out, int N, int H, int W, const int32_t *seq_lens, const int64_t *params,
                        const int32_t *grid, int grid_cols, void *stream);
 
+/* Batched edit-distance alignment -- the scoring behind CER / WER and the confusion report (evaluate.global_align is the definition,
+ * tie-breaking included): unit costs, cost[i][0] = i, cost[0][j] = j; the traceback from (n, m) prefers the diagonal
+ * step when cost[i][j] == cost[i-1][j-1] + (a[i-1] != b[j-1]), else the deletion when cost[i][j] == cost[i-1][j] + 1, else the insertion.
+ * P pairs of int32 symbol sequences (compared for equality only), packed: pair p is a[a_offs[p] .. a_offs[p+1]) (the ground truth) against
+ * b[b_offs[p] .. b_offs[p+1]) (the prediction).  a, b DEVICE; a_offs, b_offs HOST int64 (P + 1): they are checked here, decide the
+ * launches, and reach the kernels through a pinned ring of the model.  Outputs, all DEVICE (or device-visible pinned memory):
+ * counts int32 (P, 4), 16-byte aligned = (distance, insertions, deletions, substitutions) per pair; ops (optional, NULL: counts only), one
+ * byte per alignment column: 0 equal, 1 substitution, 2 deletion (a symbol of a against a gap), 3 insertion (a gap against a symbol of b).
+ * Pair p owns the slot of len_a + len_b bytes starting at byte (a_offs[p] - a_offs[0]) + (b_offs[p] - b_offs[0]); its alignment, in
+ * forward order, fills the LAST ops_len[p] bytes of the slot (ops_len int32 (P), required with ops), the bytes before are left as they
+ * were.  Limits, COCR_EINVAL before any launch: a sequence longer than 4096 symbols, negative or decreasing offsets, P < 0.  P = 0 and
+ * empty sequences are valid.  Stream-ordered; does not synchronise `stream` (a growth of the ring or of the workspace waits for the
+ * device once).  cocr_edit_align_lds: the bytes of LDS a pair of these lengths takes when its op-code table is kept in LDS, 0 when the
+ * table goes to the model's global workspace (more than 64 KB, or more than COCR_SCORE_LDS_MAX); negative on an error. */
+int cocr_edit_align(cocr_model *m, const int32_t *a, const int64_t *a_offs, const int32_t *b, const int64_t *b_offs, int P, int32_t *counts,
+                    uint8_t *ops, int32_t *ops_len, void *stream);
+int64_t cocr_edit_align_lds(cocr_model *m, int len_a, int len_b);
+
 /* Launch-overhead control: with graph replay on, cocr_forward captures its ~40 kernel launches into a hipGraph and
  * replays it.  A caller that reuses (lines, logits, N, W, dtype, stream) gets a graph on its own buffers (second
  * identical call captures, later ones replay; contents may change, addresses not).  A caller with fresh buffers per
