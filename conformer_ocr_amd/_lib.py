@@ -46,6 +46,7 @@ SYMBOLS = {
     'cocr_forget_argmax': (_I, [_P]),
     'cocr_ctc_beam': (_I, [_P, _P, _I, _I, _I, _I32P, _P, _P, _P, _P, _P, _I, _I, _P]),
     'cocr_ctc_loss': (_I, [_P, _P, _I, _I, _I, _I32P, _I32P, _I32P, _P, _P, _P]),
+    'cocr_ctc_align': (_I, [_P, _P, _I, _I, _I, _I32P, _I32P, _I32P, _P, _P, _P, _P, _P, _P]),
     'cocr_decoder_backward': (_I, [_P, _P, _I, _I, _P, _P, _P, _P]),
     'cocr_decoder_adamw': (_I, [_P, _P, _P, C.c_float, C.c_float, C.c_float, C.c_float, C.c_float, _P]),
     'cocr_train_begin': (_I, [_P]),

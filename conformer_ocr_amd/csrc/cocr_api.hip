@@ -23,6 +23,7 @@
 #include "conv.hip.h"
 #include "ctc.hip.h"
 #include "ctc_loss.hip.h"
+#include "ctc_align.hip.h"
 #include "train.hip.h"
 #include "train_enc.hip.h"
 #include "gemm.hip.h"
@@ -174,6 +175,9 @@ struct cocr_model {
     DevBuf<int32_t> loss_d, loss_h{true};   // cocr_ctc_loss: device / pinned-host rings of [lens | label lens | label offsets | labels]
     int loss_slot = 0;
     DevBuf<float> loss_ws;                  // log-softmax + alpha / beta tables
+    DevBuf<int32_t> align_d, align_h{true}; // cocr_ctc_align: rings like loss_d / loss_h
+    int align_slot = 0;
+    DevBuf<unsigned> align_ws;              // back-pointer tables of the lines too long for the LDS
     // cocr_edit_align: device / pinned-host rings of [a offsets | b offsets | launch order] (one event per slot: the slot's upload has run
     // before the host writes it again), the op-code workspace of the pairs too large for the LDS, and the LDS budget of one pair
     DevBuf<unsigned char> score_d, score_h{true};
@@ -1729,6 +1733,59 @@ extern "C" int cocr_ctc_loss(cocr_model *m, const float *probits, int N, int T, 
     HIP_TRY(m->loss_ws.grow(need));
     ProfScope ps(m, s, FAM_LOSS);
     launch_ctc_loss(s, sj, (size_t)ncls * 4, probits, N, T, ncls, d, d + N, d + 2 * N, d + 3 * N, nll, grad, m->loss_ws.p, m->loss_ws.p + (size_t)N * T * ncls);
+    LAUNCH_CHECK();
+    return COCR_OK;
+}
+
+// ------------------------------------------------------------------------------------ forced alignment (ctc_align.hip.h)
+extern "C" int cocr_ctc_align(cocr_model *m, const float *logits, int N, int T, int ncls, const int32_t *out_lens, const int32_t *targets,
+                              const int32_t *label_lens, int32_t *starts, int32_t *ends, float *conf, float *score, int32_t *counts, void *stream) {
+    if (!m || !logits || !out_lens || !label_lens || !score || !counts) return fail(COCR_EINVAL, "null argument");
+    if (N < 1 || T < 1 || ncls < 2) return fail(COCR_EINVAL, "empty problem");
+    if (T > 8000) return fail(COCR_EUNSUPPORTED, "more than 8000 frames per line");
+    size_t total = 0;
+    int max_l = 0;
+    for (int n = 0; n < N; ++n) {
+        if (label_lens[n] < 0) return fail(COCR_EINVAL, "negative target length (line %d)", n);
+        if (label_lens[n] > COCR_CTCL_MAX_LABELS) return fail(COCR_EINVAL, "line %d has %d labels; the kernel holds at most %d", n, label_lens[n], COCR_CTCL_MAX_LABELS);
+        if (out_lens[n] < 0 || out_lens[n] > T) return fail(COCR_EINVAL, "input length %d outside [0, %d] (line %d)", out_lens[n], T, n);
+        max_l = std::max(max_l, (int)label_lens[n]);
+        total += (size_t)label_lens[n];
+    }
+    if (total && (!targets || !starts || !ends || !conf)) return fail(COCR_EINVAL, "null argument");
+    for (size_t i = 0; i < total; ++i)
+        if (targets[i] < 1 || targets[i] >= ncls) return fail(COCR_EINVAL, "target %d outside [1, %d) (blank is 0)", targets[i], ncls);
+    HIP_TRY(hipSetDevice(m->device));
+    hipStream_t s = (hipStream_t)stream;
+    const size_t ints = (size_t)3 * N + total;
+    HIP_TRY(grow_pair(m->align_d, m->align_h, ints * COCR_LENS_SLOTS, (ints + ints / 2) * COCR_LENS_SLOTS));
+    const size_t per = m->align_d.n / COCR_LENS_SLOTS;         // ints per slot
+    const int slot = m->align_slot;
+    m->align_slot = (slot + 1) % COCR_LENS_SLOTS;
+    int32_t *h = m->align_h.p + (size_t)slot * per, *d = m->align_d.p + (size_t)slot * per;
+    int32_t off = 0;
+    for (int n = 0; n < N; ++n) { h[n] = out_lens[n]; h[N + n] = label_lens[n]; h[2 * N + n] = off; off += label_lens[n]; }
+    if (total) memcpy(h + 3 * N, targets, total * 4);
+    HIP_TRY(hipMemcpyAsync(d, h, ints * 4, hipMemcpyHostToDevice, s));
+    const int states = 2 * max_l + 1;
+    const int sj = states <= 64 ? 1 : states <= 128 ? 2 : states <= 256 ? 4 : 8;
+    // the back-pointer table: in LDS beside lz when both fit (the kernel has ~5 KB of static LDS), else one region per line of the workspace
+    const size_t words = ctca_bp_words(T, sj), lds_all = ctca_lz_bytes(T) + words * 4;
+    if (lds_all <= 144 * 1024) {
+        // (the kernel also has ~5 KB of static LDS: the limit raised for the dynamic part stays below 160 KB - static)
+#define COCR_ALIGN_LDS(SJ)                                                                                                                          \
+    if (lds_all > 48 * 1024) {                                                                                                                      \
+        static bool raised = false;                                                                                                                 \
+        if (!raised) { HIP_TRY(hipFuncSetAttribute((const void *)ctc_align_kernel<SJ, true>, hipFuncAttributeMaxDynamicSharedMemorySize, 150 * 1024)); raised = true; } \
+    }
+        switch (sj) { case 1: COCR_ALIGN_LDS(1); break; case 2: COCR_ALIGN_LDS(2); break; case 4: COCR_ALIGN_LDS(4); break; default: COCR_ALIGN_LDS(8); break; }
+#undef COCR_ALIGN_LDS
+        launch_ctc_align<true>(s, sj, lds_all, logits, N, T, ncls, d, d + N, d + 2 * N, d + 3 * N, starts, ends, conf, score, counts, nullptr, 0);
+    } else {
+        HIP_TRY(m->align_ws.grow((size_t)N * words));
+        launch_ctc_align<false>(s, sj, ctca_lz_bytes(T), logits, N, T, ncls, d, d + N, d + 2 * N, d + 3 * N, starts, ends, conf, score, counts,
+                                m->align_ws.p, words);
+    }
     LAUNCH_CHECK();
     return COCR_OK;
 }

@@ -267,6 +267,65 @@ class HipRecognizer:
                                               _stream_ptr(self.device)))
         return nll, grad
 
+    # ---- forced alignment (include/cocr.h: cocr_ctc_align) ----------
+    def ctc_align_async(self, logits: torch.Tensor, out_lens, targets, label_lens):
+        """Enqueues the forced alignment of every line's label sequence on the current stream, its outputs in pinned host memory;
+        returns a handle for `collect_align`.  logits (N,T,ncls) float32 on this device; out_lens (N) valid frames; targets: the
+        batch's concatenated 1-D label vector, label_lens (N) its per-line lengths (host sequences; at most 255 labels per line).
+        Does not touch the forward's per-frame argmax: a `ctc_greedy` on the same logits afterwards still takes its shortcut."""
+        if logits.device != self.device or logits.dtype != torch.float32 or logits.dim() != 3:
+            raise RuntimeError('logits must be a float32 (N,T,num_classes) tensor on the model device')
+        cont = logits.contiguous()
+        N, T, ncls = cont.shape
+        lens = np.ascontiguousarray(np.asarray(out_lens, dtype=np.int32).reshape(-1))
+        tl = np.ascontiguousarray(np.asarray(label_lens, dtype=np.int32).reshape(-1))
+        tg = np.ascontiguousarray(np.asarray(targets, dtype=np.int32).reshape(-1))
+        if lens.shape[0] != N or tl.shape[0] != N:
+            raise ValueError('out_lens and label_lens need one entry per line')
+        if int(tl.sum()) != tg.shape[0]:
+            raise ValueError('targets must hold sum(label_lens) labels')
+        i32 = C.POINTER(C.c_int32)
+        with torch.cuda.device(self.device):
+            key = ('align', N)
+            pool = self._pinned.setdefault(key, [])
+            cap = max(N, 1) * 255                                   # the kernel's bound on a line's labels
+            host = pool.pop() if pool else (torch.empty((2, cap), dtype=torch.int32).pin_memory(),
+                                            torch.empty((cap,), dtype=torch.float32).pin_memory(),
+                                            torch.empty((N,), dtype=torch.float32).pin_memory(),
+                                            torch.empty((N,), dtype=torch.int32).pin_memory())
+            ints, conf, score, counts = host
+            try:
+                _lib.check(self.lib.cocr_ctc_align(self._h, C.c_void_p(cont.data_ptr()), N, T, ncls, lens.ctypes.data_as(i32),
+                                                   tg.ctypes.data_as(i32) if tg.shape[0] else None, tl.ctypes.data_as(i32),
+                                                   C.c_void_p(ints[0].data_ptr()), C.c_void_p(ints[1].data_ptr()), C.c_void_p(conf.data_ptr()),
+                                                   C.c_void_p(score.data_ptr()), C.c_void_p(counts.data_ptr()), _stream_ptr(self.device)))
+            except Exception:
+                pool.append(host)                                   # nothing was launched: the buffers go back
+                raise
+            ev = torch.cuda.Event()
+            ev.record(torch.cuda.current_stream(self.device))
+        return (key, host, ev, (cont, tg, tl))
+
+    def collect_align(self, handle) -> List[Tuple[Optional[List[Tuple[int, int, int, float]]], float]]:
+        """Waits for a `ctc_align_async` handle; per line ([(label, start, end, conf)] -- one record per label, in order -- or None
+        where no alignment fits, the path's log-probability)."""
+        key, host, ev, (_, tg, tl) = handle
+        ev.synchronize()
+        total = int(tg.shape[0])
+        st, en = host[0].numpy()[:, :total].tolist()
+        cf = host[1].numpy()[:total].tolist()
+        sc, cnt = host[2].numpy().tolist(), host[3].numpy().tolist()
+        lab = tg.tolist()
+        out, at = [], 0
+        for n, l in enumerate(tl.tolist()):
+            out.append((list(zip(lab[at:at + l], st[at:at + l], en[at:at + l], cf[at:at + l])) if cnt[n] >= 0 else None, sc[n]))
+            at += l
+        self._pinned[key].append(host)
+        return out
+
+    def ctc_align(self, logits: torch.Tensor, out_lens, targets, label_lens):
+        return self.collect_align(self.ctc_align_async(logits, out_lens, targets, label_lens))
+
     # ---- output-layer training step (include/cocr.h: cocr_decoder_backward / cocr_decoder_adamw) ----------
     def decoder_backward(self, grad_probits: torch.Tensor, with_input_grad: bool = False):
         """Gradients of the decoder `nn.Linear` for the LAST forward on this engine: (grad_weight (ncls, D), grad_bias (ncls),

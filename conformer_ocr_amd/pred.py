@@ -381,6 +381,61 @@ class PytorchRecognitionModel(nn.Module):
         """
         return self._label_records(line, lens)
 
+    # ------------------------------------------------------------------ forced alignment (conformer_ocr_amd/align.py)
+    def _align_labels_async(self, line: torch.Tensor, lens: torch.Tensor, targets, target_lens):
+        """Forward + `cocr_ctc_align` enqueued on the current stream.  A line of more than 255 labels (the kernel's bound) is aligned
+        by `align.viterbi_align` on its own logits when the handle is collected; the device sees it without labels."""
+        from .align import MAX_DEVICE_LABELS
+        o, olens = self.forward(line, lens)
+        eng = self._engine             # (a re-pack may replace `self._engine` before the collect)
+        olens = olens.numpy()
+        tl = np.asarray(target_lens, dtype=np.int64).reshape(-1)
+        tg = np.asarray(targets, dtype=np.int64).reshape(-1)
+        if int(tl.sum()) != tg.shape[0]:
+            raise ValueError('targets must hold sum(target_lens) labels')
+        offs = np.concatenate([[0], np.cumsum(tl)])
+        long_lines = {int(n): tg[offs[n]:offs[n + 1]] for n in np.nonzero(tl > MAX_DEVICE_LABELS)[0]}
+        if long_lines:
+            keep = np.ones(tg.shape[0], dtype=bool)
+            for n in long_lines:
+                keep[offs[n]:offs[n + 1]] = False
+            tg, tl = tg[keep], np.where(tl > MAX_DEVICE_LABELS, 0, tl)
+        return eng, eng.ctc_align_async(o, olens, tg, tl), o, olens, long_lines
+
+    def _collect_align_labels(self, pending):
+        from .align import viterbi_align
+        eng, handle, o, olens, long_lines = pending
+        out = eng.collect_align(handle)
+        for n, labels in long_lines.items():
+            out[n] = viterbi_align(o[n, :int(olens[n])].transpose(0, 1).cpu().numpy(), labels)
+        return out
+
+    def align_labels(self, line: torch.Tensor, lens: torch.Tensor, targets, target_lens):
+        """Forced alignment of known label sequences: forward pass on a (N, C, H, W) batch, then per line the best path of its labels
+        (`targets`: the batch's concatenated labels, `target_lens` (N)) through the frames.  Returns per line ([(label, start, end,
+        conf)] -- one record per label -- or None where the labels do not fit the frames, the path's log-probability)."""
+        return self._collect_align_labels(self._align_labels_async(line, lens, targets, target_lens))
+
+    def align_async(self, line: torch.Tensor, lens: torch.Tensor, texts):
+        """`align` split in two for pipelined callers (`align.align_pages`): returns a handle for `collect_align`."""
+        from .align import encode_text
+        enc = [encode_text(self.codec, t) for t in texts]
+        labels = [l for lab, _ in enc for l in lab]
+        return self._align_labels_async(line, lens, labels, [len(lab) for lab, _ in enc]), [sk for _, sk in enc]
+
+    def collect_align(self, handle) -> List[Dict]:
+        from .align import line_result
+        pending, skipped = handle
+        olens = pending[3]
+        return [line_result(self.codec, recs, score, olens[n], skipped[n])
+                for n, (recs, score) in enumerate(self._collect_align_labels(pending))]
+
+    def align(self, line: torch.Tensor, lens: torch.Tensor, texts) -> List[Dict]:
+        """Forced alignment of transcriptions: `texts` (one string per line) are encoded with `self.codec.encode` and placed on the
+        lines' frames.  Returns per line {'chars': [(char, start, end, conf)] or None where the text does not fit the frames,
+        'score': the path's log-probability, 'frames': the line's output length, 'skipped': the characters the codec cannot encode}."""
+        return self.collect_align(self.align_async(line, lens, texts))
+
     @classmethod
     def load_safetensors(cls, path, **kwargs):
         """

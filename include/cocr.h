@@ -156,6 +156,18 @@ int cocr_ctc_beam(cocr_model *m, const float *logits, int N, int T, int ncls, co
 int cocr_ctc_loss(cocr_model *m, const float *probits, int N, int T, int ncls, const int32_t *out_lens, const int32_t *targets,
                   const int32_t *label_lens, float *nll, float *grad, void *stream);
 
+/* Forced alignment (the definition is conformer_ocr_amd/align.py viterbi_align): the best path of each line's KNOWN
+ * label sequence through log_softmax(logits) -- the CTC lattice with max in place of the sum; ties keep the earlier of (stay, from s-1,
+ * from s-2); the path ends in the last label or the blank after it, the blank unless the label scores strictly higher.
+ * Arguments as for cocr_ctc_loss: logits DEVICE float32 (N,T,ncls); out_lens, targets (concatenated), label_lens HOST, checked before
+ * any launch (COCR_EINVAL: a label outside [1, ncls), out_lens[n] > T, more than 255 labels in a line).  Outputs DEVICE or device-visible
+ * pinned host memory: starts / ends int32 and conf float32, sum(label_lens) each, packed in target order -- first and last frame of the
+ * label's run and the largest softmax probability of the label over it; score (N) float32, the path's log-probability; counts (N) int32
+ * = label_lens[n], or -1 where no alignment fits (score -inf; the line's starts / ends are -1, conf 0).
+ * Deterministic (no atomics).  Stream-ordered, does not synchronise (workspace growth does). */
+int cocr_ctc_align(cocr_model *m, const float *logits, int N, int T, int ncls, const int32_t *out_lens, const int32_t *targets,
+                   const int32_t *label_lens, int32_t *starts, int32_t *ends, float *conf, float *score, int32_t *counts, void *stream);
+
 /* Training step of the output layer: the part of the reference's `training_step` (model.py:147-152, autograd through
  * `nn['decoder'] = nn.Linear(encoder_dim, num_classes)`, model.py:115) between the encoder output and the criterion, and the
  * reference's default optimizer (`torch.optim.AdamW`, model.py:47,283-284).  The encoder's backward is not in this library yet;
