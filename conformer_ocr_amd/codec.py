@@ -4,7 +4,9 @@ is not available here; this is a restatement of its published behaviour (SURVEY.
 Python because it runs once per decoded line on a handful of labels."""
 from __future__ import annotations
 
-from typing import Dict, List, Sequence, Set, Tuple, Union
+from typing import Dict, List, Optional, Sequence, Set, Tuple, Union
+
+import numpy as np
 
 
 class PytorchCodec:
@@ -87,6 +89,70 @@ class PytorchCodec:
                 c2l[k] = [nxt]
                 nxt += 1
         return PytorchCodec(c2l), set()
+
+
+RESIZE_MODES = ('fail', 'union', 'new')
+
+
+def uncovered(codec: PytorchCodec, texts: Sequence[str]) -> List[str]:
+    """The characters of `texts` that no grapheme of `codec` is (sorted): what `resize_codec(..., 'fail')` names."""
+    return sorted(set(''.join(texts)) - set(codec.c2l))
+
+
+def _tokens(codec: PytorchCodec, texts: Sequence[str]) -> Tuple[Set[str], Set[str]]:
+    """`codec.encode`'s greedy longest match over `texts`: (the graphemes it matched, the single code points it skipped)."""
+    used: Set[str] = set()
+    skipped: Set[str] = set()
+    for s in texts:
+        idx = 0
+        while idx < len(s):
+            for code in codec.c_sorted:
+                if s.startswith(code, idx):
+                    used.add(code)
+                    idx += len(code)
+                    break
+            else:
+                skipped.add(s[idx])
+                idx += 1
+    return used, skipped
+
+
+def resize_codec(old: PytorchCodec, texts: Sequence[str], mode: str = 'fail',
+                 old_num_classes: Optional[int] = None) -> Tuple[PytorchCodec, np.ndarray]:
+    """Adapts a trained model's codec to the alphabet of `texts`.  Returns (new codec, row_map): row_map (int32, one entry per class of
+    the new output layer) holds the row of the OLD output layer (of `old_num_classes` rows; default `old.max_label + 1`) that row j
+    takes, or -1 for a row that starts fresh; row_map[0] == 0 is the blank.  The missing characters are the single code points
+    `old.encode` skips under its greedy longest match.
+
+    'fail'   ValueError naming the uncovered characters; otherwise `old` itself and the identity map.
+    'union'  every old grapheme keeps its labels and every old row its index (rows no grapheme uses too: a row trained as "never" is
+             not handed to a new character); the missing characters, sorted, take one label each from `old_num_classes` upward.
+    'new'    the codec becomes exactly the alphabet of `texts`: the old graphemes the encoding of `texts` uses, renumbered 1..k in
+             the order of their old labels and carrying their old rows, then the missing characters, sorted, as k+1...  Needs a
+             1:1 old codec (one label per grapheme)."""
+    if mode not in RESIZE_MODES:
+        raise ValueError(f'resize mode must be one of {RESIZE_MODES}')
+    n_old = old.max_label + 1 if old_num_classes is None else int(old_num_classes)
+    if old.max_label >= n_old:
+        raise ValueError(f'the codec uses label {old.max_label}, the output layer has {n_old} rows')
+    if mode == 'fail':
+        missing = uncovered(old, texts)
+        if missing:
+            raise ValueError(f'the model\'s codec does not cover the training alphabet: missing {"".join(missing)!r}')
+        return old, np.arange(n_old, dtype=np.int32)
+    used, skipped = _tokens(old, texts)
+    missing = sorted(skipped)
+    if mode == 'union':
+        c2l = {k: list(v) for k, v in old.c2l.items()}
+        c2l.update({c: [n_old + i] for i, c in enumerate(missing)})
+        row_map = np.concatenate([np.arange(n_old, dtype=np.int32), np.full(len(missing), -1, dtype=np.int32)])
+        return PytorchCodec(c2l, strict=old.strict), row_map
+    if any(len(v) != 1 for v in old.c2l.values()):
+        raise ValueError("resize mode 'new' needs a 1:1 codec (one label per grapheme); this one has multi-label graphemes: use 'union'")
+    kept = sorted(used, key=lambda c: old.c2l[c][0])
+    c2l = {c: [i] for i, c in enumerate(kept + missing, start=1)}
+    row_map = np.array([0] + [old.c2l[c][0] for c in kept] + [-1] * len(missing), dtype=np.int32)
+    return PytorchCodec(c2l, strict=old.strict), row_map
 
 
 def ascii_codec(num_classes: int) -> PytorchCodec:

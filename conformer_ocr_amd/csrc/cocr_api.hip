@@ -1831,6 +1831,29 @@ extern "C" int cocr_decoder_backward(cocr_model *m, const float *grad_probits, i
     return COCR_OK;
 }
 
+// fp32 master copy [W | b] of the output layer + zeroed moments: the state-dict tensors when this rank has them, else (weights received by
+// broadcast) the blob's values
+static int decoder_master_init(cocr_model *m, hipStream_t s) {
+    const size_t nw = (size_t)m->ncls * m->D, nb = (size_t)m->ncls, n = nw + nb, nw_model = (size_t)m->ncls * m->rD;
+    const size_t row_e = (size_t)m->D * 4, row_m = (size_t)m->rD * 4;      // engine / model row bytes of the decoder weight (equal unless padded)
+    HIP_TRY(hipMalloc((void **)&m->tr_state, 3 * n * 4));
+    HIP_TRY(hipMemsetAsync(m->tr_state + n, 0, 2 * n * 4, s));
+    auto w = m->host.find("decoder.weight"), b = m->host.find("decoder.bias");
+    if (w != m->host.end() && w->second.set && w->second.data.size() == nw_model && b != m->host.end() && b->second.set && b->second.data.size() == nb) {
+        HIP_TRY(hipMemsetAsync(m->tr_state, 0, nw * 4, s));
+        HIP_TRY(hipMemcpy2DAsync(m->tr_state, row_e, w->second.data.data(), row_m, row_m, m->ncls, hipMemcpyHostToDevice, s));
+        HIP_TRY(hipMemcpyAsync(m->tr_state + nw, b->second.data.data(), nb * 4, hipMemcpyHostToDevice, s));
+        HIP_TRY(hipStreamSynchronize(s));                                   // pageable sources
+    } else {
+        if (m->dtype == COCR_BF16) hipLaunchKernelGGL((to_f32_kernel<bf16_t>), dim3(64), dim3(256), 0, s, (const bf16_t *)(m->blob + m->plan.wdec), m->tr_state, nw);
+        else hipLaunchKernelGGL((to_f32_kernel<float>), dim3(64), dim3(256), 0, s, (const float *)(m->blob + m->plan.wdec), m->tr_state, nw);
+        HIP_TRY(hipMemcpyAsync(m->tr_state + nw, m->blob + m->plan.bdec, nb * 4, hipMemcpyDeviceToDevice, s));
+        LAUNCH_CHECK();
+    }
+    m->tr_step = 0;
+    return COCR_OK;
+}
+
 extern "C" int cocr_decoder_adamw(cocr_model *m, const float *grad_weight, const float *grad_bias, float lr, float beta1, float beta2, float eps,
                                   float weight_decay, void *stream) {
     if (!m || !grad_weight || !grad_bias) return fail(COCR_EINVAL, "null argument");
@@ -1840,7 +1863,7 @@ extern "C" int cocr_decoder_adamw(cocr_model *m, const float *grad_weight, const
         return fail(COCR_EINVAL, "invalid AdamW hyper-parameters");            // torch.optim.AdamW's own checks
     HIP_TRY(hipSetDevice(m->device));
     hipStream_t s = (hipStream_t)stream;
-    const size_t nw = (size_t)m->ncls * m->D, nb = (size_t)m->ncls, n = nw + nb, nw_model = (size_t)m->ncls * m->rD;
+    const size_t nw = (size_t)m->ncls * m->D, nb = (size_t)m->ncls, n = nw + nb;
     const size_t row_e = (size_t)m->D * 4, row_m = (size_t)m->rD * 4;      // engine / model row bytes of the decoder weight (equal unless padded)
     if (m->padded) {    // the caller's (ncls, rD) gradient embedded in the engine's zero-padded rows
         HIP_TRY(m->tr_pad.grow(nw));
@@ -1848,24 +1871,7 @@ extern "C" int cocr_decoder_adamw(cocr_model *m, const float *grad_weight, const
         HIP_TRY(hipMemcpy2DAsync(m->tr_pad.p, row_e, grad_weight, row_m, row_m, m->ncls, hipMemcpyDeviceToDevice, s));
         grad_weight = m->tr_pad.p;
     }
-    if (!m->tr_state) {
-        // fp32 master copy: the state-dict tensors when this rank has them, else (weights received by broadcast) the blob's values
-        HIP_TRY(hipMalloc((void **)&m->tr_state, 3 * n * 4));
-        HIP_TRY(hipMemsetAsync(m->tr_state + n, 0, 2 * n * 4, s));
-        auto w = m->host.find("decoder.weight"), b = m->host.find("decoder.bias");
-        if (w != m->host.end() && w->second.set && w->second.data.size() == nw_model && b != m->host.end() && b->second.set && b->second.data.size() == nb) {
-            HIP_TRY(hipMemsetAsync(m->tr_state, 0, nw * 4, s));
-            HIP_TRY(hipMemcpy2DAsync(m->tr_state, row_e, w->second.data.data(), row_m, row_m, m->ncls, hipMemcpyHostToDevice, s));
-            HIP_TRY(hipMemcpyAsync(m->tr_state + nw, b->second.data.data(), nb * 4, hipMemcpyHostToDevice, s));
-            HIP_TRY(hipStreamSynchronize(s));                                   // pageable sources
-        } else {
-            if (m->dtype == COCR_BF16) hipLaunchKernelGGL((to_f32_kernel<bf16_t>), dim3(64), dim3(256), 0, s, (const bf16_t *)(m->blob + m->plan.wdec), m->tr_state, nw);
-            else hipLaunchKernelGGL((to_f32_kernel<float>), dim3(64), dim3(256), 0, s, (const float *)(m->blob + m->plan.wdec), m->tr_state, nw);
-            HIP_TRY(hipMemcpyAsync(m->tr_state + nw, m->blob + m->plan.bdec, nb * 4, hipMemcpyDeviceToDevice, s));
-            LAUNCH_CHECK();
-        }
-        m->tr_step = 0;
-    }
+    if (!m->tr_state) { const int rc = decoder_master_init(m, s); if (rc) return rc; }
     const long t = ++m->tr_step;
     const float bc1 = 1.0f - (float)pow((double)beta1, (double)t), bc2s = (float)sqrt(1.0 - pow((double)beta2, (double)t));
     float *p = m->tr_state, *m1 = p + n, *m2 = m1 + n;

@@ -3,6 +3,7 @@
 //     cocr_train_step       RecognitionModel.training_step (model.py:129-152): train-mode forward (batch-statistics BatchNorm, dropout at the
 //                           reference's six sites), CTC criterion, backward through decoder AND encoder -> the gradient of every parameter
 //     cocr_train_adamw      torch.optim.AdamW over all parameters (model.py:283-284)
+//     cocr_train_adopt_decoder   the output layer a frozen-backbone phase trained (cocr_decoder_adamw), with its optimizer state, into this state
 //     cocr_train_get        a parameter / buffer / gradient by name (checkpointing, tests)
 //     cocr_train_end        the trained values back into the model's state (re-finalize to serve them)
 // fp32 and correctness-first (train_enc.hip.h); every matrix product -- forward, input gradient, weight gradient -- is the exact-fp32 MFMA GEMM
@@ -19,6 +20,7 @@ struct TrainState {
     size_t nparam = 0, ntotal = 0;            // floats: parameters first (the optimizer's range), then buffers (BatchNorm running statistics)
     float *P = nullptr, *G = nullptr, *Mo = nullptr, *Vo = nullptr;
     long step = 0;
+    long dec_steps = 0;                       // optimizer steps the output layer took BEFORE it was adopted (cocr_train_adopt_decoder): its own step count is step + dec_steps
     DevBuf<unsigned char> ws;                 // activations + scratch of one step
     DevBuf<float> pe;                         // sinusoid rows for relative positions T-1 ... -(T-1), (2T-1, D)
     int peT = 0;
@@ -164,8 +166,50 @@ extern "C" int cocr_train_adamw(cocr_model *m, float lr, float beta1, float beta
     HIP_TRY(hipSetDevice(m->device));
     t->step += 1;
     const float bc1 = 1.0f - powf(beta1, (float)t->step), bc2 = 1.0f - powf(beta2, (float)t->step);
-    hipLaunchKernelGGL(k_adamw_flat, dim3(1024), dim3(256), 0, (hipStream_t)stream, t->P, t->G, t->Mo, t->Vo, t->nparam, lr, beta1, beta2, eps, weight_decay, bc1, bc2);
+    if (t->dec_steps == 0) {
+        hipLaunchKernelGGL(k_adamw_flat, dim3(1024), dim3(256), 0, (hipStream_t)stream, t->P, t->G, t->Mo, t->Vo, t->nparam, lr, beta1, beta2, eps, weight_decay, bc1, bc2);
+    } else {
+        // per-tensor step counts: the adopted output layer is dec_steps steps ahead of every other parameter
+        const long k = t->step + t->dec_steps;
+        AdamwRanges r = {};
+        int i = 0;
+        for (const char *name : {"decoder.weight", "decoder.bias"}) {
+            const TrainEntry &e = t->idx.at(name);
+            r.lo[i] = e.off; r.hi[i] = e.off + e.n;
+            r.bc1[i] = 1.0f - powf(beta1, (float)k); r.bc2[i] = 1.0f - powf(beta2, (float)k);
+            ++i;
+        }
+        hipLaunchKernelGGL(k_adamw_flat_ranges, dim3(1024), dim3(256), 0, (hipStream_t)stream, t->P, t->G, t->Mo, t->Vo, t->nparam, lr, beta1, beta2, eps, weight_decay, bc1, bc2, r);
+    }
     LAUNCH_CHECK();
+    return COCR_OK;
+}
+
+// The output layer of `src` as its decoder-only steps left it (cocr_decoder_adamw: fp32 master copy, both moments, step count k) into the
+// training state of `dst`: device to device on `stream`, rows re-strided from the engine's (maybe padded) width to the model's own.
+// cocr_train_adamw then continues that layer at step k + 1.  A `src` that never stepped hands over its values, zero moments and k = 0.
+extern "C" int cocr_train_adopt_decoder(cocr_model *dst, cocr_model *src, void *stream) {
+    if (!dst || !src) return fail(COCR_EINVAL, "null argument");
+    TrainState *t = dst->train;
+    if (!t) return fail(COCR_ESTATE, "cocr_train_begin has not been called on the adopting model");
+    if (src->dtype < 0 || !src->blob) return fail(COCR_ESTATE, "the source model is not finalized");
+    if (src->device != dst->device) return fail(COCR_EINVAL, "the two models live on different devices (%d, %d)", src->device, dst->device);
+    auto w = t->idx.find("decoder.weight"), b = t->idx.find("decoder.bias");
+    if (w == t->idx.end() || b == t->idx.end()) return fail(COCR_ESTATE, "the training state has no output layer");
+    if (src->ncls != dst->ncls || src->rD != dst->rD || w->second.n != (size_t)src->ncls * src->rD || b->second.n != (size_t)src->ncls)
+        return fail(COCR_EINVAL, "output layers differ: (%d, %d) into (%d, %d)", src->ncls, src->rD, dst->ncls, dst->rD);
+    HIP_TRY(hipSetDevice(dst->device));
+    hipStream_t s = (hipStream_t)stream;
+    if (!src->tr_state) { const int rc = decoder_master_init(src, s); if (rc) return rc; }
+    const size_t nw = (size_t)src->ncls * src->D, n = nw + (size_t)src->ncls;
+    const size_t row_e = (size_t)src->D * 4, row_m = (size_t)src->rD * 4;
+    float *dsts[3] = {t->P, t->Mo, t->Vo};
+    for (int i = 0; i < 3; ++i) {
+        const float *from = src->tr_state + (size_t)i * n;
+        HIP_TRY(hipMemcpy2DAsync(dsts[i] + w->second.off, row_m, from, row_e, row_m, src->ncls, hipMemcpyDeviceToDevice, s));
+        HIP_TRY(hipMemcpyAsync(dsts[i] + b->second.off, from + nw, (size_t)src->ncls * 4, hipMemcpyDeviceToDevice, s));
+    }
+    t->dec_steps = src->tr_step - t->step;        // (the layer's count is dst's own count + dec_steps: an adoption after dst has stepped keeps k exact)
     return COCR_OK;
 }
 

@@ -966,3 +966,24 @@ __global__ static void k_adamw_flat(float *__restrict__ p, const float *__restri
         p[i] = w;
     }
 }
+
+// The same step with PER-TENSOR step counts (torch keeps `state['step']` per parameter): the elements of up to COCR_ADAMW_RANGES ranges of
+// the flat vector take their own bias corrections -- an output layer adopted after k frozen-backbone steps (cocr_train_adopt_decoder)
+// continues at step k + 1 while every other tensor starts at 1.  Unused ranges are empty (lo == hi); the arithmetic per element is
+// k_adamw_flat's, so equal corrections give its result bit for bit.
+#define COCR_ADAMW_RANGES 4
+struct AdamwRanges { unsigned long long lo[COCR_ADAMW_RANGES], hi[COCR_ADAMW_RANGES]; float bc1[COCR_ADAMW_RANGES], bc2[COCR_ADAMW_RANGES]; };
+__global__ static void k_adamw_flat_ranges(float *__restrict__ p, const float *__restrict__ g, float *__restrict__ m, float *__restrict__ v, size_t n, float lr,
+                                           float b1, float b2, float eps, float wd, float bc1, float bc2, AdamwRanges r) {
+    for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (size_t)gridDim.x * blockDim.x) {
+        float c1 = bc1, c2 = bc2;
+#pragma unroll
+        for (int k = 0; k < COCR_ADAMW_RANGES; ++k)
+            if (i >= r.lo[k] && i < r.hi[k]) { c1 = r.bc1[k]; c2 = r.bc2[k]; }
+        float w = p[i] * (1.0f - lr * wd);
+        const float gi = g[i], mi = b1 * m[i] + (1.0f - b1) * gi, vi = b2 * v[i] + (1.0f - b2) * gi * gi;
+        m[i] = mi; v[i] = vi;
+        w -= lr / c1 * mi / (sqrtf(vi) / sqrtf(c2) + eps);
+        p[i] = w;
+    }
+}

@@ -19,7 +19,7 @@ from typing import Dict, Iterator, List, Optional, Sequence, Tuple
 
 import numpy as np
 
-from .codec import PytorchCodec
+from .codec import PytorchCodec, resize_codec
 from .evaluate import make_batches
 
 FORMATS = ('path', 'page', 'alto', 'xml')
@@ -96,10 +96,8 @@ def build_codec(texts: Sequence[str]) -> PytorchCodec:
 
 
 def check_codec(codec: PytorchCodec, texts: Sequence[str]) -> None:
-    """ValueError naming the characters of `texts` that `codec` (a loaded model's) cannot encode: resizing a codec is not built."""
-    missing = sorted(set(''.join(texts)) - set(codec.c2l))
-    if missing:
-        raise ValueError(f'the model\'s codec does not cover the training alphabet: missing {"".join(missing)!r}')
+    """ValueError naming the characters of `texts` that `codec` (a loaded model's) cannot encode (`codec.resize_codec` grows it)."""
+    resize_codec(codec, texts, 'fail')
 
 
 def split(n: int, partition: float, seed: int) -> Tuple[np.ndarray, np.ndarray]:
@@ -127,12 +125,17 @@ class GroundTruthDataset:
 
         data = GroundTruthDataset(files, format_type='xml', augment=True)
         for batch in data.batches(epoch): trainer.training_step(batch)
-        cer = data.validate(net)"""
+        cer = data.validate(net)
+
+    `codec`: a loaded model's (default: the training alphabet's own, `build_codec`); `resize` ('fail', 'union', 'new') and
+    `codec_num_classes` (the rows of that model's output layer) go to `codec.resize_codec`, whose results are `self.codec`,
+    `self.row_map` (None without `codec`) and `self.num_classes`."""
 
     def __init__(self, training_files: Sequence[str], evaluation_files: Optional[Sequence[str]] = None, format_type: str = 'xml',
                  partition: float = 0.9, normalization: Optional[str] = 'NFD', normalize_whitespace: bool = True, height: int = 96,
                  pad: int = 16, batch_size: int = 32, edge: int = 200, seed: int = 0, augment: bool = False, augment_config=None,
-                 codec: Optional[PytorchCodec] = None, device: str = 'cuda:0'):
+                 codec: Optional[PytorchCodec] = None, device: str = 'cuda:0', resize: str = 'fail',
+                 codec_num_classes: Optional[int] = None):
         from .augment import AugmentConfig
         train = read_ground_truth(training_files, format_type, normalization, normalize_whitespace)
         if evaluation_files:
@@ -151,9 +154,13 @@ class GroundTruthDataset:
         self.augment_config = augment_config or AugmentConfig()
         if codec is None:
             codec = build_codec([ln.text for ln in train])
+            self.row_map = None
         else:
-            check_codec(codec, [ln.text for ln in train])
+            # a loaded model's codec: `resize` 'union' / 'new' adapt it to the training alphabet (codec.resize_codec); `row_map` says
+            # which row of the model's output layer (of `codec_num_classes` rows) each class of the new one takes
+            codec, self.row_map = resize_codec(codec, [ln.text for ln in train], resize, codec_num_classes)
         self.codec = codec
+        self.num_classes = codec.max_label + 1 if self.row_map is None else len(self.row_map)
         self.labels = [np.asarray(codec.encode(ln.text), dtype=np.int32) for ln in train]
         self.device = device
         self._cache()

@@ -423,6 +423,13 @@ class HipRecognizer:
         with torch.cuda.device(self.device):
             _lib.check(self.lib.cocr_train_adamw(self._h, float(lr), float(betas[0]), float(betas[1]), float(eps), float(weight_decay), _stream_ptr(self.device)))
 
+    def train_adopt_decoder(self, src: 'HipRecognizer') -> None:
+        """The output layer of `src` as its `decoder_adamw` steps left it (fp32 master copy, both moments, step count k) into this
+        engine's training state, device to device on the current stream; `train_adamw` continues that layer at step k + 1 and every
+        other parameter at its own count."""
+        with torch.cuda.device(self.device):
+            _lib.check(self.lib.cocr_train_adopt_decoder(self._h, src._h, _stream_ptr(self.device)))
+
     def train_grad_buffer(self) -> torch.Tensor:
         """The flat gradient vector of all parameters as a float32 torch view of library-owned memory (for an all-reduce)."""
         p, n = C.c_void_p(), C.c_size_t()

@@ -489,6 +489,44 @@ def save_safetensors(net: PytorchRecognitionModel, path, extra_metadata: Optiona
             tf.addfile(ti, io.BytesIO(data))
 
 
+def resize_output(net: PytorchRecognitionModel, new_codec: PytorchCodec, row_map, seed: int = 0) -> None:
+    """Output-layer surgery after `codec.resize_codec`, in place: `net.nn['decoder']` becomes a Linear of `len(row_map)` classes (frozen
+    like the constructor's) whose row j is the old layer's row `row_map[j]` bit for bit, or, for row_map[j] == -1, the fresh row
+    `synth.output_row(seed, c, encoder_dim)` of the grapheme c that `new_codec` labels j; `net.codec` and `net.hparams_record` follow.
+    The device model re-packs at the next call (`_signature` sees the replaced sub-module)."""
+    import dataclasses
+    from .synth import output_row
+    old = net.nn['decoder']
+    row_map = np.asarray(row_map, dtype=np.int64).reshape(-1)
+    n_old, fan_in = old.weight.shape
+    if row_map.shape[0] < 1 or row_map[0] != 0:
+        raise ValueError('row_map[0] must be 0: the blank keeps its row')
+    if row_map.max() >= n_old or row_map.min() < -1:
+        raise ValueError(f'row_map names rows outside the output layer\'s {n_old}')
+    if new_codec.max_label >= row_map.shape[0]:
+        raise ValueError(f'the codec uses label {new_codec.max_label}, row_map has {row_map.shape[0]} rows')
+    w_old, b_old = old.weight.detach().cpu().float().numpy(), old.bias.detach().cpu().float().numpy()
+    w, b = np.zeros((row_map.shape[0], fan_in), dtype=np.float32), np.zeros(row_map.shape[0], dtype=np.float32)
+    for j, r in enumerate(row_map):
+        if r >= 0:
+            w[j], b[j] = w_old[r], b_old[r]
+            continue
+        c = new_codec.l2c.get((j,))
+        if c is None:
+            raise ValueError(f'row {j} is new, but no grapheme of the codec has the label sequence [{j}]')
+        w[j], b[j] = output_row(seed, c, fan_in)
+    dec = nn.Linear(fan_in, row_map.shape[0], bias=True)
+    with torch.no_grad():
+        dec.weight.copy_(torch.from_numpy(w))
+        dec.bias.copy_(torch.from_numpy(b))
+    dec = dec.to(device=old.weight.device, dtype=old.weight.dtype)
+    for p in dec.parameters():
+        p.requires_grad_(False)
+    net.nn['decoder'] = dec
+    net.codec = new_codec
+    net.hparams_record = dataclasses.replace(net.hparams_record, num_classes=int(row_map.shape[0]))
+
+
 def average_checkpoints(paths, num_checkpoints: Optional[int] = None) -> Dict:
     """The reference's `avg_ckpts` (cli/train.py:37-98): element-wise mean of the `state_dict`s of the last `num_checkpoints`
     checkpoints of `paths` (sorted by name like the reference's glob); everything else is taken from the first of them.

@@ -59,6 +59,16 @@ def _bound(shape: Tuple[int, ...]) -> float:
     return math.sqrt(3.0 / (shape[1] * recept))
 
 
+def output_row(seed: int, grapheme: str, fan_in: int) -> Tuple[np.ndarray, np.float32]:
+    """The fresh output-layer row of `grapheme` (`pred.resize_output`): weight (fan_in,) float32, then the bias, both U(-a, a) with
+    a = 1 / sqrt(fan_in) -- `nn.Linear`'s default range -- from the generator of (seed, 'resize:' + grapheme): a character's row
+    does not depend on what else was added."""
+    g = _rng(seed, f'resize:{grapheme}')
+    a = 1.0 / math.sqrt(fan_in)
+    weight = g.uniform(-a, a, fan_in).astype(np.float32)
+    return weight, np.float32(g.uniform(-a, a))
+
+
 TEXT_OUT_PROJ_GAIN = 0.3       # style='text': attention out_proj scale
 TEXT_DW_SIGMA = 1.5            # style='text': Gaussian window (frames) on the conv module's depthwise taps
 

@@ -4,9 +4,9 @@
     forward (eval-mode encoder) -> CTC criterion + d loss / d probits (cocr_ctc_loss) -> decoder backward (cocr_decoder_backward)
     -> [all-reduce of the two gradients across ranks] -> AdamW (cocr_decoder_adamw)
 
-This is what the reference does while `freeze_backbone` samples remain (cli/train.py:154-155: "keep the backbone (everything but
-the last layer) frozen") and when a model is adapted to a new alphabet.  The encoder's backward is not implemented in this library;
-`DecoderTrainer` says so instead of silently training less than asked.
+This is what the reference's `freeze_backbone` asks for (cli/train.py:154-155: "keep the backbone (everything but the last layer)
+frozen") and what adapts a model to a new alphabet.  `DecoderTrainer` is that step alone; `Trainer(freeze_backbone=N)` runs it for
+the first N samples and then hands the output layer and its optimizer state over to the whole-network step.
 
 Data-parallel training: one process per GPU; each rank computes its batch's gradients, `torch.distributed.all_reduce` (backend
 "nccl" = RCCL over xGMI; two tensors, (ncls x D + ncls) x 4 bytes -- ~100 KB) combines them, every rank applies the same update: the
@@ -52,13 +52,17 @@ class DecoderTrainer:
 
     def sync_module(self) -> None:
         """Copies the trained output layer back into `net.nn['decoder']` (so `save_safetensors` / `state_dict()` see it)."""
-        st = self.net._engine.decoder_state()
-        dec = self.net.nn['decoder']
-        with torch.no_grad():
-            dec.weight.copy_(torch.from_numpy(st['decoder.weight']))
-            dec.bias.copy_(torch.from_numpy(st['decoder.bias']))
-        # the module now equals the engine's weights: keep the engine (and its optimizer state) instead of re-packing on the next forward
-        self.net._engine_sig = self.net._signature(self.net._engine.device)
+        _sync_decoder(self.net)
+
+
+def _sync_decoder(net: PytorchRecognitionModel) -> None:
+    st = net._engine.decoder_state()
+    dec = net.nn['decoder']
+    with torch.no_grad():
+        dec.weight.copy_(torch.from_numpy(st['decoder.weight']))
+        dec.bias.copy_(torch.from_numpy(st['decoder.bias']))
+    # the module now equals the engine's weights: keep the engine (and its optimizer state) instead of re-packing on the next forward
+    net._engine_sig = net._signature(net._engine.device)
 
 
 def reduce_gradients(tensors, group=None) -> None:
@@ -88,14 +92,23 @@ class Trainer:
     weight_decay=weight_decay)`, betas / eps torch's defaults); the reference's other optimizers (SGD, RMSprop with momentum) are not
     built.  Learning rate: linear warm-up over `warmup` steps exactly as `optimizer_step` applies it (the step itself runs at the rate
     set by the previous one; after step g the rate becomes min(1, (g + 1) / warmup) lr while g < warmup), then the epoch-wise schedule.
-    Data parallel: one process per GPU, the flat gradient vector is averaged by ONE all-reduce per step (torch DDP's semantics)."""
+    Data parallel: one process per GPU, the flat gradient vector is averaged by ONE all-reduce per step (torch DDP's semantics).
+
+    `freeze_backbone` (the reference's hyper-parameter; samples = this rank's lines): while `samples_seen < freeze_backbone` at the
+    start of a step, the step is the FROZEN step -- `DecoderTrainer.training_step` on `net`'s own serving engine (eval-mode forward
+    in the model's `compute_dtype`, CTC gradient, decoder backward, AdamW on the output layer at the current `lr` / weight decay);
+    no encoder parameter or BatchNorm statistic moves, `sync_module` copies the output layer only and keeps that engine and its
+    AdamW state.
+    Before the first unfrozen step the output layer's fp32 master copy, moments and step count move into the whole-network state on
+    the device (`cocr_train_adopt_decoder`); AdamW's step counts are per tensor from there on.  `global_step` and the warm-up run
+    on across both phases."""
 
     SCHEDULES = ('constant', 'exponential', 'cosine', 'step', 'reduceonplateau')
 
     def __init__(self, net: PytorchRecognitionModel, lr: float = 1e-3, weight_decay: float = 1e-3, optimizer: str = 'AdamW', warmup: int = 0,
                  schedule: str = 'constant', gamma: float = 0.1, cos_t_max: int = 50, cos_min_lr: float = 1e-4, step_size: int = 10,
                  rop_factor: float = 0.1, rop_patience: int = 5, completed_epochs: int = 0, seed: int = 0, process_group=None,
-                 distributed: Optional[bool] = None, matmul_precision: str = 'highest'):
+                 distributed: Optional[bool] = None, matmul_precision: str = 'highest', freeze_backbone: int = 0, log=None):
         if optimizer not in ('AdamW',):
             raise NotImplementedError(f'optimizer {optimizer}: only AdamW is built (the reference\'s default)')
         if schedule not in self.SCHEDULES:
@@ -110,6 +123,9 @@ class Trainer:
         self.lr = self._sched_lr
         self._best, self._bad = None, 0
         self.global_step = 0
+        self.freeze_backbone, self.samples_seen, self.frozen_steps = int(freeze_backbone), 0, 0
+        self._adopted = False                  # the frozen phase's output layer has moved into the whole-network state
+        self.log = log
         self.seed = int(seed)
         self.process_group = process_group
         if distributed is None:
@@ -133,11 +149,42 @@ class Trainer:
             return self.base_lr * self.gamma ** (e // self.step_size)                                 # StepLR
         return self.base_lr
 
+    @property
+    def frozen(self) -> bool:
+        """Whether the next step is the frozen step."""
+        return self.samples_seen < self.freeze_backbone
+
+    def _frozen_step(self, batch: Dict) -> float:
+        """`DecoderTrainer.training_step` at this Trainer's rate: only the output layer moves, on the serving engine."""
+        o = self.net.step(dict(batch, image=batch['image'].to(self.engine.device)), with_grad=True)
+        eng = self.net._engine
+        gw, gb, _ = eng.decoder_backward(o['grad_probits'])
+        if self.distributed:
+            reduce_gradients((gw, gb), self.process_group)
+        eng.decoder_adamw(gw, gb, self.lr, weight_decay=self.weight_decay)
+        self.frozen_steps += 1
+        return float(o['loss'])
+
+    def _unfreeze(self) -> None:
+        """The hand-over: the serving engine's output layer (fp32 master copy, moments, step count) into the whole-network state."""
+        self.engine.train_adopt_decoder(self.net._engine)
+        self._adopted = True
+        if self.log is not None:
+            self.log(f'backbone unfrozen after {self.samples_seen} samples ({self.frozen_steps} steps): training the whole network')
+
     def training_step(self, batch: Dict) -> float:
         """One optimizer step on `batch`; returns the batch's summed CTC loss (this rank's lines)."""
         image = batch['image']
         if image.dim() != 4 or image.shape[1] != 1:
             raise ValueError(f'expected a (N,1,H,W) line batch, got {tuple(image.shape)}')
+        if self.frozen:                                   # (tested at the start of a step: a batch is never split)
+            self.samples_seen += int(image.shape[0])
+            loss = self._frozen_step(batch)
+            self._after_step()
+            return loss
+        if self.frozen_steps and not self._adopted:
+            self._unfreeze()
+        self.samples_seen += int(image.shape[0])
         x = image.squeeze(1).to(self.engine.device)
         loss = self.engine.train_step(x, torch.as_tensor(batch['seq_lens']).cpu().numpy(), torch.as_tensor(batch['target']).cpu().numpy(),
                                       torch.as_tensor(batch['target_lens']).cpu().numpy(), dropout=self.net.dropout_p,
@@ -147,12 +194,15 @@ class Trainer:
             torch.distributed.all_reduce(g, op=torch.distributed.ReduceOp.SUM, group=self.process_group)
             g.div_(torch.distributed.get_world_size(self.process_group))
         self.engine.train_adamw(self.lr, weight_decay=self.weight_decay)
+        self._after_step()
+        return loss
+
+    def _after_step(self) -> None:
         if self.warmup and self.global_step < self.warmup:                                            # model.py:246-252
             self.lr = min(1.0, float(self.global_step + 1) / self.warmup) * self.base_lr
         elif self.warmup and self.global_step == self.warmup:
             self.lr = self._sched_lr
         self.global_step += 1
-        return loss
 
     def end_epoch(self, metric: Optional[float] = None) -> float:
         """Epoch-wise scheduler step (model.py:254-265; not during warm-up); `metric` (validation accuracy, larger is better) drives
@@ -176,12 +226,17 @@ class Trainer:
 
     def sync_module(self) -> None:
         """Copies every trained parameter and BatchNorm running statistic into `net.nn` (so `state_dict()`, `save_safetensors` and the
-        inference path -- re-packed on its next call -- see them).  Training can continue afterwards."""
+        inference path -- re-packed on its next call -- see them).  Training can continue afterwards.  While the backbone is frozen only
+        the output layer has moved: it alone is copied, and the serving engine that trains it (with its AdamW state) is kept, not
+        re-packed."""
+        if self.frozen_steps and not self._adopted:
+            _sync_decoder(self.net)
+            return
         sd = self.net.nn.state_dict()
         with torch.no_grad():
             for k, v in sd.items():
                 if k.endswith('num_batches_tracked'):
-                    v.add_(self.global_step - int(v))
+                    v.add_(self.global_step - self.frozen_steps - int(v))                              # (train-mode forwards only)
                     continue
                 v.copy_(torch.from_numpy(self.engine.train_value(k)).to(v.device).reshape(v.shape))
 
@@ -236,6 +291,18 @@ MODEL_DEFAULTS = dict(encoder_dim=144, num_encoder_layers=16, num_attention_head
                       half_step_residual=True, subsampling_conv_channels=32, subsampling_factor=4)
 
 
+def load_codec_file(path: str):
+    """The codec file of `-c/--codec`: JSON {grapheme: [labels]}, as the reference loads it (cli/train.py:296-298)."""
+    import json
+    from .codec import PytorchCodec
+    with open(path, encoding='utf-8') as fp:
+        c2l = json.load(fp)
+    if not isinstance(c2l, dict) or not c2l or not all(isinstance(k, str) and k and isinstance(v, list) and v and all(isinstance(x, int) for x in v)
+                                                       for k, v in c2l.items()):
+        raise ValueError(f'{path}: a codec file is a JSON object of grapheme -> list of integer labels')
+    return PytorchCodec(c2l)
+
+
 def main(argv=None) -> int:
     import argparse
     import glob
@@ -269,6 +336,11 @@ def main(argv=None) -> int:
     ap.add_argument('--augment', dest='augment', action='store_true', default=True)
     ap.add_argument('--no-augment', dest='augment', action='store_false')
     ap.add_argument('-i', '--load', default=None, help='safetensors archive or checkpoint to continue training')
+    ap.add_argument('--resize', choices=('fail', 'union', 'new'), default='fail',
+                    help='with --load, when the training alphabet has characters the model does not know: fail, add them to the codec and '
+                         'the output layer (union), or make the codec exactly the training alphabet (new)')
+    ap.add_argument('--freeze-backbone', type=int, default=0, help='number of samples to keep the backbone (everything but last layer) frozen')
+    ap.add_argument('-c', '--codec', default=None, help='JSON codec file {grapheme: [labels]} for a new model, instead of the training alphabet')
     ap.add_argument('-o', '--output', default='model', help='prefix of the written models')
     ap.add_argument('--device', default='cuda:0')
     ap.add_argument('--seed', type=int, default=0)
@@ -292,14 +364,33 @@ def main(argv=None) -> int:
     train_files = expand(args.training_files) + list(args.ground_truth)
     if not train_files:
         ap.error('no training data: give files or -t')
-    codec, net = None, None
+    if args.codec and args.load:
+        ap.error('-c/--codec describes a new model: a loaded model brings its codec (--resize adapts it)')
+    if args.resize != 'fail' and not args.load:
+        ap.error('--resize adapts a loaded model: give -i/--load')
+    if args.freeze_backbone < 0:
+        ap.error('--freeze-backbone is a number of samples')
+    codec, net, old_classes = None, None, None
+    if args.codec:
+        codec = load_codec_file(args.codec)
     if args.load:
         net = load_model(args.load, device=args.device)
-        codec = net.codec
-    data = GroundTruthDataset(train_files, expand(args.evaluation_files) or None, format_type=args.format_type, partition=args.partition,
-                              normalization=args.normalization, normalize_whitespace=args.normalize_whitespace, height=args.line_height,
-                              pad=args.pad, batch_size=args.batch_size, edge=args.edge, seed=args.seed, augment=args.augment, codec=codec,
-                              device=args.device)
+        codec, old_classes = net.codec, net.hparams_record.num_classes
+    try:
+        data = GroundTruthDataset(train_files, expand(args.evaluation_files) or None, format_type=args.format_type, partition=args.partition,
+                                  normalization=args.normalization, normalize_whitespace=args.normalize_whitespace, height=args.line_height,
+                                  pad=args.pad, batch_size=args.batch_size, edge=args.edge, seed=args.seed, augment=args.augment, codec=codec,
+                                  device=args.device, resize=args.resize, codec_num_classes=old_classes)
+    except ValueError as e:
+        if args.codec and str(e).startswith('the model\'s codec does not cover'):
+            raise ValueError(str(e).replace('the model\'s codec', f'the codec of {args.codec}', 1)) from None
+        raise
+    if net is not None and args.resize != 'fail':
+        from .pred import resize_output
+        was, now = set(codec.c2l), set(data.codec.c2l)
+        resize_output(net, data.codec, data.row_map, seed=args.seed)
+        print(f'resize {args.resize}: {old_classes} -> {data.num_classes} classes; kept {len(was & now)}, added {len(now - was)} '
+              f'({"".join(sorted(now - was))!r}), dropped {len(was - now)} characters')
     if net is None:
         from .pred import PytorchRecognitionModel
         hp = dict(MODEL_DEFAULTS, **json.loads(args.hyper_params or '{}'))
@@ -312,7 +403,8 @@ def main(argv=None) -> int:
     elif net.height != args.line_height:
         ap.error(f'the loaded model takes lines of {net.height} rows, not {args.line_height}')
     trainer = Trainer(net, lr=args.lrate, weight_decay=args.weight_decay, warmup=args.warmup, schedule=args.schedule,
-                      cos_t_max=args.cos_max, cos_min_lr=args.cos_min_lr, seed=args.seed, matmul_precision=args.precision)
+                      cos_t_max=args.cos_max, cos_min_lr=args.cos_min_lr, seed=args.seed, matmul_precision=args.precision,
+                      freeze_backbone=args.freeze_backbone, log=print)
     res = fit(net, data, trainer, epochs=args.epochs, quit=args.quit, min_epochs=args.min_epochs, lag=args.lag, output=args.output)
     if res['best_epoch'] < 0:
         print('Model did not improve during training.')

@@ -302,6 +302,13 @@ int cocr_train_grad_buffer(cocr_model *m, void **device_ptr, size_t *n_floats);
  * cocr_train_step, hands slices of the gradient vector to autograd and copies the running statistics out -- conformer_ocr_amd/autograd.py. */
 int cocr_train_param_buffer(cocr_model *m, void **device_ptr, size_t *n_total, size_t *n_params);
 int cocr_train_layout(cocr_model *m, const char *name, int64_t *offset, int64_t *n_elems, int *is_param);
+/* Hand-over from a frozen-backbone phase: the output layer of `src` as cocr_decoder_adamw left it -- fp32 master copy of decoder.weight /
+ * decoder.bias, both AdamW moments and the step count k -- moves into the training state of `dst` (the tensors' cocr_train_layout offsets),
+ * device to device and ordered on `stream`.  cocr_train_adamw keeps PER-TENSOR step counts from then on: the adopted layer continues
+ * with the bias corrections of step k + 1, every other parameter with its own count (torch.optim.AdamW's state['step'] per parameter);
+ * with equal counts the step is the one it was.  A `src` that never took an optimizer step hands over its values, zero moments and
+ * k = 0.  COCR_ESTATE: `dst` has no training state; COCR_EINVAL: the two output layers differ in shape or device. */
+int cocr_train_adopt_decoder(cocr_model *dst, cocr_model *src, void *stream);
 
 #ifdef __cplusplus
 }
