@@ -14,6 +14,13 @@ F32, BF16, U8, I64 = 0, 1, 2, 3
 OK, EINVAL, ESTATE, EHIP, EUNSUPPORTED = 0, -1, -2, -3, -4
 
 
+OPTIMIZERS = {'AdamW': 0, 'Adam': 1, 'SGD': 2, 'RMSprop': 3}          # include/cocr.h COCR_OPT_*
+
+
+class OptimC(C.Structure):
+    _fields_ = [('kind', C.c_int)] + [(n, C.c_float) for n in ('lr', 'weight_decay', 'beta1', 'beta2', 'eps', 'momentum', 'alpha')]
+
+
 class HParamsC(C.Structure):
     _fields_ = [(n, C.c_int32) for n in (
         'num_classes', 'height', 'encoder_dim', 'num_encoder_layers', 'num_attention_heads',
@@ -59,6 +66,12 @@ SYMBOLS = {
     'cocr_train_param_buffer': (_I, [_P, C.POINTER(_P), C.POINTER(C.c_size_t), C.POINTER(C.c_size_t)]),
     'cocr_train_layout': (_I, [_P, C.c_char_p, C.POINTER(C.c_int64), C.POINTER(C.c_int64), C.POINTER(C.c_int)]),
     'cocr_train_adopt_decoder': (_I, [_P, _P, _P]),
+    'cocr_train_optim_step': (_I, [_P, _P, _P]),
+    'cocr_decoder_optim_step': (_I, [_P, _P, _P, _P, _P]),
+    'cocr_train_optim_state': (_I, [_P, C.POINTER(C.c_int), C.POINTER(C.c_int64), C.POINTER(C.c_int64), C.POINTER(_P), C.POINTER(_P), C.POINTER(C.c_size_t)]),
+    'cocr_train_optim_restore': (_I, [_P, _I, C.c_int64, C.c_int64]),
+    'cocr_decoder_optim_state': (_I, [_P, C.POINTER(C.c_int), C.POINTER(C.c_int64), C.POINTER(_P), C.POINTER(C.c_size_t)]),
+    'cocr_decoder_optim_restore': (_I, [_P, _I, C.c_int64, _P, C.c_size_t, _P]),
     'cocr_get_tensor': (_I, [_P, C.c_char_p, _P, C.c_int64, _P]),
     'cocr_preproc_width': (C.c_int32, [C.c_int32, C.c_int32, C.c_int32, C.c_int32]),
     'cocr_preproc_lines': (_I, [_P, _P, C.POINTER(C.c_int64), _I32P, _I32P, _I32P, _I, _I, _I, _I, _P, _I32P, _P]),

@@ -189,6 +189,7 @@ struct cocr_model {
     DevBuf<float> tr_part;                  // decoder backward: per-chunk partial sums of dW | db
     float *tr_state = nullptr;                         // decoder AdamW: fp32 master [W | b], then exp_avg, then exp_avg_sq
     long tr_step = 0;
+    int tr_kind = -1;                       // the optimizer kind (COCR_OPT_*) the output layer's steps were taken with; -1: none yet
     // debug / profile
     // hipGraph replay of the forward's launch sequence, keyed by the call's shapes and buffers
     bool use_graph = false;
@@ -1851,6 +1852,7 @@ static int decoder_master_init(cocr_model *m, hipStream_t s) {
         LAUNCH_CHECK();
     }
     m->tr_step = 0;
+    m->tr_kind = -1;
     return COCR_OK;
 }
 
@@ -1872,6 +1874,8 @@ extern "C" int cocr_decoder_adamw(cocr_model *m, const float *grad_weight, const
         grad_weight = m->tr_pad.p;
     }
     if (!m->tr_state) { const int rc = decoder_master_init(m, s); if (rc) return rc; }
+    if (m->tr_kind >= 0 && m->tr_kind != COCR_OPT_ADAMW) return fail(COCR_ESTATE, "the output layer's optimizer state is of kind %d, not AdamW", m->tr_kind);
+    m->tr_kind = COCR_OPT_ADAMW;
     const long t = ++m->tr_step;
     const float bc1 = 1.0f - (float)pow((double)beta1, (double)t), bc2s = (float)sqrt(1.0 - pow((double)beta2, (double)t));
     float *p = m->tr_state, *m1 = p + n, *m2 = m1 + n;

@@ -3,7 +3,9 @@
 //     cocr_train_step       RecognitionModel.training_step (model.py:129-152): train-mode forward (batch-statistics BatchNorm, dropout at the
 //                           reference's six sites), CTC criterion, backward through decoder AND encoder -> the gradient of every parameter
 //     cocr_train_adamw      torch.optim.AdamW over all parameters (model.py:283-284)
-//     cocr_train_adopt_decoder   the output layer a frozen-backbone phase trained (cocr_decoder_adamw), with its optimizer state, into this state
+//     cocr_train_optim_step      one step of AdamW / Adam / SGD / RMSprop over all parameters (model.py:283-289); cocr_decoder_optim_step: on the output layer
+//     cocr_train_adopt_decoder   the output layer a frozen-backbone phase trained (cocr_decoder_adamw / _optim_step), with its optimizer state, into this state
+//     cocr_train_optim_state / _restore, cocr_decoder_optim_state / _restore   the optimizer state out of and back into the library (resuming a fit)
 //     cocr_train_get        a parameter / buffer / gradient by name (checkpointing, tests)
 //     cocr_train_end        the trained values back into the model's state (re-finalize to serve them)
 // fp32 and correctness-first (train_enc.hip.h); every matrix product -- forward, input gradient, weight gradient -- is the exact-fp32 MFMA GEMM
@@ -18,8 +20,9 @@ struct TrainState {
     std::map<std::string, TrainEntry> idx;
     std::vector<std::string> order;
     size_t nparam = 0, ntotal = 0;            // floats: parameters first (the optimizer's range), then buffers (BatchNorm running statistics)
-    float *P = nullptr, *G = nullptr, *Mo = nullptr, *Vo = nullptr;
+    float *P = nullptr, *G = nullptr, *Mo = nullptr, *Vo = nullptr;      // Mo / Vo: the optimizer's slot 0 / slot 1 (their meaning per kind: k_optim_flat)
     long step = 0;
+    int kind = -1;                            // the optimizer kind (COCR_OPT_*) of the steps taken so far; -1: none yet
     long dec_steps = 0;                       // optimizer steps the output layer took BEFORE it was adopted (cocr_train_adopt_decoder): its own step count is step + dec_steps
     DevBuf<unsigned char> ws;                 // activations + scratch of one step
     DevBuf<float> pe;                         // sinusoid rows for relative positions T-1 ... -(T-1), (2T-1, D)
@@ -91,6 +94,8 @@ extern "C" int cocr_train_begin(cocr_model *m) {
     HIP_TRY(hipMalloc((void **)&t->Vo, t->nparam * 4));
     HIP_TRY(hipMemcpy(t->P, flat.data(), t->ntotal * 4, hipMemcpyHostToDevice));
     HIP_TRY(hipMemset(t->G, 0, t->nparam * 4));
+    // both slots zeroed: SGD's / RMSprop's momentum buffer needs no first-step flag (torch sets buf = g' on a tensor's first step, and
+    // mu 0 + g' is exactly that), the moments and square averages start at 0 as torch's do
     HIP_TRY(hipMemset(t->Mo, 0, t->nparam * 4));
     HIP_TRY(hipMemset(t->Vo, 0, t->nparam * 4));
     return COCR_OK;
@@ -157,13 +162,20 @@ extern "C" int cocr_train_end(cocr_model *m) {
     return COCR_OK;
 }
 
+static const char *optim_name(int kind) {
+    static const char *names[] = {"AdamW", "Adam", "SGD", "RMSprop"};
+    return kind >= 0 && kind < 4 ? names[kind] : "none";
+}
+
 extern "C" int cocr_train_adamw(cocr_model *m, float lr, float beta1, float beta2, float eps, float weight_decay, void *stream) {
     if (!m) return fail(COCR_EINVAL, "null argument");
     TrainState *t = m->train;
     if (!t) return fail(COCR_ESTATE, "cocr_train_begin has not been called");
     if (!(lr >= 0.f) || !(beta1 >= 0.f && beta1 < 1.f) || !(beta2 >= 0.f && beta2 < 1.f) || !(eps >= 0.f) || !(weight_decay >= 0.f))
         return fail(COCR_EINVAL, "invalid AdamW hyper-parameters");
+    if (t->kind >= 0 && t->kind != COCR_OPT_ADAMW) return fail(COCR_ESTATE, "the optimizer state is of kind %d, not AdamW", t->kind);
     HIP_TRY(hipSetDevice(m->device));
+    t->kind = COCR_OPT_ADAMW;
     t->step += 1;
     const float bc1 = 1.0f - powf(beta1, (float)t->step), bc2 = 1.0f - powf(beta2, (float)t->step);
     if (t->dec_steps == 0) {
@@ -198,6 +210,8 @@ extern "C" int cocr_train_adopt_decoder(cocr_model *dst, cocr_model *src, void *
     if (w == t->idx.end() || b == t->idx.end()) return fail(COCR_ESTATE, "the training state has no output layer");
     if (src->ncls != dst->ncls || src->rD != dst->rD || w->second.n != (size_t)src->ncls * src->rD || b->second.n != (size_t)src->ncls)
         return fail(COCR_EINVAL, "output layers differ: (%d, %d) into (%d, %d)", src->ncls, src->rD, dst->ncls, dst->rD);
+    if (src->tr_state && src->tr_kind >= 0 && t->kind >= 0 && src->tr_kind != t->kind)
+        return fail(COCR_EINVAL, "the two states have taken steps of different optimizer kinds (%s into %s)", optim_name(src->tr_kind), optim_name(t->kind));
     HIP_TRY(hipSetDevice(dst->device));
     hipStream_t s = (hipStream_t)stream;
     if (!src->tr_state) { const int rc = decoder_master_init(src, s); if (rc) return rc; }
@@ -210,6 +224,165 @@ extern "C" int cocr_train_adopt_decoder(cocr_model *dst, cocr_model *src, void *
         HIP_TRY(hipMemcpyAsync(dsts[i] + b->second.off, from + nw, (size_t)src->ncls * 4, hipMemcpyDeviceToDevice, s));
     }
     t->dec_steps = src->tr_step - t->step;        // (the layer's count is dst's own count + dec_steps: an adoption after dst has stepped keeps k exact)
+    if (t->kind < 0) t->kind = src->tr_kind;      // (slots and count mean what they meant in `src`; SGD / RMSprop read no count)
+    return COCR_OK;
+}
+
+// ---- one step of any optimizer kind ------------------------------------------------------------------------------------------------------------
+// torch.optim's own constructor checks
+static int optim_check(const cocr_optim *o) {
+    if (!o) return fail(COCR_EINVAL, "null argument");
+    if (o->kind < COCR_OPT_ADAMW || o->kind > COCR_OPT_RMSPROP) return fail(COCR_EINVAL, "unknown optimizer kind %d", o->kind);
+    if (!(o->lr >= 0.f)) return fail(COCR_EINVAL, "invalid learning rate %g", (double)o->lr);
+    if (!(o->weight_decay >= 0.f)) return fail(COCR_EINVAL, "invalid weight_decay %g", (double)o->weight_decay);
+    if (o->kind == COCR_OPT_ADAMW || o->kind == COCR_OPT_ADAM) {
+        if (!(o->beta1 >= 0.f && o->beta1 < 1.f) || !(o->beta2 >= 0.f && o->beta2 < 1.f)) return fail(COCR_EINVAL, "invalid beta (%g, %g)", (double)o->beta1, (double)o->beta2);
+        if (!(o->eps >= 0.f)) return fail(COCR_EINVAL, "invalid epsilon %g", (double)o->eps);
+    } else {
+        if (!(o->momentum >= 0.f)) return fail(COCR_EINVAL, "invalid momentum %g", (double)o->momentum);
+        if (o->kind == COCR_OPT_RMSPROP && (!(o->eps >= 0.f) || !(o->alpha >= 0.f))) return fail(COCR_EINVAL, "invalid epsilon / alpha (%g, %g)", (double)o->eps, (double)o->alpha);
+    }
+    return COCR_OK;
+}
+
+// n elements of (P, G, S0, S1); bc1 / bc2: the bias corrections of every element outside `ranges` (Adam kinds; null: no ranges)
+static int launch_optim(hipStream_t s, const cocr_optim *o, float *P, const float *G, float *S0, float *S1, size_t n, float bc1, float bc2, const AdamwRanges *ranges,
+                        bf16_t *serve_b, float *serve_f) {
+    if (n == 0) return COCR_OK;
+    // 16 bytes per lane where all four vectors are aligned at the same elements; otherwise (a slot that starts at an odd float offset of
+    // its allocation) every element goes the scalar way
+    size_t head = std::min<size_t>(n, (size_t)((16 - ((uintptr_t)P & 15)) & 15) / 4);
+    for (const void *q : {(const void *)(P + head), (const void *)(G + head), (const void *)(S0 + head), (const void *)(S1 + head)})
+        if ((uintptr_t)q & 15) head = n;
+    const size_t nvec = (n - head) / 4;
+    const OptimArgs a = {o->lr, o->weight_decay, o->beta1, o->beta2, o->eps, o->momentum, o->alpha, bc1, bc2};
+    const AdamwRanges r = ranges ? *ranges : AdamwRanges{};
+    const dim3 grid((unsigned)std::max<size_t>(1, std::min<size_t>((std::max(nvec, n - 4 * nvec) + 255) / 256, 2048))), block(256);
+    const bool flag = (o->kind == COCR_OPT_ADAMW || o->kind == COCR_OPT_ADAM) ? ranges != nullptr : o->momentum > 0.f;
+#define COCR_OPTIM_LAUNCH(K, F) hipLaunchKernelGGL((k_optim_flat<K, F>), grid, block, 0, s, P, G, S0, S1, n, head, nvec, a, r, serve_b, serve_f)
+    switch (o->kind * 2 + (flag ? 1 : 0)) {
+        case COCR_OPT_ADAMW * 2: COCR_OPTIM_LAUNCH(COCR_OPT_ADAMW, false); break;
+        case COCR_OPT_ADAMW * 2 + 1: COCR_OPTIM_LAUNCH(COCR_OPT_ADAMW, true); break;
+        case COCR_OPT_ADAM * 2: COCR_OPTIM_LAUNCH(COCR_OPT_ADAM, false); break;
+        case COCR_OPT_ADAM * 2 + 1: COCR_OPTIM_LAUNCH(COCR_OPT_ADAM, true); break;
+        case COCR_OPT_SGD * 2: COCR_OPTIM_LAUNCH(COCR_OPT_SGD, false); break;
+        case COCR_OPT_SGD * 2 + 1: COCR_OPTIM_LAUNCH(COCR_OPT_SGD, true); break;
+        case COCR_OPT_RMSPROP * 2: COCR_OPTIM_LAUNCH(COCR_OPT_RMSPROP, false); break;
+        default: COCR_OPTIM_LAUNCH(COCR_OPT_RMSPROP, true); break;
+    }
+#undef COCR_OPTIM_LAUNCH
+    LAUNCH_CHECK();
+    return COCR_OK;
+}
+
+extern "C" int cocr_train_optim_step(cocr_model *m, const cocr_optim *o, void *stream) {
+    if (!m || !o) return fail(COCR_EINVAL, "null argument");
+    TrainState *t = m->train;
+    if (!t) return fail(COCR_ESTATE, "cocr_train_begin has not been called");
+    { const int rc = optim_check(o); if (rc) return rc; }
+    if (t->kind >= 0 && t->kind != o->kind) return fail(COCR_ESTATE, "the optimizer state is %s's: a %s step cannot follow", optim_name(t->kind), optim_name(o->kind));
+    HIP_TRY(hipSetDevice(m->device));
+    t->kind = o->kind;
+    t->step += 1;
+    float bc1 = 1.f, bc2 = 1.f;
+    AdamwRanges r = {};
+    bool ranges = false;
+    if (o->kind == COCR_OPT_ADAMW || o->kind == COCR_OPT_ADAM) {      // (the corrections of cocr_train_adamw, expression for expression)
+        bc1 = 1.0f - powf(o->beta1, (float)t->step); bc2 = 1.0f - powf(o->beta2, (float)t->step);
+        if (t->dec_steps != 0) {
+            // per-tensor step counts: the adopted output layer is dec_steps steps ahead of every other parameter
+            const long k = t->step + t->dec_steps;
+            int i = 0;
+            for (const char *name : {"decoder.weight", "decoder.bias"}) {
+                const TrainEntry &e = t->idx.at(name);
+                r.lo[i] = e.off; r.hi[i] = e.off + e.n;
+                r.bc1[i] = 1.0f - powf(o->beta1, (float)k); r.bc2[i] = 1.0f - powf(o->beta2, (float)k);
+                ++i;
+            }
+            ranges = true;
+        }
+    }
+    return launch_optim((hipStream_t)stream, o, t->P, t->G, t->Mo, t->Vo, t->nparam, bc1, bc2, ranges ? &r : nullptr, nullptr, nullptr);
+}
+
+// The same step on the output layer's own state (fp32 master copy [W | b], slot 0, slot 1: created on the first call), the frozen-backbone
+// phase; the updated values also go where the next cocr_forward reads them (the compute dtype's copy of the weight, the fp32 bias).
+extern "C" int cocr_decoder_optim_step(cocr_model *m, const float *grad_weight, const float *grad_bias, const cocr_optim *o, void *stream) {
+    if (!m || !grad_weight || !grad_bias || !o) return fail(COCR_EINVAL, "null argument");
+    if (m->dtype < 0 || !m->blob) return fail(COCR_ESTATE, "model not finalized");
+    if (m->owner) return fail(COCR_ESTATE, "this model shares another model's weights: step the owner");
+    { const int rc = optim_check(o); if (rc) return rc; }
+    if (m->tr_state && m->tr_kind >= 0 && m->tr_kind != o->kind)
+        return fail(COCR_ESTATE, "the output layer's optimizer state is %s's: a %s step cannot follow", optim_name(m->tr_kind), optim_name(o->kind));
+    HIP_TRY(hipSetDevice(m->device));
+    hipStream_t s = (hipStream_t)stream;
+    const size_t nw = (size_t)m->ncls * m->D, nb = (size_t)m->ncls, n = nw + nb;
+    const size_t row_e = (size_t)m->D * 4, row_m = (size_t)m->rD * 4;      // engine / model row bytes of the decoder weight (equal unless padded)
+    if (m->padded) {    // the caller's (ncls, rD) gradient embedded in the engine's zero-padded rows
+        HIP_TRY(m->tr_pad.grow(nw));
+        HIP_TRY(hipMemsetAsync(m->tr_pad.p, 0, nw * 4, s));
+        HIP_TRY(hipMemcpy2DAsync(m->tr_pad.p, row_e, grad_weight, row_m, row_m, m->ncls, hipMemcpyDeviceToDevice, s));
+        grad_weight = m->tr_pad.p;
+    }
+    if (!m->tr_state) { const int rc = decoder_master_init(m, s); if (rc) return rc; }
+    m->tr_kind = o->kind;
+    const long k = ++m->tr_step;
+    float bc1 = 1.f, bc2 = 1.f;
+    if (o->kind == COCR_OPT_ADAMW || o->kind == COCR_OPT_ADAM) { bc1 = 1.0f - powf(o->beta1, (float)k); bc2 = 1.0f - powf(o->beta2, (float)k); }
+    float *p = m->tr_state, *s0 = p + n, *s1 = s0 + n;
+    const bool bf = m->dtype == COCR_BF16;
+    int rc = launch_optim(s, o, p, grad_weight, s0, s1, nw, bc1, bc2, nullptr, bf ? (bf16_t *)(m->blob + m->plan.wdec) : nullptr, bf ? nullptr : (float *)(m->blob + m->plan.wdec));
+    if (rc) return rc;
+    return launch_optim(s, o, p + nw, grad_bias, s0 + nw, s1 + nw, nb, bc1, bc2, nullptr, nullptr, (float *)(m->blob + m->plan.bdec));
+}
+
+// ---- the optimizer state out of and back into the library (resuming a fit) -----------------------------------------------------------------------
+extern "C" int cocr_train_optim_state(cocr_model *m, int *kind, int64_t *step, int64_t *dec_steps, void **slot0, void **slot1, size_t *n_floats) {
+    if (!m || !kind || !step || !dec_steps || !slot0 || !slot1 || !n_floats) return fail(COCR_EINVAL, "null argument");
+    TrainState *t = m->train;
+    if (!t) return fail(COCR_ESTATE, "cocr_train_begin has not been called");
+    *kind = t->kind; *step = t->step; *dec_steps = t->dec_steps;
+    *slot0 = t->Mo; *slot1 = t->Vo; *n_floats = t->nparam;
+    return COCR_OK;
+}
+
+extern "C" int cocr_train_optim_restore(cocr_model *m, int kind, int64_t step, int64_t dec_steps) {
+    if (!m) return fail(COCR_EINVAL, "null argument");
+    TrainState *t = m->train;
+    if (!t) return fail(COCR_ESTATE, "cocr_train_begin has not been called");
+    if (kind < -1 || kind > COCR_OPT_RMSPROP) return fail(COCR_EINVAL, "unknown optimizer kind %d", kind);
+    if (step < 0 || step + dec_steps < 0 || (kind < 0 && step != 0)) return fail(COCR_EINVAL, "invalid step counts (%lld, %lld) for kind %d", (long long)step, (long long)dec_steps, kind);
+    t->kind = kind; t->step = (long)step; t->dec_steps = (long)dec_steps;
+    return COCR_OK;
+}
+
+extern "C" int cocr_decoder_optim_state(cocr_model *m, int *kind, int64_t *step, void **state, size_t *n_floats) {
+    if (!m || !kind || !step || !state || !n_floats) return fail(COCR_EINVAL, "null argument");
+    if (m->dtype < 0 || !m->blob) return fail(COCR_ESTATE, "model not finalized");
+    *kind = m->tr_state ? m->tr_kind : -1;
+    *step = m->tr_state ? m->tr_step : 0;
+    *state = m->tr_state;
+    *n_floats = 3 * ((size_t)m->ncls * m->D + (size_t)m->ncls);
+    return COCR_OK;
+}
+
+extern "C" int cocr_decoder_optim_restore(cocr_model *m, int kind, int64_t step, const float *state_device, size_t n_floats, void *stream) {
+    if (!m || !state_device) return fail(COCR_EINVAL, "null argument");
+    if (m->dtype < 0 || !m->blob) return fail(COCR_ESTATE, "model not finalized");
+    if (m->owner) return fail(COCR_ESTATE, "this model shares another model's weights: restore the owner");
+    const size_t nw = (size_t)m->ncls * m->D, nb = (size_t)m->ncls, n = nw + nb;
+    if (n_floats != 3 * n) return fail(COCR_EINVAL, "the output layer's state has %zu floats, not %zu", 3 * n, n_floats);
+    if (kind < -1 || kind > COCR_OPT_RMSPROP || step < 0 || (kind < 0 && step != 0)) return fail(COCR_EINVAL, "invalid kind %d / step %lld", kind, (long long)step);
+    HIP_TRY(hipSetDevice(m->device));
+    hipStream_t s = (hipStream_t)stream;
+    if (!m->tr_state) { const int rc = decoder_master_init(m, s); if (rc) return rc; }
+    HIP_TRY(hipMemcpyAsync(m->tr_state, state_device, 3 * n * 4, hipMemcpyDeviceToDevice, s));
+    m->tr_kind = kind; m->tr_step = (long)step;
+    const bool bf = m->dtype == COCR_BF16;
+    hipLaunchKernelGGL(k_serve_copy, dim3(64), dim3(256), 0, s, (const float *)m->tr_state, nw, bf ? (bf16_t *)(m->blob + m->plan.wdec) : (bf16_t *)nullptr,
+                       bf ? (float *)nullptr : (float *)(m->blob + m->plan.wdec));
+    hipLaunchKernelGGL(k_serve_copy, dim3(1), dim3(256), 0, s, (const float *)(m->tr_state + nw), nb, (bf16_t *)nullptr, (float *)(m->blob + m->plan.bdec));
+    LAUNCH_CHECK();
     return COCR_OK;
 }
 

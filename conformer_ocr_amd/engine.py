@@ -358,6 +358,43 @@ class HipRecognizer:
             _lib.check(self.lib.cocr_decoder_adamw(self._h, C.c_void_p(grad_weight.data_ptr()), C.c_void_p(grad_bias.data_ptr()), float(lr),
                                                    float(betas[0]), float(betas[1]), float(eps), float(weight_decay), _stream_ptr(self.device)))
 
+    @staticmethod
+    def _optim(kind: str, lr: float, weight_decay: float, betas, eps: float, momentum: float, alpha: float) -> '_lib.OptimC':
+        if kind not in _lib.OPTIMIZERS:
+            raise ValueError(f'unknown optimizer {kind!r}: one of {", ".join(_lib.OPTIMIZERS)}')
+        return _lib.OptimC(_lib.OPTIMIZERS[kind], float(lr), float(weight_decay), float(betas[0]), float(betas[1]), float(eps), float(momentum), float(alpha))
+
+    def decoder_optim_step(self, kind: str, grad_weight: torch.Tensor, grad_bias: torch.Tensor, lr: float, weight_decay: float = 0.0,
+                           betas=(0.9, 0.999), eps: float = 1e-8, momentum: float = 0.0, alpha: float = 0.99) -> None:
+        """One step of torch.optim.{AdamW, Adam, SGD, RMSprop} (`kind`) on the decoder, state kept inside the engine; betas / eps
+        reach the Adam kinds, momentum SGD and RMSprop, alpha / eps RMSprop.  The first step fixes the kind."""
+        for g in (grad_weight, grad_bias):
+            if g.device != self.device or g.dtype != torch.float32 or not g.is_contiguous():
+                raise RuntimeError('gradients must be contiguous float32 tensors on the model device')
+        if grad_weight.shape != (self.hp.num_classes, self.hp.encoder_dim) or grad_bias.shape != (self.hp.num_classes,):
+            raise ValueError('gradient shapes do not match the decoder')
+        o = self._optim(kind, lr, weight_decay, betas, eps, momentum, alpha)
+        with torch.cuda.device(self.device):
+            _lib.check(self.lib.cocr_decoder_optim_step(self._h, C.c_void_p(grad_weight.data_ptr()), C.c_void_p(grad_bias.data_ptr()), C.byref(o),
+                                                        _stream_ptr(self.device)))
+
+    def decoder_optim_state(self) -> Dict:
+        """The output layer's optimizer state: {'kind': name or None, 'step', 'state': float32 torch view of the library's
+        [master copy | slot 0 | slot 1] vector, or None before the first step}."""
+        kind, step, p, n = C.c_int(), C.c_int64(), C.c_void_p(), C.c_size_t()
+        _lib.check(self.lib.cocr_decoder_optim_state(self._h, C.byref(kind), C.byref(step), C.byref(p), C.byref(n)))
+        names = {v: k for k, v in _lib.OPTIMIZERS.items()}
+        return {'kind': names.get(kind.value), 'step': int(step.value), 'state': self._device_view(p.value, n.value) if p.value else None}
+
+    def decoder_optim_restore(self, kind: Optional[str], step: int, state: torch.Tensor) -> None:
+        """Puts a `decoder_optim_state` back: the vector (float32, this device), the kind and the step count; the serving copy of
+        the output layer follows the master copy."""
+        if state.device != self.device or state.dtype != torch.float32 or not state.is_contiguous() or state.dim() != 1:
+            raise RuntimeError('the state must be a contiguous float32 vector on the model device')
+        with torch.cuda.device(self.device):
+            _lib.check(self.lib.cocr_decoder_optim_restore(self._h, -1 if kind is None else _lib.OPTIMIZERS[kind], int(step), C.c_void_p(state.data_ptr()),
+                                                           state.numel(), _stream_ptr(self.device)))
+
     def decoder_state(self) -> Dict[str, np.ndarray]:
         """{'decoder.weight', 'decoder.bias'}: float32 host copies of the (trained) output layer."""
         out = {}
@@ -430,16 +467,49 @@ class HipRecognizer:
         with torch.cuda.device(self.device):
             _lib.check(self.lib.cocr_train_adopt_decoder(self._h, src._h, _stream_ptr(self.device)))
 
+    def _device_view(self, ptr: int, n: int) -> torch.Tensor:
+        """`n` floats of library-owned device memory as a float32 torch view."""
+        class _Mem:
+            def __init__(s, owner):
+                s.owner = owner
+                s.__cuda_array_interface__ = {'shape': (n,), 'typestr': '<f4', 'data': (ptr, False), 'version': 2}
+        return torch.as_tensor(_Mem(self), device=self.device)
+
     def train_grad_buffer(self) -> torch.Tensor:
         """The flat gradient vector of all parameters as a float32 torch view of library-owned memory (for an all-reduce)."""
         p, n = C.c_void_p(), C.c_size_t()
         _lib.check(self.lib.cocr_train_grad_buffer(self._h, C.byref(p), C.byref(n)))
+        return self._device_view(p.value, n.value)
 
-        class _Mem:
-            def __init__(s, owner):
-                s.owner = owner
-                s.__cuda_array_interface__ = {'shape': (n.value,), 'typestr': '<f4', 'data': (p.value, False), 'version': 2}
-        return torch.as_tensor(_Mem(self), device=self.device)
+    def train_value_buffer(self) -> torch.Tensor:
+        """The flat value vector (all parameters in the gradient vector's layout, then the BatchNorm running statistics) as a float32
+        torch view of library-owned memory."""
+        p, n, npar = C.c_void_p(), C.c_size_t(), C.c_size_t()
+        _lib.check(self.lib.cocr_train_param_buffer(self._h, C.byref(p), C.byref(n), C.byref(npar)))
+        return self._device_view(p.value, n.value)
+
+    def train_optim_step(self, kind: str, lr: float, weight_decay: float = 0.0, betas=(0.9, 0.999), eps: float = 1e-8, momentum: float = 0.0,
+                         alpha: float = 0.99) -> None:
+        """One step of torch.optim.{AdamW, Adam, SGD, RMSprop} (`kind`) on all parameters with the gradients of the last `train_step`;
+        betas / eps reach the Adam kinds, momentum SGD and RMSprop, alpha / eps RMSprop (defaults are torch's).  The first step
+        fixes the kind: another kind afterwards raises."""
+        o = self._optim(kind, lr, weight_decay, betas, eps, momentum, alpha)
+        with torch.cuda.device(self.device):
+            _lib.check(self.lib.cocr_train_optim_step(self._h, C.byref(o), _stream_ptr(self.device)))
+
+    def train_optim_state(self) -> Dict:
+        """The whole-network optimizer state: {'kind': name or None before the first step, 'step', 'dec_steps', 'slot0', 'slot1'}; the
+        slots are float32 torch views of the library's two state vectors (the gradient vector's layout; their meaning per kind:
+        include/cocr.h)."""
+        kind, step, dec, p0, p1, n = C.c_int(), C.c_int64(), C.c_int64(), C.c_void_p(), C.c_void_p(), C.c_size_t()
+        _lib.check(self.lib.cocr_train_optim_state(self._h, C.byref(kind), C.byref(step), C.byref(dec), C.byref(p0), C.byref(p1), C.byref(n)))
+        names = {v: k for k, v in _lib.OPTIMIZERS.items()}
+        return {'kind': names.get(kind.value), 'step': int(step.value), 'dec_steps': int(dec.value),
+                'slot0': self._device_view(p0.value, n.value), 'slot1': self._device_view(p1.value, n.value)}
+
+    def train_optim_restore(self, kind: Optional[str], step: int, dec_steps: int = 0) -> None:
+        """The counters of a restored state, after the caller has written `train_value_buffer()` and the two slots."""
+        _lib.check(self.lib.cocr_train_optim_restore(self._h, -1 if kind is None else _lib.OPTIMIZERS[kind], int(step), int(dec_steps)))
 
     def train_end(self) -> None:
         """Trained values back into the model's state; `finalize()` again to serve them."""

@@ -276,7 +276,7 @@ int cocr_profile(cocr_model *m, int on);
 int cocr_profile_read(cocr_model *m, char *names, size_t names_len, double *ms, int64_t *launches, int max_entries);
 
 /* ---- Training step of the whole network: RecognitionModel.training_step (model.py:129-152) + torch.optim.AdamW (model.py:283-284).
- * fp32.  cocr_train_begin copies every parameter / buffer given through cocr_set_tensor to the device (AdamW state zeroed);
+ * fp32.  cocr_train_begin copies every parameter / buffer given through cocr_set_tensor to the device (optimizer state zeroed);
  * cocr_train_step runs the TRAIN-mode forward (BatchNorm1d batch statistics over all positions of the padded batch + running-statistics
  * update, dropout at the reference's six sites with probabilities dropout_p = {input, feed_forward, attention, conv}, masks from
  * (seed, site, index)), the criterion nn.CTCLoss(reduction='sum', zero_infinity=True) on log_softmax(probits), and the backward through
@@ -309,6 +309,41 @@ int cocr_train_layout(cocr_model *m, const char *name, int64_t *offset, int64_t 
  * with equal counts the step is the one it was.  A `src` that never took an optimizer step hands over its values, zero moments and
  * k = 0.  COCR_ESTATE: `dst` has no training state; COCR_EINVAL: the two output layers differ in shape or device. */
 int cocr_train_adopt_decoder(cocr_model *dst, cocr_model *src, void *stream);
+
+/* One optimizer step of any of the reference's four kinds (`--optimizer`, model.py:283-289) on the gradients of the last cocr_train_step:
+ * cocr_train_optim_step over all parameters, cocr_decoder_optim_step on the output layer of a finalized model (the frozen-backbone
+ * phase; as cocr_decoder_adamw it keeps an fp32 master copy and writes the values where the next cocr_forward reads them).
+ * Per element, in fp32, torch's single-tensor definitions; g' = g + weight_decay p for every kind but AdamW:
+ *   AdamW    p *= 1 - lr weight_decay;  m = beta1 m + (1 - beta1) g;  v = beta2 v + (1 - beta2) g^2;
+ *            p -= lr / (1 - beta1^t) m / (sqrt(v) / sqrt(1 - beta2^t) + eps)         -- bit for bit what cocr_train_adamw computes
+ *   Adam     the same moments and update on g', no decoupled decay (L2 decay folded into the gradient)
+ *   SGD      buf = momentum buf + g';  p -= lr buf;  momentum = 0: p -= lr g' (dampening 0, no Nesterov, as the reference constructs it)
+ *   RMSprop  sq = alpha sq + (1 - alpha) g'^2;  a = sqrt(sq) + eps;  momentum > 0: buf = momentum buf + g' / a, p -= lr buf;
+ *            else p -= lr g' / a                                                       (not centered)
+ * The optimizer state is two float vectors ("slots") beside the parameters, zeroed by cocr_train_begin; their meaning depends on the kind:
+ *   AdamW, Adam: slot 0 exp_avg, slot 1 exp_avg_sq;   SGD: slot 0 momentum buffer;   RMSprop: slot 0 square_avg, slot 1 momentum buffer.
+ * A state remembers the kind of its first step: a step of another kind is COCR_ESTATE (cocr_train_adamw / cocr_decoder_adamw count as
+ * AdamW steps).  Hyper-parameters outside torch's own checks (negative lr, weight_decay, eps, momentum or alpha, a beta outside [0, 1))
+ * are COCR_EINVAL.  Unused fields of cocr_optim are ignored (torch's defaults: beta 0.9 / 0.999, eps 1e-8, alpha 0.99).
+ * cocr_train_adopt_decoder hands over slots and step count whatever the kind and refuses (COCR_EINVAL) two states that have taken
+ * steps of different kinds; the per-tensor step counts matter to AdamW and Adam only.  Stream-ordered, no synchronisation. */
+enum { COCR_OPT_ADAMW = 0, COCR_OPT_ADAM = 1, COCR_OPT_SGD = 2, COCR_OPT_RMSPROP = 3 };
+typedef struct { int kind; float lr, weight_decay, beta1, beta2, eps, momentum, alpha; } cocr_optim;
+int cocr_train_optim_step(cocr_model *m, const cocr_optim *o, void *stream);
+int cocr_decoder_optim_step(cocr_model *m, const float *grad_weight, const float *grad_bias, const cocr_optim *o, void *stream);
+
+/* The optimizer state out of the library and back, for continuing an interrupted fit.
+ * cocr_train_optim_state: the kind (-1 before the first step), the step count, the steps an adopted output layer is ahead, and DEVICE
+ * pointers to the two slots (*n_floats each: the layout of cocr_train_grad_buffer).  The caller copies them out; to restore it writes
+ * values (cocr_train_param_buffer) and slots back and then calls cocr_train_optim_restore with the three counters.
+ * cocr_decoder_optim_state: the output layer's state of a finalized model, *state a DEVICE pointer to *n_floats floats
+ * [master copy | slot 0 | slot 1] in the engine's layout, NULL before the first step (*n_floats is set either way).
+ * cocr_decoder_optim_restore copies such a vector in (device to device, ordered on `stream`), sets kind and step count, and writes the
+ * master copy's values where cocr_forward reads them.  COCR_EINVAL: n_floats does not fit the model, or invalid counters. */
+int cocr_train_optim_state(cocr_model *m, int *kind, int64_t *step, int64_t *dec_steps, void **slot0, void **slot1, size_t *n_floats);
+int cocr_train_optim_restore(cocr_model *m, int kind, int64_t step, int64_t dec_steps);
+int cocr_decoder_optim_state(cocr_model *m, int *kind, int64_t *step, void **state, size_t *n_floats);
+int cocr_decoder_optim_restore(cocr_model *m, int kind, int64_t step, const float *state_device, size_t n_floats, void *stream);
 
 #ifdef __cplusplus
 }

@@ -1,6 +1,11 @@
 #!/usr/bin/env python3
-"""Time of one training step of the whole network (cocr_train_step + cocr_train_adamw; fp32) and a short training run on synthetic text
-lines:   python tools/train_bench.py [--config cfg2] [--batch 32] [--width 1200] [--steps 5] [--fit 0]
+"""Time of one training step of the whole network (cocr_train_step + the optimizer step; fp32) and a short training run on synthetic text
+lines:   python tools/train_bench.py [--config cfg2] [--batch 32] [--width 1200] [--steps 5] [--fit 0] [--optimizer KIND]
+--optimizer KIND (AdamW, Adam, SGD, RMSprop; --momentum M): the Trainer steps with that optimizer, and the optimizer step ALONE is timed
+with HIP events next to the whole step -- `cocr_train_optim_step` of that kind and, alternating with it in the same process,
+`cocr_train_adamw` (the kernel AdamW had before the general one), each on an engine of its own holding the gradients of a real step:
+--optim-rounds rounds of --optim-reps back-to-back calls between two events; the median / least / largest round per call and the
+bytes per second the median implies (4 n x (vectors read + vectors written), n = the parameter count).
 --fit K: K steps on text lines (conformer_ocr_amd.synth.make_text_lines) from random weights, printing the loss and the greedy CER of
 the trained model against the ground truth every few steps (the inference path serves the trained weights after sync)."""
 import argparse
@@ -27,6 +32,10 @@ ap.add_argument('--width', type=int, default=1200)
 ap.add_argument('--steps', type=int, default=5)
 ap.add_argument('--fit', type=int, default=0)
 ap.add_argument('--lr', type=float, default=1e-3)
+ap.add_argument('--optimizer', default=None, choices=('AdamW', 'Adam', 'SGD', 'RMSprop'))
+ap.add_argument('--momentum', type=float, default=0.9)
+ap.add_argument('--optim-reps', type=int, default=50)
+ap.add_argument('--optim-rounds', type=int, default=9)
 ap.add_argument('--matmul', default='highest', help="'highest' (exact fp32 products) or 'medium' (bf16-rounded operands, the reference's training setting)")
 args = ap.parse_args()
 kw = {'num_encoder_layers': args.layers} if args.layers else {}
@@ -39,7 +48,7 @@ net = net.to('cuda:0').eval()
 image, lens, texts, _ = synth.make_text_lines(args.batch, hp.height, args.width, seed=3)
 batch = {'image': torch.from_numpy(image).cuda(), 'seq_lens': torch.from_numpy(lens), 'target': torch.tensor([c for t in texts for c in t]),
          'target_lens': torch.tensor([len(t) for t in texts])}
-tr = Trainer(net, lr=args.lr, weight_decay=1e-2, warmup=10, matmul_precision=args.matmul)
+tr = Trainer(net, lr=args.lr, weight_decay=1e-2, warmup=10, matmul_precision=args.matmul, optimizer=args.optimizer or 'AdamW', momentum=args.momentum)
 out = {'config': args.config, 'layers': hp.num_encoder_layers, 'batch': args.batch, 'width': args.width}
 tr.training_step(batch)
 torch.cuda.synchronize()
@@ -49,6 +58,45 @@ for _ in range(args.steps):
 torch.cuda.synchronize()
 dt = (time.perf_counter() - t0) / args.steps
 out.update(ms_per_step=round(dt * 1e3, 2), lines_per_s=round(args.batch / dt, 1), last_loss=loss)
+if args.optimizer:
+    from conformer_ocr_amd.engine import HipRecognizer
+
+    def optim_engine():
+        eng = HipRecognizer(hp, torch.device('cuda', 0), 'fp32')
+        eng.load_state(state)
+        eng.train_begin()
+        eng.train_grad_buffer().copy_(tr.engine.train_grad_buffer())           # the gradients of the last real step
+        return eng
+
+    kind = args.optimizer
+    mom = args.momentum if kind in ('SGD', 'RMSprop') else 0.0
+    old_eng, new_eng = optim_engine(), optim_engine()
+    n = new_eng.train_grad_buffer().numel()
+    # vectors of n floats the step reads + writes: P twice, G once, every slot it uses twice
+    slots = {'AdamW': 2, 'Adam': 2, 'SGD': 1 if mom > 0 else 0, 'RMSprop': 2 if mom > 0 else 1}[kind]
+    calls = {'cocr_train_adamw': lambda: old_eng.train_adamw(args.lr, weight_decay=1e-2),
+             f'cocr_train_optim_step[{kind}]': lambda: new_eng.train_optim_step(kind, args.lr, weight_decay=1e-2, momentum=mom)}
+    times = {k: [] for k in calls}
+    for fn in calls.values():
+        for _ in range(5):
+            fn()
+    torch.cuda.synchronize()
+    for _ in range(args.optim_rounds):
+        for name, fn in calls.items():                                         # alternating: both see the same neighbours on the machine
+            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            e0.record()
+            for _ in range(args.optim_reps):
+                fn()
+            e1.record()
+            e1.synchronize()
+            times[name].append(e0.elapsed_time(e1) * 1e3 / args.optim_reps)
+    rep = {'params': n, 'momentum': mom}
+    for name, ts in times.items():
+        ts = sorted(ts)
+        nbytes = 4 * n * (3 + 2 * (2 if name == 'cocr_train_adamw' else slots))
+        rep[name] = {'us_median': round(ts[len(ts) // 2], 2), 'us_min': round(ts[0], 2), 'us_max': round(ts[-1], 2), 'bytes': nbytes,
+                     'GB_per_s': round(nbytes / ts[len(ts) // 2] / 1e3, 1)}
+    out['optimizer_step'] = rep
 if args.fit:
     hist = []
     for step in range(args.fit):
