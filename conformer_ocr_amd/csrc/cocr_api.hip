@@ -1856,41 +1856,6 @@ static int decoder_master_init(cocr_model *m, hipStream_t s) {
     return COCR_OK;
 }
 
-extern "C" int cocr_decoder_adamw(cocr_model *m, const float *grad_weight, const float *grad_bias, float lr, float beta1, float beta2, float eps,
-                                  float weight_decay, void *stream) {
-    if (!m || !grad_weight || !grad_bias) return fail(COCR_EINVAL, "null argument");
-    if (m->dtype < 0 || !m->blob) return fail(COCR_ESTATE, "model not finalized");
-    if (m->owner) return fail(COCR_ESTATE, "this model shares another model's weights: step the owner");
-    if (!(lr >= 0.f) || !(beta1 >= 0.f && beta1 < 1.f) || !(beta2 >= 0.f && beta2 < 1.f) || !(eps >= 0.f) || !(weight_decay >= 0.f))
-        return fail(COCR_EINVAL, "invalid AdamW hyper-parameters");            // torch.optim.AdamW's own checks
-    HIP_TRY(hipSetDevice(m->device));
-    hipStream_t s = (hipStream_t)stream;
-    const size_t nw = (size_t)m->ncls * m->D, nb = (size_t)m->ncls, n = nw + nb;
-    const size_t row_e = (size_t)m->D * 4, row_m = (size_t)m->rD * 4;      // engine / model row bytes of the decoder weight (equal unless padded)
-    if (m->padded) {    // the caller's (ncls, rD) gradient embedded in the engine's zero-padded rows
-        HIP_TRY(m->tr_pad.grow(nw));
-        HIP_TRY(hipMemsetAsync(m->tr_pad.p, 0, nw * 4, s));
-        HIP_TRY(hipMemcpy2DAsync(m->tr_pad.p, row_e, grad_weight, row_m, row_m, m->ncls, hipMemcpyDeviceToDevice, s));
-        grad_weight = m->tr_pad.p;
-    }
-    if (!m->tr_state) { const int rc = decoder_master_init(m, s); if (rc) return rc; }
-    if (m->tr_kind >= 0 && m->tr_kind != COCR_OPT_ADAMW) return fail(COCR_ESTATE, "the output layer's optimizer state is of kind %d, not AdamW", m->tr_kind);
-    m->tr_kind = COCR_OPT_ADAMW;
-    const long t = ++m->tr_step;
-    const float bc1 = 1.0f - (float)pow((double)beta1, (double)t), bc2s = (float)sqrt(1.0 - pow((double)beta2, (double)t));
-    float *p = m->tr_state, *m1 = p + n, *m2 = m1 + n;
-    if (m->dtype == COCR_BF16)
-        hipLaunchKernelGGL((adamw_kernel<bf16_t>), dim3(ceil_div((int)nw, 256)), dim3(256), 0, s, p, grad_weight, m1, m2, nw, lr, beta1, beta2, eps, weight_decay, bc1, bc2s,
-                           (bf16_t *)(m->blob + m->plan.wdec), (float *)nullptr);
-    else
-        hipLaunchKernelGGL((adamw_kernel<float>), dim3(ceil_div((int)nw, 256)), dim3(256), 0, s, p, grad_weight, m1, m2, nw, lr, beta1, beta2, eps, weight_decay, bc1, bc2s,
-                           (float *)nullptr, (float *)(m->blob + m->plan.wdec));
-    hipLaunchKernelGGL((adamw_kernel<float>), dim3(ceil_div((int)nb, 256)), dim3(256), 0, s, p + nw, grad_bias, m1 + nw, m2 + nw, nb, lr, beta1, beta2, eps, weight_decay, bc1, bc2s,
-                       (float *)nullptr, (float *)(m->blob + m->plan.bdec));
-    LAUNCH_CHECK();
-    return COCR_OK;
-}
-
 extern "C" int cocr_get_tensor(cocr_model *m, const char *name, float *host_out, int64_t max_elems, void *stream) {
     if (!m || !name || !host_out) return fail(COCR_EINVAL, "null argument");
     const bool is_w = !strcmp(name, "decoder.weight"), is_b = !strcmp(name, "decoder.bias");

@@ -101,6 +101,8 @@ __global__ __launch_bounds__(256) void decoder_igrad_kernel(const float *__restr
 // torch.optim.AdamW (decoupled weight decay, no amsgrad), one step over n parameters:
 //   p *= 1 - lr wd;  m = b1 m + (1 - b1) g;  v = b2 v + (1 - b2) g^2;  p -= (lr / (1 - b1^t)) m / (sqrt(v) / sqrt(1 - b2^t) + eps)
 // The fp32 master copy stays in `p`; `blob_t` / `blob_f32` receive the value the forward reads (compute dtype / fp32), whichever is given.
+// Kept beside k_optim_flat<AdamW> on purpose: bc1 and sqrt(1 - b2^t) come from the host in double and the update is grouped
+// (lr / bc1) (m / denom), so folding this into the general step would move every frozen-backbone fit's master weights in the last place.
 template <typename T>
 __global__ __launch_bounds__(256) void adamw_kernel(float *__restrict__ p, const float *__restrict__ g, float *__restrict__ m1, float *__restrict__ m2, size_t n,
                                                     float lr, float b1, float b2, float eps, float wd, float bc1, float bc2_sqrt, T *__restrict__ blob_t,

@@ -305,28 +305,37 @@ extern "C" int cocr_train_optim_step(cocr_model *m, const cocr_optim *o, void *s
     return launch_optim((hipStream_t)stream, o, t->P, t->G, t->Mo, t->Vo, t->nparam, bc1, bc2, ranges ? &r : nullptr, nullptr, nullptr);
 }
 
-// The same step on the output layer's own state (fp32 master copy [W | b], slot 0, slot 1: created on the first call), the frozen-backbone
-// phase; the updated values also go where the next cocr_forward reads them (the compute dtype's copy of the weight, the fp32 bias).
-extern "C" int cocr_decoder_optim_step(cocr_model *m, const float *grad_weight, const float *grad_bias, const cocr_optim *o, void *stream) {
-    if (!m || !grad_weight || !grad_bias || !o) return fail(COCR_EINVAL, "null argument");
+// What a step on the output layer's own state (fp32 master copy [W | b], slot 0, slot 1: created on the first call; the frozen-backbone
+// phase) starts with, whichever kernel follows: the checks, the caller's gradient at the engine's row width (*grad_weight), the sticky
+// kind, the step count (*k).
+static int decoder_step_begin(cocr_model *m, const float **grad_weight, const float *grad_bias, const cocr_optim *o, hipStream_t s, long *k) {
+    if (!m || !*grad_weight || !grad_bias || !o) return fail(COCR_EINVAL, "null argument");
     if (m->dtype < 0 || !m->blob) return fail(COCR_ESTATE, "model not finalized");
     if (m->owner) return fail(COCR_ESTATE, "this model shares another model's weights: step the owner");
     { const int rc = optim_check(o); if (rc) return rc; }
-    if (m->tr_state && m->tr_kind >= 0 && m->tr_kind != o->kind)
-        return fail(COCR_ESTATE, "the output layer's optimizer state is %s's: a %s step cannot follow", optim_name(m->tr_kind), optim_name(o->kind));
     HIP_TRY(hipSetDevice(m->device));
-    hipStream_t s = (hipStream_t)stream;
-    const size_t nw = (size_t)m->ncls * m->D, nb = (size_t)m->ncls, n = nw + nb;
-    const size_t row_e = (size_t)m->D * 4, row_m = (size_t)m->rD * 4;      // engine / model row bytes of the decoder weight (equal unless padded)
     if (m->padded) {    // the caller's (ncls, rD) gradient embedded in the engine's zero-padded rows
+        const size_t nw = (size_t)m->ncls * m->D, row_e = (size_t)m->D * 4, row_m = (size_t)m->rD * 4;
         HIP_TRY(m->tr_pad.grow(nw));
         HIP_TRY(hipMemsetAsync(m->tr_pad.p, 0, nw * 4, s));
-        HIP_TRY(hipMemcpy2DAsync(m->tr_pad.p, row_e, grad_weight, row_m, row_m, m->ncls, hipMemcpyDeviceToDevice, s));
-        grad_weight = m->tr_pad.p;
+        HIP_TRY(hipMemcpy2DAsync(m->tr_pad.p, row_e, *grad_weight, row_m, row_m, m->ncls, hipMemcpyDeviceToDevice, s));
+        *grad_weight = m->tr_pad.p;
     }
     if (!m->tr_state) { const int rc = decoder_master_init(m, s); if (rc) return rc; }
+    if (m->tr_kind >= 0 && m->tr_kind != o->kind)
+        return fail(COCR_ESTATE, "the output layer's optimizer state is %s's: a %s step cannot follow", optim_name(m->tr_kind), optim_name(o->kind));
     m->tr_kind = o->kind;
-    const long k = ++m->tr_step;
+    *k = ++m->tr_step;
+    return COCR_OK;
+}
+
+// The step of cocr_train_optim_step on that state; the updated values also go where the next cocr_forward reads them (the compute
+// dtype's copy of the weight, the fp32 bias).
+extern "C" int cocr_decoder_optim_step(cocr_model *m, const float *grad_weight, const float *grad_bias, const cocr_optim *o, void *stream) {
+    hipStream_t s = (hipStream_t)stream;
+    long k;
+    { const int rc = decoder_step_begin(m, &grad_weight, grad_bias, o, s, &k); if (rc) return rc; }
+    const size_t nw = (size_t)m->ncls * m->D, nb = (size_t)m->ncls, n = nw + nb;
     float bc1 = 1.f, bc2 = 1.f;
     if (o->kind == COCR_OPT_ADAMW || o->kind == COCR_OPT_ADAM) { bc1 = 1.0f - powf(o->beta1, (float)k); bc2 = 1.0f - powf(o->beta2, (float)k); }
     float *p = m->tr_state, *s0 = p + n, *s1 = s0 + n;
@@ -334,6 +343,29 @@ extern "C" int cocr_decoder_optim_step(cocr_model *m, const float *grad_weight, 
     int rc = launch_optim(s, o, p, grad_weight, s0, s1, nw, bc1, bc2, nullptr, bf ? (bf16_t *)(m->blob + m->plan.wdec) : nullptr, bf ? nullptr : (float *)(m->blob + m->plan.wdec));
     if (rc) return rc;
     return launch_optim(s, o, p + nw, grad_bias, s0 + nw, s1 + nw, nb, bc1, bc2, nullptr, nullptr, (float *)(m->blob + m->plan.bdec));
+}
+
+// torch.optim.AdamW on the same state through adamw_kernel (train.hip.h), the step every frozen-backbone AdamW fit has taken.  NOT
+// cocr_decoder_optim_step with kind AdamW: see the note at the kernel.
+extern "C" int cocr_decoder_adamw(cocr_model *m, const float *grad_weight, const float *grad_bias, float lr, float beta1, float beta2, float eps,
+                                  float weight_decay, void *stream) {
+    const cocr_optim o = {COCR_OPT_ADAMW, lr, weight_decay, beta1, beta2, eps};
+    hipStream_t s = (hipStream_t)stream;
+    long t;
+    { const int rc = decoder_step_begin(m, &grad_weight, grad_bias, &o, s, &t); if (rc) return rc; }
+    const size_t nw = (size_t)m->ncls * m->D, nb = (size_t)m->ncls, n = nw + nb;
+    const float bc1 = 1.0f - (float)pow((double)beta1, (double)t), bc2s = (float)sqrt(1.0 - pow((double)beta2, (double)t));
+    float *p = m->tr_state, *m1 = p + n, *m2 = m1 + n;
+    if (m->dtype == COCR_BF16)
+        hipLaunchKernelGGL((adamw_kernel<bf16_t>), dim3(ceil_div((int)nw, 256)), dim3(256), 0, s, p, grad_weight, m1, m2, nw, lr, beta1, beta2, eps, weight_decay, bc1, bc2s,
+                           (bf16_t *)(m->blob + m->plan.wdec), (float *)nullptr);
+    else
+        hipLaunchKernelGGL((adamw_kernel<float>), dim3(ceil_div((int)nw, 256)), dim3(256), 0, s, p, grad_weight, m1, m2, nw, lr, beta1, beta2, eps, weight_decay, bc1, bc2s,
+                           (float *)nullptr, (float *)(m->blob + m->plan.wdec));
+    hipLaunchKernelGGL((adamw_kernel<float>), dim3(ceil_div((int)nb, 256)), dim3(256), 0, s, p + nw, grad_bias, m1 + nw, m2 + nw, nb, lr, beta1, beta2, eps, weight_decay, bc1, bc2s,
+                       (float *)nullptr, (float *)(m->blob + m->plan.bdec));
+    LAUNCH_CHECK();
+    return COCR_OK;
 }
 
 // ---- the optimizer state out of and back into the library (resuming a fit) -----------------------------------------------------------------------

@@ -349,14 +349,17 @@ class HipRecognizer:
     def decoder_adamw(self, grad_weight: torch.Tensor, grad_bias: torch.Tensor, lr: float, betas=(0.9, 0.999), eps: float = 1e-8,
                       weight_decay: float = 1e-2) -> None:
         """One torch.optim.AdamW step on the decoder (state kept inside the engine); defaults are torch's."""
+        self._check_decoder_grads(grad_weight, grad_bias)
+        with torch.cuda.device(self.device):
+            _lib.check(self.lib.cocr_decoder_adamw(self._h, C.c_void_p(grad_weight.data_ptr()), C.c_void_p(grad_bias.data_ptr()), float(lr),
+                                                   float(betas[0]), float(betas[1]), float(eps), float(weight_decay), _stream_ptr(self.device)))
+
+    def _check_decoder_grads(self, grad_weight: torch.Tensor, grad_bias: torch.Tensor) -> None:
         for g in (grad_weight, grad_bias):
             if g.device != self.device or g.dtype != torch.float32 or not g.is_contiguous():
                 raise RuntimeError('gradients must be contiguous float32 tensors on the model device')
         if grad_weight.shape != (self.hp.num_classes, self.hp.encoder_dim) or grad_bias.shape != (self.hp.num_classes,):
             raise ValueError('gradient shapes do not match the decoder')
-        with torch.cuda.device(self.device):
-            _lib.check(self.lib.cocr_decoder_adamw(self._h, C.c_void_p(grad_weight.data_ptr()), C.c_void_p(grad_bias.data_ptr()), float(lr),
-                                                   float(betas[0]), float(betas[1]), float(eps), float(weight_decay), _stream_ptr(self.device)))
 
     @staticmethod
     def _optim(kind: str, lr: float, weight_decay: float, betas, eps: float, momentum: float, alpha: float) -> '_lib.OptimC':
@@ -368,11 +371,7 @@ class HipRecognizer:
                            betas=(0.9, 0.999), eps: float = 1e-8, momentum: float = 0.0, alpha: float = 0.99) -> None:
         """One step of torch.optim.{AdamW, Adam, SGD, RMSprop} (`kind`) on the decoder, state kept inside the engine; betas / eps
         reach the Adam kinds, momentum SGD and RMSprop, alpha / eps RMSprop.  The first step fixes the kind."""
-        for g in (grad_weight, grad_bias):
-            if g.device != self.device or g.dtype != torch.float32 or not g.is_contiguous():
-                raise RuntimeError('gradients must be contiguous float32 tensors on the model device')
-        if grad_weight.shape != (self.hp.num_classes, self.hp.encoder_dim) or grad_bias.shape != (self.hp.num_classes,):
-            raise ValueError('gradient shapes do not match the decoder')
+        self._check_decoder_grads(grad_weight, grad_bias)
         o = self._optim(kind, lr, weight_decay, betas, eps, momentum, alpha)
         with torch.cuda.device(self.device):
             _lib.check(self.lib.cocr_decoder_optim_step(self._h, C.c_void_p(grad_weight.data_ptr()), C.c_void_p(grad_bias.data_ptr()), C.byref(o),
@@ -419,7 +418,7 @@ class HipRecognizer:
         """`RecognitionModel.training_step` without the optimizer (reference model.py:129-152): train-mode forward, summed CTC loss,
         backward through decoder and encoder.  lines (N,H,W) float32 / uint8 on this device; lens pixel widths; targets the
         concatenated labels, label_lens their per-line counts; dropout = (input, feed_forward, attention, conv) probabilities.
-        Returns the loss; the gradients stay on the device (`train_grad`, `train_adamw`)."""
+        Returns the loss; the gradients stay on the device (`train_grad`, `train_optim_step`)."""
         if lines.device != self.device or lines.dim() != 3:
             raise ValueError('expected a (N,H,W) batch on the model device')
         ldt = _lib.U8 if lines.dtype == torch.uint8 else _lib.F32
@@ -461,8 +460,8 @@ class HipRecognizer:
             _lib.check(self.lib.cocr_train_adamw(self._h, float(lr), float(betas[0]), float(betas[1]), float(eps), float(weight_decay), _stream_ptr(self.device)))
 
     def train_adopt_decoder(self, src: 'HipRecognizer') -> None:
-        """The output layer of `src` as its `decoder_adamw` steps left it (fp32 master copy, both moments, step count k) into this
-        engine's training state, device to device on the current stream; `train_adamw` continues that layer at step k + 1 and every
+        """The output layer of `src` as its decoder steps left it (fp32 master copy, both slots, step count k) into this engine's
+        training state, device to device on the current stream; the optimizer step continues that layer at step k + 1 and every
         other parameter at its own count."""
         with torch.cuda.device(self.device):
             _lib.check(self.lib.cocr_train_adopt_decoder(self._h, src._h, _stream_ptr(self.device)))

@@ -186,7 +186,7 @@ def test_adoption_refuses_states_of_different_kinds():
         dst.train_adopt_decoder(src)
     with pytest.raises(RuntimeError, match='cannot follow'):
         src.decoder_optim_step('SGD', gw, gb, LR)
-    with pytest.raises(RuntimeError, match='not AdamW'):
+    with pytest.raises(RuntimeError, match="the output layer's optimizer state is RMSprop's: a AdamW step cannot follow"):
         src.decoder_adamw(gw, gb, LR)
 
 

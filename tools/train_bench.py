@@ -1,11 +1,12 @@
 #!/usr/bin/env python3
 """Time of one training step of the whole network (cocr_train_step + the optimizer step; fp32) and a short training run on synthetic text
-lines:   python tools/train_bench.py [--config cfg2] [--batch 32] [--width 1200] [--steps 5] [--fit 0] [--optimizer KIND]
+lines:   python tools/train_bench.py [--config cfg2] [--batch 32] [--width 1200] [--steps 5] [--fit 0] [--optimizer KIND [--dec-steps N]]
 --optimizer KIND (AdamW, Adam, SGD, RMSprop; --momentum M): the Trainer steps with that optimizer, and the optimizer step ALONE is timed
 with HIP events next to the whole step -- `cocr_train_optim_step` of that kind and, alternating with it in the same process,
 `cocr_train_adamw` (the kernel AdamW had before the general one), each on an engine of its own holding the gradients of a real step:
 --optim-rounds rounds of --optim-reps back-to-back calls between two events; the median / least / largest round per call and the
-bytes per second the median implies (4 n x (vectors read + vectors written), n = the parameter count).
+bytes per second the median implies (4 n x (vectors read + vectors written), n = the parameter count).  --dec-steps N: the output layer
+N steps ahead on both engines (`train_optim_restore`), the per-tensor bias corrections as after a frozen phase.
 --fit K: K steps on text lines (conformer_ocr_amd.synth.make_text_lines) from random weights, printing the loss and the greedy CER of
 the trained model against the ground truth every few steps (the inference path serves the trained weights after sync)."""
 import argparse
@@ -34,6 +35,7 @@ ap.add_argument('--fit', type=int, default=0)
 ap.add_argument('--lr', type=float, default=1e-3)
 ap.add_argument('--optimizer', default=None, choices=('AdamW', 'Adam', 'SGD', 'RMSprop'))
 ap.add_argument('--momentum', type=float, default=0.9)
+ap.add_argument('--dec-steps', type=int, default=0)
 ap.add_argument('--optim-reps', type=int, default=50)
 ap.add_argument('--optim-rounds', type=int, default=9)
 ap.add_argument('--matmul', default='highest', help="'highest' (exact fp32 products) or 'medium' (bf16-rounded operands, the reference's training setting)")
@@ -61,16 +63,18 @@ out.update(ms_per_step=round(dt * 1e3, 2), lines_per_s=round(args.batch / dt, 1)
 if args.optimizer:
     from conformer_ocr_amd.engine import HipRecognizer
 
-    def optim_engine():
+    def optim_engine(eng_kind=None):
         eng = HipRecognizer(hp, torch.device('cuda', 0), 'fp32')
         eng.load_state(state)
         eng.train_begin()
         eng.train_grad_buffer().copy_(tr.engine.train_grad_buffer())           # the gradients of the last real step
+        if args.dec_steps:                                                      # the Adam kinds' per-tensor bias corrections, as after a frozen phase
+            eng.train_optim_restore('AdamW' if eng_kind is None else eng_kind, 0, args.dec_steps)
         return eng
 
     kind = args.optimizer
     mom = args.momentum if kind in ('SGD', 'RMSprop') else 0.0
-    old_eng, new_eng = optim_engine(), optim_engine()
+    old_eng, new_eng = optim_engine(), optim_engine(kind)
     n = new_eng.train_grad_buffer().numel()
     # vectors of n floats the step reads + writes: P twice, G once, every slot it uses twice
     slots = {'AdamW': 2, 'Adam': 2, 'SGD': 1 if mom > 0 else 0, 'RMSprop': 2 if mom > 0 else 1}[kind]
