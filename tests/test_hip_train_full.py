@@ -325,3 +325,31 @@ def test_training_from_random_weights_learns_to_read_the_text_lines():
     assert losses[-1] < 0.01 * losses[0]
     tr.sync_module()
     assert cer() <= 0.02
+
+
+@pytest.mark.parametrize('mode', ['highest', 'medium'])
+def test_a_step_after_another_shape_equals_the_first_bit_for_bit(mode):
+    """What one engine carries from shape to shape -- the workspace plan, the arena of kept bf16 Linear inputs and its offset table, the
+    deferred-finals arena, the positional rows -- is rebuilt per step: a step at (3, 64), one at a larger batch and width (every buffer
+    grows), then the first again gives the first's loss and EVERY gradient bit for bit, with all dropout sites on at a fixed seed.  'tiny'
+    reaches the bf16 Linear path in 'medium' (every Linear but the 11-class decoder has dimensions that are multiples of 8).  The
+    reference is the first step, which the tests above pin on the float64 oracle."""
+    c = CASES['tiny']
+    hp = c['hp']()
+    state = synth.make_state_dict(hp, seed=c['seed'], decoder_gain=1.0)
+    image, lens = synth.make_lines(c['n'], hp.height, c['W'], seed=c['seed'], widths=c['widths'])
+    tg, tl = [x for s in c['targets'] for x in s], [len(s) for s in c['targets']]
+    big, big_lens = synth.make_lines(5, hp.height, 200, seed=c['seed'] + 1, widths=[200, 64, 133, 37, 171])
+    big_tg, big_tl = [3, 1, 4, 1, 5, 9, 2, 6, 5, 3, 5], [3, 2, 3, 1, 2]
+    x, xb = torch.from_numpy(image[:, 0]).cuda(), torch.from_numpy(big[:, 0]).cuda()
+    eng = HipRecognizer(hp, torch.device('cuda', 0), 'fp32')
+    eng.load_state(state)
+    eng.train_begin(mode)
+    p = (0.1, 0.1, 0.1, 0.1)
+    l1 = eng.train_step(x, lens, tg, tl, dropout=p, seed=11)
+    g1 = eng.train_grad_buffer().clone()
+    l2 = eng.train_step(xb, big_lens, big_tg, big_tl, dropout=p, seed=11)
+    assert l2 != l1 and not torch.equal(g1, eng.train_grad_buffer())
+    l3 = eng.train_step(x, lens, tg, tl, dropout=p, seed=11)
+    assert np.float32(l3).tobytes() == np.float32(l1).tobytes(), (l1, l3)
+    assert torch.equal(g1, eng.train_grad_buffer())
