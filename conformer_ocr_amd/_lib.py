@@ -52,6 +52,9 @@ SYMBOLS = {
     'cocr_ctc_greedy': (_I, [_P, _P, _I, _I, _I, _I32P, _P, _P, _P, _P, _P, _I, _P]),
     'cocr_forget_argmax': (_I, [_P]),
     'cocr_ctc_beam': (_I, [_P, _P, _I, _I, _I, _I32P, _P, _P, _P, _P, _P, _I, _I, _P]),
+    'cocr_lm_create': (_I, [_P, _I, _I, _P, _P, _P, C.c_int64, _P, _P, C.c_int64, C.POINTER(_P)]),
+    'cocr_lm_destroy': (None, [_P]),
+    'cocr_ctc_beam_lm': (_I, [_P, _P, _P, _I, _I, _I, _I32P, _P, _P, _P, _P, _P, _I, _I, _I, C.c_float, C.c_float, _P, _P]),
     'cocr_ctc_loss': (_I, [_P, _P, _I, _I, _I, _I32P, _I32P, _I32P, _P, _P, _P]),
     'cocr_ctc_align': (_I, [_P, _P, _I, _I, _I, _I32P, _I32P, _I32P, _P, _P, _P, _P, _P, _P]),
     'cocr_decoder_backward': (_I, [_P, _P, _I, _I, _P, _P, _P, _P]),

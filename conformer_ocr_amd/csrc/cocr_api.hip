@@ -22,6 +22,7 @@
 #include "common.hip.h"
 #include "conv.hip.h"
 #include "ctc.hip.h"
+#include "ctc_lm.hip.h"
 #include "ctc_loss.hip.h"
 #include "ctc_align.hip.h"
 #include "train.hip.h"
@@ -172,6 +173,7 @@ struct cocr_model {
     bool amax_ok = false;                   // the forward's launch sequence (plain or captured) ends with the argmax epilogue
     DevBuf<float> tr_pad;                   // padded models: engine-layout staging of the output layer's gradient tensors
     DevBuf<unsigned char> beam_bp;          // cocr_ctc_beam: back-pointers, then log Z or the frame records
+    DevBuf<unsigned char> lm_scratch;       // cocr_ctc_beam_lm: back-pointers, then the frame records
     DevBuf<int32_t> loss_d, loss_h{true};   // cocr_ctc_loss: device / pinned-host rings of [lens | label lens | label offsets | labels]
     int loss_slot = 0;
     DevBuf<float> loss_ws;                  // log-softmax + alpha / beta tables
@@ -1694,6 +1696,93 @@ extern "C" int cocr_ctc_beam(cocr_model *m, const float *logits, int N, int T, i
         hipLaunchKernelGGL(ctc_beam_kernel, dim3(N), dim3(64), lds, s, logits, T, ncls, m->d_lens_cur, beam, labels, starts, ends, conf, counts,
                            max_per_line, bp, logz);
     }
+    LAUNCH_CHECK();
+    return COCR_OK;
+}
+
+// ------------------------------------------------------------------------------------ beam search with an n-gram model (ctc_lm.hip.h)
+struct cocr_lm {
+    int device = 0, order = 0, ncls = 0;
+    int64_t nslots = 0, cslots = 0;
+    DevBuf<float> unigram, nlogp, cbow;
+    DevBuf<unsigned long long> nkeys, ckeys;
+};
+
+static int lm_check_table(const char *what, const int64_t *keys, const float *vals, int64_t slots) {
+    if (slots < 2 || slots > (1ll << 30) || (slots & (slots - 1))) return fail(COCR_EINVAL, "%s: slot count %lld is not a power of two in 2..2^30", what, (long long)slots);
+    if (!keys || !vals) return fail(COCR_EINVAL, "%s: null table", what);
+    for (int64_t i = 0; i < slots; ++i)
+        if (keys[i] == 0) return COCR_OK;
+    return fail(COCR_EINVAL, "%s: no empty slot (a probe sequence would not end)", what);
+}
+
+extern "C" int cocr_lm_create(cocr_model *m, int order, int ncls, const float *unigram, const int64_t *ngram_keys, const float *ngram_logp,
+                              int64_t ngram_slots, const int64_t *ctx_keys, const float *ctx_bow, int64_t ctx_slots, cocr_lm **out) {
+    if (!m || !unigram || !out) return fail(COCR_EINVAL, "null argument");
+    if (order < 1 || order > COCR_LM_CTX + 1) return fail(COCR_EINVAL, "order must be in 1..%d", COCR_LM_CTX + 1);
+    if (ncls < 2 || ncls > 65535) return fail(COCR_EINVAL, "ncls must be in 2..65535");
+    int rc = lm_check_table("ngram table", ngram_keys, ngram_logp, ngram_slots);
+    if (rc) return rc;
+    if ((rc = lm_check_table("context table", ctx_keys, ctx_bow, ctx_slots))) return rc;
+    HIP_TRY(hipSetDevice(m->device));
+    cocr_lm *lm = new cocr_lm();
+    lm->device = m->device; lm->order = order; lm->ncls = ncls; lm->nslots = ngram_slots; lm->cslots = ctx_slots;
+    hipError_t e = lm->unigram.grow((size_t)ncls);
+    if (e == hipSuccess) e = lm->nkeys.grow((size_t)ngram_slots);
+    if (e == hipSuccess) e = lm->nlogp.grow((size_t)ngram_slots);
+    if (e == hipSuccess) e = lm->ckeys.grow((size_t)ctx_slots);
+    if (e == hipSuccess) e = lm->cbow.grow((size_t)ctx_slots);
+    if (e == hipSuccess) e = hipMemcpy(lm->unigram.p, unigram, (size_t)ncls * 4, hipMemcpyHostToDevice);
+    if (e == hipSuccess) e = hipMemcpy(lm->nkeys.p, ngram_keys, (size_t)ngram_slots * 8, hipMemcpyHostToDevice);
+    if (e == hipSuccess) e = hipMemcpy(lm->nlogp.p, ngram_logp, (size_t)ngram_slots * 4, hipMemcpyHostToDevice);
+    if (e == hipSuccess) e = hipMemcpy(lm->ckeys.p, ctx_keys, (size_t)ctx_slots * 8, hipMemcpyHostToDevice);
+    if (e == hipSuccess) e = hipMemcpy(lm->cbow.p, ctx_bow, (size_t)ctx_slots * 4, hipMemcpyHostToDevice);
+    if (e != hipSuccess) { delete lm; return fail(COCR_EHIP, "copying the language model to the device failed: %s", hipGetErrorString(e)); }
+    *out = lm;
+    return COCR_OK;
+}
+
+extern "C" void cocr_lm_destroy(cocr_lm *lm) {
+    if (!lm) return;
+    (void)hipSetDevice(lm->device);
+    delete lm;
+}
+
+extern "C" int cocr_ctc_beam_lm(cocr_model *m, cocr_lm *lm, const float *logits, int N, int T, int ncls, const int32_t *out_lens, int32_t *labels,
+                                int32_t *starts, int32_t *ends, float *conf, int32_t *counts, int max_per_line, int beam, int classes, float alpha,
+                                float beta, float *score, void *stream) {
+    if (!m || !lm || !logits || !out_lens || !labels || !starts || !ends || !conf || !counts) return fail(COCR_EINVAL, "null argument");
+    if (N < 1 || T < 1 || ncls < 2 || max_per_line < 1) return fail(COCR_EINVAL, "empty problem");
+    if (T > 8000) return fail(COCR_EUNSUPPORTED, "more than 8000 frames per line");
+    if (beam < 1 || beam > COCR_BEAM_MAX) return fail(COCR_EINVAL, "beam must be in 1..%d", COCR_BEAM_MAX);
+    if (classes < 1 || classes > COCR_LM_KMAX) return fail(COCR_EINVAL, "classes must be in 1..%d", COCR_LM_KMAX);
+    if (ncls != lm->ncls) return fail(COCR_EINVAL, "the logits have %d classes, the language model %d", ncls, lm->ncls);
+    if (lm->device != m->device) return fail(COCR_EINVAL, "the language model lives on device %d, the model on %d", lm->device, m->device);
+    if (!std::isfinite(alpha) || !std::isfinite(beta)) return fail(COCR_EINVAL, "alpha and beta must be finite");
+    HIP_TRY(hipSetDevice(m->device));
+    hipStream_t s = (hipStream_t)stream;
+    int rc = upload_lens(m, out_lens, N, s);
+    if (rc) return rc;
+    const int K = std::min(classes, ncls - 1);
+    // scratch: back-pointers [N][T][COCR_BEAM_MAX] i32, then the frame records [N][T][COCR_LM_REC] f32
+    const size_t bp_bytes = (size_t)N * T * COCR_BEAM_MAX * 4;
+    HIP_TRY(m->lm_scratch.grow(bp_bytes + (size_t)N * T * COCR_LM_REC * 4));
+    int32_t *bp = reinterpret_cast<int32_t *>(m->lm_scratch.p);
+    float *rec = reinterpret_cast<float *>(m->lm_scratch.p + bp_bytes);
+    const size_t dyn = (size_t)T * ((size_t)beam * 4 + 8);                     // back-pointers + the label stack of the final walk, in LDS when they fit
+    const int bp_in_lds = dyn <= 96 * 1024;
+    if (bp_in_lds && dyn > 16 * 1024) {                                        // (the kernel has ~30 KB of static LDS)
+        static bool raised = false;
+        if (!raised) { HIP_TRY(hipFuncSetAttribute((const void *)ctc_lm_walk_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, 96 * 1024)); raised = true; }
+    }
+    cocr_lm_tables L;
+    L.unigram = lm->unigram.p; L.nkeys = lm->nkeys.p; L.nlogp = lm->nlogp.p; L.ckeys = lm->ckeys.p; L.cbow = lm->cbow.p;
+    L.nmask = (unsigned)(lm->nslots - 1); L.cmask = (unsigned)(lm->cslots - 1); L.order = lm->order;
+    ProfScope ps(m, s, FAM_BEAM);
+    hipLaunchKernelGGL(ctc_lm_topk_kernel, dim3(ceil_div(N * T, 4)), dim3(256), 0, s, logits, T, ncls, N * T, m->d_lens_cur, K, rec);
+    LAUNCH_CHECK();
+    hipLaunchKernelGGL(ctc_lm_walk_kernel, dim3(N), dim3(256), bp_in_lds ? dyn : 0, s, logits, T, ncls, m->d_lens_cur, beam, K, L, alpha, beta, labels, starts,
+                       ends, conf, counts, score, max_per_line, rec, bp, bp_in_lds);
     LAUNCH_CHECK();
     return COCR_OK;
 }

@@ -35,6 +35,8 @@ class _DeviceDecoder:
         lg = torch.from_numpy(m).to(dev).unsqueeze(0)
         if self.kind == 'greedy':
             return eng.ctc_greedy(lg, [T])[0]
+        if self.kind == 'lm':
+            return self.decode(eng, lg, [T])[0]
         return eng.ctc_beam(lg, [T], self.beam_size)[0]
 
     def __call__(self, outputs: np.ndarray) -> List[Tuple[int, int, int, float]]:
@@ -58,6 +60,31 @@ class BeamDecoder(_DeviceDecoder):
 
     def __repr__(self):
         return f'beam_decoder<hip,{self.beam_size}>'
+
+
+class LMDecoder(_DeviceDecoder):
+    """The beam search with a character n-gram model in the ranking (shallow fusion; DESIGN.md section 7g, include/cocr.h
+    cocr_ctc_beam_lm).  `lm`: an `lm.NGramLM` or the path of its file.  alpha weighs the model's log-probabilities, beta is a
+    bonus per label, `classes` the candidate classes per frame.  The defaults 0.5 / 0 / 8 are placeholders, not tuned on real
+    material: `python -m conformer_ocr_amd.lm tune` finds the values for yours."""
+    kind = 'lm'
+
+    def __init__(self, lm, beam_size: int = 16, alpha: float = 0.5, beta: float = 0.0, classes: int = 8):
+        if isinstance(lm, (str, bytes)) or hasattr(lm, '__fspath__'):
+            from .lm import NGramLM
+            lm = NGramLM.load(lm)
+        self.lm = lm
+        self.beam_size, self.alpha, self.beta, self.classes = int(beam_size), float(alpha), float(beta), int(classes)
+
+    def decode_async(self, eng, logits, out_lens):
+        """The whole batch in one launch pair on `eng`'s device; a handle for `eng.collect` / `eng.collect_labels`."""
+        return eng.ctc_beam_lm_async(logits, out_lens, self.lm, self.beam_size, self.classes, self.alpha, self.beta)
+
+    def decode(self, eng, logits, out_lens):
+        return eng.collect(self.decode_async(eng, logits, out_lens))
+
+    def __repr__(self):
+        return f'lm_beam_decoder<hip,{self.beam_size},order {self.lm.order},alpha {self.alpha:g},beta {self.beta:g},classes {self.classes}>'
 
 
 _scratch = {}

@@ -241,6 +241,27 @@ class HipRecognizer:
     def ctc_beam(self, logits: torch.Tensor, out_lens, beam: int = 16) -> List[List[Tuple[int, int, int, float]]]:
         return self._decode(self.lib.cocr_ctc_beam, logits, out_lens, extra=(int(beam),))
 
+    def ctc_beam_lm_async(self, logits: torch.Tensor, out_lens, lm, beam: int = 16, classes: int = 8, alpha: float = 0.5, beta: float = 0.0,
+                          score: Optional[torch.Tensor] = None):
+        """`cocr_ctc_beam_lm` (include/cocr.h) enqueued on the current stream: the beam search with the n-gram
+        model `lm` (an `lm.NGramLM`; its tables are copied to this device once) in the ranking.  Returns a handle for `collect` /
+        `collect_labels`.  `score`: an optional pinned or device float32 (N,2) tensor for (CTC log-probability, lmv) per line."""
+        dlm = lm.to_device(self)
+        sp = C.c_void_p(score.data_ptr()) if score is not None else None
+
+        def fn(h, *args):
+            return self.lib.cocr_ctc_beam_lm(h, dlm.handle, *args)
+        key, host, ev, keep = self._decode_async(fn, logits, out_lens, extra=(int(beam), int(classes), C.c_float(alpha), C.c_float(beta), sp))
+        return (key, host, ev, keep + (dlm, score))
+
+    def ctc_beam_lm(self, logits: torch.Tensor, out_lens, lm, beam: int = 16, classes: int = 8, alpha: float = 0.5, beta: float = 0.0,
+                    return_scores: bool = False):
+        """Per line [(label, start, end, conf)]; with return_scores also a (N,2) float32 array: the CTC log-probability
+        logaddexp(p_b, p_nb) of the returned prefix, and its language-model term lmv."""
+        score = torch.empty((logits.shape[0], 2), dtype=torch.float32).pin_memory() if return_scores else None
+        recs = self.collect(self.ctc_beam_lm_async(logits, out_lens, lm, beam, classes, alpha, beta, score))
+        return (recs, score.numpy().copy()) if return_scores else recs
+
     def ctc_loss(self, probits: torch.Tensor, out_lens, targets, label_lens, with_grad: bool = True):
         """nn.CTCLoss(reduction='sum', zero_infinity=True) on log_softmax(probits) (reference model.py:119,136-142) on the device.
         probits (N,T,ncls) float32 on this device; out_lens (N) valid frames; targets: the batch's concatenated 1-D label vector,

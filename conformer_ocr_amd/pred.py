@@ -22,7 +22,7 @@ import torch
 from torch import nn
 
 from .codec import PytorchCodec
-from .ctc_decoder import BeamDecoder, GreedyDecoder, greedy_decoder
+from .ctc_decoder import BeamDecoder, GreedyDecoder, LMDecoder, greedy_decoder
 from .engine import HipRecognizer
 from .spec import HParams, encoder_state_spec
 
@@ -273,6 +273,8 @@ class PytorchRecognitionModel(nn.Module):
             return self._engine.ctc_greedy(o, olens.numpy())
         if isinstance(self.ctc_decoder, BeamDecoder):
             return self._engine.ctc_beam(o, olens.numpy(), self.ctc_decoder.beam_size)
+        if isinstance(self.ctc_decoder, LMDecoder):
+            return self.ctc_decoder.decode(self._engine, o, olens.numpy())
         # a user-supplied decoder: the reference's own host loop (pred.py:158-162)
         o = o.transpose(1, 2).cpu().float().numpy()
         return [self.ctc_decoder(seq[:, :int(seq_len)]) for seq, seq_len in zip(o, olens)]
@@ -291,13 +293,15 @@ class PytorchRecognitionModel(nn.Module):
         preserved (pred.py:148-164).
         """
         lut = self._codec_lut()
-        if lut is not None and isinstance(self.ctc_decoder, (GreedyDecoder, BeamDecoder)):
+        if lut is not None and isinstance(self.ctc_decoder, (GreedyDecoder, BeamDecoder, LMDecoder)):
             # device decode + a 1:1 codec: label arrays -> characters by one table lookup per line (the record lists of `predict_labels`
             # and the codec's tuple walk cost 0.26 ms per 32 lines on the host, after the GPU had finished: a fifth of the call)
             o, olens = self.forward(line, lens)
             eng = self._engine
             if isinstance(self.ctc_decoder, GreedyDecoder):
                 h = eng.ctc_greedy_async(o, olens.numpy())
+            elif isinstance(self.ctc_decoder, LMDecoder):
+                h = self.ctc_decoder.decode_async(eng, o, olens.numpy())
             else:
                 h = eng._decode_async(eng.lib.cocr_ctc_beam, o, olens.numpy(), extra=(int(self.ctc_decoder.beam_size),))
             size = lut.shape[0]
@@ -335,6 +339,8 @@ class PytorchRecognitionModel(nn.Module):
             return ('device', eng.ctc_greedy_async(o, olens.numpy()), eng)
         if isinstance(self.ctc_decoder, BeamDecoder):
             return ('device', eng._decode_async(eng.lib.cocr_ctc_beam, o, olens.numpy(), extra=(int(self.ctc_decoder.beam_size),)), eng)
+        if isinstance(self.ctc_decoder, LMDecoder):
+            return ('device', self.ctc_decoder.decode_async(eng, o, olens.numpy()), eng)
         o = o.transpose(1, 2).cpu().float().numpy()           # a user-supplied decoder: the reference's own host loop
         return ('host', [self.ctc_decoder(seq[:, :int(seq_len)]) for seq, seq_len in zip(o, olens)], None)
 

@@ -1,7 +1,8 @@
 """Evaluation of trained models on ground truth from the command line -- the reference's `cocr test` (cli/test.py):
 
     python -m conformer_ocr_amd.test -m MODEL [-m MODEL2 ...] [-f path|page|alto|xml] [-e LIST ...] [-B 32] [--pad 16] [-u NFD|NFC|NFKD|NFKC]
-                                     [--no-normalize-whitespace] [--device cuda:0] [--edge 200] [--scorer device|host] FILES...
+                                     [--no-normalize-whitespace] [--device cuda:0] [--edge 200] [--scorer device|host]
+                                     [--beam N] [--lm FILE [--lm-weight A] [--lm-bonus B] [--lm-classes K]] FILES...
 
 FILES (globs allowed) and the names listed in the -e manifests (one per line) are PAGE / ALTO documents or, with `-f path`, line images
 `foo.png` beside `foo.gt.txt`.  Every line with text and usable geometry is recognized (pages in bounded groups, so a test set larger
@@ -41,6 +42,8 @@ def parser() -> argparse.ArgumentParser:
     ap.add_argument('-d', '--device', default='cuda:0')
     ap.add_argument('--edge', type=int, default=200, help='width bucket edge: lines are padded to a multiple of it')
     ap.add_argument('--scorer', choices=('device', 'host'), default='device', help='where the alignments of the report are computed')
+    from .ocr import add_decoder_arguments
+    add_decoder_arguments(ap)
     return ap
 
 
@@ -117,11 +120,15 @@ def main(argv=None) -> int:
         return usage('no usable line in the evaluation data')
     import numpy as np
     from .evaluate import score_strings
-    from .ocr import load_model
+    from .ocr import load_model, set_decoder
     truths = [ln.text for ln in gt]
     cer_list, wer_list = [], []
     for model in args.model:
         net = load_model(model, device=args.device)
+        try:
+            set_decoder(net, args)
+        except ValueError as e:
+            return usage(f'{model}: {e}')
         print(f'Evaluating {model}', flush=True)
         preds = recognize_ground_truth(net, gt, args.batch_size, args.edge, args.pad, args.device)
         res = score_strings(net, preds, truths, report=True, model_name=model, scorer=args.scorer)

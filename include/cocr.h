@@ -145,6 +145,27 @@ int cocr_ctc_beam(cocr_model *m, const float *logits, int N, int T, int ncls, co
                   int32_t *labels, int32_t *starts, int32_t *ends, float *conf, int32_t *counts,
                   int max_per_line, int beam, void *stream);
 
+/* A character n-gram language model on the device (built by conformer_ocr_amd/lm.py).  All arrays HOST, copied
+ * before return: unigram float32 (ncls), natural logs, entry 0 (blank) unused; two open-addressing tables with linear probing and key 0
+ * = empty: (ngram_keys int64, ngram_logp float32) of ngram_slots entries for the n-grams of order >= 2, (ctx_keys, ctx_bow) of ctx_slots
+ * entries for the back-off weights of the contexts.  COCR_EINVAL: a slot count that is no power of two, a table without an empty slot,
+ * order outside 1..8, ncls outside 2..65535.  The model is bound to `m`'s device, not to `m`. */
+typedef struct cocr_lm cocr_lm;
+int cocr_lm_create(cocr_model *m, int order, int ncls, const float *unigram, const int64_t *ngram_keys, const float *ngram_logp,
+                   int64_t ngram_slots, const int64_t *ctx_keys, const float *ctx_bow, int64_t ctx_slots, cocr_lm **lm);
+void cocr_lm_destroy(cocr_lm *lm);
+
+/* cocr_ctc_beam with the language model in the ranking (shallow fusion; the definition is conformer_ocr_amd/lm.py beam_decode_host):
+ * a frame's candidate classes are blank + its min(classes, ncls - 1) best non-blank classes (ties: smaller class); a prefix created as
+ * parent + (s,) carries lmv = lmv(parent) + (alpha * lm(parent, s) + beta); candidates rank by logaddexp(p_b, p_nb) + lmv.  Buffers and
+ * ownership as for cocr_ctc_beam.  score: (N,2) float32, DEVICE or pinned host, or NULL: the CTC log-probability logaddexp(p_b, p_nb)
+ * of the returned prefix and its lmv.  beam <= 32, 1 <= classes <= 64, ncls = the language model's.  With alpha = beta = 0 and
+ * classes >= beam + 1 every output equals cocr_ctc_beam's.  A damaged table may give wrong text, never a hang: every probe sequence ends
+ * at an empty slot or after `slots` probes.  Deterministic (no atomics).  Stream-ordered, does not synchronise (workspace growth does). */
+int cocr_ctc_beam_lm(cocr_model *m, cocr_lm *lm, const float *logits, int N, int T, int ncls, const int32_t *out_lens,
+                     int32_t *labels, int32_t *starts, int32_t *ends, float *conf, int32_t *counts, int max_per_line,
+                     int beam, int classes, float alpha, float beta, float *score, void *stream);
+
 /* The loss of the reference's training / validation step, RecognitionModel._step (model.py:119,136-142):
  *     nn.CTCLoss(reduction='sum', zero_infinity=True)(log_softmax(probits, -1).transpose(0, 1), target, encoder_lens, label_lens)
  * and its gradient with respect to `probits` (what autograd hands to the decoder's backward).  probits DEVICE float32 (N,T,ncls), the
