@@ -77,7 +77,7 @@ class Oracle:
                  fused_frontend: bool = True):
         self.hp = hp
         self.dtype = dtype
-        self.training = False          # train mode (`forward_train`): BatchNorm batch statistics; dropout probabilities 0
+        self.training = False          # train mode (`forward_train`): BatchNorm batch statistics; dropout through `self.dropout` (identity here)
         self.bn_batch_stats: Dict[int, Tuple[torch.Tensor, torch.Tensor]] = {}
         self.bf16 = bool(bf16_operands)
         # bf16 mode: the fused frontend kernel (256 conv channels) also rounds pixels, the 3x3 taps and Z1; the
@@ -110,6 +110,20 @@ class Oracle:
         """Round to bfloat16 (nearest even) and back -- identity outside the bf16-operand mode."""
         return x.to(torch.bfloat16).to(self.dtype) if self.bf16 else x
 
+    def linear(self, x: torch.Tensor, w: torch.Tensor, b: Optional[torch.Tensor] = None) -> torch.Tensor:
+        """Every Linear / pointwise-conv product of the network, y = x w^T (+ b), passes through here (the attention's own products do
+        not).  A subclass may restate another arithmetic for it (tests/train_ref.py: the training step's 'medium' matmul precision)."""
+        y = x @ w.t()
+        return y if b is None else y + b
+
+    def dropout(self, x: torch.Tensor, site: str, l: int = 0, which: int = 0) -> torch.Tensor:
+        """The reference's six dropout sites pass through here; identity by default (eval mode, and train mode with probabilities 0).
+        site: 'input' (after the frontend's output linear, convolution.py:225), 'ff_hidden' (after SiLU, feed_forward.py:49), 'ff_out'
+        (before the residual's factor, feed_forward.py:51), 'attn_weights' (after softmax, before attn @ v, attention.py:98; x is
+        (B,h,T,T)), 'attn_out' (after out_proj, attention.py:151), 'conv_out' (after the second pointwise conv, convolution.py:144;
+        x is (B,T,D) here).  l: the block; which: 0 / 1 for the block's first / second feed-forward module."""
+        return x
+
     # ------------------------------------------------------------------ frontend
     def front_conv12(self, x_bhw: torch.Tensor) -> torch.Tensor:
         """F1+F2 (convolution.py:192-205 applied to the (B,1,W,H) view of pred.py:119 / convolution.py:233).
@@ -128,7 +142,7 @@ class Oracle:
     def front_pw(self, z2_btfc: torch.Tensor, idx: int = 3) -> torch.Tensor:
         """F3 (convolution.py:207-213): Z3[b,t,f,o] = relu(b3[o] + sum_c w3[o,c] Z2[b,t,f,c])."""
         w3 = self.w[f'encoder.conv_subsample.conv.{idx}.weight'].flatten(1)   # (C,C)
-        return self.r(F.relu(z2_btfc @ w3.t() + self.w[f'encoder.conv_subsample.conv.{idx}.bias']))
+        return self.r(F.relu(self.linear(z2_btfc, w3, self.w[f'encoder.conv_subsample.conv.{idx}.bias'])))
 
     def front_dw(self, z_btfc: torch.Tensor, idx: int) -> torch.Tensor:
         """extra stride-2 depthwise stage for subsampling_factor > 4 (convolution.py:200-205, loop body)."""
@@ -142,7 +156,7 @@ class Oracle:
         """F4+F5 (convolution.py:224,235-236): Y[b,t,:] = Wout vec_{c,f}(Z3[b,:,t,:]) + bout, vec index c*F+f."""
         B, T, Fh, C = z3_btfc.shape
         v = z3_btfc.permute(0, 1, 3, 2).reshape(B, T, C * Fh)
-        return v @ self.w['encoder.conv_subsample.out.0.weight'].t() + self.w['encoder.conv_subsample.out.0.bias']
+        return self.dropout(self.linear(v, self.w['encoder.conv_subsample.out.0.weight'], self.w['encoder.conv_subsample.out.0.bias']), 'input')
 
     def frontend(self, x_bhw: torch.Tensor, taps: Optional[dict] = None) -> torch.Tensor:
         if self.hp.sampling_num == 1:
@@ -179,15 +193,16 @@ class Oracle:
         y + f * (W2 silu(W1 LN(y) + b1) + b2), f = 0.5 with half_step_residual."""
         p = f'encoder.layers.{l}.sequential.{which}.module.sequential.'
         t = self._ln_op(y, p + '0')
-        t = self.r(F.silu(t @ self.w[p + '1.linear.weight'].t() + self.w[p + '1.linear.bias']))
-        t = t @ self.w[p + '4.linear.weight'].t() + self.w[p + '4.linear.bias']
-        return y + self.hp.ff_residual_factor * t
+        t = self.r(F.silu(self.linear(t, self.w[p + '1.linear.weight'], self.w[p + '1.linear.bias'])))
+        t = self.dropout(t, 'ff_hidden', l, int(which != 0))
+        t = self.linear(t, self.w[p + '4.linear.weight'], self.w[p + '4.linear.bias'])
+        return y + self.hp.ff_residual_factor * self.dropout(t, 'ff_out', l, int(which != 0))
 
     def pos_table(self, l: int) -> torch.Tensor:
         """P_full = PE_full Wpos^T (attention.py:62,85 on embedding.py:66's table), 9999 x D; row 4999 <-> p = 0."""
         if l not in self._ptab:      # input-independent: computed once per layer, like a load-time constant
             p = f'encoder.layers.{l}.sequential.1.module.attention.'
-            self._ptab[l] = self.r(self._pe @ self.w[p + 'pos_proj.linear.weight'].t())
+            self._ptab[l] = self.r(self.linear(self._pe, self.w[p + 'pos_proj.linear.weight']))
         return self._ptab[l]
 
     def mhsa(self, y: torch.Tensor, l: int, taps: Optional[dict] = None) -> torch.Tensor:
@@ -199,9 +214,9 @@ class Oracle:
         m = f'encoder.layers.{l}.sequential.1.module.'
         a = m + 'attention.'
         xn = self._ln_op(y, m + 'layer_norm')
-        q = self.r(xn @ self.w[a + 'query_proj.linear.weight'].t() + self.w[a + 'query_proj.linear.bias']).view(B, T, h, dh)
-        k = self.r(xn @ self.w[a + 'key_proj.linear.weight'].t() + self.w[a + 'key_proj.linear.bias']).view(B, T, h, dh)
-        v = self.r(xn @ self.w[a + 'value_proj.linear.weight'].t() + self.w[a + 'value_proj.linear.bias']).view(B, T, h, dh)
+        q = self.r(self.linear(xn, self.w[a + 'query_proj.linear.weight'], self.w[a + 'query_proj.linear.bias'])).view(B, T, h, dh)
+        k = self.r(self.linear(xn, self.w[a + 'key_proj.linear.weight'], self.w[a + 'key_proj.linear.bias'])).view(B, T, h, dh)
+        v = self.r(self.linear(xn, self.w[a + 'value_proj.linear.weight'], self.w[a + 'value_proj.linear.bias'])).view(B, T, h, dh)
         if T > self._maxlen:                                                   # embedding.py:35-41: the table is rebuilt for a longer input
             self._maxlen = T
             self._pe = sinusoid_table(hp.encoder_dim, T).to(self.dtype)
@@ -220,7 +235,7 @@ class Oracle:
             pos_all = qv @ Pband.permute(1, 2, 0)                               # (B,h,T,2T-1)
             pos = torch.gather(pos_all, 3, gidx)
             score = (content + pos) / math.sqrt(dh)
-            attn = torch.softmax(score, -1)
+            attn = self.dropout(torch.softmax(score, -1), 'attn_weights', l)
             ctx = (attn @ v.permute(0, 2, 1, 3)).permute(0, 2, 1, 3).reshape(B, T, D)
         else:
             # the library folds log2(e)/sqrt(dh) into the query operands BEFORE rounding them (scores in log2 units,
@@ -233,7 +248,7 @@ class Oracle:
             s2 = content + pos
             pn = self.r(torch.exp2(s2 - s2.max(-1, keepdim=True).values))
             ctx = self.r((pn @ v.permute(0, 2, 1, 3)) / pn.sum(-1, keepdim=True)).permute(0, 2, 1, 3).reshape(B, T, D)
-        out = ctx @ self.w[a + 'out_proj.linear.weight'].t() + self.w[a + 'out_proj.linear.bias']
+        out = self.dropout(self.linear(ctx, self.w[a + 'out_proj.linear.weight'], self.w[a + 'out_proj.linear.bias']), 'attn_out', l)
         if taps is not None:
             taps[f'l{l}.q'] = q
             taps[f'l{l}.k'] = k
@@ -250,7 +265,7 @@ class Oracle:
         k = hp.conv_kernel_size
         c = f'encoder.layers.{l}.sequential.2.module.sequential.'
         t = self._ln_op(y, c + '0')
-        a = t @ self.w[c + '2.conv.weight'].squeeze(-1).t() + self.w[c + '2.conv.bias']   # (B,T,2D)
+        a = self.linear(t, self.w[c + '2.conv.weight'].squeeze(-1), self.w[c + '2.conv.bias'])   # (B,T,2D)
         g = self.r(a[..., :D] * torch.sigmoid(a[..., D:]))
         if glu is not None:
             g = glu
@@ -270,7 +285,7 @@ class Oracle:
             bdw = self.w[c + '5.bias'] - self.w[c + '5.running_mean'] * s
             u = bdw + sum(gp[:, tau:tau + T, :] * wdw[:, tau] for tau in range(k))
         u = self.r(F.silu(u))
-        out = u @ self.w[c + '7.conv.weight'].squeeze(-1).t() + self.w[c + '7.conv.bias']
+        out = self.dropout(self.linear(u, self.w[c + '7.conv.weight'].squeeze(-1), self.w[c + '7.conv.bias']), 'conv_out', l)
         if taps is not None:
             taps[f'l{l}.glu'] = g
             taps[f'l{l}.dw'] = u
@@ -305,7 +320,7 @@ class Oracle:
     def forward_train(self, line: torch.Tensor, lens, taps: Optional[dict] = None) -> Tuple[torch.Tensor, torch.Tensor]:
         """The training forward of RecognitionModel._step (model.py:129-135): the same modules in train mode -- BatchNorm with batch
         statistics (`bn_batch_stats[l]` = (mean, biased variance) of block l, for the running-statistics update), dropout
-        probabilities 0 -- with autograd enabled: set `requires_grad_` on the entries of `self.w` and call `.backward()` on a loss."""
+        as `self.dropout` restates it (identity unless overridden: probabilities 0) -- with autograd enabled: set `requires_grad_` on the entries of `self.w` and call `.backward()` on a loss."""
         self.training = True
         try:
             return self._forward(line, lens, taps)
@@ -317,7 +332,7 @@ class Oracle:
         y = self.frontend(x, taps)
         for l in range(self.hp.num_encoder_layers):
             y = self.block(y, l, taps)
-        logits = self.r(y) @ self.w['decoder.weight'].t() + self.w['decoder.bias']      # (bf16 mode: the decoder reads the bf16 `xn`)
+        logits = self.linear(self.r(y), self.w['decoder.weight'], self.w['decoder.bias'])      # (bf16 mode: the decoder reads the bf16 `xn`)
         if taps is not None:
             taps['logits'] = logits
         return logits, out_len(lens, self.hp.sampling_num)
