@@ -118,6 +118,40 @@ template <typename E> static hipError_t grow_pair(DevBuf<E> &dev, DevBuf<E> &hos
     return e;
 }
 
+// A ring of COCR_RING_SLOTS slots for the small host tables an entry point sends ahead of its kernels: a device buffer and its pinned
+// host twin (an async copy from pageable memory can block the host).  stage() hands out the next slot, 16-byte
+// aligned, once the upload that last used it has run (one event per slot; a wait only for a caller more than COCR_RING_SLOTS calls
+// ahead of the device); commit() enqueues the slot's copy and records its event.  A slot too small regrows the ring by half again as
+// much, both buffers or neither, after a device synchronise: uploads of earlier calls still read the old buffers.
+#define COCR_RING_SLOTS 16
+struct UploadRing {
+    DevBuf<unsigned char> dev, host{true};
+    hipEvent_t ev[COCR_RING_SLOTS] = {};
+    int slot = 0;                       // the slot stage() handed out last, and its byte offset in both buffers
+    size_t at = 0;
+    ~UploadRing() {
+        for (hipEvent_t e : ev)
+            if (e) (void)hipEventDestroy(e);
+    }
+    template <typename E> hipError_t stage(size_t bytes, E *&h, E *&d) {
+        const size_t need = (bytes + 15) / 16 * 16 * COCR_RING_SLOTS;
+        hipError_t e = hipSuccess;
+        if (need > dev.n || need > host.n) {
+            if ((e = hipDeviceSynchronize()) != hipSuccess) return e;
+            if ((e = grow_pair(dev, host, need, (bytes + bytes / 2 + 15) / 16 * 16 * COCR_RING_SLOTS)) != hipSuccess) return e;
+        }
+        slot = (slot + 1) % COCR_RING_SLOTS;
+        e = ev[slot] ? hipEventSynchronize(ev[slot]) : hipEventCreateWithFlags(&ev[slot], hipEventDisableTiming);
+        at = dev.n / COCR_RING_SLOTS / 16 * 16 * (size_t)slot;
+        h = reinterpret_cast<E *>(host.p + at); d = reinterpret_cast<E *>(dev.p + at);
+        return e;
+    }
+    hipError_t commit(size_t bytes, hipStream_t s) {
+        const hipError_t e = hipMemcpyAsync(dev.p + at, host.p + at, bytes, hipMemcpyHostToDevice, s);
+        return e != hipSuccess ? e : hipEventRecord(ev[slot], s);
+    }
+};
+
 struct ProfRec { int fam; hipEvent_t a, b; };
 struct TrainState;
 
@@ -163,9 +197,7 @@ struct cocr_model {
     int pos_maxlen = COCR_POS_MAXLEN;                  // relative positions the P tables cover: -(max_len - 1) .. max_len - 1
     DevBuf<unsigned char> pre_buf;         // line pre-processing: descriptors, tap tables, intermediates
     DevBuf<unsigned char> page_buf;        // line extraction: descriptors, column frames, polygons, span table
-    DevBuf<int32_t> d_lens, h_lens{true};  // device / pinned-host rings of per-line lengths (upload_lens)
-    int32_t *d_lens_cur = nullptr;
-    int lens_slot = 0;
+    UploadRing lens_ring;                  // per-line lengths of the decode entry points (upload_lens)
     DevBuf<int32_t> ctc_lab;                // per-frame argmax / maximum of the greedy decoder (ensure_ctc_scratch)
     DevBuf<float> ctc_val;
     const float *amax_logits = nullptr;     // the logits buffer whose per-frame argmax / maximum the last forward left in ctc_lab / ctc_val (decoder epilogue)
@@ -174,17 +206,12 @@ struct cocr_model {
     DevBuf<float> tr_pad;                   // padded models: engine-layout staging of the output layer's gradient tensors
     DevBuf<unsigned char> beam_bp;          // cocr_ctc_beam: back-pointers, then log Z or the frame records
     DevBuf<unsigned char> lm_scratch;       // cocr_ctc_beam_lm: back-pointers, then the frame records
-    DevBuf<int32_t> loss_d, loss_h{true};   // cocr_ctc_loss: device / pinned-host rings of [lens | label lens | label offsets | labels]
-    int loss_slot = 0;
+    UploadRing target_ring;                 // cocr_ctc_loss, cocr_ctc_align: [lens | label lens | label offsets | labels] (upload_targets)
     DevBuf<float> loss_ws;                  // log-softmax + alpha / beta tables
-    DevBuf<int32_t> align_d, align_h{true}; // cocr_ctc_align: rings like loss_d / loss_h
-    int align_slot = 0;
     DevBuf<unsigned> align_ws;              // back-pointer tables of the lines too long for the LDS
-    // cocr_edit_align: device / pinned-host rings of [a offsets | b offsets | launch order] (one event per slot: the slot's upload has run
-    // before the host writes it again), the op-code workspace of the pairs too large for the LDS, and the LDS budget of one pair
-    DevBuf<unsigned char> score_d, score_h{true};
-    hipEvent_t score_ev[4] = {nullptr, nullptr, nullptr, nullptr};
-    int score_slot = 0;
+    // cocr_edit_align: the ring of [a offsets | b offsets | launch order], the op-code workspace of the pairs too large for the LDS,
+    // and the LDS budget of one pair
+    UploadRing score_ring;
     DevBuf<unsigned> score_ws;
     int score_lds_max = 64 * 1024;   // COCR_SCORE_LDS_MAX: bytes of LDS one pair may take (tests / A/B: 0 puts every op-code table in the global workspace)
     int lastN = 0, lastT = 0;                          // shape of the last forward: its encoder output is still in `xn`
@@ -367,8 +394,6 @@ extern "C" void cocr_destroy(cocr_model *m) {
     train_free(m);
     free_workspace(m);
     clear_taps(m);
-    for (hipEvent_t &e : m->score_ev)
-        if (e) { (void)hipEventDestroy(e); e = nullptr; }
     drop_weights(m);
     if (m->stamps) {
         (void)hipDeviceSynchronize();
@@ -1607,18 +1632,13 @@ extern "C" int cocr_collate_lines(const void *const *lines, const int32_t *width
 // ------------------------------------------------------------------------------------ CTC
 // The per-line lengths reach the decode kernels through a PINNED host ring: an async copy from pageable memory goes through the
 // runtime's staging buffers, and a third such copy in flight (three batches on three streams, each copy queued behind its
-// forward) blocked the host until the first forward had finished -- 5.5 ms per run start.  Slots are reused after
-// COCR_LENS_SLOTS further decode calls of this model (one model = one stream = a handful of calls in flight at most).
-#define COCR_LENS_SLOTS 16
-static int upload_lens(cocr_model *m, const int32_t *lens, int N, hipStream_t s) {
-    HIP_TRY(grow_pair(m->d_lens, m->h_lens, (size_t)N * COCR_LENS_SLOTS));
-    const size_t per = m->d_lens.n / COCR_LENS_SLOTS;          // lengths per slot
-    const int slot = m->lens_slot;
-    m->lens_slot = (slot + 1) % COCR_LENS_SLOTS;
-    int32_t *h = m->h_lens.p + (size_t)slot * per;
+// forward) blocked the host until the first forward had finished -- 5.5 ms per run start.  `d_lens`: the lengths on the device.
+static int upload_lens(cocr_model *m, const int32_t *lens, int N, hipStream_t s, const int32_t *&d_lens) {
+    int32_t *h, *d;
+    HIP_TRY(m->lens_ring.stage((size_t)N * 4, h, d));
     memcpy(h, lens, (size_t)N * 4);
-    m->d_lens_cur = m->d_lens.p + (size_t)slot * per;
-    HIP_TRY(hipMemcpyAsync(m->d_lens_cur, h, (size_t)N * 4, hipMemcpyHostToDevice, s));
+    HIP_TRY(m->lens_ring.commit((size_t)N * 4, s));
+    d_lens = d;
     return COCR_OK;
 }
 
@@ -1639,17 +1659,18 @@ extern "C" int cocr_ctc_greedy(cocr_model *m, const float *logits, int N, int T,
     if (T > 8000) return fail(COCR_EUNSUPPORTED, "more than 8000 frames per line");
     HIP_TRY(hipSetDevice(m->device));
     hipStream_t s = (hipStream_t)stream;
-    int rc = upload_lens(m, out_lens, N, s);
+    const int32_t *d_lens;
+    int rc = upload_lens(m, out_lens, N, s, d_lens);
     if (rc) return rc;
     const bool have_argmax = logits == m->amax_logits && N * T == m->amax_rows && ncls == m->ncls;      // the decoder's epilogue computed it for these logits
     if (!have_argmax && (rc = ensure_ctc_scratch(m, (size_t)N * T))) return rc;
     ProfScope ps(m, s, FAM_GREEDY);
     if (!have_argmax) {
         m->amax_logits = nullptr;                             // the scratch no longer belongs to the last forward's logits
-        hipLaunchKernelGGL(ctc_argmax_kernel, dim3(ceil_div(N * T, 4)), dim3(256), 0, s, logits, T, ncls, N * T, m->d_lens_cur, m->ctc_lab.p, m->ctc_val.p);
+        hipLaunchKernelGGL(ctc_argmax_kernel, dim3(ceil_div(N * T, 4)), dim3(256), 0, s, logits, T, ncls, N * T, d_lens, m->ctc_lab.p, m->ctc_val.p);
         LAUNCH_CHECK();
     }
-    hipLaunchKernelGGL(ctc_collapse_kernel, dim3(N), dim3(64), (size_t)T * 8, s, T, m->d_lens_cur, m->ctc_lab.p, m->ctc_val.p, labels, starts, ends, conf, counts,
+    hipLaunchKernelGGL(ctc_collapse_kernel, dim3(N), dim3(64), (size_t)T * 8, s, T, d_lens, m->ctc_lab.p, m->ctc_val.p, labels, starts, ends, conf, counts,
                        max_per_line);
     LAUNCH_CHECK();
     return COCR_OK;
@@ -1663,7 +1684,8 @@ extern "C" int cocr_ctc_beam(cocr_model *m, const float *logits, int N, int T, i
     if (ncls > 65535) return fail(COCR_EUNSUPPORTED, "more than 65535 classes");
     HIP_TRY(hipSetDevice(m->device));
     hipStream_t s = (hipStream_t)stream;
-    int rc = upload_lens(m, out_lens, N, s);
+    const int32_t *d_lens;
+    int rc = upload_lens(m, out_lens, N, s, d_lens);
     if (rc) return rc;
     const bool fast = ncls <= 256 && !m->beam_ref;            // ctc_beam_rank_kernel + ctc_beam_walk_kernel: frames ranked in parallel, a static pruned candidate set per frame
     const int K = std::min(beam + 1, ncls - 1);
@@ -1676,24 +1698,19 @@ extern "C" int cocr_ctc_beam(cocr_model *m, const float *logits, int N, int T, i
         unsigned char *rec = reinterpret_cast<unsigned char *>(bp + (size_t)N * T * COCR_BEAM_MAX);
         const size_t dyn = (size_t)T * ((size_t)beam * 4 + 8);                 // back-pointers + the label stack of the final walk, in LDS when they fit
         const int bp_in_lds = dyn <= 96 * 1024;
-        hipLaunchKernelGGL(ctc_beam_rank_kernel, dim3(N * T), dim3(256), 0, s, logits, T, ncls, m->d_lens_cur, K, rec);
-#define COCR_BEAM_WALK(SL)                                                                                                                          \
-    {                                                                                                                                               \
-        if (bp_in_lds && dyn > 48 * 1024) {      /* (the kernel also has ~12 KB of static LDS: the limit raised for the dynamic part stays below 160 KB - static) */ \
-            static bool raised = false;                                                                                                             \
-            if (!raised) { HIP_TRY(hipFuncSetAttribute((const void *)ctc_beam_walk_kernel<SL>, hipFuncAttributeMaxDynamicSharedMemorySize, 96 * 1024)); raised = true; } \
-        } \
-        hipLaunchKernelGGL(ctc_beam_walk_kernel<SL>, dim3(N), dim3(256), bp_in_lds ? dyn : 0, s, logits, T, ncls, m->d_lens_cur, beam, K, labels, starts, \
-                           ends, conf, counts, max_per_line, rec, bp, bp_in_lds, m->stamps ? m->stamps + 240 : nullptr);                            \
-    }
-        if (beam <= 16) COCR_BEAM_WALK(2) else COCR_BEAM_WALK(3)      // candidates per lane of a wave: <= 88 for beam <= 16, <= 184 for beam 32
-#undef COCR_BEAM_WALK
+        hipLaunchKernelGGL(ctc_beam_rank_kernel, dim3(N * T), dim3(256), 0, s, logits, T, ncls, d_lens, K, rec);
+        auto walk = ctc_beam_walk_kernel<3>;                          // candidates per lane of a wave: <= 88 for beam <= 16, <= 184 for beam 32
+        if (beam <= 16) walk = ctc_beam_walk_kernel<2>;
+        // (the kernel also has ~12 KB of static LDS: the limit raised for the dynamic part stays below 160 KB - static)
+        if (bp_in_lds) HIP_TRY(raise_lds_limit((const void *)walk, dyn, 48 * 1024, 96 * 1024));
+        hipLaunchKernelGGL(walk, dim3(N), dim3(256), bp_in_lds ? dyn : 0, s, logits, T, ncls, d_lens, beam, K, labels, starts,
+                           ends, conf, counts, max_per_line, rec, bp, bp_in_lds, m->stamps ? m->stamps + 240 : nullptr);
     } else {
         float *logz = reinterpret_cast<float *>(bp + (size_t)N * T * COCR_BEAM_MAX);
         const size_t lds = ((size_t)ncls + (size_t)beam * ncls) * 4 + COCR_BEAM_MAX * (11 * 4 + 2 * 8) + 64;
         if (lds > 150 * 1024) return fail(COCR_EUNSUPPORTED, "beam x classes too large for the LDS candidate table");
         HIP_TRY(raise_lds_limit((const void *)ctc_beam_kernel, lds));
-        hipLaunchKernelGGL(ctc_beam_kernel, dim3(N), dim3(64), lds, s, logits, T, ncls, m->d_lens_cur, beam, labels, starts, ends, conf, counts,
+        hipLaunchKernelGGL(ctc_beam_kernel, dim3(N), dim3(64), lds, s, logits, T, ncls, d_lens, beam, labels, starts, ends, conf, counts,
                            max_per_line, bp, logz);
     }
     LAUNCH_CHECK();
@@ -1761,7 +1778,8 @@ extern "C" int cocr_ctc_beam_lm(cocr_model *m, cocr_lm *lm, const float *logits,
     if (!std::isfinite(alpha) || !std::isfinite(beta)) return fail(COCR_EINVAL, "alpha and beta must be finite");
     HIP_TRY(hipSetDevice(m->device));
     hipStream_t s = (hipStream_t)stream;
-    int rc = upload_lens(m, out_lens, N, s);
+    const int32_t *d_lens;
+    int rc = upload_lens(m, out_lens, N, s, d_lens);
     if (rc) return rc;
     const int K = std::min(classes, ncls - 1);
     // scratch: back-pointers [N][T][COCR_BEAM_MAX] i32, then the frame records [N][T][COCR_LM_REC] f32
@@ -1771,58 +1789,67 @@ extern "C" int cocr_ctc_beam_lm(cocr_model *m, cocr_lm *lm, const float *logits,
     float *rec = reinterpret_cast<float *>(m->lm_scratch.p + bp_bytes);
     const size_t dyn = (size_t)T * ((size_t)beam * 4 + 8);                     // back-pointers + the label stack of the final walk, in LDS when they fit
     const int bp_in_lds = dyn <= 96 * 1024;
-    if (bp_in_lds && dyn > 16 * 1024) {                                        // (the kernel has ~30 KB of static LDS)
-        static bool raised = false;
-        if (!raised) { HIP_TRY(hipFuncSetAttribute((const void *)ctc_lm_walk_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, 96 * 1024)); raised = true; }
-    }
+    if (bp_in_lds) HIP_TRY(raise_lds_limit((const void *)ctc_lm_walk_kernel, dyn, 16 * 1024, 96 * 1024));      // (the kernel has ~30 KB of static LDS)
     cocr_lm_tables L;
     L.unigram = lm->unigram.p; L.nkeys = lm->nkeys.p; L.nlogp = lm->nlogp.p; L.ckeys = lm->ckeys.p; L.cbow = lm->cbow.p;
     L.nmask = (unsigned)(lm->nslots - 1); L.cmask = (unsigned)(lm->cslots - 1); L.order = lm->order;
     ProfScope ps(m, s, FAM_BEAM);
-    hipLaunchKernelGGL(ctc_lm_topk_kernel, dim3(ceil_div(N * T, 4)), dim3(256), 0, s, logits, T, ncls, N * T, m->d_lens_cur, K, rec);
+    hipLaunchKernelGGL(ctc_lm_topk_kernel, dim3(ceil_div(N * T, 4)), dim3(256), 0, s, logits, T, ncls, N * T, d_lens, K, rec);
     LAUNCH_CHECK();
-    hipLaunchKernelGGL(ctc_lm_walk_kernel, dim3(N), dim3(256), bp_in_lds ? dyn : 0, s, logits, T, ncls, m->d_lens_cur, beam, K, L, alpha, beta, labels, starts,
+    hipLaunchKernelGGL(ctc_lm_walk_kernel, dim3(N), dim3(256), bp_in_lds ? dyn : 0, s, logits, T, ncls, d_lens, beam, K, L, alpha, beta, labels, starts,
                        ends, conf, counts, score, max_per_line, rec, bp, bp_in_lds);
     LAUNCH_CHECK();
     return COCR_OK;
 }
 
 // ------------------------------------------------------------------------------------ CTC loss (ctc_loss.hip.h)
+// The targets of a batch on the device, and the kernel form for its longest line: sj 64-state columns per lane.
+struct CtcTargets { const int32_t *lens, *label_lens, *label_off, *labels; int sj; };
+
+// Loss and forced alignment: checks the per-line lengths and the labels, then sends [lens | label lens | label offsets | labels]
+// through the targets ring.  `outputs_ok`: the caller's per-label output pointers are set (asked for only where there are labels);
+// `too_long`: the status for a line of more than COCR_CTCL_MAX_LABELS labels.
+static int upload_targets(cocr_model *m, int N, int T, int ncls, const int32_t *out_lens, const int32_t *targets, const int32_t *label_lens,
+                          bool outputs_ok, int too_long, void *stream, CtcTargets &t) {
+    size_t total = 0;
+    int max_l = 0;
+    for (int n = 0; n < N; ++n) {
+        if (label_lens[n] < 0) return fail(COCR_EINVAL, "negative target length (line %d)", n);
+        if (label_lens[n] > COCR_CTCL_MAX_LABELS) return fail(too_long, "line %d has %d labels; the kernel holds at most %d", n, label_lens[n], COCR_CTCL_MAX_LABELS);
+        if (out_lens[n] < 0 || out_lens[n] > T) return fail(COCR_EINVAL, "input length %d outside [0, %d] (line %d)", out_lens[n], T, n);
+        max_l = std::max(max_l, (int)label_lens[n]);
+        total += (size_t)label_lens[n];
+    }
+    if (total && (!targets || !outputs_ok)) return fail(COCR_EINVAL, "null argument");
+    for (size_t i = 0; i < total; ++i)
+        if (targets[i] < 1 || targets[i] >= ncls) return fail(COCR_EINVAL, "target %d outside [1, %d) (blank is 0)", targets[i], ncls);
+    HIP_TRY(hipSetDevice(m->device));
+    const size_t ints = (size_t)3 * N + total;
+    int32_t *h, *d;
+    HIP_TRY(m->target_ring.stage(ints * 4, h, d));
+    int32_t off = 0;
+    for (int n = 0; n < N; ++n) { h[n] = out_lens[n]; h[N + n] = label_lens[n]; h[2 * N + n] = off; off += label_lens[n]; }
+    if (total) memcpy(h + 3 * N, targets, total * 4);
+    HIP_TRY(m->target_ring.commit(ints * 4, (hipStream_t)stream));
+    const int states = 2 * max_l + 1;
+    t = {d, d + N, d + 2 * N, d + 3 * N, states <= 64 ? 1 : states <= 128 ? 2 : states <= 256 ? 4 : 8};
+    return COCR_OK;
+}
+
 extern "C" int cocr_ctc_loss(cocr_model *m, const float *probits, int N, int T, int ncls, const int32_t *out_lens, const int32_t *targets,
                              const int32_t *label_lens, float *nll, float *grad, void *stream) {
     if (!m || !probits || !out_lens || !label_lens || !nll) return fail(COCR_EINVAL, "null argument");
     if (N < 1 || T < 1 || ncls < 2) return fail(COCR_EINVAL, "empty problem");
     if (ncls > 16384) return fail(COCR_EUNSUPPORTED, "more than 16384 classes");
-    size_t total = 0;
-    int max_l = 0;
-    for (int n = 0; n < N; ++n) {
-        if (label_lens[n] < 0) return fail(COCR_EINVAL, "negative target length (line %d)", n);
-        if (label_lens[n] > COCR_CTCL_MAX_LABELS) return fail(COCR_EUNSUPPORTED, "line %d has %d labels; the kernel holds at most %d", n, label_lens[n], COCR_CTCL_MAX_LABELS);
-        if (out_lens[n] < 0 || out_lens[n] > T) return fail(COCR_EINVAL, "input length %d outside [0, %d] (line %d)", out_lens[n], T, n);
-        max_l = std::max(max_l, (int)label_lens[n]);
-        total += (size_t)label_lens[n];
-    }
-    if (total && !targets) return fail(COCR_EINVAL, "null argument");
-    for (size_t i = 0; i < total; ++i)
-        if (targets[i] < 1 || targets[i] >= ncls) return fail(COCR_EINVAL, "target %d outside [1, %d) (blank is 0)", targets[i], ncls);
-    HIP_TRY(hipSetDevice(m->device));
+    CtcTargets t;
+    const int rc = upload_targets(m, N, T, ncls, out_lens, targets, label_lens, true, COCR_EUNSUPPORTED, stream, t);
+    if (rc) return rc;
     hipStream_t s = (hipStream_t)stream;
-    const size_t ints = (size_t)3 * N + total;
-    HIP_TRY(grow_pair(m->loss_d, m->loss_h, ints * COCR_LENS_SLOTS, (ints + ints / 2) * COCR_LENS_SLOTS));
-    const size_t per = m->loss_d.n / COCR_LENS_SLOTS;          // ints per slot
-    const int slot = m->loss_slot;
-    m->loss_slot = (slot + 1) % COCR_LENS_SLOTS;
-    int32_t *h = m->loss_h.p + (size_t)slot * per, *d = m->loss_d.p + (size_t)slot * per;
-    int32_t off = 0;
-    for (int n = 0; n < N; ++n) { h[n] = out_lens[n]; h[N + n] = label_lens[n]; h[2 * N + n] = off; off += label_lens[n]; }
-    if (total) memcpy(h + 3 * N, targets, total * 4);
-    HIP_TRY(hipMemcpyAsync(d, h, ints * 4, hipMemcpyHostToDevice, s));
-    const int states = 2 * max_l + 1;
-    const int sj = states <= 64 ? 1 : states <= 128 ? 2 : states <= 256 ? 4 : 8;
+    const int sj = t.sj;
     const size_t need = (size_t)N * T * ((size_t)ncls + 2 * 64 * sj);
     HIP_TRY(m->loss_ws.grow(need));
     ProfScope ps(m, s, FAM_LOSS);
-    launch_ctc_loss(s, sj, (size_t)ncls * 4, probits, N, T, ncls, d, d + N, d + 2 * N, d + 3 * N, nll, grad, m->loss_ws.p, m->loss_ws.p + (size_t)N * T * ncls);
+    launch_ctc_loss(s, sj, (size_t)ncls * 4, probits, N, T, ncls, t.lens, t.label_lens, t.label_off, t.labels, nll, grad, m->loss_ws.p, m->loss_ws.p + (size_t)N * T * ncls);
     LAUNCH_CHECK();
     return COCR_OK;
 }
@@ -1833,47 +1860,22 @@ extern "C" int cocr_ctc_align(cocr_model *m, const float *logits, int N, int T, 
     if (!m || !logits || !out_lens || !label_lens || !score || !counts) return fail(COCR_EINVAL, "null argument");
     if (N < 1 || T < 1 || ncls < 2) return fail(COCR_EINVAL, "empty problem");
     if (T > 8000) return fail(COCR_EUNSUPPORTED, "more than 8000 frames per line");
-    size_t total = 0;
-    int max_l = 0;
-    for (int n = 0; n < N; ++n) {
-        if (label_lens[n] < 0) return fail(COCR_EINVAL, "negative target length (line %d)", n);
-        if (label_lens[n] > COCR_CTCL_MAX_LABELS) return fail(COCR_EINVAL, "line %d has %d labels; the kernel holds at most %d", n, label_lens[n], COCR_CTCL_MAX_LABELS);
-        if (out_lens[n] < 0 || out_lens[n] > T) return fail(COCR_EINVAL, "input length %d outside [0, %d] (line %d)", out_lens[n], T, n);
-        max_l = std::max(max_l, (int)label_lens[n]);
-        total += (size_t)label_lens[n];
-    }
-    if (total && (!targets || !starts || !ends || !conf)) return fail(COCR_EINVAL, "null argument");
-    for (size_t i = 0; i < total; ++i)
-        if (targets[i] < 1 || targets[i] >= ncls) return fail(COCR_EINVAL, "target %d outside [1, %d) (blank is 0)", targets[i], ncls);
-    HIP_TRY(hipSetDevice(m->device));
+    CtcTargets t;
+    const int rc = upload_targets(m, N, T, ncls, out_lens, targets, label_lens, starts && ends && conf, COCR_EINVAL, stream, t);
+    if (rc) return rc;
     hipStream_t s = (hipStream_t)stream;
-    const size_t ints = (size_t)3 * N + total;
-    HIP_TRY(grow_pair(m->align_d, m->align_h, ints * COCR_LENS_SLOTS, (ints + ints / 2) * COCR_LENS_SLOTS));
-    const size_t per = m->align_d.n / COCR_LENS_SLOTS;         // ints per slot
-    const int slot = m->align_slot;
-    m->align_slot = (slot + 1) % COCR_LENS_SLOTS;
-    int32_t *h = m->align_h.p + (size_t)slot * per, *d = m->align_d.p + (size_t)slot * per;
-    int32_t off = 0;
-    for (int n = 0; n < N; ++n) { h[n] = out_lens[n]; h[N + n] = label_lens[n]; h[2 * N + n] = off; off += label_lens[n]; }
-    if (total) memcpy(h + 3 * N, targets, total * 4);
-    HIP_TRY(hipMemcpyAsync(d, h, ints * 4, hipMemcpyHostToDevice, s));
-    const int states = 2 * max_l + 1;
-    const int sj = states <= 64 ? 1 : states <= 128 ? 2 : states <= 256 ? 4 : 8;
+    const int sj = t.sj;
     // the back-pointer table: in LDS beside lz when both fit (the kernel has ~5 KB of static LDS), else one region per line of the workspace
     const size_t words = ctca_bp_words(T, sj), lds_all = ctca_lz_bytes(T) + words * 4;
     if (lds_all <= 144 * 1024) {
+        auto kern = ctc_align_kernel<8, true>;
+        switch (sj) { case 1: kern = ctc_align_kernel<1, true>; break; case 2: kern = ctc_align_kernel<2, true>; break; case 4: kern = ctc_align_kernel<4, true>; break; }
         // (the kernel also has ~5 KB of static LDS: the limit raised for the dynamic part stays below 160 KB - static)
-#define COCR_ALIGN_LDS(SJ)                                                                                                                          \
-    if (lds_all > 48 * 1024) {                                                                                                                      \
-        static bool raised = false;                                                                                                                 \
-        if (!raised) { HIP_TRY(hipFuncSetAttribute((const void *)ctc_align_kernel<SJ, true>, hipFuncAttributeMaxDynamicSharedMemorySize, 150 * 1024)); raised = true; } \
-    }
-        switch (sj) { case 1: COCR_ALIGN_LDS(1); break; case 2: COCR_ALIGN_LDS(2); break; case 4: COCR_ALIGN_LDS(4); break; default: COCR_ALIGN_LDS(8); break; }
-#undef COCR_ALIGN_LDS
-        launch_ctc_align<true>(s, sj, lds_all, logits, N, T, ncls, d, d + N, d + 2 * N, d + 3 * N, starts, ends, conf, score, counts, nullptr, 0);
+        HIP_TRY(raise_lds_limit((const void *)kern, lds_all, 48 * 1024, 150 * 1024));
+        launch_ctc_align<true>(s, sj, lds_all, logits, N, T, ncls, t.lens, t.label_lens, t.label_off, t.labels, starts, ends, conf, score, counts, nullptr, 0);
     } else {
         HIP_TRY(m->align_ws.grow((size_t)N * words));
-        launch_ctc_align<false>(s, sj, ctca_lz_bytes(T), logits, N, T, ncls, d, d + N, d + 2 * N, d + 3 * N, starts, ends, conf, score, counts,
+        launch_ctc_align<false>(s, sj, ctca_lz_bytes(T), logits, N, T, ncls, t.lens, t.label_lens, t.label_off, t.labels, starts, ends, conf, score, counts,
                                 m->align_ws.p, words);
     }
     LAUNCH_CHECK();
@@ -2163,18 +2165,9 @@ extern "C" int cocr_edit_align(cocr_model *m, const int32_t *a, const int64_t *a
     const int ws_groups = (int)std::min<size_t>(cls[3].size(), 32);      // workgroups of the workspace launch, one region each
     if (ws_groups) HIP_TRY(m->score_ws.grow((size_t)ws_groups * ws_words));
     // the tables of this call, through the pinned ring
-    const size_t offs_bytes = (size_t)(P + 1) * 8, bytes = 2 * offs_bytes + (size_t)P * 4, slots = 4;
-    const size_t per_need = (bytes + 15) & ~(size_t)15;
-    if (per_need * slots > m->score_d.n || per_need * slots > m->score_h.n) {
-        HIP_TRY(hipDeviceSynchronize());                          // uploads of earlier calls still read the old ring
-        HIP_TRY(grow_pair(m->score_d, m->score_h, per_need * slots, (per_need + per_need / 2 + 15) / 16 * 16 * slots));
-    }
-    const size_t per = m->score_d.n / slots / 16 * 16;
-    const int slot = m->score_slot;
-    m->score_slot = (slot + 1) % (int)slots;
-    if (!m->score_ev[slot]) HIP_TRY(hipEventCreateWithFlags(&m->score_ev[slot], hipEventDisableTiming));
-    else HIP_TRY(hipEventSynchronize(m->score_ev[slot]));         // four calls back: long finished unless the caller never collects
-    unsigned char *h = m->score_h.p + (size_t)slot * per, *d = m->score_d.p + (size_t)slot * per;
+    const size_t offs_bytes = (size_t)(P + 1) * 8, bytes = 2 * offs_bytes + (size_t)P * 4;
+    unsigned char *h, *d;
+    HIP_TRY(m->score_ring.stage(bytes, h, d));
     memcpy(h, a_offs, offs_bytes);
     memcpy(h + offs_bytes, b_offs, offs_bytes);
     int *order = reinterpret_cast<int *>(h + 2 * offs_bytes);
@@ -2184,8 +2177,7 @@ extern "C" int cocr_edit_align(cocr_model *m, const int32_t *a, const int64_t *a
         first[c] = at;
         for (int p : cls[c]) order[at++] = p;
     }
-    HIP_TRY(hipMemcpyAsync(d, h, bytes, hipMemcpyHostToDevice, s));
-    HIP_TRY(hipEventRecord(m->score_ev[slot], s));
+    HIP_TRY(m->score_ring.commit(bytes, s));
     const long long *d_ao = reinterpret_cast<const long long *>(d), *d_bo = reinterpret_cast<const long long *>(d + offs_bytes);
     const int *d_order = reinterpret_cast<const int *>(d + 2 * offs_bytes);
     for (int c = 0; c < 3; ++c) {

@@ -20,6 +20,7 @@
 // direct 8-byte-per-lane store of the accumulator layout -- 32-byte row fragments -- took 2/3 of the kernel.)
 #pragma once
 #include <algorithm>
+#include <mutex>
 #include <set>
 #include <type_traits>
 
@@ -753,11 +754,15 @@ __global__ __launch_bounds__(256) void gemm_stream_kernel(GemmArgs<T> p, Epi epi
 }
 
 // ---- host side ---------------------------------------------------------------------------------------
-static inline hipError_t raise_lds_limit(const void *kern, size_t lds) {
-    if (lds <= 64 * 1024) return hipSuccess;
+// A launch with more than `above` bytes of dynamic LDS needs the kernel's limit raised first, to `limit` (a kernel with static LDS
+// of its own passes figures that leave room for it).  Models on several threads launch at once: the set is locked.
+static inline hipError_t raise_lds_limit(const void *kern, size_t lds, size_t above = 64 * 1024, int limit = 160 * 1024) {
+    if (lds <= above) return hipSuccess;
+    static std::mutex mu;
     static std::set<const void *> raised;      // per kernel instantiation, once
+    std::lock_guard<std::mutex> lock(mu);
     if (raised.count(kern)) return hipSuccess;
-    hipError_t e = hipFuncSetAttribute(kern, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
+    hipError_t e = hipFuncSetAttribute(kern, hipFuncAttributeMaxDynamicSharedMemorySize, limit);
     if (e == hipSuccess) raised.insert(kern);
     return e;
 }

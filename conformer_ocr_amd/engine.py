@@ -19,7 +19,19 @@ def _stream_ptr(device: torch.device) -> C.c_void_p:
     return C.c_void_p(torch.cuda.current_stream(device).cuda_stream)
 
 
-_LAST_WRITER: Dict[int, int] = {}          # logits buffer address -> sequence number of the last `forward` (of any engine) that wrote it
+def _target_arrays(N: int, out_lens, targets, label_lens):
+    """The contiguous int32 host vectors (lens, label lens, labels) `cocr_ctc_loss` and `cocr_ctc_align` take for N lines."""
+    lens = np.ascontiguousarray(np.asarray(out_lens, dtype=np.int32).reshape(-1))
+    tl = np.ascontiguousarray(np.asarray(label_lens, dtype=np.int32).reshape(-1))
+    tg = np.ascontiguousarray(np.asarray(targets, dtype=np.int32).reshape(-1))
+    if lens.shape[0] != N or tl.shape[0] != N:
+        raise ValueError('out_lens and label_lens need one entry per line')
+    if int(tl.sum()) != tg.shape[0]:
+        raise ValueError('targets must hold sum(label_lens) labels')
+    return lens, tl, tg
+
+
+_LAST_WRITER: Dict[int, int] = {}         # logits buffer address -> sequence number of the last `forward` (of any engine) that wrote it
 
 
 class HipRecognizer:
@@ -271,13 +283,7 @@ class HipRecognizer:
             raise RuntimeError('probits must be a float32 (N,T,num_classes) tensor on the model device')
         probits = probits.contiguous()
         N, T, ncls = probits.shape
-        lens = np.ascontiguousarray(np.asarray(out_lens, dtype=np.int32).reshape(-1))
-        tl = np.ascontiguousarray(np.asarray(label_lens, dtype=np.int32).reshape(-1))
-        tg = np.ascontiguousarray(np.asarray(targets, dtype=np.int32).reshape(-1))
-        if lens.shape[0] != N or tl.shape[0] != N:
-            raise ValueError('out_lens and label_lens need one entry per line')
-        if int(tl.sum()) != tg.shape[0]:
-            raise ValueError('targets must hold sum(label_lens) labels')
+        lens, tl, tg = _target_arrays(N, out_lens, targets, label_lens)
         nll = torch.empty((N,), dtype=torch.float32, device=self.device)
         grad = torch.empty_like(probits) if with_grad else None
         i32 = C.POINTER(C.c_int32)
@@ -298,13 +304,7 @@ class HipRecognizer:
             raise RuntimeError('logits must be a float32 (N,T,num_classes) tensor on the model device')
         cont = logits.contiguous()
         N, T, ncls = cont.shape
-        lens = np.ascontiguousarray(np.asarray(out_lens, dtype=np.int32).reshape(-1))
-        tl = np.ascontiguousarray(np.asarray(label_lens, dtype=np.int32).reshape(-1))
-        tg = np.ascontiguousarray(np.asarray(targets, dtype=np.int32).reshape(-1))
-        if lens.shape[0] != N or tl.shape[0] != N:
-            raise ValueError('out_lens and label_lens need one entry per line')
-        if int(tl.sum()) != tg.shape[0]:
-            raise ValueError('targets must hold sum(label_lens) labels')
+        lens, tl, tg = _target_arrays(N, out_lens, targets, label_lens)
         i32 = C.POINTER(C.c_int32)
         with torch.cuda.device(self.device):
             key = ('align', N)
