@@ -65,7 +65,8 @@ def check(name, eng, loss, ref, rel=2e-3, floor=1e-5, loss_rel=2e-4, running_tol
         errs[k] = (float(np.abs(eng.train_grad(k) - r).max()), float(np.abs(r).max()))
     worst = max(errs.items(), key=lambda kv: kv[1][0] / (kv[1][1] + floor / rel))
     print(f'{name}: loss {loss!r} vs {loss64!r} (rel {abs(loss - loss64) / abs(loss64):.2e}); worst gradient {worst[0]}: '
-          f'err {worst[1][0]:.3e} of max {worst[1][1]:.3e} (ratio {worst[1][0] / max(worst[1][1], 1e-300):.2e})')
+          f'err {worst[1][0]:.3e} of max {worst[1][1]:.3e} (ratio {worst[1][0] / max(worst[1][1], 1e-300):.2e}, {worst[1][0] / (rel * worst[1][1] + floor):.3f} '
+          f'of its bound); largest err / max|ref| over the tensors with max|ref| > 1e-9: {max(e[0] / e[1] for e in errs.values() if e[1] > 1e-9):.2e}')
     assert abs(loss - loss64) <= loss_rel * abs(loss64), (loss, loss64)
     bad = {k: e for k, e in errs.items() if not e[0] <= rel * e[1] + floor}
     if rel_per_tensor:

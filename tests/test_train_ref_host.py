@@ -1,6 +1,7 @@
 """No GPU: the host restatement of the training step's dropout (tests/train_ref.py) -- the statistics of the mask generator itself, and the
 placement of the six sites in the oracle against the REFERENCE's own nn.Dropout modules (tests/golden/tiny_train_drop.npz).  The GPU tests
-of tests/test_hip_train_pin.py compare the HIP step with what is checked here."""
+of tests/test_hip_train_pin.py compare the HIP step with what is checked here.  Also: the recorded 'medium' figures, and what each case of
+tests/test_hip_train_shapes.py must keep selecting, evaluated from the hyper-parameters alone."""
 import itertools
 import os
 
@@ -9,7 +10,8 @@ import pytest
 
 from tests.train_ref import (DROP_ATTN_OUT, DROP_ATTN_WEIGHTS, DROP_CONV_OUT, DROP_FF_HIDDEN, DROP_FF_OUT, DROP_SITE_INPUT, drop_keep, drop_scale,
                              drop_site, medium_e_ref, medium_e_ref_sampled, oracle_train_grads_dropped, bn_running,
-                             DROP_SEED, E_BN, E_REF, NO_DROP, P4, inputs, tiny_sampled_e_ref)
+                             DROP_SEED, E_BN, E_REF, NO_DROP, P4, inputs, tiny_sampled_e_ref,
+                             CASES, MEDIUM_SHAPE_CASES, SHAPE_CASES, SHAPE_PRE, assert_shape_selects, medium_e_ref_runs, train_wg_splits)
 
 N = 1 << 20
 SEED = 20240229
@@ -148,3 +150,35 @@ def test_recorded_per_tensor_figures_of_tiny_hold_other_float32_runs():
     print(f'held-out float32 runs: worst {worst[0]:.2f} x its recorded figure ({worst[1]}); recomputed figures: worst factor {drift[0]:.2f} ({drift[1]})')
     assert worst[0] <= 4.0, worst
     assert drift[0] <= 4.0, drift
+
+
+@pytest.mark.parametrize('name', MEDIUM_SHAPE_CASES)
+def test_recorded_e_ref_of_the_shape_cases_is_what_the_rounded_oracle_gives(name):
+    """E_REF / E_BN of the four 'medium' cases of tests/test_hip_train_shapes.py against fresh float32 runs, as for 'tiny' above: the recorded
+    value inside the spread of the unperturbed run and two runs on states moved by one ulp (one float64 run shared: 'widest' costs seconds
+    per run), widened by 1.5 either way; the running statistics within 4 x the recorded figure."""
+    runs = medium_e_ref_runs(*inputs(name), perturbed=2, perturb_seed=2)
+    spread = sorted(e for e, _ in runs)
+    print(f'{name}: e_ref {runs[0][0]:.3e}, perturbed {spread[0]:.3e} .. {spread[-1]:.3e} (recorded {E_REF[(name, False)]:.3e}); '
+          f'e_bn {runs[0][1]:.2e} (recorded {E_BN[(name, False)]:.2e})')
+    assert spread[0] / 1.5 <= E_REF[(name, False)] <= 1.5 * spread[-1]
+    assert runs[0][1] <= 4 * E_BN[(name, False)] + 1e-7
+
+
+def test_train_wg_splits_restated():
+    """train_step.hip.h `train_wg_splits` at the products the cases name: 128 x 128 tiles, 512 / tiles clamped to [1, 32]."""
+    assert [train_wg_splits(*nk) for nk in ((1024, 256), (256, 256), (576, 144), (144, 768), (2048, 512), (1024, 512), (4096, 1024), (1024, 4096),
+                                            (1024, 16384), (2048, 1024), (1024, 1024), (97, 256), (129, 128))] == [32, 32, 32, 32, 8, 16, 2, 2, 1, 4, 8, 32, 32]
+
+
+@pytest.mark.parametrize('name', list(SHAPE_CASES))
+def test_every_shape_case_still_selects_its_branch(name):
+    """What a case of tests/test_hip_train_shapes.py exists for (train_ref.SHAPE_PRE: dh % 32 and dh % 4, dh > 64, K > 32, K != 31 and K <= 32,
+    D > 256, T > 64, the tfc inequality, the split counts), from the hyper-parameters and the padded width: a shape edit fails here first.
+    One encoder block, at most 75 output frames, ragged widths and targets that fit."""
+    f = assert_shape_selects(name)
+    c, hp = CASES[name], CASES[name]['hp']()
+    assert set(SHAPE_PRE) == set(SHAPE_CASES) and hp.num_encoder_layers == 1 and f['T'] <= 75
+    assert len(c['widths']) == len(c['targets']) == c['n'] and max(c['widths']) == c['W'] and len(set(c['widths'])) == c['n']
+    assert all(0 < x < hp.num_classes for s in c['targets'] for x in s)
+    assert hp.encoder_dim % 16 == 0 and hp.encoder_dim <= 1024 and f['dh'] <= 128 and f['dh'] * f['heads'] == f['D']

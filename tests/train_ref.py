@@ -196,6 +196,21 @@ def medium_e_ref_sampled(hp, state, image, lens, targets, p4=(0.0, 0.0, 0.0, 0.0
     return {k: max(r[k] for r in each) for k in each[0]}, each
 
 
+def medium_e_ref_runs(hp, state, image, lens, targets, p4=(0.0, 0.0, 0.0, 0.0), seed=0, perturbed=2, perturb_seed=0):
+    """[(e_ref, e_bn)] of 1 + `perturbed` float32 evaluations against ONE float64 one: the first is `medium_e_ref`'s own pair (the unperturbed
+    state), the others run on `perturbed_state` copies.  For the larger models, where a float64 run per sample would cost seconds."""
+    _, p64, g64, bn64 = oracle_train_grads_medium(hp, state, image, lens, targets, p4, seed, torch.float64)
+    M = p64.shape[0] * p64.shape[1]
+    r64 = bn_running(state, bn64, M)
+    rng, out = np.random.default_rng(perturb_seed), []
+    for i in range(1 + perturbed):
+        _, _, g32, bn32 = oracle_train_grads_medium(hp, state if i == 0 else perturbed_state(state, rng), image, lens, targets, p4, seed, torch.float32)
+        r32 = bn_running(state, bn32, M)
+        out.append((max(float(np.abs(g32[k].astype(np.float64) - g64[k]).max() / np.abs(g64[k]).max()) for k in g64 if np.abs(g64[k]).max() > 1e-9),
+                    max(float(np.abs(r64[k] - r32[k]).max()) for k in r64)))
+    return out
+
+
 def bn_running(state, bn: Dict[int, tuple], M: int) -> Dict[str, np.ndarray]:
     """The BatchNorm running statistics a step leaves: momentum 0.1, unbiased batch variance over the M = N T positions."""
     out = {}
@@ -206,7 +221,7 @@ def bn_running(state, bn: Dict[int, tuple], M: int) -> Dict[str, np.ndarray]:
     return out
 
 
-# ---- the cases and recorded figures of tests/test_hip_train_pin.py (here so that non-GPU tests can use them without the engine) -------------------
+# ---- the cases and recorded figures of tests/test_hip_train_pin.py and tests/test_hip_train_shapes.py (here so that non-GPU tests can use them without the engine) -------------------
 P4 = (0.1, 0.2, 0.3, 0.4)          # (input, feed_forward, attention, conv): four distinct values, as in tiny_train_drop.npz
 DROP_SEED = 20240229
 NO_DROP = (0.0, 0.0, 0.0, 0.0)
@@ -233,6 +248,98 @@ CASES = {
                       targets=[[5, 9, 9, 3], [17], [2, 2], [40, 7, 7], [1], [3, 1, 4, 1], [59, 26], [5, 35, 8]]),
 }
 
+# ---- one case per kernel form that the model's dimensions select (tests/test_hip_train_shapes.py; what each one must keep selecting:
+# SHAPE_PRE below).  One encoder block each, at most 75 output frames; heights other than 96 only shrink the frontend.
+SHAPE_CASES = {
+    # the reference's default model: row attention at dh = 36 with T = 75 > 64 (a lane walks two keys), D = 144 / ff = 576 / 2 D = 288 (partial
+    # 128-wide tiles in every weight gradient), 32 conv channels, the <31> depthwise kernels with 144 of 256 lanes live
+    'cfg1_1': dict(hp=lambda: synth.hparams('cfg1', num_encoder_layers=1), seed=41, n=3, W=300, widths=[300, 137, 222],
+                   targets=[[5, 9, 9, 3], [17], [2, 2, 40]]),
+    # dh = 72: the second pass of every `d += 64` loop of the row kernels, per-wave LDS rows of 72 floats
+    'cfg1_h2': dict(hp=lambda: synth.hparams('cfg1', num_encoder_layers=1, num_attention_heads=2, height=32), seed=42, n=2, W=280, widths=[280, 171],
+                    targets=[[5, 9, 9, 3], [17, 2]]),
+    # dh = 18: the scalar path of the row kernels (dh % 4 != 0)
+    'cfg1_h8': dict(hp=lambda: synth.hparams('cfg1', num_encoder_layers=1, num_attention_heads=8, height=32), seed=43, n=2, W=280, widths=[280, 171],
+                    targets=[[5, 9, 9, 3], [17, 2]]),
+    # dh = 32: batched attention with ONE 32-wide k-chunk; T = 70, Tk = 96, Rk = 160: every padded dimension is padded
+    'h8': dict(hp=lambda: synth.hparams('cfg2', num_encoder_layers=1, num_attention_heads=8, height=32), seed=44, n=2, W=280, widths=[280, 171],
+               targets=[[5, 9, 9, 3], [17, 2]]),
+    # dh = 128, the largest head: batched attention with four k-chunks
+    'h2': dict(hp=lambda: synth.hparams('cfg2', num_encoder_layers=1, num_attention_heads=2, height=32), seed=45, n=2, W=280, widths=[280, 171],
+               targets=[[5, 9, 9, 3], [17, 2]]),
+    # kernel 15 at D = 256: k_dw1d_rows<., 0> / k_dw1d_bwd_w<0> with every lane live; T = 35 = two 16-frame chunks and one of 3 frames, halos
+    # of 7 frames crossing chunk and line ends
+    'k15': dict(hp=lambda: synth.hparams('cfg2', num_encoder_layers=1, conv_kernel_size=15, height=32), seed=46, n=2, W=140, widths=[140, 93],
+                targets=[[5, 9, 3], [17]]),
+    # kernel 33 > 32: the flat depthwise kernels (forward, input gradient with flip = 1, tap gradient)
+    'k33': dict(hp=lambda: synth.hparams('cfg2', num_encoder_layers=1, conv_kernel_size=33, height=32), seed=47, n=2, W=280, widths=[280, 171],
+                targets=[[5, 9, 9, 3], [17, 2]]),
+    # D = 512: two column blocks in the depthwise / column-sum / BatchNorm kernels, 8 heads of 64, 8 splits in the feed-forward weight gradients
+    'd512k7': dict(hp=lambda: synth.hparams('cfg4', num_encoder_layers=1, conv_kernel_size=7, height=32), seed=48, n=2, W=140, widths=[140, 93],
+                   targets=[[5, 9, 3], [17]]),
+    # the full-step feed-forward residual (ffr = 1), expansion 2 (ff = 512), 97 classes (nclp = 100: k_pad_cols, scalar column sums, `gemm`'s own
+    # rounding rule under 'medium')
+    'nohalf97ff2': dict(hp=lambda: synth.hparams('cfg2', num_encoder_layers=1, half_step_residual=False, num_classes=97,
+                                                 feed_forward_expansion_factor=2, height=32), seed=49, n=2, W=140, widths=[140, 93],
+                        targets=[[5, 9, 3], [96]]),
+    # D = 1024, the widest accepted: four column blocks, dh = 128, the frontend's output linear (1024, 16384) = 1024 tiles -> splits == 1 (the
+    # weight gradient written directly), feed-forward (4096, 1024) -> 2 splits, F (C + 1) 4 = 65664 > 65536 bytes -> the flat tfc
+    'widest': dict(hp=lambda: synth.hparams('cfg4', num_encoder_layers=1, encoder_dim=1024, num_attention_heads=8, subsampling_conv_channels=512,
+                                            height=128, conv_kernel_size=15), seed=50, n=2, W=140, widths=[140, 93], targets=[[5, 9, 3], [17]]),
+}
+CASES.update(SHAPE_CASES)
+MEDIUM_SHAPE_CASES = ('cfg1_1', 'd512k7', 'nohalf97ff2', 'widest')
+
+
+def train_wg_splits(Nc: int, Kr: int) -> int:
+    """train_step.hip.h `train_wg_splits`: `tiles = ceil_div(Nc, COCR_FO_BM) * ceil_div(Kr, COCR_FO_BN)` with 128 x 128 tiles,
+    `max(1, min(32, 512 / tiles))`."""
+    tiles = -(-Nc // 128) * -(-Kr // 128)
+    return max(1, min(32, 512 // tiles))
+
+
+def shape_facts(name) -> Dict[str, int]:
+    """The dimensions train_plan (train_step.hip.h) derives for a case, from its hyper-parameters and padded width alone."""
+    hp, W = CASES[name]['hp'](), CASES[name]['W']
+    stages = {2: 1, 4: 2, 8: 3}[hp.subsampling_factor]
+    down = lambda x: functools.reduce(lambda l, _: (l - 1) // 2 + 1, range(stages), x)          # (out_len1 per stride-2 stage)
+    D, C, T, F = hp.encoder_dim, hp.subsampling_conv_channels, down(W), down(hp.height)
+    f = dict(D=D, C=C, T=T, F=F, K=hp.conv_kernel_size, heads=hp.num_attention_heads, dh=D // hp.num_attention_heads, ncls=hp.num_classes,
+             ff=hp.feed_forward_expansion_factor * D, Tk=(T + 31) // 32 * 32, Rk=(2 * T - 1 + 31) // 32 * 32, nclp=(hp.num_classes + 3) // 4 * 4,
+             col_blocks=-(-D // 256), chunks=-(-T // 16), tfc_lds=F * (C + 1) * 4, half=bool(hp.half_step_residual))
+    f.update(s_up=train_wg_splits(f['ff'], D), s_down=train_wg_splits(D, f['ff']), s_dd=train_wg_splits(D, D), s_glu=train_wg_splits(2 * D, D),
+             s_out=train_wg_splits(D, C * F), s_dec=train_wg_splits(hp.num_classes, D), s_cc=train_wg_splits(C, C))
+    return f
+
+
+# What each case exists for, as a predicate over `shape_facts`: asserted by the GPU test before it runs and by tests/test_train_ref_host.py
+# without a GPU, so that a later change of shapes cannot silently lose the branch.  The code lines: p.attn_gemm = dh % 32 == 0 and
+# train_wg_splits (train_step.hip.h), `d += 64` / `(dh & 3) == 0` (k_attn_* of train_enc.hip.h), K == 31 / K <= 32 / else (conv_fwd, conv_bwd),
+# ceil_div(D, 256) column blocks, the LDS test of `tfc`, ffr, `Nc % 4` (lin_bwd, colsum).
+SHAPE_PRE = {
+    'cfg1_1': lambda f: f['dh'] == 36 and f['dh'] % 32 != 0 and f['dh'] % 4 == 0 and f['T'] > 64 and f['K'] == 31 and f['D'] < 256
+    and all(x % 128 != 0 for x in (f['D'], f['ff'], 2 * f['D'])) and all(x % 8 == 0 for x in (f['D'], f['ff'], f['C'], f['C'] * f['F'], f['ncls']))
+    and (f['s_up'], f['s_down'], f['s_dd'], f['s_glu'], f['s_out'], f['s_dec'], f['s_cc']) == (32,) * 7,
+    'cfg1_h2': lambda f: f['dh'] == 72 and f['dh'] > 64 and f['dh'] % 32 != 0 and f['dh'] % 4 == 0 and f['T'] > 64,
+    'cfg1_h8': lambda f: f['dh'] == 18 and f['dh'] % 4 != 0 and f['dh'] % 32 != 0 and f['T'] > 64,
+    'h8': lambda f: f['dh'] == 32 and f['dh'] % 32 == 0 and f['dh'] // 32 == 1 and f['T'] > 64 and (f['T'], f['Tk'], f['Rk']) == (70, 96, 160)
+    and f['T'] < f['Tk'] and 2 * f['T'] - 1 < f['Rk'],
+    'h2': lambda f: f['dh'] == 128 and f['dh'] % 32 == 0 and f['T'] > 64 and f['T'] < f['Tk'],
+    'k15': lambda f: f['K'] != 31 and f['K'] <= 32 and f['D'] >= 256 and f['chunks'] == 3 and f['T'] % 16 != 0 and (f['K'] - 1) // 2 > f['T'] % 16,
+    'k33': lambda f: f['K'] > 32,
+    'd512k7': lambda f: f['D'] > 256 and f['col_blocks'] == 2 and f['dh'] == 64 and f['K'] != 31 and f['K'] <= 32
+    and (f['s_up'], f['s_down'], f['s_dd'], f['s_glu'], f['s_out']) == (8, 8, 32, 16, 8),
+    'nohalf97ff2': lambda f: not f['half'] and f['ff'] == 2 * f['D'] and f['ncls'] % 4 != 0 and f['nclp'] == 100 and f['ncls'] % 8 != 0 and f['nclp'] % 8 != 0,
+    'widest': lambda f: f['D'] == 1024 and f['D'] > 256 and f['col_blocks'] == 4 and f['dh'] == 128 and f['dh'] % 32 == 0 and f['K'] != 31 and f['K'] <= 32
+    and f['tfc_lds'] > 64 * 1024 and (f['s_out'], f['s_up'], f['s_down'], f['s_dd'], f['s_glu']) == (1, 2, 2, 8, 4),
+}
+
+
+def assert_shape_selects(name):
+    f = shape_facts(name)
+    assert SHAPE_PRE[name](f), (name, f)
+    return f
+
 
 @functools.lru_cache(maxsize=None)
 def inputs(name):
@@ -249,9 +356,12 @@ def inputs(name):
 # E_BN: the same measure on the BatchNorm running statistics after the step (absolute: they are O(0.1 .. 1)); their bound is the suite's 1e-5
 # plus 4 E_BN.  Keys: (case, dropout on).
 E_BN = {('tiny', False): 7.8e-9, ('tiny', True): 2.6e-7, ('cfg2x2_232', False): 2.42e-4, ('cfg2x2_232', True): 1.14e-4,
-        ('rows', False): 9.3e-6, ('rows', True): 1.96e-5}
+        ('rows', False): 9.3e-6, ('rows', True): 1.96e-5,
+        ('cfg1_1', False): 2.68e-5, ('d512k7', False): 1.00e-4, ('nohalf97ff2', False): 3.94e-5, ('widest', False): 1.18e-4}
 E_REF = {('tiny', False): 5.11e-3, ('tiny', True): 1.04e-2, ('cfg2x2_232', False): 5.54e-3, ('cfg2x2_232', True): 1.03e-2,
-         ('rows', False): 3.09e-3, ('rows', True): 2.88e-3}
+         ('rows', False): 3.09e-3, ('rows', True): 2.88e-3,
+         # (SHAPE_CASES; four float32 runs on states moved by one ulp give 4.1e-3 .. 5.2e-3, 6.3e-3 .. 8.1e-3, 4.6e-3 .. 6.1e-3, 6.1e-3 .. 8.1e-3)
+         ('cfg1_1', False): 4.44e-3, ('d512k7', False): 5.97e-3, ('nohalf97ff2', False): 3.48e-3, ('widest', False): 4.85e-3}
 
 
 def tiny_sampled_e_ref() -> Dict[str, float]:
