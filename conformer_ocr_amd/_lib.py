@@ -85,6 +85,7 @@ SYMBOLS = {
     'cocr_edit_align_lds': (C.c_int64, [_P, _I, _I]),
     'cocr_set_graph': (_I, [_P, _I]),
     'cocr_set_chain_rows': (_I, [_P, _I]),
+    'cocr_get_chain_rows': (_I, [_P, _I, _I, C.POINTER(C.c_int)]),
     'cocr_set_debug': (_I, [_P, _I]),
     'cocr_debug_tap': (_I, [_P, C.c_char_p, _P, C.c_int64, C.POINTER(C.c_int64)]),
     'cocr_profile': (_I, [_P, _I]),

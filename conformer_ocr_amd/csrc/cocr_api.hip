@@ -184,6 +184,9 @@ struct cocr_model {
     // 256 MB Infinity Cache -- every forward then streamed its weights from HBM).  `wgen`: bumped whenever the owner's buffers may have moved.
     cocr_model *owner = nullptr;
     unsigned long long wgen = 1, seen_wgen = 0;
+    // the models that read THIS model's weights (cocr_share_weights; left again by drop_weights): with the owner, the batches one caller
+    // can keep in flight on one set of weights -- chain_rows_for picks the rows per workgroup of the chain launches from their number
+    std::vector<cocr_model *> sharers;
     // workspace
     int capN = 0, capW = 0;
     std::vector<void *> ws_allocs;
@@ -222,7 +225,7 @@ struct cocr_model {
     // debug / profile
     // hipGraph replay of the forward's launch sequence, keyed by the call's shapes and buffers
     bool use_graph = false;
-    struct GraphEntry { const void *lines; float *logits; int N, W, dtype; hipStream_t s; hipGraphExec_t exec; };
+    struct GraphEntry { const void *lines; float *logits; int N, W, dtype; hipStream_t s; hipGraphExec_t exec; int rows; };      // rows: Form::chain_rows of the captured launches
     std::vector<GraphEntry> graphs, graph_seen;
     bool debug = false;
     unsigned long long *stamps = nullptr;   // COCR_CHAIN_STAMPS=1 (dev builds): host-visible cycle stamps of the frontend / attention / beam kernels, printed at destroy
@@ -379,9 +382,13 @@ static void clear_taps(cocr_model *m) {
 
 // the weights and their derived copies: released when they are the model's own, forgotten when they are an owner's (cocr_share_weights)
 static void drop_weights(cocr_model *m) {
-    if (!m->owner)
+    if (!m->owner) {
         for (void *p : {(void *)m->blob, (void *)m->packed, (void *)m->ptab, (void *)m->fpack})
             if (p) (void)hipFree(p);
+    } else {
+        auto &sh = m->owner->sharers;       // one batch in flight fewer on the owner's weights
+        sh.erase(std::remove(sh.begin(), sh.end(), m), sh.end());
+    }
     m->owner = nullptr;
     m->blob = m->packed = m->ptab = nullptr;
     m->fpack = nullptr;
@@ -394,6 +401,13 @@ extern "C" void cocr_destroy(cocr_model *m) {
     train_free(m);
     free_workspace(m);
     clear_taps(m);
+    for (cocr_model *sh : m->sharers) {                 // models that still read these weights: left unfinalized, not with pointers to freed memory
+        drop_graphs(sh);
+        sh->owner = nullptr;
+        sh->blob = sh->packed = sh->ptab = nullptr;
+        sh->fpack = nullptr;
+    }
+    m->sharers.clear();
     drop_weights(m);
     if (m->stamps) {
         (void)hipDeviceSynchronize();
@@ -609,6 +623,7 @@ extern "C" int cocr_share_weights(cocr_model *m, cocr_model *owner) {
     if (m->dtype != owner->dtype || !m->blob || m->owner) { const int rc = alloc_blob(m, owner->dtype); if (rc) return rc; }     // dims, plan
     drop_weights(m);
     m->owner = owner;
+    owner->sharers.push_back(m);
     m->seen_wgen = 0;                               // the next forward adopts the owner's pointers
     m->blob = owner->blob;                          // ("finalized" tests look at it)
     drop_graphs(m);
@@ -1009,7 +1024,49 @@ struct Form {
     bool taps;         // debug taps (cocr_set_debug): the chains run their TAPS instantiation; per product, the second feed-forward module
                        // runs as two GEMMs with its closing LayerNorm apart (the stream is tapped before and after it)
     bool argmax;       // the decoder product's epilogue also leaves the per-frame argmax / maximum for cocr_ctc_greedy
+    int chain_rows;    // chains: rows of the (M, D) activation one workgroup owns (chain_rows_for); 0 without chains
 };
+
+// Hardware queues the runtime multiplexes this process's streams onto: GPU_MAX_HW_QUEUES as the runtime reads it (once; 4 when unset or
+// not a number), 1..32.
+static int hw_queue_count() {
+    static const int n = [] {
+        const char *e = getenv("GPU_MAX_HW_QUEUES");
+        char *end = nullptr;
+        long v = e ? strtol(e, &end, 10) : 4;
+        if (e && (end == e || *end)) v = 4;
+        return (int)std::min(32L, std::max(1L, v));
+    }();
+    return n;
+}
+
+// Rows per workgroup of the chain launches of a forward over M rows, an instantiated form (rowchain_pick_mt).
+//   * cocr_set_chain_rows / COCR_CHAIN_ROWS: the caller's choice, mapped to the nearest form.
+//   * A model alone on its weights (S = 1): by M as ever -- the tallest form from 50 workgroups on, else 32 rows.
+//   * S >= 2 models on one set of weights (cocr_share_weights: one per batch a caller keeps in flight): their streams share
+//     Q = queues - 1 hardware queues (one serves the null stream), and streams on one queue run in turn, so S forwards take
+//     ceil(S / Q) turns and c = S / ceil(S / Q) of them overlap.  The tallest form (fewest weight bytes streamed per row) whose
+//     workgroups x c still cover the chip's 256 CUs: with fewer, CUs idle while every forward waits for its tall blocks (two 96-row
+//     launches of 9600 rows put 200 workgroups on 256 CUs; 64 rows: 300).  Among the forms with at least 50 workgroups, as above; when
+//     none of them covers the chip, the shortest.  DESIGN.md "Hardware queues and the rows per workgroup" has the measurements.
+static int chain_rows_for(const cocr_model *m, int M) {
+    const bool d256 = m->D == 256;
+    auto form = [&](int hint) { return 16 * (d256 ? rowchain_pick_mt<256>(M, hint) : rowchain_pick_mt<512>(M, hint)); };
+    if (m->chain_rows > 0) return form(m->chain_rows);
+    const cocr_model *root = m->owner ? m->owner : m;
+    const int S = 1 + (int)root->sharers.size();
+    if (S < 2) return form(0);
+    const int Q = std::max(1, hw_queue_count() - 1), turns = ceil_div(S, Q);      // c = S / turns
+    static const int forms256[] = {96, 64, 48}, forms512[] = {64};
+    const int *forms = d256 ? forms256 : forms512, nforms = d256 ? 3 : 1;
+    int rows = 32;
+    for (int i = 0; i < nforms; ++i) {
+        if (M < 50 * forms[i]) continue;
+        rows = forms[i];
+        if ((long)ceil_div(M, rows) * S >= 256L * turns) break;
+    }
+    return rows;
+}
 
 // split-K over 2 workgroup groups (2 measured best of 2, 4, 8: 63 vs 74 vs 91 us for product + reduction)
 #ifndef COCR_FO_SPLITS
@@ -1036,6 +1093,7 @@ static Form forward_form(const cocr_model *m, int N, int W) {
     f.ffn_fused = bf16 && f.rowln && ffn_fused_supported<int>(D, m->ff);
     f.dw_fused = m->ksz == 31 && (!m->no_dw_fuse || f.taps);
     f.argmax = m->ncls <= 128 && D % (128 / es) == 0;       // (whole k-steps of the decoder product)
+    f.chain_rows = f.chain ? chain_rows_for(m, M) : 0;
     return f;
 }
 
@@ -1291,7 +1349,7 @@ template <typename T> static int encoder_chains(const Fwd<T> &c) {
     auto CW = [&](size_t off) { return (const bf16_t *)(m->packed + off); };      // chain weights: fragment-major copies (ensure_packed)
     auto launch = [&](const ChainArgs &a, int fam) -> int {
         ProfScope ps(m, c.s, fam);
-        GEMM_TRY(D == 256 ? launch_rowchain_256(c.s, a, taps, m->chain_rows) : launch_rowchain_512(c.s, a, taps, m->chain_rows));
+        GEMM_TRY(D == 256 ? launch_rowchain_256(c.s, a, taps, c.f.chain_rows) : launch_rowchain_512(c.s, a, taps, c.f.chain_rows));
         return COCR_OK;
     };
     // the fp32 stream between the chain launches: in the kernels' register order (ChainArgs::x_in_blocked); the first launch reads
@@ -1578,27 +1636,32 @@ static int forward_entry(cocr_model *m, const void *lines, int line_dtype, int N
         return COCR_OK;
     };
     for (auto &g : m->graphs)
+        if (g.N == N && g.W == W && g.rows != form.chain_rows) {      // captured with another grid (a model joined or left the group since): as cocr_set_chain_rows
+            drop_graphs(m);
+            break;
+        }
+    for (auto &g : m->graphs)
         if (same(g)) { HIP_TRY(hipGraphLaunch(g.exec, s)); return COCR_OK; }
     bool seen = false, seen_shape = false;
     for (auto &g : m->graph_seen) { seen = seen || same(g); seen_shape = seen_shape || same_shape(g); }
     if (seen && shape_ready) {                       // the caller reuses its buffers: capture on them
         hipGraphExec_t exec = nullptr;
         if ((rc = capture(lines, logits, &exec))) return rc;
-        m->graphs.push_back({lines, logits, N, W, line_dtype, s, exec});
+        m->graphs.push_back({lines, logits, N, W, line_dtype, s, exec, form.chain_rows});
         HIP_TRY(hipGraphLaunch(exec, s));
         return COCR_OK;
     }
     if (m->graph_seen.size() >= 32) m->graph_seen.erase(m->graph_seen.begin());
-    m->graph_seen.push_back({lines, logits, N, W, line_dtype, s, nullptr});
+    m->graph_seen.push_back({lines, logits, N, W, line_dtype, s, nullptr, 0});
     for (auto &g : m->graphs)
         if (same_shape(g)) return staged_launch(g.exec);
     if (!seen_shape || !shape_ready) {               // first call of this shape: plain, on the caller's buffers
-        m->graph_seen.push_back({nullptr, nullptr, N, W, line_dtype, s, nullptr});
+        m->graph_seen.push_back({nullptr, nullptr, N, W, line_dtype, s, nullptr, 0});
         return run();
     }
     hipGraphExec_t exec = nullptr;                   // second call of the shape with other buffers: capture the staged sequence
     if ((rc = capture(m->g_lines, m->g_logits, &exec))) return rc;
-    m->graphs.push_back({nullptr, nullptr, N, W, line_dtype, s, exec});
+    m->graphs.push_back({nullptr, nullptr, N, W, line_dtype, s, exec, form.chain_rows});
     return staged_launch(exec);
 }
 
@@ -2278,6 +2341,14 @@ extern "C" int cocr_set_chain_rows(cocr_model *m, int rows) {
         drop_graphs(m);
     }
     m->chain_rows = rows;
+    return COCR_OK;
+}
+
+extern "C" int cocr_get_chain_rows(cocr_model *m, int N, int W, int *rows) {
+    if (!m || !rows) return fail(COCR_EINVAL, "null argument");
+    if (m->dtype < 0 || !m->blob) return fail(COCR_ESTATE, "model not finalized");
+    if (N < 1 || W < 1) return fail(COCR_EINVAL, "empty batch");
+    *rows = forward_form(m, N, W).chain_rows;
     return COCR_OK;
 }
 

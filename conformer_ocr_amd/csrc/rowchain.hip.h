@@ -822,18 +822,6 @@ static inline hipError_t launch_rowchain_mt(hipStream_t s, const ChainArgs &a) {
     return hipGetLastError();
 }
 
-// Rows per workgroup.  Throughput (several batches in flight, `rows` = 0): the most rows the registers and LDS allow (the weight stream
-// is read once per workgroup).  One batch in flight: the largest block that still gives every CU of the chip a workgroup.
-template <int D> static inline int rowchain_pick_mt(int M, int rows_hint) {
-    constexpr int MAXMT = D == 256 ? 6 : 4;
-    if (rows_hint > 0) {
-        const int mt = std::min(MAXMT, std::max(2, rows_hint / 16));
-        return (D == 256 && (mt == 4 || mt == 5)) ? 3 : (D == 512 && mt == 3) ? 4 : mt;      // instantiated: 6, 3, 2 (D = 256); 4, 2 (D = 512)
-    }
-    if (M >= 16 * MAXMT * 50) return MAXMT;
-    return 2;
-}
-
 // HAS_TAPS: whether the debug instantiation exists for this chain shape (the shapes the default forward uses)
 template <int D, int DWK, int K0, int K1, int K2, int K3, bool HAS_TAPS>
 static inline hipError_t launch_rowchain_cfg(hipStream_t s, const ChainArgs &a, bool taps, int rows_hint) {
@@ -848,7 +836,7 @@ static inline hipError_t launch_rowchain_cfg(hipStream_t s, const ChainArgs &a, 
         if constexpr (D == 256) { if (narrow) return launch_rowchain_mt<D, MTV, DWK, K0, K1, K2, K3, false, 5, 2>(s, a); } \
         return launch_rowchain_mt<D, MTV, DWK, K0, K1, K2, K3, false>(s, a);                                     \
     }
-    if constexpr (D == 256) { COCR_RC(6) COCR_RC(3) } else { COCR_RC(4) }
+    if constexpr (D == 256) { COCR_RC(6) COCR_RC(4) COCR_RC(3) } else { COCR_RC(4) }
     COCR_RC(2)
 #undef COCR_RC
     return hipErrorInvalidValue;

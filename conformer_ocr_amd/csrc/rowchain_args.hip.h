@@ -3,6 +3,8 @@
 #pragma once
 #include <hip/hip_runtime.h>
 
+#include <algorithm>
+
 #include "common.hip.h"
 
 enum { ST_ROWLN = 0, ST_FFN = 1, ST_GLU = 2, ST_QKV = 3, ST_FRONT = 4 };
@@ -46,6 +48,20 @@ struct ChainArgs {
 
 static inline bool rowchain_supported(int D, int FF, int dh) { return (D == 256 || D == 512) && FF % 256 == 0 && FF >= 256 && FF <= 2048 && dh % 8 == 0 && D % dh == 0; }
 
-// `taps`: the debug instantiation; `rows_hint`: rows per workgroup (0 = pick by the number of rows, see rowchain_pick_mt)
+// 16-row tiles per workgroup (MT) of the instantiated forms.  `rows_hint` > 0: the nearest form.  0: by the number of rows alone -- the most
+// rows the registers and LDS allow (the weight stream is read once per workgroup) from 50 workgroups on, else 32.  Which hint a forward
+// passes is cocr_api.hip's decision (chain_rows_for).
+template <int D> static inline int rowchain_pick_mt(int M, int rows_hint) {
+    constexpr int MAXMT = D == 256 ? 6 : 4;
+    if (rows_hint > 0) {
+        const int mt = std::min(MAXMT, std::max(2, rows_hint / 16));
+        // instantiated: 6, 4, 3, 2 (D = 256); 4, 2 (D = 512).  No MT = 5: the operand loop's two halves (HT = MT / 2) need an even MT above 3
+        return (D == 256 && mt == 5) ? 4 : (D == 512 && mt == 3) ? 4 : mt;
+    }
+    if (M >= 16 * MAXMT * 50) return MAXMT;
+    return 2;
+}
+
+// `taps`: the debug instantiation; `rows_hint`: rows per workgroup (0 = pick by the number of rows), see rowchain_pick_mt
 hipError_t launch_rowchain_256(hipStream_t s, const ChainArgs &a, bool taps, int rows_hint);
 hipError_t launch_rowchain_512(hipStream_t s, const ChainArgs &a, bool taps, int rows_hint);

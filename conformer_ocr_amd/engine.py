@@ -145,6 +145,12 @@ class HipRecognizer:
         """Rows per workgroup of the row-chain kernels (0 = automatic): see include/cocr.h."""
         _lib.check(self.lib.cocr_set_chain_rows(self._h, int(rows)))
 
+    def chain_rows(self, n: int, w: int) -> int:
+        """Rows per workgroup the next forward of an (n, H, w) batch runs its row-chain launches with: see include/cocr.h."""
+        rows = C.c_int()
+        _lib.check(self.lib.cocr_get_chain_rows(self._h, int(n), int(w), C.byref(rows)))
+        return int(rows.value)
+
     def forward(self, lines: torch.Tensor, lens: Sequence[int], out: Optional[torch.Tensor] = None) -> Tuple[torch.Tensor, np.ndarray]:
         """lines: (N,H,W) float32 or uint8 on this device, contiguous.  Returns (logits (N,T,ncls) f32 device, out_lens int32 host).
         `out`: optional preallocated logits buffer (keeps the output address fixed for graph replay)."""

@@ -195,8 +195,9 @@ class PytorchRecognitionModel(nn.Module):
         """`n` packed copies of the device model for callers that keep several batches in flight, one per stream
         (conformer_ocr_amd/evaluate.py `recognize(..., streams=n)`): each has its own workspace and captured launch sequences and reads the
         first engine's weights (`cocr_share_weights`); the
-        row-chain kernels run their throughput form (96-row blocks: every weight byte streamed once per block -- with several batches
-        in flight the chip is full anyway).  Rebuilt when the parameters change, like `engine()`."""
+        row-chain kernels run the throughput form the library picks for `n` copies on this process's hardware queues (`cocr_get_chain_rows`:
+        96-row blocks when four batches really overlap, 64-row ones when the streams share three queues).  Rebuilt when the parameters
+        change, like `engine()`."""
         from . import hw_queues_note
         hw_queues_note(n)
         eng0 = self.engine(device)

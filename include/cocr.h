@@ -278,11 +278,22 @@ int64_t cocr_edit_align_lds(cocr_model *m, int len_a, int len_b);
 int cocr_set_graph(cocr_model *m, int on);
 
 /* Rows of the (N*T, D) activation one workgroup of the row-chain kernels owns (bf16 mode, encoder_dim 256 / 512).
- * 0 (default): by the batch's row count -- the largest block (96 rows at D = 256, 64 at D = 512: every weight byte is
- * streamed once per block, the cheapest form when several batches are in flight).  A caller with ONE batch in flight
+ * 0 (default): by the batch's row count and by how many batches this process can really overlap (cocr_get_chain_rows) -- the
+ * largest block that keeps the chip covered (up to 96 rows at D = 256, 64 at D = 512: every weight byte is streamed once per
+ * block, the cheapest form when several batches are in flight).  A caller with ONE batch in flight
  * gets a shorter forward from smaller blocks (e.g. 48: twice the workgroups, 32 lines x 300 frames = 200 workgroups).
  * Same results bit for bit (a row's arithmetic does not depend on the block it is in). */
 int cocr_set_chain_rows(cocr_model *m, int rows);
+
+/* The rows per workgroup the next cocr_forward of an (N, H, W) batch would run its row-chain launches with (0: this model's
+ * forward does not use them).  Host arithmetic, no GPU call.  A value set with cocr_set_chain_rows (or COCR_CHAIN_ROWS) is
+ * mapped to the nearest built form (D = 256: 96, 64, 48, 32; D = 512: 64, 32).  Otherwise a model alone on its weights gets
+ * the tallest form from 50 workgroups on, else 32.  Models that share one set of weights (cocr_share_weights: S of them, the
+ * owner included) are taken for S batches in flight: their streams run on max(1, GPU_MAX_HW_QUEUES - 1) hardware queues
+ * (the variable as read once by this library: 4 when unset, 1..32), streams on one queue run in turn, so
+ * c = S / ceil(S / queues) forwards overlap; the tallest form with at least 50 workgroups whose workgroups x c cover the 256
+ * CUs is chosen, else the shortest such form.  32 x 300 frames, four models: 64 rows on 4 queues, 96 on 8. */
+int cocr_get_chain_rows(cocr_model *m, int N, int W, int *rows);
 
 /* Test taps: with debug on, cocr_forward keeps a float32 copy of every stage output
  * ("front.z2", "front.z3", "front.y", "l<i>.ffn1|mhsa|conv|ffn2|out", "l<i>.q|k|v|ctx|glu|dw").

@@ -4,6 +4,7 @@
     python tools/summarize_rocprof.py stats  <dir with *_kernel_stats.csv>        > profiles/rNN_kernel_stats.csv
     python tools/summarize_rocprof.py pmc    <FETCH_SIZE dir> <WRITE_SIZE dir>    > profiles/rNN_pmc_traffic.csv
     python tools/summarize_rocprof.py sq     <dir of one --pmc SQ_... pass>       > profiles/rNN_sq_counters.csv
+    python tools/summarize_rocprof.py overlap <dir of a --kernel-trace run with several batches in flight> > profiles/rNN_overlap.csv
 
 PMC traffic follows MI355X_MICROARCH.md (HBM / rocprofv3): FETCH_SIZE and WRITE_SIZE are collected in separate passes and
 are reported in KiB; on gfx950 FETCH_SIZE counts wide coalesced reads at half their bytes, so read bytes = 2 x FETCH_SIZE;
@@ -67,9 +68,66 @@ def sq(d):
         w.writerow([k[:160], n] + [round(avg.get(c, 0.0), 1) for c in names] + [frac])
 
 
+def overlap(d, first=r'frontend\d*_kernel', chain=r'rowchain_kernel<256, \d, 31, 0, 1, 1, 3'):
+    """A --kernel-trace run of several batches in flight: which hardware queues the forwards ran on and how many of them executed at
+    once.  A forward is the run of dispatches on ONE queue from a frontend kernel (`first`) up to the next one (the packets of a
+    captured forward enter their queue together, so two streams that share a queue show as forwards back to back).  Only the steady
+    second half of the trace counts.  Printed: per queue its forwards, its busy share and how many forwards ran per forward of the
+    least loaded queue; the time-weighted number of forwards executing at once (sum of their first-start .. last-end spans over the
+    wall time); the same for kernels; the dominant chain's launches (grid, workgroups, mean duration)."""
+    f = max(glob.glob(d + '/**/*_kernel_trace.csv', recursive=True), key=os.path.getmtime)
+    rows = []
+    for r in csv.DictReader(open(f)):
+        wg = max(1, int(r.get('Workgroup_Size_X') or r.get('Workgroup_Size') or 1))
+        grid = int(r.get('Grid_Size_X') or r.get('Grid_Size') or 0)
+        rows.append((int(r['Start_Timestamp']), int(r['End_Timestamp']), r['Queue_Id'], r['Kernel_Name'], grid // wg))
+    rows.sort()
+    t_half = rows[len(rows) // 2][0]
+    per_queue = collections.defaultdict(list)
+    for r in rows:
+        per_queue[r[2]].append(r)
+    forwards = collections.defaultdict(list)          # queue -> [first start, last end, kernel ns] of each forward that starts in the steady half
+    for q, rs in per_queue.items():
+        cur = None
+        for s, e, _, name, _ in rs:
+            if re.search(first, name):
+                cur = [s, e, 0] if s >= t_half else None
+                if cur:
+                    forwards[q].append(cur)
+            if cur:
+                cur[1] = max(cur[1], e)
+                cur[2] += e - s
+    spans = [fw for q in forwards for fw in forwards[q]]
+    if not spans:
+        sys.exit('no forward found: no kernel matches ' + first)
+    t0, t1 = min(s[0] for s in spans), max(s[1] for s in spans)
+    wall = t1 - t0
+    steady = [r for r in rows if r[0] >= t0 and r[1] <= t1]
+    w = csv.writer(sys.stdout)
+    w.writerow(['what', 'key', 'count', 'value', 'unit'])
+    least = min(len(v) for v in forwards.values())
+    for q in sorted(forwards, key=lambda q: -len(forwards[q])):
+        fw = forwards[q]
+        w.writerow(['queue forwards', q, len(fw), round(len(fw) / least, 2), 'forwards per forward of the least loaded queue'])
+        w.writerow(['queue forward span', q, len(fw), round(sum(e - s for s, e, _ in fw) / len(fw) / 1e3, 1), 'us, mean first start .. last end'])
+        w.writerow(['queue busy', q, len(fw), round(sum(k for _, _, k in fw) / wall, 3), 'kernel time / wall'])
+    w.writerow(['queues with forwards', '', len(forwards), len(forwards), 'queues'])
+    w.writerow(['forwards executing at once', '', len(spans), round(sum(e - s for s, e, _ in spans) / wall, 2), 'time-weighted'])
+    w.writerow(['kernels executing at once', '', len(steady), round(sum(e - s for s, e, *_ in steady) / wall, 2), 'time-weighted'])
+    w.writerow(['forward rate', '', len(spans), round(len(spans) / (wall / 1e9), 1), 'forwards / s under the profiler'])
+    dom = collections.defaultdict(list)
+    for s, e, _, name, nwg in steady:
+        if re.search(chain, name):
+            dom[(re.sub(r'\(.*', '', name)[:80], nwg)].append(e - s)
+    for (name, nwg), v in sorted(dom.items(), key=lambda kv: -sum(kv[1])):
+        w.writerow(['chain launch', name, len(v), round(sum(v) / len(v) / 1e3, 1), f'us mean, {nwg} workgroups'])
+
+
 if __name__ == '__main__':
     if sys.argv[1] == 'stats':
         stats(sys.argv[2])
+    elif sys.argv[1] == 'overlap':
+        overlap(sys.argv[2])
     elif sys.argv[1] == 'sq':
         sq(sys.argv[2])
     else:
