@@ -191,7 +191,7 @@ struct cocr_model {
     int capN = 0, capW = 0;
     std::vector<void *> ws_allocs;
     void *z_a = nullptr, *z_b = nullptr;
-    float *x = nullptr;
+    float *x = nullptr, *x2 = nullptr;  // the fp32 stream; its second buffer (the chains with the out-proj -> GLU head read one and write the other)
     void *g_lines = nullptr;           // staged graph replay (cocr_forward): library-owned copies of the caller's lines / logits
     float *g_logits = nullptr;
     void *xn = nullptr, *hid = nullptr, *q = nullptr, *k = nullptr, *vt = nullptr, *ctx = nullptr, *glu = nullptr, *dwo = nullptr;
@@ -234,6 +234,7 @@ struct cocr_model {
     bool no_front96 = false;     // COCR_NO_FRONT96=1: frontend conv stages as separate kernels (A/B)
     bool no_front32 = false;     // COCR_NO_FRONT32=1: 32 conv channels: the pointwise conv as a GEMM launch of its own (A/B)
     bool no_dw_fuse = false;     // COCR_NO_DW_FUSE=1: depthwise conv as its own launch (A/B)
+    bool no_a_fuse = false;      // COCR_NO_A_FUSE=1: out-proj -> GLU (chain A) as a launch of its own in front of chain B instead of chain B's head (A/B)
     int chain_rows = 0;          // rows per workgroup of the row-chain kernels (cocr_set_chain_rows / COCR_CHAIN_ROWS); 0 = by the number of rows
     bool no_front_chain = false; // COCR_NO_FRONT_CHAIN=1: the frontend's output linear as a split-K GEMM + reduction in front of the first chain launch (A/B)
     bool ffn_probe = false;      // COCR_FFN_PROBE=1: one extra FFN-only row-chain launch per forward (measurement; results discarded)
@@ -244,7 +245,7 @@ struct cocr_model {
     bool chain_xcd = true;       // COCR_CHAIN_XCD=0: row blocks in plain workgroup order (A/B)
     bool no_chain = false;       // COCR_NO_CHAIN=1: one kernel per GEMM / FFN instead of the row-local chains (A/B measurements)
     std::map<std::string, std::pair<float *, int64_t>> taps;
-    DevBuf<float> tapbuf;        // debug: 4 fp32 (M, D) tap targets of the chain kernels' TAPS instantiation + one bf16 (M, D)
+    DevBuf<float> tapbuf;        // debug: 5 fp32 (M, D) tap targets of the chain kernels' TAPS instantiation + one bf16 (M, D)
     TrainState *train = nullptr;   // cocr_train_begin .. cocr_train_end (train_api.hip.h)
     bool profile = false;
     std::vector<ProfRec> prof;
@@ -288,6 +289,7 @@ static const Switch SWITCHES[] = {
     {"COCR_CHAIN_XCD", &cocr_model::chain_xcd, nullptr},
     {"COCR_NO_KSKIP", &cocr_model::no_kskip, nullptr},
     {"COCR_NO_DW_FUSE", &cocr_model::no_dw_fuse, nullptr},
+    {"COCR_NO_A_FUSE", &cocr_model::no_a_fuse, nullptr},
     {"COCR_NO_FRONT96", &cocr_model::no_front96, nullptr},
     {"COCR_NO_FRONT32", &cocr_model::no_front32, nullptr},
     {"COCR_BEAM_REF", &cocr_model::beam_ref, nullptr},
@@ -843,6 +845,7 @@ extern "C" int cocr_reserve(cocr_model *m, int N, int W) {
     if ((rc = ws_alloc(m, &m->z_a, zbytes))) return rc;
     if ((rc = ws_alloc(m, &m->z_b, zbytes))) return rc;
     if ((rc = ws_alloc(m, (void **)&m->x, (M + 128) * m->D * 4))) return rc;      // (+ 128 rows: the row-chain kernels keep the stream in whole row blocks of up to 96 rows)
+    if ((rc = ws_alloc(m, (void **)&m->x2, (M + 128) * m->D * 4))) return rc;
     if ((rc = ws_alloc(m, &m->xn, M * m->D * es))) return rc;
     if ((rc = ws_alloc(m, &m->hid, M * m->ff * es))) return rc;
     m->qkv_bytes = (size_t)N * m->heads * Tp * m->dhp * es;
@@ -1021,6 +1024,7 @@ struct Form {
     bool chain;        // encoder as row-local chains (rowchain.hip.h), else one kernel per product
     bool ffn_fused;    // per product: the feed-forward module in one kernel, its hidden tensor on chip (ffn.hip.h)
     bool dw_fused;     // chains: the depthwise conv as the prologue of chain B, else a launch of its own
+    bool a_fused;      // chains: chain A (out-proj -> GLU) as the head of chain B (rowchain.hip.h: one row tile of halo), else a launch of its own
     bool taps;         // debug taps (cocr_set_debug): the chains run their TAPS instantiation; per product, the second feed-forward module
                        // runs as two GEMMs with its closing LayerNorm apart (the stream is tapped before and after it)
     bool argmax;       // the decoder product's epilogue also leaves the per-frame argmax / maximum for cocr_ctc_greedy
@@ -1094,6 +1098,7 @@ static Form forward_form(const cocr_model *m, int N, int W) {
     f.dw_fused = m->ksz == 31 && (!m->no_dw_fuse || f.taps);
     f.argmax = m->ncls <= 128 && D % (128 / es) == 0;       // (whole k-steps of the decoder product)
     f.chain_rows = f.chain ? chain_rows_for(m, M) : 0;
+    f.a_fused = f.chain && f.dw_fused && !m->no_a_fuse && rowchain_head_supported(D, m->ksz, f.chain_rows);
     return f;
 }
 
@@ -1329,7 +1334,8 @@ template <typename T> static int encoder_products(const Fwd<T> &c) {
     return COCR_OK;
 }
 
-// ---- encoder as row-local chains (rowchain.hip.h, bf16): 3 launches per block (attention core, chain A, chain B).  Debug taps: the
+// ---- encoder as row-local chains (rowchain.hip.h, bf16): 3 launches per block (attention core, chain A, chain B), or 2 where chain A runs
+// as chain B's head (Form::a_fused).  Debug taps: the
 // TAPS instantiation of the SAME kernels copies what never leaves the chip (or is overwritten inside the launch) into tapbuf; everything
 // else is read from the buffers the launches leave behind.
 template <typename T> static int encoder_chains(const Fwd<T> &c) {
@@ -1339,17 +1345,17 @@ template <typename T> static int encoder_chains(const Fwd<T> &c) {
     const size_t MD = (size_t)M * D;
     const bool taps = c.f.taps;
     int rc;
-    float *tp[4] = {nullptr, nullptr, nullptr, nullptr};
+    float *tp[5] = {nullptr, nullptr, nullptr, nullptr, nullptr};      // (tp[4]: the head's "mhsa" -- a fused launch writes the four others too)
     bf16_t *tap_dw = nullptr;
     if (taps) {
-        HIP_TRY(m->tapbuf.grow(MD * 4 + MD / 2));
-        for (int i = 0; i < 4; ++i) tp[i] = m->tapbuf.p + (size_t)i * MD;
-        tap_dw = reinterpret_cast<bf16_t *>(m->tapbuf.p + 4 * MD);
+        HIP_TRY(m->tapbuf.grow(MD * 5 + MD / 2));
+        for (int i = 0; i < 5; ++i) tp[i] = m->tapbuf.p + (size_t)i * MD;
+        tap_dw = reinterpret_cast<bf16_t *>(m->tapbuf.p + 5 * MD);
     }
     auto CW = [&](size_t off) { return (const bf16_t *)(m->packed + off); };      // chain weights: fragment-major copies (ensure_packed)
     auto launch = [&](const ChainArgs &a, int fam) -> int {
         ProfScope ps(m, c.s, fam);
-        GEMM_TRY(D == 256 ? launch_rowchain_256(c.s, a, taps, c.f.chain_rows) : launch_rowchain_512(c.s, a, taps, c.f.chain_rows));
+        GEMM_TRY(a.nhead ? launch_rowchain_256_head(c.s, a, taps, c.f.chain_rows) : D == 256 ? launch_rowchain_256(c.s, a, taps, c.f.chain_rows) : launch_rowchain_512(c.s, a, taps, c.f.chain_rows));
         return COCR_OK;
     };
     // the fp32 stream between the chain launches: in the kernels' register order (ChainArgs::x_in_blocked); the first launch reads
@@ -1397,18 +1403,25 @@ template <typename T> static int encoder_chains(const Fwd<T> &c) {
         const LayerW &w = P.layers[l];
         const bool last = l + 1 == m->L;
         if ((rc = attention(c, l, (m->stamps && l == 5) ? m->stamps + 192 : nullptr))) return rc;
-        {   // out-proj + residual + conv-module LayerNorm -> pointwise conv 1 + GLU
+        // out-proj + residual + conv-module LayerNorm -> pointwise conv 1 + GLU: a launch of its own, or the head of the next one
+        ChainStage ha = st_rowln(w.wo, w.bo, 1.0f, w.c_ln_g, w.c_ln_b);
+        ChainStage hg{}; hg.kind = ST_GLU; hg.W = CW(w.wpw1); hg.bias = c.F32(w.bpw1); hg.N = 2 * D; hg.out = (bf16_t *)c.glu;
+        ha.tap_pre = tp[4];
+        if (!c.f.a_fused) {
             ChainArgs a = base(c.ctx, 2);
-            a.st[0] = st_rowln(w.wo, w.bo, 1.0f, w.c_ln_g, w.c_ln_b); a.st[0].store_x = 1;
-            ChainStage g{}; g.kind = ST_GLU; g.W = CW(w.wpw1); g.bias = c.F32(w.bpw1); g.N = 2 * D; g.out = (bf16_t *)c.glu;
-            a.st[1] = g;
-            a.st[0].tap_pre = tp[0];
+            a.st[0] = ha; a.st[0].store_x = 1; a.st[0].tap_pre = tp[0];
+            a.st[1] = hg;
             if ((rc = c.tap(l, "ctx", c.ctx, MD)) || (rc = launch(a, FAM_CH_A)) || (rc = c.tap_x(l, "mhsa", tp[0])) || (rc = c.tap(l, "glu", c.glu, MD))) return rc;
-        }
+        } else if ((rc = c.tap(l, "ctx", c.ctx, MD))) return rc;
         if (!c.f.dw_fused && (rc = dwconv(c, w))) return rc;
         // [depthwise conv + BN + SiLU ->] pointwise conv 2 + residual + LayerNorm -> FFN 2 (+ closing LayerNorm [+ next block's]) [-> next block's FFN 1 -> its q/k/v]
         ChainArgs a = base(c.dwo, 2);
         if (c.f.dw_fused) { a.dw_in = (const bf16_t *)c.glu; a.dw_w = c.F32(w.dww); a.dw_b = c.F32(w.dwb); a.tap_dw = tap_dw; }
+        if (c.f.a_fused) {      // the head reads the stream (with its halo rows) from one buffer, the launch writes the other
+            a.A0 = (const bf16_t *)c.ctx; a.dw_in = nullptr; a.nhead = 2; a.st[4] = ha; a.st[5] = hg;
+            a.xh = (l & 1) ? m->x2 : c.x; a.x = (l & 1) ? c.x : m->x2;
+            if (!taps) a.st[5].out = nullptr;
+        }
         a.st[0] = st_rowln(w.wpw2, w.bpw2, 1.0f, w.ffn[1].ln_g, w.ffn[1].ln_b);
         a.st[0].tap_pre = tp[0];
         if (!last) {
@@ -1425,6 +1438,7 @@ template <typename T> static int encoder_chains(const Fwd<T> &c) {
             a.st[1].tap_pre = tp[1];
             if ((rc = launch(a, FAM_CH_LAST))) return rc;
         }
+        if (c.f.a_fused && ((rc = c.tap_x(l, "mhsa", tp[4])) || (rc = c.tap(l, "glu", c.glu, MD)))) return rc;
         // every chain B: the depthwise output, the stream after the conv module and after FFN 2
         if ((rc = c.tap(l, "dw", c.f.dw_fused ? (const T *)tap_dw : (const T *)c.dwo, MD)) || (rc = c.tap_x(l, "conv", tp[0])) || (rc = c.tap_x(l, "ffn2", tp[1])))
             return rc;

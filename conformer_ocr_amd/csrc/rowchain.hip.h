@@ -8,6 +8,9 @@
 //     chain B (after the GLU):               depthwise conv + BatchNorm + SiLU  ->  pointwise conv 2 + residual + LayerNorm  ->  FFN 2
 //                                            (+ block-final LayerNorm + next block's LayerNorm)  ->  next block's FFN 1 (+ LayerNorm)
 //                                            ->  its q/k/v projection
+// Chain A is row-local throughout, and chain B needs it only for its own rows and the depthwise conv's +-15 frames around them: at 64, 48 and
+// 32 rows (D = 256, conv kernel 31) chain A runs as the HEAD of chain B's launch, on the workgroup's rows plus one 16-row tile on either
+// side (template parameters H0, H1 below) -- one launch less per block, the GLU output and the stream between the two never in memory.
 // Reference lines: attention.py:70,103 (out_proj), convolution.py:138-143 (pointwise convs, GLU, depthwise conv, BatchNorm, SiLU),
 // feed_forward.py:45-52, modules.py:32 (residual), encoder.py:62-99.
 //
@@ -78,8 +81,16 @@ template <int D, int MT> constexpr bool rowchain_pair_form() { return COCR_RC_PA
 
 // slack behind the two hidden-chunk images (the q / k / v output tiles' padded rows reach into it)
 template <int D, int MT> constexpr size_t rowchain_slack_bytes() { return rowchain_pair_form<D, MT>() ? 2048 : 4096; }
-template <int D, int MT> constexpr size_t rowchain_lds_bytes() {
-    return (size_t)(D / 64) * 16 * MT * 128 + 2 * 4 * (size_t)(16 * MT) * 128 + rowchain_slack_bytes<D, MT>() + 16 * (size_t)D + 12 * (size_t)(16 * MT) + 64;
+// operand image + hidden images + slack.  HEAD (the out-proj -> GLU head in front of the depthwise prologue): the head's operand image of
+// MT + 2 row tiles and, BEHIND it (the GLU epilogue writes window rows while other waves still read the image), the GLU window of the
+// same rows ([row][2 D bytes]) alias that area; where they need more (48 and 32 rows) the area grows.
+template <int D, int MT, bool HEAD = false> constexpr size_t rowchain_area_bytes() {
+    constexpr size_t imgx = (size_t)(D / 64) * 16 * MT * 128, area = imgx + 2 * 4 * (size_t)(16 * MT) * 128 + rowchain_slack_bytes<D, MT>();
+    constexpr size_t harea = (size_t)(D / 64) * 16 * (MT + 2) * 128 + (size_t)16 * (MT + 2) * 2 * D;
+    return HEAD && harea > area ? harea : area;
+}
+template <int D, int MT, bool HEAD = false> constexpr size_t rowchain_lds_bytes() {
+    return rowchain_area_bytes<D, MT, HEAD>() + 16 * (size_t)D + 12 * (size_t)(16 * MT) + 64;
 }
 // channels per pass of the depthwise prologue (window + taps of that many channels in LDS at a time): the co-resident form takes 128
 template <int D, int MT> constexpr int rowchain_dw_pass() { return rowchain_pair_form<D, MT>() ? 128 : 256; }
@@ -99,9 +110,20 @@ template <int D, int MT, int DWK> constexpr int rowchain_taps_place() {
 // hidden chunk that hold real columns; the k-steps beyond them multiply zeros and are skipped (their weight fragments are still streamed:
 // the ring's bookkeeping stays one shape).  8 / 8 = nothing skipped.  The reference's default model (encoder_dim 144, feed-forward 576 in
 // a 256 / 768-wide engine): 5 / 2.
-template <int D, int MT, int DWK, int K0, int K1, int K2, int K3, bool TAPS, int KD = 8, int KL = 8>
+//
+// H0 / H1: the HEAD of a depthwise-prologue chain (ST_ROWLN, ST_GLU = ChainArgs::st[4], st[5]; -1 = none): what used to be the launch in front
+// of it -- out-proj + residual + conv-module LayerNorm -> pointwise conv 1 + GLU -- computed by the workgroup itself for its own rows AND one
+// 16-row tile on either side (MT + 2 row tiles), which is all the depthwise conv's +-15-frame halo needs (16, not 15: in the blocked stream
+// layout the halo tiles are whole tiles of the neighbouring row blocks).  The GLU values go straight into the depthwise window in LDS and
+// the stream of the own rows stays in the accumulators from the attention residual to the end of the launch.  Every row's values are
+// computed with the arithmetic of the stand-alone launch, whichever workgroup computes them: bit-identical.  Halo rows outside [0, M)
+// (clamped addresses, a clamped neighbour block) and frames of other lines hold values no tap reads (the tap range, `tpos`).
+template <int D, int MT, int DWK, int K0, int K1, int K2, int K3, bool TAPS, int KD = 8, int KL = 8, int H0 = -1, int H1 = -1>
 __global__ __launch_bounds__(512, (rowchain_pair_form<D, MT>() ? 4 : 2)) void rowchain_kernel(ChainArgs p) {
     typedef bf16_t T;
+    constexpr bool HEAD = H0 >= 0;
+    constexpr int ME = MT + 2;                 // row tiles of the head
+    static_assert(!HEAD || (H0 == ST_ROWLN && H1 == ST_GLU && K0 == ST_ROWLN && DWK == 31 && D == 256 && ME <= 6 && !rowchain_pair_form<D, MT>()), "head: out-proj -> GLU in front of the 31-tap prologue, 256 wide, at most 6 row tiles");
     static_assert(D == 256 || D == 512, "encoder_dim of the row-chain kernels");
     static_assert(MT >= 2 && MT <= 6, "16-row tiles per workgroup");
     static_assert(KD >= 1 && KD <= 8 && KL >= 1 && KL <= 8 && (D == 256 || (KD == 8 && KL == 8)), "skipped k-steps: the 256-wide engine only");
@@ -127,12 +149,14 @@ __global__ __launch_bounds__(512, (rowchain_pair_form<D, MT>() ? 4 : 2)) void ro
     constexpr int PROW = 80;                   // LayerNorm partials: 8 waves x (sum, sum of squares) per row, padded 64 -> 80 bytes (the 16 rows a
                                                // ds_read_b128 lane group touches then fall on 16 different bank quads)
     constexpr int HSB = 2 * IMGH + (int)rowchain_slack_bytes<D, MT>();       // hidden images + slack (output tiles, depthwise window, LayerNorm partials alias them)
+    constexpr int AREA = (int)rowchain_area_bytes<D, MT, HEAD>();            // = IMGX + HSB, or what the head's image + window need
+    constexpr int PANELE = 16 * ME * 128, IMGE = (D / 64) * PANELE;          // head: its operand image (ME tiles) at xa
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
     unsigned char *xa = smem;                  // operand image
     unsigned char *hs = smem + IMGX;           // 2 hidden-chunk images
-    float *lnp = reinterpret_cast<float *>(smem + IMGX + HSB);                       // LayerNorm parameters of the running stage: g1, b1, g2, b2 (4 x D floats)
-    long long *rowoff = reinterpret_cast<long long *>(smem + IMGX + HSB + 16 * D);   // row -> offset of its (line, frame) in the q / k / v layouts
-    int *tpos = reinterpret_cast<int *>(smem + IMGX + HSB + 16 * D + 8 * BMC);      // frame index of each row inside its line
+    float *lnp = reinterpret_cast<float *>(smem + AREA);                           // LayerNorm parameters of the running stage: g1, b1, g2, b2 (4 x D floats)
+    long long *rowoff = reinterpret_cast<long long *>(smem + AREA + 16 * D);   // row -> offset of its (line, frame) in the q / k / v layouts
+    int *tpos = reinterpret_cast<int *>(smem + AREA + 16 * D + 8 * BMC);      // frame index of each row inside its line
 
     const int tid = threadIdx.x, lane = tid & 63;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
@@ -162,6 +186,20 @@ __global__ __launch_bounds__(512, (rowchain_pair_form<D, MT>() ? 4 : 2)) void ro
     constexpr int WINB = ((DWROWS + RPI - 1) / RPI) * 1024;
     static_assert(DWK == 0 || (size_t)WINB <= (size_t)HSB, "depthwise window (CW channels at a time) must fit the hidden-image area");
     static_assert((size_t)BMC * OSD <= (size_t)HSB && 2 * (size_t)BMC * OS <= (size_t)HSB, "output tiles alias the hidden-image area");
+    // head: the GLU window of the ME tiles' rows m0 - 16 .. m0 + BMC + 15 lies behind the head's operand image; row 0 of the depthwise window
+    // (m0 - PAD) is its row 1
+    unsigned char *winx = smem + IMGE;
+    static_assert(!HEAD || (IMGE >= IMGX && IMGE + 16 * ME * WS <= AREA && CW == D && DWPAD == 15), "head: window behind both operand images");
+    const unsigned char *win = HEAD ? winx + (16 - DWPAD) * WS : hs;
+    // head: the attention context of the ME tiles' rows -> operand image (addresses clamped to [0, M)); ME wave-instructions per wave
+    auto head_dma = [&]() {
+#pragma unroll
+        for (int u = 0; u < (D / 64) * ME / 4; ++u) {
+            const int id = wave + 8 * u, pnl = id / (2 * ME), rg = id - pnl * (2 * ME), row = rg * 8 + lrow;
+            const T *src = p.A0 + (size_t)min(max(m0 - 16 + row, 0), M - 1) * D + pnl * 64 + ((cpos ^ (row & 7)) * 8);
+            __builtin_amdgcn_global_load_lds((gbl_ptr_t)src, (lds_ptr_t)(xa + pnl * PANELE + rg * 1024), 16, 0, 0);
+        }
+    };
     // depthwise window of channel pass `h`: rows m0 - PAD .. m0 + BMC + PAD - 1 of the GLU output (addresses clamped; frames outside the row's
     // own line are excluded by the tap range below), [row][WS bytes] at hs: one wave-instruction = RPI rows
     auto dw_window = [&](int h) {
@@ -195,6 +233,8 @@ __global__ __launch_bounds__(512, (rowchain_pair_form<D, MT>() ? 4 : 2)) void ro
             const T *src = p.A0 + (size_t)min(m0 + row, M - 1) * D + pnl * 64 + ((cpos ^ (row & 7)) * 8);
             __builtin_amdgcn_global_load_lds((gbl_ptr_t)src, (lds_ptr_t)(xa + pnl * PANEL + rg * 1024), 16, 0, 0);
         }
+    } else if constexpr (HEAD) {
+        head_dma();
     } else {
         dw_window(0);
     }
@@ -206,7 +246,8 @@ __global__ __launch_bounds__(512, (rowchain_pair_form<D, MT>() ? 4 : 2)) void ro
     typedef float dw_f32x2 __attribute__((ext_vector_type(2)));
     dw_f32x2 dw_wt[DWK ? DWK : 1], dw_bias = {0.f, 0.f};
     constexpr int TAPLACE = rowchain_taps_place<D, MT, DWK>();
-    unsigned char *tapa = TAPLACE == 1 ? hs + WINB : smem + rowchain_lds_bytes<D, MT>();
+    static_assert(!HEAD || TAPLACE == 2, "head: the taps in their own area (the window is the head's to write)");
+    unsigned char *tapa = TAPLACE == 1 ? hs + WINB : smem + rowchain_lds_bytes<D, MT, HEAD>();
     constexpr int TPI = 256 / CW;                  // tap rows (CW floats) per wave-instruction
     auto dw_taps = [&](int h) {
         if constexpr (DWK != 0 && TAPLACE != 0) {
@@ -241,7 +282,7 @@ __global__ __launch_bounds__(512, (rowchain_pair_form<D, MT>() ? 4 : 2)) void ro
     constexpr int RING = rowchain_pair_form<D, MT>() ? 8 : 16;
     bf16x8 ring[RING];
     auto fill = [&](const T *slice, int f) { ring[f % RING] = *reinterpret_cast<const bf16x8 *>(slice + f * 512 + lane * 8); };
-    const T *cur_run = p.st[0].W + (size_t)wave * (FRONT0 ? p.st[0].K / 256 : KS) * SLICE;      // the run whose fragments the ring holds (RING = 8)
+    const T *cur_run = p.st[HEAD ? 4 : 0].W + (size_t)wave * (FRONT0 ? p.st[0].K / 256 : KS) * SLICE;      // the run whose fragments the ring holds (RING = 8)
     {
 #pragma unroll
         for (int f = 0; f < RING; ++f) fill(cur_run, f);
@@ -277,7 +318,20 @@ __global__ __launch_bounds__(512, (rowchain_pair_form<D, MT>() ? 4 : 2)) void ro
             }
         }
     };
-    constexpr int EARLY_XS = (DWK == 0 && !FRONT0) ? MT * NJ : 0;     // stream loads in flight at the first wait
+    // head: the stream of the ME tiles (blocked layout: the last tile of row block rblk - 1, the own tiles, the first tile of block rblk + 1;
+    // at the ends of the batch the own block stands in -- those rows are outside every line).  The own tiles become xs after the head.
+    f32x4 xe[HEAD ? ME : 1][NJ];
+    if constexpr (HEAD) {
+        const int nblk = gridDim.x;
+#pragma unroll
+        for (int e = 0; e < ME; ++e) {
+            const int blk = e == 0 ? max(rblk - 1, 0) : e == ME - 1 ? min(rblk + 1, nblk - 1) : rblk, tile = e == 0 ? MT - 1 : e == ME - 1 ? 0 : e - 1;
+            const float *src = p.xh + (((size_t)blk * 8 + wave) * MT + tile) * (NJ * 256) + lane * 4;
+#pragma unroll
+            for (int c = 0; c < NJ; ++c) xe[e][c] = *reinterpret_cast<const f32x4 *>(src + c * 256);
+        }
+    }
+    constexpr int EARLY_XS = HEAD ? ME * NJ : (DWK == 0 && !FRONT0) ? MT * NJ : 0;     // stream loads in flight at the first wait
     if constexpr (DWK == 0 && !FRONT0) load_stream();                 // (FRONT: the stream is born in this launch)
     __builtin_amdgcn_sched_barrier(0);
     if (tid < BMC) {
@@ -289,13 +343,13 @@ __global__ __launch_bounds__(512, (rowchain_pair_form<D, MT>() ? 4 : 2)) void ro
     // the operand DMAs (older than the ring and stream loads) have landed.  The count is the FEWEST loads that can be in flight behind them:
     // a first step that skips k-steps never reads its last ring slots and the compiler drops those loads (with 16 here and 10 loads issued the
     // wait let the depthwise window arrive late: wrong rows in the first launch on fresh LDS, right ones by luck afterwards)
-    constexpr int RING0 = RING == 16 ? 2 * (K0 == ST_ROWLN ? KKR::value : K0 == ST_FFN ? KKP1::value : 8)
+    constexpr int RING0 = HEAD ? 16 : RING == 16 ? 2 * (K0 == ST_ROWLN ? KKR::value : K0 == ST_FFN ? KKP1::value : 8)
                                      : (2 * (K0 == ST_ROWLN ? KKR::value : K0 == ST_FFN ? KKP1::value : 8) < 8 ? 2 * (K0 == ST_ROWLN ? KKR::value : K0 == ST_FFN ? KKP1::value : 8) : 8);
     asm volatile("s_waitcnt vmcnt(%0)" :: "n"(RING0 + EARLY_XS) : "memory");
     lds_fence_barrier();
     RSTAMP()                                       // 2: operand tile / window landed
 
-    if constexpr (DWK != 0) {
+    auto dw_prologue = [&]() { if constexpr (DWK != 0) {      // (run below, behind the head where there is one)
         // Depthwise conv (kernel DWK, zero padding at the line ends, BatchNorm folded) + SiLU on the GLU output (convolution.py:140-142),
         // for the workgroup's rows from the (BMC + DWK - 1)-row window in LDS, written straight into the operand image; 256 channels at a
         // time.  thread = one channel pair x BMC / 4 rows (groups of 8); a wave's lanes share their rows, so the boundary test is uniform.
@@ -326,7 +380,7 @@ __global__ __launch_bounds__(512, (rowchain_pair_form<D, MT>() ? 4 : 2)) void ro
                 f32x2_t acc[G];
 #pragma unroll
                 for (int i = 0; i < G; ++i) acc[i] = bias;
-                const unsigned char *wbase = hs + (size_t)rb * WS + c * 2;
+                const unsigned char *wbase = win + (size_t)rb * WS + c * 2;
                 if (t0 >= DWPAD && t0 + (G - 1) + DWPAD < T_) {        // all G rows inside one line, full tap range
 #pragma unroll
                     for (int rin = 0; rin < G + DWK - 1; ++rin) {
@@ -385,28 +439,30 @@ __global__ __launch_bounds__(512, (rowchain_pair_form<D, MT>() ? 4 : 2)) void ro
             }
             lds_fence_barrier();                             // this pass of the operand image complete; the window is free
         }
-        load_stream();
+        if constexpr (!HEAD) load_stream();        // (head: the stream is in the registers already)
         __builtin_amdgcn_sched_barrier(0);
         RSTAMP()                                   // 3: depthwise prologue done
-    }
+    } };
 
     // One step: acc[rows][32 columns of this wave] += image[256 k] . ring ; ring <- the 16 fragments at `nxt`.  `side(kk)` is independent VALU
     // work folded into the k-step.  `fresh`: the accumulators start from zero -- the first k-step's MFMAs take the constant 0 as their C
     // operand instead of registers zeroed by v_mov (the VALU is the scarce unit of this kernel).
-    auto step = [&](const unsigned char *img, auto &acc, int c0, const T *nxt, auto &&side, auto FRESH, auto KKC) {      // acc[MT][..]: tiles c0, c0 + 1
+    // (MTC: the row tiles of the image and of `acc` -- MT, or the head's MT + 2)
+    auto step_n = [&](auto MTC, const unsigned char *img, auto &acc, int c0, const T *nxt, auto &&side, auto FRESH, auto KKC) {      // acc[MTN][..]: tiles c0, c0 + 1
+        constexpr int MTN = decltype(MTC)::value, PANELN = 16 * MTN * 128;
         constexpr bool fresh = decltype(FRESH)::value;
         constexpr int KK = decltype(KKC)::value;           // k-steps with real columns (the others multiply zeros: skipped)
 #pragma unroll
         for (int kk = 0; kk < KK; ++kk) {
             // row tiles in two halves: half the operand registers live
-            constexpr int HT = MT > 3 ? MT / 2 : MT;
+            constexpr int HT = (MTN > 3 && MTN % 2 == 0) ? MTN / 2 : MTN;
 #pragma unroll
-            for (int h0 = 0; h0 < MT; h0 += HT) {
+            for (int h0 = 0; h0 < MTN; h0 += HT) {
                 bf16x8 a[HT];
 #pragma unroll
                 for (int i = 0; i < HT; ++i) {
                     if constexpr (COCR_RC_EXP & 256) { if (kk == 0) a[i] = lds_frag_swz(img + (16 * (h0 + i) + r16) * 128, 0, g, swz, T()); else asm volatile("" : "+v"(a[i])); }
-                    else a[i] = lds_frag_swz(img + (kk >> 1) * PANEL + (16 * (h0 + i) + r16) * 128, kk & 1, g, swz, T());
+                    else a[i] = lds_frag_swz(img + (kk >> 1) * PANELN + (16 * (h0 + i) + r16) * 128, kk & 1, g, swz, T());
                 }
 #pragma unroll
                 for (int j = 0; j < 2; ++j)
@@ -440,6 +496,9 @@ __global__ __launch_bounds__(512, (rowchain_pair_form<D, MT>() ? 4 : 2)) void ro
         }
         cur_run = nxt;
     };
+    typedef std::integral_constant<int, MT> MTC0;
+    typedef std::integral_constant<int, ME> MEC;
+    auto step = [&](const unsigned char *img, auto &acc, int c0, const T *nxt, auto &&side, auto FRESH, auto KKC) { step_n(MTC0{}, img, acc, c0, nxt, side, FRESH, KKC); };
     auto no_side = [](int) {};
     // LayerNorm parameters of a stage -> LDS, requested at the stage's start by waves 0..3 (one array each); the epilogue's vmcnt(16) + barrier
     // publishes them (at least one step = 16 younger ring loads lies between)
@@ -460,16 +519,18 @@ __global__ __launch_bounds__(512, (rowchain_pair_form<D, MT>() ? 4 : 2)) void ro
         b.v[1] = *reinterpret_cast<const f32x4 *>(bias + 32 * wave + 16 + 4 * g);
         return b;
     };
-    auto add_bias_to_stream = [&](const float *bias, float alpha) {       // xs += alpha * bias: the stream becomes the product's initial accumulator
+    auto add_bias_n = [&](auto MTC, auto &xs, const float *bias, float alpha) {       // xs += alpha * bias: the stream becomes the product's initial accumulator
+        constexpr int MTN = decltype(MTC)::value;
 #pragma unroll
         for (int ns = 0; ns < NS; ++ns) {
             const Bias2 b = load_bias(bias + 256 * ns);
 #pragma unroll
             for (int j = 0; j < 2; ++j)
 #pragma unroll
-                for (int i = 0; i < MT; ++i) xs[i][2 * ns + j] += b.v[j] * alpha;
+                for (int i = 0; i < MTN; ++i) xs[i][2 * ns + j] += b.v[j] * alpha;
         }
     };
+    auto add_bias_to_stream = [&](const float *bias, float alpha) { add_bias_n(MTC0{}, xs, bias, alpha); };
     // fp32 stream -> global in the accumulator layout (16 bytes per lane, 64-byte row segments; once per launch and consumer)
     auto store_stream = [&](float *dst) {
         if constexpr (COCR_RC_EXP & 2) { asm volatile("" :: "v"(xs[0][0][0])); return; }
@@ -492,11 +553,12 @@ __global__ __launch_bounds__(512, (rowchain_pair_form<D, MT>() ? 4 : 2)) void ro
     // Row statistics of the stream registers: per-lane sums of its NJ x 4 values per row tile, butterflies over the 4 lanes of a row, per-wave
     // partials (sum, sum of squares) in LDS at `pbuf` [row][wave], one barrier, then every lane adds the 8 waves' partials of its MT rows.
     // One pass (E[x^2] - mean^2 in fp32 over D <= 512 values of magnitude ~1: the bf16 operand this feeds has 8 significant bits).
-    auto row_stats = [&](unsigned char *pbuf, bool wait_params, float (&mean)[MT], float (&rstd)[MT]) {
-        if constexpr (COCR_RC_EXP & 32) { for (int i = 0; i < MT; ++i) { mean[i] = 0.f; rstd[i] = 1.f; } lds_fence_barrier(); return; }
-        float s[MT], ss[MT];
+    auto row_stats_n = [&](auto MTC, auto &xs, unsigned char *pbuf, bool wait_params, auto &mean, auto &rstd) {
+        constexpr int MTN = decltype(MTC)::value;
+        if constexpr (COCR_RC_EXP & 32) { for (int i = 0; i < MTN; ++i) { mean[i] = 0.f; rstd[i] = 1.f; } lds_fence_barrier(); return; }
+        float s[MTN], ss[MTN];
 #pragma unroll
-        for (int i = 0; i < MT; ++i) {
+        for (int i = 0; i < MTN; ++i) {
             // (explicit fused multiply-adds here and in `normalise`: every instantiation -- rows per workgroup, debug taps -- must round a row's
             // statistics the same way, whatever the compiler's contraction choices are in that instantiation)
             f32x4 a = xs[i][0], b = xs[i][0] * xs[i][0];
@@ -506,8 +568,8 @@ __global__ __launch_bounds__(512, (rowchain_pair_form<D, MT>() ? 4 : 2)) void ro
             ss[i] = (b[0] + b[1]) + (b[2] + b[3]);
         }
 #pragma unroll
-        for (int i0 = 0; i0 < MT; i0 += 4) {
-            const int i1 = min(i0 + 1, MT - 1), i2 = min(i0 + 2, MT - 1), i3 = min(i0 + 3, MT - 1);
+        for (int i0 = 0; i0 < MTN; i0 += 4) {
+            const int i1 = min(i0 + 1, MTN - 1), i2 = min(i0 + 2, MTN - 1), i3 = min(i0 + 3, MTN - 1);
             const float ts = butterfly4(s[i0], s[i1], s[i2], s[i3]), tss = butterfly4(ss[i0], ss[i1], ss[i2], ss[i3]);
             const int tile = g == 0 ? i0 : g == 1 ? i2 : g == 2 ? i1 : i3;              // which tile's totals this lane's row holds
             *reinterpret_cast<f32x2 *>(pbuf + (16 * tile + r16) * PROW + wave * 8) = (f32x2){ts, tss};
@@ -519,7 +581,7 @@ __global__ __launch_bounds__(512, (rowchain_pair_form<D, MT>() ? 4 : 2)) void ro
         lds_fence_barrier();
         const float inv_d = p.inv_d;                       // (raw moments: zero-padded columns add nothing, the divisor is the real width)
 #pragma unroll
-        for (int i = 0; i < MT; ++i) {
+        for (int i = 0; i < MTN; ++i) {
             const unsigned char *pr = pbuf + (16 * i + r16) * PROW;
             f32x4 v = *reinterpret_cast<const f32x4 *>(pr);
             if constexpr (!(COCR_RC_EXP & 4)) {
@@ -532,9 +594,11 @@ __global__ __launch_bounds__(512, (rowchain_pair_form<D, MT>() ? 4 : 2)) void ro
             rstd[i] = __builtin_amdgcn_rsqf(fmaxf(__builtin_fmaf(-mean[i], mean[i], ex2), 0.f) + 1e-5f);
         }
     };
+    auto row_stats = [&](unsigned char *pbuf, bool wait_params, float (&mean)[MT], float (&rstd)[MT]) { row_stats_n(MTC0{}, xs, pbuf, wait_params, mean, rstd); };
     // (x - mean) rstd gamma + beta for this lane's columns; which: 0 = (g1, b1), 1 = (g2, b2).  IN_PLACE: the stream itself is normalised
     // (chained LayerNorms); otherwise the result goes to the operand image (and the stream stays).
-    auto normalise = [&](int which, const float (&mean)[MT], const float (&rstd)[MT], auto IN_PLACE) {
+    auto normalise_n = [&](auto MTC, auto &xs, int which, const auto &mean, const auto &rstd, auto IN_PLACE) {
+        constexpr int MTN = decltype(MTC)::value, PANELN = 16 * MTN * 128;
         constexpr bool in_place = decltype(IN_PLACE)::value;
         if constexpr (COCR_RC_EXP & 8192) return;
         const float *ga = lnp + which * 2 * D, *be = ga + D;
@@ -543,7 +607,7 @@ __global__ __launch_bounds__(512, (rowchain_pair_form<D, MT>() ? 4 : 2)) void ro
             const int col = 256 * (c >> 1) + 32 * wave + 16 * (c & 1) + 4 * g;
             const f32x4 gv = *reinterpret_cast<const f32x4 *>(ga + col), bv = *reinterpret_cast<const f32x4 *>(be + col);
 #pragma unroll
-            for (int i = 0; i < MT; ++i) {
+            for (int i = 0; i < MTN; ++i) {
                 const float r = rstd[i], mr = -mean[i] * r;
                 const f32x4 y = __builtin_elementwise_fma(__builtin_elementwise_fma(xs[i][c], (f32x4){r, r, r, r}, (f32x4){mr, mr, mr, mr}), gv, bv);
                 if constexpr (in_place) {
@@ -551,11 +615,12 @@ __global__ __launch_bounds__(512, (rowchain_pair_form<D, MT>() ? 4 : 2)) void ro
                 } else {
                     const int row = 16 * i + r16;
                     const bf16x4 o = {(T)y[0], (T)y[1], (T)y[2], (T)y[3]};
-                    *reinterpret_cast<bf16x4 *>(xa + (col >> 6) * PANEL + row * 128 + ((((col & 63) >> 3) ^ (row & 7)) << 4) + (col & 4) * 2) = o;
+                    *reinterpret_cast<bf16x4 *>(xa + (col >> 6) * PANELN + row * 128 + ((((col & 63) >> 3) ^ (row & 7)) << 4) + (col & 4) * 2) = o;
                 }
             }
         }
     };
+    auto normalise = [&](int which, const float (&mean)[MT], const float (&rstd)[MT], auto IN_PLACE) { normalise_n(MTC0{}, xs, which, mean, rstd, IN_PLACE); };
     // Residual + LayerNorm(s) of a stage whose product has left x_new in the stream registers.
     //   single:  x <- x_new ;            operand <- LN1(x)
     //   chained: x <- LN1(x_new) ;       operand <- LN2(x)          (block-final LayerNorm + the next block's first)
@@ -803,6 +868,75 @@ __global__ __launch_bounds__(512, (rowchain_pair_form<D, MT>() ? 4 : 2)) void ro
         }
     };
     auto first_slice = [&](int i) -> const T * { return p.st[i].W + (size_t)wave * ((i == 0 && FRONT0) ? p.st[0].K / 256 : KS) * SLICE; };
+    // The head (D = 256: one column step, one k slice per product): the ROWLN and GLU stage code above at ME row tiles -- the stream xe, the
+    // operand image of ME tiles at xa, the GLU values into the window.
+    auto run_head = [&]() { if constexpr (HEAD) {
+        const ChainStage &hr = p.st[4], &hg = p.st[5];
+        auto gslice = [&](int s2) { return hg.W + (size_t)(s2 * 8 + wave) * SLICE; };
+        request_ln_params(hr);
+        {   // x_new = x + bias + ctx Wo^T, as the first stage of a launch computes it: the product from zero, then stream + bias, then their sum
+            f32x4 acc[ME][NJ];
+            step_n(MEC{}, xa, acc, 0, gslice(0), no_side, std::true_type{}, KK8{});
+            add_bias_n(MEC{}, xe, hr.bias, 1.0f);
+#pragma unroll
+            for (int i = 0; i < ME; ++i)
+#pragma unroll
+                for (int c = 0; c < NJ; ++c) xe[i][c] += acc[i][c];
+        }
+        RSTAMP()                                   // head: out-proj done
+        if constexpr (TAPS) {
+            if (hr.tap_pre) {                      // the stream after the attention residual, own rows
+#pragma unroll
+                for (int i = 0; i < MT; ++i) {
+                    if (m0 + 16 * i + r16 < mend) {
+                        float *xrow = hr.tap_pre + (size_t)(m0 + 16 * i + r16) * D + 32 * wave + 4 * g;
+#pragma unroll
+                        for (int c = 0; c < NJ; ++c) *reinterpret_cast<f32x4 *>(xrow + 256 * (c >> 1) + 16 * (c & 1)) = xe[i + 1][c];
+                    }
+                }
+            }
+        }
+        {
+            float mean[ME], rstd[ME];
+            row_stats_n(MEC{}, xe, winx, true, mean, rstd);      // (partials in the window area: nothing is there yet)
+            normalise_n(MEC{}, xe, 0, mean, rstd, std::false_type{});
+        }
+        lds_fence_barrier();                       // the conv module's operand image (ME tiles) complete
+        // the own rows' stream stays in the registers to the end of the launch (a renaming: the loops are unrolled)
+#pragma unroll
+        for (int i = 0; i < MT; ++i)
+#pragma unroll
+            for (int c = 0; c < NJ; ++c) xs[i][c] = xe[i + 1][c];
+        RSTAMP()                                   // head: LayerNorm done
+        // pointwise conv 1 + GLU: wave w's pair = (value tile, gate tile) of channels 128 step + 16 w .. +15; the bf16 values the stand-alone
+        // launch stores go into the window instead
+#pragma unroll 1
+        for (int s2 = 0; s2 < 2; ++s2) {
+            const Bias2 bb = load_bias(hg.bias + s2 * 256);
+            f32x4 acc[ME][2];
+            step_n(MEC{}, xa, acc, 0, s2 == 0 ? gslice(1) : first_slice(0), no_side, std::true_type{}, KKG{});
+#pragma unroll
+            for (int i = 0; i < ME; ++i) {
+                const int row = 16 * i + r16;
+                bf16x4 o;
+#pragma unroll
+                for (int q = 0; q < 4; ++q) o[q] = (T)((acc[i][0][q] + bb.v[0][q]) * sigmoid_f(acc[i][1][q] + bb.v[1][q]));
+                *reinterpret_cast<bf16x4 *>(winx + row * WS + (s2 * 128 + 16 * wave + 4 * g) * 2) = o;
+            }
+        }
+        lds_fence_barrier();                       // window complete; every wave is done with the head's operand image
+        if constexpr (TAPS) {
+            if (hg.out) {                          // the GLU output, own rows
+                for (int id = tid; id < BMC * (D / 8); id += 512) {
+                    const int row = id / (D / 8), ch = id - row * (D / 8);
+                    if (m0 + row < mend) copy16(hg.out + (size_t)(m0 + row) * D + ch * 8, reinterpret_cast<const T *>(winx + (16 + row) * WS + ch * 16));
+                }
+            }
+        }
+        RSTAMP()                                   // head: GLU done
+    } };
+    run_head();
+    dw_prologue();
     run_stage(std::integral_constant<int, K0>{}, std::true_type{}, p.st[0], K1 >= 0 ? first_slice(1) : first_slice(0));
     run_stage(std::integral_constant<int, K1>{}, std::false_type{}, p.st[1], K2 >= 0 ? first_slice(2) : first_slice(0));
     run_stage(std::integral_constant<int, K2>{}, std::false_type{}, p.st[2], K3 >= 0 ? first_slice(3) : first_slice(0));
@@ -811,11 +945,11 @@ __global__ __launch_bounds__(512, (rowchain_pair_form<D, MT>() ? 4 : 2)) void ro
 #undef RSTAMP
 }
 
-template <int D, int MT, int DWK, int K0, int K1, int K2, int K3, bool TAPS, int KD = 8, int KL = 8>
+template <int D, int MT, int DWK, int K0, int K1, int K2, int K3, bool TAPS, int KD = 8, int KL = 8, int H0 = -1, int H1 = -1>
 static inline hipError_t launch_rowchain_mt(hipStream_t s, const ChainArgs &a) {
-    constexpr size_t lds = rowchain_lds_bytes<D, MT>() + (rowchain_taps_place<D, MT, DWK>() == 2 ? (size_t)(DWK + 1) * 1024 : 0);
+    constexpr size_t lds = rowchain_lds_bytes<D, MT, (H0 >= 0)>() + (rowchain_taps_place<D, MT, DWK>() == 2 ? (size_t)(DWK + 1) * 1024 : 0);
     static_assert(lds <= 160 * 1024, "LDS of one workgroup");
-    auto kern = rowchain_kernel<D, MT, DWK, K0, K1, K2, K3, TAPS, KD, KL>;
+    auto kern = rowchain_kernel<D, MT, DWK, K0, K1, K2, K3, TAPS, KD, KL, H0, H1>;
     hipError_t e = raise_lds_limit((const void *)kern, lds);
     if (e != hipSuccess) return e;
     hipLaunchKernelGGL(kern, dim3(ceil_div(a.M, 16 * MT)), dim3(512), lds, s, a);
@@ -842,10 +976,37 @@ static inline hipError_t launch_rowchain_cfg(hipStream_t s, const ChainArgs &a, 
     return hipErrorInvalidValue;
 }
 
+// The depthwise-prologue chains behind the out-proj -> GLU head (ChainArgs::nhead = 2), 256 wide: 64, 48 and 32 rows (the 96-row form would
+// hold 8 row tiles of accumulators and stream in the head: it keeps its two launches).  Debug taps and the narrow k-steps as above.
+template <int K2, int K3>
+static inline hipError_t launch_rowchain_head_cfg(hipStream_t s, const ChainArgs &a, bool taps, int rows_hint) {
+    const int mt = rowchain_pick_mt<256>(a.M, rows_hint);
+    const bool narrow = a.kd == 5 && a.kl == 2 && !taps;
+#define COCR_RC(MTV)                                                                                                                \
+    if (mt == MTV) {                                                                                                                \
+        if (taps) return launch_rowchain_mt<256, MTV, 31, ST_ROWLN, ST_FFN, K2, K3, true, 8, 8, ST_ROWLN, ST_GLU>(s, a);              \
+        if (narrow) return launch_rowchain_mt<256, MTV, 31, ST_ROWLN, ST_FFN, K2, K3, false, 5, 2, ST_ROWLN, ST_GLU>(s, a);           \
+        return launch_rowchain_mt<256, MTV, 31, ST_ROWLN, ST_FFN, K2, K3, false, 8, 8, ST_ROWLN, ST_GLU>(s, a);                       \
+    }
+    COCR_RC(4) COCR_RC(3) COCR_RC(2)
+#undef COCR_RC
+    return hipErrorInvalidValue;
+}
+template <int D>      // (a template so that only the unit that calls it instantiates the kernels)
+static inline hipError_t launch_rowchain_head(hipStream_t s, const ChainArgs &a, bool taps, int rows_hint) {
+    static_assert(D == 256, "the head: encoder_dim 256");
+    const int k0 = a.st[0].kind, k1 = a.nstages > 1 ? a.st[1].kind : -1, k2 = a.nstages > 2 ? a.st[2].kind : -1, k3 = a.nstages > 3 ? a.st[3].kind : -1;
+    if (a.nhead != 2 || a.st[4].kind != ST_ROWLN || a.st[5].kind != ST_GLU || !a.dw_w || !a.A0 || !a.xh || a.xh == a.x || !a.x_in_blocked) return hipErrorInvalidValue;
+    if (k0 == ST_ROWLN && k1 == ST_FFN && k2 == ST_FFN && k3 == ST_QKV) return launch_rowchain_head_cfg<ST_FFN, ST_QKV>(s, a, taps, rows_hint);
+    if (k0 == ST_ROWLN && k1 == ST_FFN && k2 == -1) return launch_rowchain_head_cfg<-1, -1>(s, a, taps, rows_hint);
+    return hipErrorInvalidValue;
+}
+
 // the chain shapes the forward uses; stage weights point at the fragment-major copies
 template <int D>
 static inline hipError_t launch_rowchain(hipStream_t s, const ChainArgs &a, bool taps, int rows_hint) {
     const int k0 = a.st[0].kind, k1 = a.nstages > 1 ? a.st[1].kind : -1, k2 = a.nstages > 2 ? a.st[2].kind : -1, k3 = a.nstages > 3 ? a.st[3].kind : -1;
+    if (a.nhead) return hipErrorInvalidValue;      // (launch_rowchain_head)
     if (a.dw_in) {                       // depthwise-conv prologue (kernel 31): the chains that follow the conv module's GLU
         if (k0 == ST_ROWLN && k1 == ST_FFN && k2 == ST_FFN && k3 == ST_QKV) return launch_rowchain_cfg<D, 31, ST_ROWLN, ST_FFN, ST_FFN, ST_QKV, true>(s, a, taps, rows_hint);
         if (k0 == ST_ROWLN && k1 == ST_FFN && k2 == -1) return launch_rowchain_cfg<D, 31, ST_ROWLN, ST_FFN, -1, -1, true>(s, a, taps, rows_hint);

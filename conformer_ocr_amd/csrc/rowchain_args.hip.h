@@ -29,12 +29,16 @@ struct ChainStage {
 struct ChainArgs {
     const bf16_t *A0;      // first operand rows (M, D) (unused with the depthwise prologue); (M, st[0].K) when the first stage is FRONT
     float *x;              // fp32 residual stream (M, D): read at the start, written by the stages that have store_x
+    const float *xh;       // head (nhead = 2): the stream the head reads, blocked, own rows and one 16-row tile of each neighbouring row block.  NOT `x`:
+                           // a workgroup stores its rows' new stream to `x` while its neighbours may still be reading their halo tiles
     int x_in_blocked, x_out_blocked;   // the stream in the kernels' own register order instead of row-major: [row block][wave][row tile][column
                                        // tile][lane] float4, i.e. every wave-instruction moves 1 KB of consecutive bytes (row-major, a wave's
                                        // 16 rows x 4 lanes x 16 bytes are sixteen 64-byte pieces).  Producer and consumer must use the same
                                        // rows per workgroup; the buffer holds whole row blocks (cocr_api: workspace).
     bf16_t *xn;            // normalised operand (M, D), written when a stage asks for it
     int M, nstages;
+    int nhead;             // 0, or 2: st[4], st[5] = out-proj + residual + LayerNorm, pointwise conv 1 + GLU run in front of the depthwise prologue on the
+                           // workgroup's rows and one row tile on either side (A0 = the attention context; the GLU values stay in LDS)
     int kd, kl;            // zero-padded narrow models: k-steps (of 32) with real columns in a K = D product / in the FFN's last hidden chunk (8 = all)
     int xcd_order;         // row blocks in XCD-contiguous order (rowchain.hip.h); every launch of a forward uses the same setting (blocked stream layout)
     const bf16_t *dw_in;   // depthwise-conv prologue: GLU output (M, D)
@@ -43,7 +47,7 @@ struct ChainArgs {
     int dh, dhp, heads, T_, Tp;       // attention layout of the QKV stage
     float inv_d;           // 1 / (LayerNorm width): 1 / D, or 1 / (the model's own encoder_dim) when D is a zero-padded width (cocr_api: set_engine_dims)
     unsigned long long *stamps;    // dev builds (COCR_CHAIN_STAMPS_BUILD): host-visible cycle stamps [wave][64] of workgroup 7, or null
-    ChainStage st[4];
+    ChainStage st[6];      // the stages, then the head's two
 };
 
 static inline bool rowchain_supported(int D, int FF, int dh) { return (D == 256 || D == 512) && FF % 256 == 0 && FF >= 256 && FF <= 2048 && dh % 8 == 0 && D % dh == 0; }
@@ -65,3 +69,6 @@ template <int D> static inline int rowchain_pick_mt(int M, int rows_hint) {
 // `taps`: the debug instantiation; `rows_hint`: rows per workgroup (0 = pick by the number of rows), see rowchain_pick_mt
 hipError_t launch_rowchain_256(hipStream_t s, const ChainArgs &a, bool taps, int rows_hint);
 hipError_t launch_rowchain_512(hipStream_t s, const ChainArgs &a, bool taps, int rows_hint);
+// the depthwise-prologue chains with the out-proj -> GLU head (ChainArgs::nhead = 2): encoder_dim 256, 64 / 48 / 32 rows (rowchain_d256_head.hip)
+hipError_t launch_rowchain_256_head(hipStream_t s, const ChainArgs &a, bool taps, int rows_hint);
+static inline bool rowchain_head_supported(int D, int conv_kernel, int rows) { return D == 256 && conv_kernel == 31 && rows >= 32 && rows <= 64; }

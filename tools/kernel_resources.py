@@ -1,13 +1,19 @@
 #!/usr/bin/env python3
-"""Prints VGPR / scratch / occupancy / LDS per kernel of libcocr_hip (hipcc -Rpass-analysis)."""
+"""Prints VGPR / scratch / occupancy / LDS per kernel of libcocr_hip (hipcc -Rpass-analysis); an argument filters by kernel name."""
+import glob
+import os
 import re
 import subprocess
 import sys
-import os
+import tempfile
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-cmd = ['/opt/rocm/bin/hipcc', '--offload-arch=gfx950', '-O3', '-std=c++17', '-fPIC', '-shared', '-mllvm', '-amdgpu-mfma-vgpr-form', '-I', ROOT + '/include',
-       ROOT + '/conformer_ocr_amd/csrc/cocr_api.hip', '-o', '/tmp/_res.so', '-Rpass-analysis=kernel-resource-usage']
-out = subprocess.run(cmd, capture_output=True, text=True).stderr
+flags = ['/opt/rocm/bin/hipcc', '--offload-arch=gfx950', '-O3', '-std=c++17', '-fPIC', '-fno-gpu-rdc', '-mllvm', '-amdgpu-mfma-vgpr-form', '-I', ROOT + '/include',
+         '-Rpass-analysis=kernel-resource-usage']
+# every translation unit of the library (cocr_api.hip and the row-chain instantiation units), compiled side by side
+with tempfile.TemporaryDirectory() as tmp:
+    procs = [subprocess.Popen(flags + ['-c', u, '-o', os.path.join(tmp, os.path.basename(u) + '.o')], stderr=subprocess.PIPE, text=True)
+             for u in sorted(glob.glob(ROOT + '/conformer_ocr_amd/csrc/*.hip'))]
+    out = ''.join(p.communicate()[1] for p in procs)
 cur, rows = None, []
 for l in out.splitlines():
     m = re.search(r'Function Name: (\S+)', l)
