@@ -13,6 +13,7 @@
 #include <cstdlib>
 #include <cstring>
 #include <map>
+#include <memory>
 #include <string>
 #include <thread>
 #include <vector>
@@ -37,6 +38,7 @@
 #include "page.hip.h"
 #include "augment.hip.h"
 #include "score.hip.h"
+#include "weights.hip.h"
 
 // ------------------------------------------------------------------------------------ errors
 static thread_local char g_err[512] = "";
@@ -64,23 +66,6 @@ struct HostTensor {
     std::vector<float> data;
     std::vector<int64_t> shape;
     bool set = false;
-};
-
-struct FfnW { size_t ln_g, ln_b, w1, b1, w2, b2; };
-struct LayerW {
-    FfnW ffn[2];
-    size_t a_ln_g, a_ln_b, wqkv, bqkv, ub, vb, wpos, wo, bo;       // wpos: pos_proj weight, fp32 (D, D): the positional tables are DERIVED from it
-    size_t c_ln_g, c_ln_b, wpw1, bpw1, dww, dwb, wpw2, bpw2;
-    size_t f_ln_g, f_ln_b;
-};
-struct StageW { size_t dw_w, dw_b, pw_w, pw_b; };   // one (depthwise, pointwise) frontend stage
-struct BlobPlan {
-    size_t w0, b0;                 // frontend conv.0 taps [C][9], bias
-    std::vector<StageW> stages;    // sampling_num - 1 stages; stage 0's depthwise is fused with conv.0
-    size_t wout, bout;
-    std::vector<LayerW> layers;
-    size_t wdec, bdec;
-    size_t total = 0;
 };
 
 // A grow-only scratch buffer of E: device memory, or pinned host memory.  grow() releases the old memory and records capacity 0
@@ -165,28 +150,11 @@ struct cocr_model {
     std::vector<int> feats;   // height after each stride-2 stage: feats[0] = F1, ...
     std::map<std::string, HostTensor> host;
     std::vector<std::string> names;
-    // packed weights
+    // the weights this model reads, its own or another model's (weights.hip.h): never null.  `dtype`, the engine dimensions above and
+    // `padded` mirror that set's layout and are written by adopt_layout alone; `seen_gen`: the set's generation at this model's last forward
+    WeightsRef w;
     int dtype = -1;
-    unsigned char *blob = nullptr;
-    BlobPlan plan;
-    // fragment-major copies of the row-chain kernels' weight matrices (rowchain.hip.h), at the blob's offsets; derived from the blob,
-    // rebuilt before the next forward whenever the blob may have changed (finalize, import, cocr_weight_blob handed out)
-    unsigned char *packed = nullptr;
-    bf16_t *fpack = nullptr;     // fused frontend kernel (frontend.hip.h): conv.0 A-fragments, then the depthwise block-diagonal B-fragments
-    bool packed_stale = true;
-    // positional tables P_l = PE Wpos_l^T, [layer][9999][heads][dhp] in the compute dtype: derived from the blob's wpos matrices on this device
-    // (finalize, import, handed-out blob pointer) -- 61 of the former 104 MB of the cfg2 blob, which every rank can compute for itself
-    unsigned char *ptab = nullptr;
-    size_t ptab_stride = 0;
-    bool ptab_stale = true;
-    // cocr_share_weights: this model reads `owner`'s blob / packed copies / tables instead of holding its own (several packed copies of one
-    // model, each with its workspace, for callers that keep several batches in flight: four private copies are 4 x ~100 MB, more than the
-    // 256 MB Infinity Cache -- every forward then streamed its weights from HBM).  `wgen`: bumped whenever the owner's buffers may have moved.
-    cocr_model *owner = nullptr;
-    unsigned long long wgen = 1, seen_wgen = 0;
-    // the models that read THIS model's weights (cocr_share_weights; left again by drop_weights): with the owner, the batches one caller
-    // can keep in flight on one set of weights -- chain_rows_for picks the rows per workgroup of the chain launches from their number
-    std::vector<cocr_model *> sharers;
+    unsigned long long seen_gen = 0;
     // workspace
     int capN = 0, capW = 0;
     std::vector<void *> ws_allocs;
@@ -197,7 +165,6 @@ struct cocr_model {
     void *xn = nullptr, *hid = nullptr, *q = nullptr, *k = nullptr, *vt = nullptr, *ctx = nullptr, *glu = nullptr, *dwo = nullptr;
     size_t qkv_bytes = 0;
     int vtN = -1, vtT = -1;    // shape the q/k/vt buffers were last zeroed for
-    int pos_maxlen = COCR_POS_MAXLEN;                  // relative positions the P tables cover: -(max_len - 1) .. max_len - 1
     DevBuf<unsigned char> pre_buf;         // line pre-processing: descriptors, tap tables, intermediates
     DevBuf<unsigned char> page_buf;        // line extraction: descriptors, column frames, polygons, span table
     UploadRing lens_ring;                  // per-line lengths of the decode entry points (upload_lens)
@@ -223,10 +190,8 @@ struct cocr_model {
     long tr_step = 0;
     int tr_kind = -1;                       // the optimizer kind (COCR_OPT_*) the output layer's steps were taken with; -1: none yet
     // debug / profile
-    // hipGraph replay of the forward's launch sequence, keyed by the call's shapes and buffers
-    bool use_graph = false;
-    struct GraphEntry { const void *lines; float *logits; int N, W, dtype; hipStream_t s; hipGraphExec_t exec; int rows; };      // rows: Form::chain_rows of the captured launches
-    std::vector<GraphEntry> graphs, graph_seen;
+    bool use_graph = false;      // cocr_set_graph: hipGraph replay of the forward's launch sequence
+    GraphCache graphs;
     bool debug = false;
     unsigned long long *stamps = nullptr;   // COCR_CHAIN_STAMPS=1 (dev builds): host-visible cycle stamps of the frontend / attention / beam kernels, printed at destroy
     bool no_pad = false;         // COCR_NO_PAD=1: never run a narrow model as a zero-padded 256-wide one
@@ -257,13 +222,6 @@ static const char *FAMILIES[] = {"frontend_fused", "frontend_conv12", "frontend_
                                  "dwconv", "gemm_pw2", "gemm_decoder", "ctc_greedy", "ctc_beam", "ctc_loss", "ffn_probe", "event_pair_overhead"};
 enum { FAM_FRONT96, FAM_CONV12, FAM_FDW, FAM_FPW, FAM_FOUT, FAM_LN, FAM_FFN_UP, FAM_FFN_DOWN, FAM_FFN_FUSED, FAM_CH_FIRST, FAM_CH_FRONT, FAM_CH_A, FAM_CH_B, FAM_CH_LAST, FAM_QKV, FAM_ATTN, FAM_AOUT, FAM_GLU,
        FAM_DW, FAM_PW2, FAM_DEC, FAM_GREEDY, FAM_BEAM, FAM_LOSS, FAM_FFN_PROBE, FAM_EMPTY, FAM_COUNT };
-
-// captured launch sequences point at the model's buffers, tables and launch shapes: dropped whenever one of them changes
-static void drop_graphs(cocr_model *m) {
-    for (auto &g : m->graphs) (void)hipGraphExecDestroy(g.exec);
-    m->graphs.clear();
-    m->graph_seen.clear();
-}
 
 static int out_len1(int l) { return l >= 1 ? (l - 1) / 2 + 1 : 0; }
 
@@ -322,6 +280,7 @@ extern "C" int cocr_create(const cocr_hparams *hp, int device, cocr_model **out)
     m->ff = hp->feed_forward_expansion_factor * hp->encoder_dim; m->ksz = hp->conv_kernel_size;
     m->rD = m->D; m->rff = m->ff; m->rdh = m->dh;
     m->ncls = hp->num_classes; m->H = hp->height; m->snum = snum;
+    weights_own(m->w, m, device);                       // (an empty set: not finalized)
     for (const Switch &w : SWITCHES) {
         const char *e = getenv(w.name);
         if (!e) continue;
@@ -375,6 +334,7 @@ static void free_workspace(cocr_model *m) {
     m->ws_allocs.clear();
     m->capN = m->capW = 0;
     m->vtN = m->vtT = -1;
+    m->lastN = m->lastT = 0;                            // (the last forward's encoder output went with it)
 }
 static void clear_taps(cocr_model *m) {
     for (auto &kv : m->taps) (void)hipFree(kv.second.first);
@@ -382,18 +342,49 @@ static void clear_taps(cocr_model *m) {
     m->tapbuf.release();
 }
 
-// the weights and their derived copies: released when they are the model's own, forgotten when they are an owner's (cocr_share_weights)
-static void drop_weights(cocr_model *m) {
-    if (!m->owner) {
-        for (void *p : {(void *)m->blob, (void *)m->packed, (void *)m->ptab, (void *)m->fpack})
-            if (p) (void)hipFree(p);
-    } else {
-        auto &sh = m->owner->sharers;       // one batch in flight fewer on the owner's weights
-        sh.erase(std::remove(sh.begin(), sh.end(), m), sh.end());
+// COCR_CHAIN_STAMPS=1 (dev builds): what the stamped kernels left
+static void print_stamps(const cocr_model *m) {
+    if (m->stamps[1024]) {                          // row-chain kernel (dominant form), workgroup 7: per wave, cycles between stamps
+        for (int w = 0; w < 8; ++w) {
+            const unsigned long long *q = m->stamps + 1024 + 64 * w;
+            fprintf(stderr, "chain wave %d (start +%llu):", w, q[0] - m->stamps[1024]);
+            for (int i = 1; i < 64 && q[i]; ++i) fprintf(stderr, " %llu", q[i] - q[i - 1]);
+            fprintf(stderr, "  total %llu\n", [&] { int i = 1; while (i < 64 && q[i]) ++i; return q[i - 1] - q[0]; }());
+        }
     }
-    m->owner = nullptr;
-    m->blob = m->packed = m->ptab = nullptr;
-    m->fpack = nullptr;
+    fprintf(stderr, "frontend stamps:");
+    for (int i = 129; i < 192 && m->stamps[i]; ++i) fprintf(stderr, " %llu", m->stamps[i] - m->stamps[128]);
+    fprintf(stderr, "\nbeam walk cycles of the stay wave, then of extension wave 0 (pairs + reads, keys, barrier + ranks, update, tail):");
+    for (int i = 240; i < 250 && m->stamps[i]; ++i) fprintf(stderr, " %llu", m->stamps[i]);
+    fprintf(stderr, "\nattention stamps:");
+    for (int i = 193; i < 240 && m->stamps[i]; ++i) fprintf(stderr, " %llu", m->stamps[i] - m->stamps[192]);
+    fprintf(stderr, "\n");
+    {   // per-workgroup (start, end, hardware id) of the stamped attention launch: residency and tail
+        const unsigned long long *w = m->stamps + 192 + 64;
+        unsigned long long t0 = ~0ull, t1 = 0;
+        int nwg = 0;
+        for (int i = 0; i < 1200 && w[3 * i]; ++i) { t0 = std::min(t0, w[3 * i]); t1 = std::max(t1, w[3 * i + 1]); nwg = i + 1; }
+        if (nwg) {
+            fprintf(stderr, "attention workgroups %d, span %.2f us (100 MHz ticks)\n", nwg, (t1 - t0) * 0.01);
+            std::map<unsigned long long, int> per_cu;
+            int hist_start[32] = {0};
+            double dur = 0;
+            for (int i = 0; i < nwg; ++i) {
+                const unsigned long long hw = w[3 * i + 2];
+                const unsigned long long cu = ((hw >> 32) << 16) | ((hw >> 8) & 0xff) | (((hw >> 13) & 7) << 8);
+                per_cu[cu]++;
+                hist_start[std::min<unsigned long long>((w[3 * i] - t0) / 100, 31)]++;
+                dur += (w[3 * i + 1] - w[3 * i]) * 0.01;
+            }
+            fprintf(stderr, "  mean workgroup duration %.2f us; distinct CUs %zu; start-time histogram (1 us bins):", dur / nwg, per_cu.size());
+            for (int b = 0; b < 32; ++b) fprintf(stderr, " %d", hist_start[b]);
+            int cnt[8] = {0};
+            for (auto &kv : per_cu) cnt[std::min(kv.second, 7)]++;
+            fprintf(stderr, "\n  CUs by number of workgroups received (0..7+):");
+            for (int b = 0; b < 8; ++b) fprintf(stderr, " %d", cnt[b]);
+            fprintf(stderr, "\n");
+        }
+    }
 }
 
 static void train_free(cocr_model *m);
@@ -403,64 +394,16 @@ extern "C" void cocr_destroy(cocr_model *m) {
     train_free(m);
     free_workspace(m);
     clear_taps(m);
-    for (cocr_model *sh : m->sharers) {                 // models that still read these weights: left unfinalized, not with pointers to freed memory
-        drop_graphs(sh);
-        sh->owner = nullptr;
-        sh->blob = sh->packed = sh->ptab = nullptr;
-        sh->fpack = nullptr;
-    }
-    m->sharers.clear();
-    drop_weights(m);
+    weights_leave(m->w, m);                             // (an owner: the models that still read its weights are left unfinalized)
     if (m->stamps) {
         (void)hipDeviceSynchronize();
-        if (m->stamps[1024]) {                          // row-chain kernel (dominant form), workgroup 7: per wave, cycles between stamps
-            for (int w = 0; w < 8; ++w) {
-                const unsigned long long *q = m->stamps + 1024 + 64 * w;
-                fprintf(stderr, "chain wave %d (start +%llu):", w, q[0] - m->stamps[1024]);
-                for (int i = 1; i < 64 && q[i]; ++i) fprintf(stderr, " %llu", q[i] - q[i - 1]);
-                fprintf(stderr, "  total %llu\n", [&] { int i = 1; while (i < 64 && q[i]) ++i; return q[i - 1] - q[0]; }());
-            }
-        }
-        fprintf(stderr, "frontend stamps:");
-        for (int i = 129; i < 192 && m->stamps[i]; ++i) fprintf(stderr, " %llu", m->stamps[i] - m->stamps[128]);
-        fprintf(stderr, "\nbeam walk cycles of the stay wave, then of extension wave 0 (pairs + reads, keys, barrier + ranks, update, tail):");
-        for (int i = 240; i < 250 && m->stamps[i]; ++i) fprintf(stderr, " %llu", m->stamps[i]);
-        fprintf(stderr, "\nattention stamps:");
-        for (int i = 193; i < 240 && m->stamps[i]; ++i) fprintf(stderr, " %llu", m->stamps[i] - m->stamps[192]);
-        fprintf(stderr, "\n");
-        {   // per-workgroup (start, end, hardware id) of the stamped attention launch: residency and tail
-            const unsigned long long *w = m->stamps + 192 + 64;
-            unsigned long long t0 = ~0ull, t1 = 0;
-            int nwg = 0;
-            for (int i = 0; i < 1200 && w[3 * i]; ++i) { t0 = std::min(t0, w[3 * i]); t1 = std::max(t1, w[3 * i + 1]); nwg = i + 1; }
-            if (nwg) {
-                fprintf(stderr, "attention workgroups %d, span %.2f us (100 MHz ticks)\n", nwg, (t1 - t0) * 0.01);
-                std::map<unsigned long long, int> per_cu;
-                int hist_start[32] = {0};
-                double dur = 0;
-                for (int i = 0; i < nwg; ++i) {
-                    const unsigned long long hw = w[3 * i + 2];
-                    const unsigned long long cu = ((hw >> 32) << 16) | ((hw >> 8) & 0xff) | (((hw >> 13) & 7) << 8);
-                    per_cu[cu]++;
-                    hist_start[std::min<unsigned long long>((w[3 * i] - t0) / 100, 31)]++;
-                    dur += (w[3 * i + 1] - w[3 * i]) * 0.01;
-                }
-                fprintf(stderr, "  mean workgroup duration %.2f us; distinct CUs %zu; start-time histogram (1 us bins):", dur / nwg, per_cu.size());
-                for (int b = 0; b < 32; ++b) fprintf(stderr, " %d", hist_start[b]);
-                int cnt[8] = {0};
-                for (auto &kv : per_cu) cnt[std::min(kv.second, 7)]++;
-                fprintf(stderr, "\n  CUs by number of workgroups received (0..7+):");
-                for (int b = 0; b < 8; ++b) fprintf(stderr, " %d", cnt[b]);
-                fprintf(stderr, "\n");
-            }
-        }
+        print_stamps(m);
         (void)hipHostFree(m->stamps);
     }
     if (m->tr_state) (void)hipFree(m->tr_state);
-    drop_graphs(m);
     for (auto &r : m->prof) { (void)hipEventDestroy(r.a); (void)hipEventDestroy(r.b); }
     for (auto e : m->ev_pool) (void)hipEventDestroy(e);
-    delete m;                                           // (its scratch buffers release themselves)
+    delete m;                                           // (its scratch buffers and captured launches release themselves)
 }
 
 extern "C" int cocr_set_tensor(cocr_model *m, const char *name, const void *host, int dtype, int ndim, const int64_t *shape) {
@@ -491,12 +434,29 @@ extern "C" int cocr_missing_tensors(cocr_model *m, char *buf, size_t buflen) {
 // ------------------------------------------------------------------------------------ blob
 static size_t esize(int dtype) { return dtype == COCR_BF16 ? 2 : 4; }
 
+// The row-chain kernels exist for encoder_dim 256 and 512.  A narrower model (the reference's default: encoder_dim 144, 4 heads of 36,
+// feed-forward 576) ran one kernel per product and was SLOWER than the 256-wide model.  In bf16 mode such a model (and one between 256
+// and 512 wide) is run as a zero-padded 256-wide (512-wide) one: every tensor is embedded in the 256 / 768-wide layout at pack time (model dimension: identity + zeros; head dimension:
+// head h at columns [64 h, 64 h + d_head); feed-forward: identity + zeros), so every padded activation column is exactly zero at every
+// stage (zero weights and biases, zero LayerNorm gain and shift, silu(0) = 0, 0 * sigmoid(0) = 0) and the real columns see the same
+// sums.  What does not follow from the padding is stated separately: LayerNorm divides by the REAL width (the statistics are raw
+// moments: zeros add nothing), the attention scale is 1 / sqrt(real d_head), the sinusoids use the real encoder_dim.
+struct EngineDims { int D, ff, dh, dhp; bool padded; };
+static EngineDims engine_dims(const cocr_model *m, int dtype) {
+    const int wide = m->rD < 256 ? 256 : 512;            // 128 <= encoder_dim < 256 -> 256; 256 < encoder_dim < 512 -> 512
+    const int slot = m->heads > 0 && wide % m->heads == 0 ? wide / m->heads : 0;
+    const bool pad = dtype == COCR_BF16 && !m->no_pad && m->rD >= 128 && m->rD < 512 && m->rD != 256 && slot >= m->rdh && slot % 32 == 0 && slot <= 128 &&
+                     round_up(m->rff, 256) <= (wide == 256 ? 1024 : 2048);
+    return {pad ? wide : m->rD, pad ? round_up(m->rff, 256) : m->rff, pad ? slot : m->rdh, pad ? slot : round_up(m->rdh, 32), pad};
+}
+
 static BlobPlan make_plan(const cocr_model *m, int dtype) {
     BlobPlan p;
     size_t off = 0;
     auto take = [&](size_t bytes) { size_t o = off; off += (bytes + 255) / 256 * 256; return o; };
     const size_t es = esize(dtype);
-    const int D = m->D, C = m->C, ff = m->ff;
+    const EngineDims e = engine_dims(m, dtype);
+    const int D = e.D, C = m->C, ff = e.ff;
     p.w0 = take((size_t)C * 9 * 4); p.b0 = take((size_t)C * 4);
     for (int s = 0; s < m->snum - 1; ++s) {
         StageW st;
@@ -564,46 +524,46 @@ static int expect_shape(const cocr_model *m, const std::string &name, std::initi
     return COCR_OK;
 }
 
-static int ensure_ptab(cocr_model *m, hipStream_t s);
-
-// The row-chain kernels exist for encoder_dim 256 and 512.  A narrower model (the reference's default: encoder_dim 144, 4 heads of 36,
-// feed-forward 576) ran one kernel per product and was SLOWER than the 256-wide model.  In bf16 mode such a model (and one between 256
-// and 512 wide) is run as a zero-padded 256-wide (512-wide) one: every tensor is embedded in the 256 / 768-wide layout at pack time (model dimension: identity + zeros; head dimension:
-// head h at columns [64 h, 64 h + d_head); feed-forward: identity + zeros), so every padded activation column is exactly zero at every
-// stage (zero weights and biases, zero LayerNorm gain and shift, silu(0) = 0, 0 * sigmoid(0) = 0) and the real columns see the same
-// sums.  What does not follow from the padding is stated separately: LayerNorm divides by the REAL width (the statistics are raw
-// moments: zeros add nothing), the attention scale is 1 / sqrt(real d_head), the sinusoids use the real encoder_dim.
 static void free_workspace(cocr_model *m);
-static int set_engine_dims(cocr_model *m, int dtype) {
-    const int wide = m->rD < 256 ? 256 : 512;            // 128 <= encoder_dim < 256 -> 256; 256 < encoder_dim < 512 -> 512
-    const int slot = m->heads > 0 && wide % m->heads == 0 ? wide / m->heads : 0;
-    const bool pad = dtype == COCR_BF16 && !m->no_pad && m->rD >= 128 && m->rD < 512 && m->rD != 256 && slot >= m->rdh && slot % 32 == 0 && slot <= 128 &&
-                     round_up(m->rff, 256) <= (wide == 256 ? 1024 : 2048);
-    const int D = pad ? wide : m->rD, ff = pad ? round_up(m->rff, 256) : m->rff, dh = pad ? slot : m->rdh, dhp = pad ? slot : round_up(m->rdh, 32);
-    if (D != m->D || ff != m->ff || dh != m->dh || dhp != m->dhp) {      // workspace and captured launches belong to the old layout
-        HIP_TRY(hipDeviceSynchronize());
-        drop_graphs(m);
-        free_workspace(m);
-        m->capN = m->capW = 0;
-    }
-    m->D = D; m->ff = ff; m->dh = dh; m->dhp = dhp; m->padded = pad;
+// A model's compute dtype and engine dimensions (engine_dims) mirror the layout of the weights it reads; adopt_layout, through this
+// function, is the only writer.
+static void set_engine_dims(cocr_model *m, int dtype) {
+    const EngineDims e = engine_dims(m, dtype);
+    m->D = e.D; m->ff = e.ff; m->dh = e.dh; m->dhp = e.dhp; m->padded = e.padded;
+    m->dtype = dtype;
+}
+static void forget_decoder_state(cocr_model *m) {     // the output layer's optimizer state belongs to the old weights
+    if (m->tr_state) { (void)hipFree(m->tr_state); m->tr_state = nullptr; m->tr_step = 0; }
+}
+// Brings `m` to the layout of the set it reads; every entry point that reads the blob or sizes anything from the plan calls this first.
+// Where the layouts differ -- the set was (re)finalized in another compute dtype since `m` last looked -- the model's workspace,
+// captured launches, last forward and output-layer optimizer state describe the old layout and go.
+static int adopt_layout(cocr_model *m) {
+    if (m->dtype == m->w->dtype) return COCR_OK;
+    HIP_TRY(hipSetDevice(m->device));
+    HIP_TRY(hipDeviceSynchronize());
+    m->graphs.drop();
+    free_workspace(m);
+    m->amax_logits = nullptr;
+    forget_decoder_state(m);
+    set_engine_dims(m, m->w->dtype);
     return COCR_OK;
 }
 
+// an empty (zeroed) blob of `dtype` that `m` owns: in the set it owns already, else in a new one (weights of its own again)
 static int alloc_blob(cocr_model *m, int dtype) {
     if (dtype != COCR_BF16 && dtype != COCR_F32) return fail(COCR_EINVAL, "compute dtype must be COCR_BF16 or COCR_F32");
     HIP_TRY(hipSetDevice(m->device));
-    { const int rc = set_engine_dims(m, dtype); if (rc) return rc; }
-    drop_weights(m);                                  // (weights of its own again)
-    m->wgen++;
-    m->ptab_stale = true;
-    if (m->tr_state) { (void)hipFree(m->tr_state); m->tr_state = nullptr; m->tr_step = 0; }      // optimizer state belongs to the old weights
-    m->packed_stale = true;
-    m->plan = make_plan(m, dtype);
-    m->dtype = dtype;
-    HIP_TRY(hipMalloc((void **)&m->blob, m->plan.total));
-    HIP_TRY(hipMemset(m->blob, 0, m->plan.total));
-    return COCR_OK;
+    weights_own(m->w, m, m->device);
+    m->graphs.drop();
+    m->seen_gen = 0;
+    forget_decoder_state(m);
+    Weights &w = *m->w;
+    w.dtype = dtype;
+    w.plan = make_plan(m, dtype);
+    HIP_TRY(hipMalloc((void **)&w.blob, w.plan.total));
+    HIP_TRY(hipMemset(w.blob, 0, w.plan.total));
+    return adopt_layout(m);
 }
 
 extern "C" int cocr_finalize_empty(cocr_model *m, int compute_dtype) {
@@ -616,29 +576,26 @@ extern "C" int cocr_finalize_empty(cocr_model *m, int compute_dtype) {
 
 extern "C" int cocr_share_weights(cocr_model *m, cocr_model *owner) {
     if (!m || !owner || m == owner) return fail(COCR_EINVAL, "two different models expected");
-    if (owner->owner) return fail(COCR_EINVAL, "the owner itself shares another model's weights");
-    if (owner->dtype < 0 || !owner->blob) return fail(COCR_ESTATE, "the owner is not finalized");
+    if (owner->w->blob && !owner->w->owned_by(owner)) return fail(COCR_EINVAL, "the owner itself shares another model's weights");
+    if (!owner->w->blob) return fail(COCR_ESTATE, "the owner is not finalized");
     if (m->device != owner->device || memcmp(&m->hp, &owner->hp, sizeof m->hp) != 0) return fail(COCR_EINVAL, "models of the same hyper-parameters on the same device expected");
     if (m->train || owner->train) return fail(COCR_ESTATE, "not while a training state exists");
     HIP_TRY(hipSetDevice(m->device));
     HIP_TRY(hipDeviceSynchronize());
-    if (m->dtype != owner->dtype || !m->blob || m->owner) { const int rc = alloc_blob(m, owner->dtype); if (rc) return rc; }     // dims, plan
-    drop_weights(m);
-    m->owner = owner;
-    owner->sharers.push_back(m);
-    m->seen_wgen = 0;                               // the next forward adopts the owner's pointers
-    m->blob = owner->blob;                          // ("finalized" tests look at it)
-    drop_graphs(m);
-    return COCR_OK;
+    weights_join(m->w, m, owner->w);
+    m->graphs.drop();
+    m->seen_gen = 0;
+    forget_decoder_state(m);
+    return adopt_layout(m);
 }
 
 extern "C" int cocr_weight_blob(cocr_model *m, void **device_ptr, size_t *bytes) {
     if (!m || !device_ptr || !bytes) return fail(COCR_EINVAL, "null argument");
-    if (!m->blob) return fail(COCR_ESTATE, "model not finalized");
-    if (m->owner) return fail(COCR_ESTATE, "this model shares another model's weights: address the owner");
-    *device_ptr = m->blob;
-    *bytes = m->plan.total;
-    m->packed_stale = m->ptab_stale = true;          // the caller may write through the pointer: derived copies are rebuilt by the next forward
+    if (!m->w->blob) return fail(COCR_ESTATE, "model not finalized");
+    if (!m->w->owned_by(m)) return fail(COCR_ESTATE, "this model shares another model's weights: address the owner");
+    *device_ptr = m->w->blob;
+    *bytes = m->w->plan.total;
+    m->w->invalidate();          // the caller may write through the pointer
     return COCR_OK;
 }
 
@@ -646,22 +603,22 @@ extern "C" int cocr_weight_blob(cocr_model *m, void **device_ptr, size_t *bytes)
 // memory): rank 0 exports, broadcasts, the other ranks import.  Stream-ordered on `stream`.
 extern "C" int cocr_blob_export(cocr_model *m, void *dst_device, size_t bytes, void *stream) {
     if (!m || !dst_device) return fail(COCR_EINVAL, "null argument");
-    if (!m->blob) return fail(COCR_ESTATE, "model not finalized");
-    if (m->owner) return fail(COCR_ESTATE, "this model shares another model's weights: address the owner");      // (its own `blob` is a view that the owner may have re-allocated)
-    if (bytes != m->plan.total) return fail(COCR_EINVAL, "blob is %zu bytes, buffer %zu", m->plan.total, bytes);
+    if (!m->w->blob) return fail(COCR_ESTATE, "model not finalized");
+    if (!m->w->owned_by(m)) return fail(COCR_ESTATE, "this model shares another model's weights: address the owner");
+    if (bytes != m->w->plan.total) return fail(COCR_EINVAL, "blob is %zu bytes, buffer %zu", m->w->plan.total, bytes);
     HIP_TRY(hipSetDevice(m->device));
-    HIP_TRY(hipMemcpyAsync(dst_device, m->blob, bytes, hipMemcpyDeviceToDevice, (hipStream_t)stream));
+    HIP_TRY(hipMemcpyAsync(dst_device, m->w->blob, bytes, hipMemcpyDeviceToDevice, (hipStream_t)stream));
     return COCR_OK;
 }
 extern "C" int cocr_blob_import(cocr_model *m, const void *src_device, size_t bytes, void *stream) {
     if (!m || !src_device) return fail(COCR_EINVAL, "null argument");
-    if (!m->blob) return fail(COCR_ESTATE, "model not finalized");
-    if (bytes != m->plan.total) return fail(COCR_EINVAL, "blob is %zu bytes, buffer %zu", m->plan.total, bytes);
-    if (m->owner) return fail(COCR_ESTATE, "this model shares another model's weights: address the owner");
+    if (!m->w->blob) return fail(COCR_ESTATE, "model not finalized");
+    if (bytes != m->w->plan.total) return fail(COCR_EINVAL, "blob is %zu bytes, buffer %zu", m->w->plan.total, bytes);
+    if (!m->w->owned_by(m)) return fail(COCR_ESTATE, "this model shares another model's weights: address the owner");
     HIP_TRY(hipSetDevice(m->device));
-    HIP_TRY(hipMemcpyAsync(m->blob, src_device, bytes, hipMemcpyDeviceToDevice, (hipStream_t)stream));
-    m->packed_stale = m->ptab_stale = true;
-    if (m->tr_state) { (void)hipFree(m->tr_state); m->tr_state = nullptr; m->tr_step = 0; }
+    HIP_TRY(hipMemcpyAsync(m->w->blob, src_device, bytes, hipMemcpyDeviceToDevice, (hipStream_t)stream));
+    m->w->invalidate();
+    forget_decoder_state(m);
     return COCR_OK;
 }
 
@@ -684,9 +641,9 @@ extern "C" int cocr_finalize(cocr_model *m, int dtype) {
     if (dtype != COCR_BF16 && dtype != COCR_F32) return fail(COCR_EINVAL, "compute dtype must be COCR_BF16 or COCR_F32");
     HIP_TRY(hipSetDevice(m->device));
     int rc;
-    if ((rc = set_engine_dims(m, dtype))) return rc;
     // tensor shapes: the model's own (rD, rff, h x rdh); blob layout: the engine's (D, ff, h x dh) -- the same unless the model is padded
-    const int rD = m->rD, rff = m->rff, rdh = m->rdh, D = m->D, C = m->C, ff = m->ff, k = m->ksz, h = m->heads, dh = m->dh;
+    const EngineDims e = engine_dims(m, dtype);
+    const int rD = m->rD, rff = m->rff, rdh = m->rdh, D = e.D, C = m->C, ff = e.ff, k = m->ksz, h = m->heads, dh = e.dh;
     std::vector<int> Mm(D), Fm(ff), Am(D), Gm((size_t)2 * D), ident_cls(m->ncls);      // engine index -> model index (-1: zero)
     for (int c = 0; c < D; ++c) Mm[c] = c < rD ? c : -1;                                // model dimension
     for (int c = 0; c < ff; ++c) Fm[c] = c < rff ? c : -1;                              // feed-forward dimension
@@ -772,8 +729,8 @@ extern "C" int cocr_finalize(cocr_model *m, int dtype) {
     GET("decoder.bias", m->ncls); put_f32(st + plan.bdec, t->data.data(), m->ncls);
 #undef GET
     if ((rc = alloc_blob(m, dtype))) return rc;
-    HIP_TRY(hipMemcpy(m->blob, st, plan.total, hipMemcpyHostToDevice));
-    if ((rc = ensure_ptab(m, nullptr))) return rc;
+    HIP_TRY(hipMemcpy(m->w->blob, st, plan.total, hipMemcpyHostToDevice));
+    if ((rc = m->w->ensure_ptab(nullptr))) return rc;
     HIP_TRY(hipDeviceSynchronize());
     return COCR_OK;
 }
@@ -782,8 +739,9 @@ extern "C" int cocr_finalize(cocr_model *m, int dtype) {
 // fp32 from the blob's own wpos matrices and stored head-padded in the compute dtype.  Runs on `s` ahead of a forward's launches (stream
 // order covers a blob import issued on the same stream), never inside a graph capture; the same kernel on the same inputs on every rank,
 // so a rank that received the blob by broadcast holds bit-identical tables.
-template <typename T> static int compute_pos_tables(cocr_model *m, hipStream_t s) {
-    const int D = m->D, rD = m->rD, maxlen = m->pos_maxlen, R = 2 * maxlen - 1;      // (a padded model: rD sinusoids, zeros behind them)
+template <typename T> int Weights::compute_pos_tables(hipStream_t s) {
+    const cocr_model *m = users.front();
+    const int D = m->D, rD = m->rD, maxlen = pos_maxlen, R = 2 * maxlen - 1;      // (a padded model: rD sinusoids, zeros behind them)
     std::vector<float> pe((size_t)R * D, 0.0f);
     for (int r = 0; r < R; ++r) {
         const float pos = (float)(maxlen - 1 - r);           // +(max_len - 1) ... -(max_len - 1)
@@ -798,23 +756,36 @@ template <typename T> static int compute_pos_tables(cocr_model *m, hipStream_t s
     HIP_TRY(hipMalloc((void **)&d_pe, pe.size() * 4));
     HIP_TRY(hipMemcpyAsync(d_pe, pe.data(), pe.size() * 4, hipMemcpyHostToDevice, s));
     for (int l = 0; l < m->L; ++l) {
-        EpiPosTable<T> epi{(T *)(m->ptab + (size_t)l * m->ptab_stride), m->dh, m->dhp, m->heads};
-        HIP_TRY(launch_gemm<float>(s, d_pe, D, (const float *)(m->blob + m->plan.layers[l].wpos), D, R, D, D, epi));
+        EpiPosTable<T> epi{(T *)(ptab + (size_t)l * ptab_stride), m->dh, m->dhp, m->heads};
+        HIP_TRY(launch_gemm<float>(s, d_pe, D, (const float *)(blob + plan.layers[l].wpos), D, R, D, D, epi));
     }
     HIP_TRY(hipStreamSynchronize(s));            // (pe is host memory of this call; one-time start-up work)
     HIP_TRY(hipFree(d_pe));
     return COCR_OK;
 }
-static int ensure_ptab(cocr_model *m, hipStream_t s) {
-    if (!m->ptab_stale) return COCR_OK;
-    m->ptab_stride = (size_t)(2 * m->pos_maxlen - 1) * m->heads * m->dhp * esize(m->dtype);
-    if (!m->ptab) {
-        HIP_TRY(hipMalloc((void **)&m->ptab, m->ptab_stride * m->L));
-        HIP_TRY(hipMemsetAsync(m->ptab, 0, m->ptab_stride * m->L, s));          // padded head dims read as zero
+int Weights::ensure_ptab(hipStream_t s) {
+    if (!ptab_stale) return COCR_OK;
+    const cocr_model *m = users.front();
+    ptab_stride = (size_t)(2 * pos_maxlen - 1) * m->heads * m->dhp * esize(dtype);
+    if (!ptab) {
+        HIP_TRY(hipMalloc((void **)&ptab, ptab_stride * m->L));
+        HIP_TRY(hipMemsetAsync(ptab, 0, ptab_stride * m->L, s));          // padded head dims read as zero
     }
-    int rc = m->dtype == COCR_BF16 ? compute_pos_tables<bf16_t>(m, s) : compute_pos_tables<float>(m, s);
+    int rc = dtype == COCR_BF16 ? compute_pos_tables<bf16_t>(s) : compute_pos_tables<float>(s);
     if (rc) return rc;
-    m->ptab_stale = false;
+    ptab_stale = false;
+    return COCR_OK;
+}
+// The attention core reads the band of whole 64-key tiles unclamped: the tables must cover |relative position| < Tp64 = round_up(T, 64).
+// A longer line than the tables hold: rebuilt longer by the next ensure_ptab (the reference's RelPositionalEncoding.extend_pe,
+// embedding.py:35-41; a position's encoding does not depend on the table length, so shorter lines keep their results)
+int Weights::cover_positions(int Tp64) {
+    if (Tp64 + 64 <= pos_maxlen) return COCR_OK;
+    HIP_TRY(hipDeviceSynchronize());
+    if (ptab) { (void)hipFree(ptab); ptab = nullptr; }
+    pos_maxlen = round_up(Tp64 + 64, 1024);
+    ptab_stale = true;
+    ++gen;                                       // captured launches point at the old tables
     return COCR_OK;
 }
 
@@ -827,13 +798,14 @@ static int ws_alloc(cocr_model *m, void **p, size_t bytes) {
 
 extern "C" int cocr_reserve(cocr_model *m, int N, int W) {
     if (!m) return fail(COCR_EINVAL, "null argument");
-    if (m->dtype < 0) return fail(COCR_ESTATE, "model not finalized");
+    if (!m->w->blob) return fail(COCR_ESTATE, "model not finalized");
     if (N < 1 || W < 1) return fail(COCR_EINVAL, "empty batch");
+    { const int rc = adopt_layout(m); if (rc) return rc; }
     if (N <= m->capN && W <= m->capW) return COCR_OK;
     HIP_TRY(hipSetDevice(m->device));
     HIP_TRY(hipDeviceSynchronize());
     N = std::max(N, m->capN); W = std::max(W, m->capW);
-    drop_graphs(m);     // captured launches point into the old workspace
+    m->graphs.drop();     // captured launches point into the old workspace
     free_workspace(m);
     const size_t es = esize(m->dtype);
     int T = W;
@@ -1057,8 +1029,7 @@ static int chain_rows_for(const cocr_model *m, int M) {
     const bool d256 = m->D == 256;
     auto form = [&](int hint) { return 16 * (d256 ? rowchain_pick_mt<256>(M, hint) : rowchain_pick_mt<512>(M, hint)); };
     if (m->chain_rows > 0) return form(m->chain_rows);
-    const cocr_model *root = m->owner ? m->owner : m;
-    const int S = 1 + (int)root->sharers.size();
+    const int S = (int)m->w->users.size();
     if (S < 2) return form(0);
     const int Q = std::max(1, hw_queue_count() - 1), turns = ceil_div(S, Q);      // c = S / turns
     static const int forms256[] = {96, 64, 48}, forms512[] = {64};
@@ -1115,12 +1086,12 @@ template <typename T> struct Fwd {
     float *const x;             // the fp32 residual stream
     T *const xn, *const hid, *const q, *const k, *const v, *const ctx, *const glu, *const dwo;
     Fwd(cocr_model *m_, const Form &f_, int N_, int W_, hipStream_t s_)
-        : m(m_), f(f_), s(s_), P(m_->plan), N(N_), W(W_), D(m_->D), T1(out_len1(W_)), T2(m_->snum == 1 ? T1 : out_len1(T1)), F1(m_->feats[0]),
+        : m(m_), f(f_), s(s_), P(m_->w->plan), N(N_), W(W_), D(m_->D), T1(out_len1(W_)), T2(m_->snum == 1 ? T1 : out_len1(T1)), F1(m_->feats[0]),
           F2(m_->feats[m_->snum == 1 ? 0 : 1]), Tn(cocr_out_len(W_, m_->hp.subsampling_factor)), M(N_ * Tn), Tp(round_up(Tn, 64)),
           ffr(m_->hp.half_step_residual ? 0.5f : 1.0f), scale(1.0f / sqrtf((float)m_->rdh)), za((T *)m_->z_a), zb((T *)m_->z_b), x(m_->x),
           xn((T *)m_->xn), hid((T *)m_->hid), q((T *)m_->q), k((T *)m_->k), v((T *)m_->vt), ctx((T *)m_->ctx), glu((T *)m_->glu), dwo((T *)m_->dwo) {}
-    const float *F32(size_t off) const { return (const float *)(m->blob + off); }
-    const T *WT(size_t off) const { return (const T *)(m->blob + off); }
+    const float *F32(size_t off) const { return (const float *)(m->w->blob + off); }
+    const T *WT(size_t off) const { return (const T *)(m->w->blob + off); }
     template <typename S> int tap(int l, const char *what, const S *src, size_t n) const {      // debug tap "what" (l < 0) or "l<l>.what"
         if (!f.taps) return COCR_OK;
         char nm[64];
@@ -1158,8 +1129,8 @@ template <typename T, typename TIn> static int frontend(const Fwd<T> &c, const T
     if (form == FRONT_96) {
         ProfScope ps(m, s, FAM_FRONT96);
         const size_t n0 = (size_t)(C / 16) * 64 * 4;
-        GEMM_TRY(launch_frontend96<TIn>(s, lines, N, H, W, T1, F1, T2, m->fpack, c.F32(P.b0), m->fpack + n0, c.F32(P.stages[0].dw_b),
-                                        (const bf16_t *)(m->packed + P.stages[0].pw_w), c.F32(P.stages[0].pw_b), (bf16_t *)zb, m->stamps ? m->stamps + 128 : nullptr));
+        GEMM_TRY(launch_frontend96<TIn>(s, lines, N, H, W, T1, F1, T2, m->w->fpack, c.F32(P.b0), m->w->fpack + n0, c.F32(P.stages[0].dw_b),
+                                        (const bf16_t *)(m->w->packed + P.stages[0].pw_w), c.F32(P.stages[0].pw_b), (bf16_t *)zb, m->stamps ? m->stamps + 128 : nullptr));
     } else if (form == FRONT_PW32) {
         ProfScope ps(m, s, FAM_CONV12);
         const size_t lds = (size_t)(4 * 16 + 3) * ((H + 11) & ~3) * 4 + (size_t)16 * F2 * 80;      // line tile + Z2 rows of 16 frames
@@ -1280,8 +1251,8 @@ template <typename T> static int ffn(const Fwd<T> &c, const FfnW &fw, size_t g1,
 template <typename T, int DHP> static hipError_t attention_dhp(const Fwd<T> &c, int l, unsigned long long *stamps) {
     const cocr_model *m = c.m;
     const LayerW &w = c.P.layers[l];
-    return launch_attention<T, DHP>(c.s, c.N, c.q, c.k, c.v, (const T *)(m->ptab + (size_t)l * m->ptab_stride), c.F32(w.ub), c.F32(w.vb), c.ctx, c.Tn,
-                                    c.Tp, m->heads, m->dh, c.scale, m->pos_maxlen - 1, stamps, m->att_tiled, m->att_resident_min, m->att_resident_long);
+    return launch_attention<T, DHP>(c.s, c.N, c.q, c.k, c.v, (const T *)(m->w->ptab + (size_t)l * m->w->ptab_stride), c.F32(w.ub), c.F32(w.vb), c.ctx, c.Tn,
+                                    c.Tp, m->heads, m->dh, c.scale, m->w->pos_maxlen - 1, stamps, m->att_tiled, m->att_resident_min, m->att_resident_long);
 }
 // block l's attention core: ctx <- attention(q, k, v) (launch_attention chooses the kernel)
 template <typename T> static int attention(const Fwd<T> &c, int l, unsigned long long *stamps) {
@@ -1352,7 +1323,7 @@ template <typename T> static int encoder_chains(const Fwd<T> &c) {
         for (int i = 0; i < 5; ++i) tp[i] = m->tapbuf.p + (size_t)i * MD;
         tap_dw = reinterpret_cast<bf16_t *>(m->tapbuf.p + 5 * MD);
     }
-    auto CW = [&](size_t off) { return (const bf16_t *)(m->packed + off); };      // chain weights: fragment-major copies (ensure_packed)
+    auto CW = [&](size_t off) { return (const bf16_t *)(m->w->packed + off); };      // chain weights: fragment-major copies (ensure_packed)
     auto launch = [&](const ChainArgs &a, int fam) -> int {
         ProfScope ps(m, c.s, fam);
         GEMM_TRY(a.nhead ? launch_rowchain_256_head(c.s, a, taps, c.f.chain_rows) : D == 256 ? launch_rowchain_256(c.s, a, taps, c.f.chain_rows) : launch_rowchain_512(c.s, a, taps, c.f.chain_rows));
@@ -1490,31 +1461,31 @@ static int forward_impl(cocr_model *m, const Form &f, const TIn *lines, int N, i
 // (Re)builds the fragment-major weight copies that the form's row chains and fused frontend read.  Runs on `s` ahead of the forward's
 // launches (stream order covers a blob import issued on the same stream), never inside a graph capture.  What it packs does not depend
 // on the batch shape (forward_form).
-static int ensure_packed(cocr_model *m, const Form &f, hipStream_t s) {
-    if ((!f.chain && f.front != FRONT_96) || !m->packed_stale) return COCR_OK;
-    if (!m->packed) HIP_TRY(hipMalloc((void **)&m->packed, m->plan.total));
+int Weights::ensure_packed(const Form &f, hipStream_t s) {
+    if ((!f.chain && f.front != FRONT_96) || !packed_stale) return COCR_OK;
+    const cocr_model *m = users.front();
+    if (!packed) HIP_TRY(hipMalloc((void **)&packed, plan.total));
     const int D = m->D, ff = m->ff, C = m->C;
     auto pack = [&](size_t off, int N, int K, float scale = 1.0f) {
-        hipLaunchKernelGGL(pack_frag_kernel, dim3(std::min(1024, ceil_div(N * K / 8, 256))), dim3(256), 0, s, (const bf16_t *)(m->blob + off),
-                           (bf16_t *)(m->packed + off), N, K, scale);
+        hipLaunchKernelGGL(pack_frag_kernel, dim3(std::min(1024, ceil_div(N * K / 8, 256))), dim3(256), 0, s, (const bf16_t *)(blob + off),
+                           (bf16_t *)(packed + off), N, K, scale);
     };
     const float ffr = m->hp.half_step_residual ? 0.5f : 1.0f;       // the FFN's residual factor rides on the packed copy of its second matrix (exact)
     if (f.chain)
-        for (const LayerW &w : m->plan.layers) {
+        for (const LayerW &w : plan.layers) {
             for (int i = 0; i < 2; ++i) { pack(w.ffn[i].w1, ff, D); pack(w.ffn[i].w2, D, ff, ffr); }
             pack(w.wqkv, 3 * D, D); pack(w.wo, D, D); pack(w.wpw1, 2 * D, D); pack(w.wpw2, D, D);
         }
-    if (f.out == OUT_IN_CHAIN) pack(m->plan.wout, D, m->feats.back() * C);      // the FRONT stage's matrix
+    if (f.out == OUT_IN_CHAIN) pack(plan.wout, D, m->feats.back() * C);      // the FRONT stage's matrix
     if (f.front == FRONT_96) {
-        pack(m->plan.stages[0].pw_w, C, C);
+        pack(plan.stages[0].pw_w, C, C);
         const size_t n0 = (size_t)(C / 16) * 64 * 4, n2 = (size_t)(C / 16) * 5 * 64 * 8;
-        if (!m->fpack) HIP_TRY(hipMalloc((void **)&m->fpack, (n0 + n2) * sizeof(bf16_t)));
-        hipLaunchKernelGGL(frontend_pack_kernel, dim3(ceil_div((int)n2, 256)), dim3(256), 0, s, (const float *)(m->blob + m->plan.w0),
-                           (const float *)(m->blob + m->plan.stages[0].dw_w), m->fpack, m->fpack + n0, C);
+        if (!fpack) HIP_TRY(hipMalloc((void **)&fpack, (n0 + n2) * sizeof(bf16_t)));
+        hipLaunchKernelGGL(frontend_pack_kernel, dim3(ceil_div((int)n2, 256)), dim3(256), 0, s, (const float *)(blob + plan.w0),
+                           (const float *)(blob + plan.stages[0].dw_w), fpack, fpack + n0, C);
     }
     LAUNCH_CHECK();
-    m->packed_stale = false;
-    drop_graphs(m);     // (pointers unchanged, but keep replay and rebuild ordered simply)
+    packed_stale = false;
     return COCR_OK;
 }
 
@@ -1532,151 +1503,84 @@ extern "C" int cocr_forget_argmax(cocr_model *m) {
     m->amax_logits = nullptr;
     return COCR_OK;
 }
+static int run_forward(cocr_model *m, const Form &form, const void *in, int line_dtype, int N, int W, float *out, hipStream_t s) {
+    if (m->dtype == COCR_BF16) {
+        if (line_dtype == COCR_F32) return forward_impl<bf16_t, float>(m, form, (const float *)in, N, W, out, s);
+        if (line_dtype == COCR_U8) return forward_impl<bf16_t, uint8_t>(m, form, (const uint8_t *)in, N, W, out, s);
+    } else {
+        if (line_dtype == COCR_F32) return forward_impl<float, float>(m, form, (const float *)in, N, W, out, s);
+        if (line_dtype == COCR_U8) return forward_impl<float, uint8_t>(m, form, (const uint8_t *)in, N, W, out, s);
+    }
+    return fail(COCR_EINVAL, "line dtype must be COCR_F32 or COCR_U8");
+}
+
+// The derived copies that the form reads, rebuilt where they are stale (rarely: new weights, longer tables), and this model brought up to
+// the set's generation.  A set with several users, or one that has been rebuilt before, is rebuilt with the device idle: other models
+// may read it on other streams.  (Any user packs what every user's form reads: models that share weights share the switches.)
+static int sync_weights(cocr_model *m, const Form &form, hipStream_t s) {
+    Weights &w = *m->w;
+    if (w.stale()) {
+        const bool idle = w.users.size() > 1 || w.gen > 1;
+        int rc;
+        if (idle) HIP_TRY(hipDeviceSynchronize());
+        if ((rc = w.ensure_packed(form, s)) || (rc = w.ensure_ptab(s))) return rc;
+        HIP_TRY(idle ? hipDeviceSynchronize() : hipStreamSynchronize(s));
+        ++w.gen;
+    }
+    if (m->seen_gen != w.gen) {      // captured launches may point at moved buffers, or run ahead of a rebuild
+        m->graphs.drop();
+        m->seen_gen = w.gen;
+    }
+    return COCR_OK;
+}
+
+// Launch-bound regime (~120 kernels of 10-40 us per forward): the second identical call captures the launch sequence into a
+// hipGraph, later identical calls replay it (one host call instead of ~120).  GraphCache says which sequence a call gets.
+static int forward_graphed(cocr_model *m, const Form &form, const void *lines, int line_dtype, int N, int W, float *logits, hipStream_t s) {
+    const int Tn = cocr_out_len(W, m->hp.subsampling_factor);
+    const GraphCache::Call call{lines, logits, N, W, line_dtype, form.chain_rows};
+    hipGraphExec_t exec = nullptr;
+    const GraphCache::Action act = m->graphs.next(call, m->vtN == N && m->vtT == Tn, &exec);
+    if (act == GraphCache::PLAIN) return run_forward(m, form, lines, line_dtype, N, W, logits, s);
+    const bool staged = act == GraphCache::STAGED_REPLAY || act == GraphCache::STAGED_CAPTURE;
+    if (act == GraphCache::CAPTURE || act == GraphCache::STAGED_CAPTURE) {
+        hipGraph_t graph = nullptr;
+        HIP_TRY(hipStreamBeginCapture(s, hipStreamCaptureModeThreadLocal));
+        const int r = run_forward(m, form, staged ? m->g_lines : lines, line_dtype, N, W, staged ? m->g_logits : logits, s);
+        const hipError_t ce = hipStreamEndCapture(s, &graph);
+        if (r) { if (graph) (void)hipGraphDestroy(graph); return r; }
+        if (ce != hipSuccess) return fail(COCR_EHIP, "hipStreamEndCapture failed: %s", hipGetErrorString(ce));
+        HIP_TRY(hipGraphInstantiate(&exec, graph, nullptr, nullptr, 0));
+        (void)hipGraphDestroy(graph);
+        m->graphs.add(staged ? GraphCache::staged(call) : call, exec);
+    }
+    if (staged) HIP_TRY(hipMemcpyAsync(m->g_lines, lines, (size_t)N * m->H * W * (line_dtype == COCR_F32 ? 4 : 1), hipMemcpyDefault, s));
+    HIP_TRY(hipGraphLaunch(exec, s));
+    if (staged) HIP_TRY(hipMemcpyAsync(logits, m->g_logits, (size_t)N * Tn * m->ncls * 4, hipMemcpyDeviceToDevice, s));
+    return COCR_OK;
+}
+
 static int forward_entry(cocr_model *m, const void *lines, int line_dtype, int N, int H, int W, const int32_t *in_lens,
                          float *logits, int32_t *out_lens, void *stream) {
     if (!m || !lines || !logits) return fail(COCR_EINVAL, "null argument");
-    if (m->dtype < 0 || !m->blob) return fail(COCR_ESTATE, "model not finalized");
+    if (!m->w->blob) return fail(COCR_ESTATE, "model not finalized");
     if (H != m->H) return fail(COCR_EINVAL, "line height %d does not match the model's height %d", H, m->H);
     if (N < 1 || W < 1) return fail(COCR_EINVAL, "empty batch");
+    if (line_dtype != COCR_F32 && line_dtype != COCR_U8) return fail(COCR_EINVAL, "line dtype must be COCR_F32 or COCR_U8");
+    const int Tn = cocr_out_len(W, m->hp.subsampling_factor);
+    if (round_up(Tn, 64) > 65536) return fail(COCR_EUNSUPPORTED, "more than 65536 output frames");
     HIP_TRY(hipSetDevice(m->device));
-    {   // the attention core reads the band of whole 64-key tiles unclamped: the tables must cover |relative position| < round_up(T, 64).
-        // A longer line than the tables hold: rebuild them (the reference's RelPositionalEncoding.extend_pe, embedding.py:35-41;
-        // a position's encoding does not depend on the table length, so shorter lines keep their results)
-        const int Tp64 = round_up(cocr_out_len(W, m->hp.subsampling_factor), 64);
-        if (Tp64 > 65536) return fail(COCR_EUNSUPPORTED, "more than 65536 output frames");
-        cocr_model *root = m->owner ? m->owner : m;      // whose tables these are
-        if (Tp64 + 64 > root->pos_maxlen) {
-            HIP_TRY(hipDeviceSynchronize());
-            drop_graphs(m);      // captured launches point at the old tables
-            if (root->ptab) { (void)hipFree(root->ptab); root->ptab = nullptr; }
-            root->pos_maxlen = round_up(Tp64 + 64, 1024);
-            root->ptab_stale = true;
-            root->wgen++;
-        }
-    }
     int rc;
-    if (m->owner && (m->owner->dtype != m->dtype || m->owner->plan.total != m->plan.total)) {
-        // the owner was finalized again in another compute dtype since cocr_share_weights: this model's layout, plan, workspace and
-        // captured launches describe the old blob -- re-derived here, before anything is sized or launched from them
-        cocr_model *o = m->owner;
-        if (o->dtype < 0 || !o->blob) return fail(COCR_ESTATE, "the model whose weights this one shares is not finalized");
-        HIP_TRY(hipDeviceSynchronize());
-        if ((rc = set_engine_dims(m, o->dtype))) return rc;
-        drop_graphs(m);
-        free_workspace(m);
-        m->plan = make_plan(m, o->dtype);
-        m->dtype = o->dtype;
-        m->blob = o->blob;
-        m->amax_logits = nullptr;
-        m->seen_wgen = 0;
-    }
-    rc = cocr_reserve(m, N, W);
-    if (rc) return rc;
+    if ((rc = adopt_layout(m)) || (rc = m->w->cover_positions(round_up(Tn, 64))) || (rc = cocr_reserve(m, N, W))) return rc;
     if (in_lens && out_lens)
         for (int i = 0; i < N; ++i) out_lens[i] = cocr_out_len(in_lens[i], m->hp.subsampling_factor);
     hipStream_t s = (hipStream_t)stream;
     const Form form = forward_form(m, N, W);
-    if (m->owner) {
-        // shared weights: the derived copies are the owner's; rebuilt (rarely: new weights, longer tables) with the device idle, because
-        // other models that share them run on other streams; then this model's view of the pointers is refreshed.  (The owner packs
-        // what this model's form reads: models that share weights share the switches.)
-        cocr_model *o = m->owner;
-        if (o->packed_stale || o->ptab_stale) {
-            HIP_TRY(hipDeviceSynchronize());
-            if ((rc = ensure_packed(o, form, s)) || (rc = ensure_ptab(o, s))) return rc;
-            HIP_TRY(hipDeviceSynchronize());
-            o->wgen++;
-        }
-        if (m->seen_wgen != o->wgen) {
-            m->blob = o->blob; m->packed = o->packed; m->fpack = o->fpack; m->ptab = o->ptab; m->ptab_stride = o->ptab_stride; m->pos_maxlen = o->pos_maxlen;
-            m->packed_stale = m->ptab_stale = false;
-            m->seen_wgen = o->wgen;
-            drop_graphs(m);      // captured launches may point at moved buffers
-        }
-    } else {
-        const bool rebuilt = m->packed_stale || m->ptab_stale;
-        if (rebuilt && m->wgen > 1) HIP_TRY(hipDeviceSynchronize());       // (models may share these buffers: cocr_share_weights)
-        if ((rc = ensure_packed(m, form, s)) || (rc = ensure_ptab(m, s))) return rc;
-        if (rebuilt) { m->wgen++; HIP_TRY(hipStreamSynchronize(s)); }
-        if (m->seen_wgen != m->wgen) {                  // (a model that shares these buffers may have regrown the tables)
-            if (m->seen_wgen) drop_graphs(m);
-            m->seen_wgen = m->wgen;
-        }
-    }
+    if ((rc = sync_weights(m, form, s))) return rc;
     m->lastN = N;
-    m->lastT = cocr_out_len(W, m->hp.subsampling_factor);
-    auto run_on = [&](const void *in, float *out) -> int {
-        if (m->dtype == COCR_BF16) {
-            if (line_dtype == COCR_F32) return forward_impl<bf16_t, float>(m, form, (const float *)in, N, W, out, s);
-            if (line_dtype == COCR_U8) return forward_impl<bf16_t, uint8_t>(m, form, (const uint8_t *)in, N, W, out, s);
-        } else {
-            if (line_dtype == COCR_F32) return forward_impl<float, float>(m, form, (const float *)in, N, W, out, s);
-            if (line_dtype == COCR_U8) return forward_impl<float, uint8_t>(m, form, (const uint8_t *)in, N, W, out, s);
-        }
-        return fail(COCR_EINVAL, "line dtype must be COCR_F32 or COCR_U8");
-    };
-    auto run = [&]() -> int { return run_on(lines, logits); };
-    if (line_dtype != COCR_F32 && line_dtype != COCR_U8) return fail(COCR_EINVAL, "line dtype must be COCR_F32 or COCR_U8");
-    if (!m->use_graph || m->debug || m->profile || s == nullptr) return run();
-    // Launch-bound regime (~120 kernels of 10-40 us per forward): the second identical call captures the launch sequence
-    // into a hipGraph, later identical calls replay it (one host call instead of ~120).
-    // Two kinds of captured sequences:
-    //   * keyed by the caller's buffers (lines, logits, N, W, dtype, stream): a loop that reuses its buffers replays with no extra copy;
-    //   * STAGED, keyed by (N, W, dtype, stream) only: a caller that hands over fresh buffers every call (a data loader's batches, torch's
-    //     allocator) gets one device-to-device copy of the lines into a library-owned staging buffer, the replay, and one copy of the
-    //     logits out (~20 MB at 32 x 96 x 1200 f32: a few microseconds) instead of ~40 host-side launches.
-    const int Tn = cocr_out_len(W, m->hp.subsampling_factor);
-    const bool shape_ready = m->vtN == N && m->vtT == Tn;      // the first call of a shape runs plain: one-time attribute / zeroing work
-    // (the stream is not part of either key: an instantiated graph launches on any stream, and one model serves one stream at a time anyway)
-    auto same = [&](const cocr_model::GraphEntry &g) { return g.lines == lines && g.logits == logits && g.N == N && g.W == W && g.dtype == line_dtype; };
-    auto same_shape = [&](const cocr_model::GraphEntry &g) { return g.lines == nullptr && g.N == N && g.W == W && g.dtype == line_dtype; };
-    auto capture = [&](const void *in, float *out, hipGraphExec_t *exec) -> int {
-        hipGraph_t graph = nullptr;
-        HIP_TRY(hipStreamBeginCapture(s, hipStreamCaptureModeThreadLocal));
-        int r = run_on(in, out);
-        hipError_t ce = hipStreamEndCapture(s, &graph);
-        if (r) { if (graph) (void)hipGraphDestroy(graph); return r; }
-        if (ce != hipSuccess) return fail(COCR_EHIP, "hipStreamEndCapture failed: %s", hipGetErrorString(ce));
-        HIP_TRY(hipGraphInstantiate(exec, graph, nullptr, nullptr, 0));
-        (void)hipGraphDestroy(graph);
-        if (m->graphs.size() >= 16) { (void)hipGraphExecDestroy(m->graphs.front().exec); m->graphs.erase(m->graphs.begin()); }
-        return COCR_OK;
-    };
-    const size_t in_bytes = (size_t)N * H * W * (line_dtype == COCR_F32 ? 4 : 1), out_bytes = (size_t)N * Tn * m->ncls * 4;
-    auto staged_launch = [&](hipGraphExec_t exec) -> int {
-        HIP_TRY(hipMemcpyAsync(m->g_lines, lines, in_bytes, hipMemcpyDefault, s));
-        HIP_TRY(hipGraphLaunch(exec, s));
-        HIP_TRY(hipMemcpyAsync(logits, m->g_logits, out_bytes, hipMemcpyDeviceToDevice, s));
-        return COCR_OK;
-    };
-    for (auto &g : m->graphs)
-        if (g.N == N && g.W == W && g.rows != form.chain_rows) {      // captured with another grid (a model joined or left the group since): as cocr_set_chain_rows
-            drop_graphs(m);
-            break;
-        }
-    for (auto &g : m->graphs)
-        if (same(g)) { HIP_TRY(hipGraphLaunch(g.exec, s)); return COCR_OK; }
-    bool seen = false, seen_shape = false;
-    for (auto &g : m->graph_seen) { seen = seen || same(g); seen_shape = seen_shape || same_shape(g); }
-    if (seen && shape_ready) {                       // the caller reuses its buffers: capture on them
-        hipGraphExec_t exec = nullptr;
-        if ((rc = capture(lines, logits, &exec))) return rc;
-        m->graphs.push_back({lines, logits, N, W, line_dtype, s, exec, form.chain_rows});
-        HIP_TRY(hipGraphLaunch(exec, s));
-        return COCR_OK;
-    }
-    if (m->graph_seen.size() >= 32) m->graph_seen.erase(m->graph_seen.begin());
-    m->graph_seen.push_back({lines, logits, N, W, line_dtype, s, nullptr, 0});
-    for (auto &g : m->graphs)
-        if (same_shape(g)) return staged_launch(g.exec);
-    if (!seen_shape || !shape_ready) {               // first call of this shape: plain, on the caller's buffers
-        m->graph_seen.push_back({nullptr, nullptr, N, W, line_dtype, s, nullptr, 0});
-        return run();
-    }
-    hipGraphExec_t exec = nullptr;                   // second call of the shape with other buffers: capture the staged sequence
-    if ((rc = capture(m->g_lines, m->g_logits, &exec))) return rc;
-    m->graphs.push_back({nullptr, nullptr, N, W, line_dtype, s, exec, form.chain_rows});
-    return staged_launch(exec);
+    m->lastT = Tn;
+    if (!m->use_graph || m->debug || m->profile || s == nullptr) return run_forward(m, form, lines, line_dtype, N, W, logits, s);
+    return forward_graphed(m, form, lines, line_dtype, N, W, logits, s);
 }
 
 // ------------------------------------------------------------------------------------ host-side collation
@@ -1722,7 +1626,7 @@ static int upload_lens(cocr_model *m, const int32_t *lens, int N, hipStream_t s,
 static int ensure_ctc_scratch(cocr_model *m, size_t rows) {
     if (rows <= m->ctc_lab.n && rows <= m->ctc_val.n) return COCR_OK;
     HIP_TRY(hipDeviceSynchronize());                          // (captured launches that point at the old scratch are dropped with it)
-    drop_graphs(m);
+    m->graphs.drop();
     m->amax_logits = nullptr;
     HIP_TRY(m->ctc_lab.grow(rows));
     HIP_TRY(m->ctc_val.grow(rows));
@@ -1963,7 +1867,8 @@ extern "C" int cocr_ctc_align(cocr_model *m, const float *logits, int N, int T, 
 extern "C" int cocr_decoder_backward(cocr_model *m, const float *grad_probits, int N, int T, float *grad_weight, float *grad_bias, float *grad_output,
                                      void *stream) {
     if (!m || !grad_probits || !grad_weight || !grad_bias) return fail(COCR_EINVAL, "null argument");
-    if (m->dtype < 0 || !m->blob) return fail(COCR_ESTATE, "model not finalized");
+    if (!m->w->blob) return fail(COCR_ESTATE, "model not finalized");
+    { const int rc = adopt_layout(m); if (rc) return rc; }
     if (N != m->lastN || T != m->lastT || !m->xn) return fail(COCR_ESTATE, "no forward of shape (%d lines, %d frames) precedes this call (last forward: %d, %d)", N, T, m->lastN, m->lastT);
     HIP_TRY(hipSetDevice(m->device));
     hipStream_t s = (hipStream_t)stream;
@@ -1989,8 +1894,8 @@ extern "C" int cocr_decoder_backward(cocr_model *m, const float *grad_probits, i
     hipLaunchKernelGGL(chunk_reduce_kernel, dim3(ceil_div(C, 256)), dim3(256), 0, s, part_b, chunks, (size_t)C, grad_bias);
     LAUNCH_CHECK();
     if (grad_output) {
-        if (m->dtype == COCR_BF16) hipLaunchKernelGGL((decoder_igrad_kernel<bf16_t>), dim3(ceil_div(M, 16)), dim3(256), 0, s, grad_probits, (const bf16_t *)(m->blob + m->plan.wdec), M, C, D, go_dst);
-        else hipLaunchKernelGGL((decoder_igrad_kernel<float>), dim3(ceil_div(M, 16)), dim3(256), 0, s, grad_probits, (const float *)(m->blob + m->plan.wdec), M, C, D, go_dst);
+        if (m->dtype == COCR_BF16) hipLaunchKernelGGL((decoder_igrad_kernel<bf16_t>), dim3(ceil_div(M, 16)), dim3(256), 0, s, grad_probits, (const bf16_t *)(m->w->blob + m->w->plan.wdec), M, C, D, go_dst);
+        else hipLaunchKernelGGL((decoder_igrad_kernel<float>), dim3(ceil_div(M, 16)), dim3(256), 0, s, grad_probits, (const float *)(m->w->blob + m->w->plan.wdec), M, C, D, go_dst);
         LAUNCH_CHECK();
     }
     if (m->padded) {
@@ -2014,9 +1919,9 @@ static int decoder_master_init(cocr_model *m, hipStream_t s) {
         HIP_TRY(hipMemcpyAsync(m->tr_state + nw, b->second.data.data(), nb * 4, hipMemcpyHostToDevice, s));
         HIP_TRY(hipStreamSynchronize(s));                                   // pageable sources
     } else {
-        if (m->dtype == COCR_BF16) hipLaunchKernelGGL((to_f32_kernel<bf16_t>), dim3(64), dim3(256), 0, s, (const bf16_t *)(m->blob + m->plan.wdec), m->tr_state, nw);
-        else hipLaunchKernelGGL((to_f32_kernel<float>), dim3(64), dim3(256), 0, s, (const float *)(m->blob + m->plan.wdec), m->tr_state, nw);
-        HIP_TRY(hipMemcpyAsync(m->tr_state + nw, m->blob + m->plan.bdec, nb * 4, hipMemcpyDeviceToDevice, s));
+        if (m->dtype == COCR_BF16) hipLaunchKernelGGL((to_f32_kernel<bf16_t>), dim3(64), dim3(256), 0, s, (const bf16_t *)(m->w->blob + m->w->plan.wdec), m->tr_state, nw);
+        else hipLaunchKernelGGL((to_f32_kernel<float>), dim3(64), dim3(256), 0, s, (const float *)(m->w->blob + m->w->plan.wdec), m->tr_state, nw);
+        HIP_TRY(hipMemcpyAsync(m->tr_state + nw, m->w->blob + m->w->plan.bdec, nb * 4, hipMemcpyDeviceToDevice, s));
         LAUNCH_CHECK();
     }
     m->tr_step = 0;
@@ -2352,7 +2257,7 @@ extern "C" int cocr_set_chain_rows(cocr_model *m, int rows) {
     if (!m) return fail(COCR_EINVAL, "null argument");
     if (rows < 0 || rows > 96) return fail(COCR_EINVAL, "rows per workgroup must be in 0..96");
     if (rows != m->chain_rows) {          // captured launch sequences use the old grid
-        drop_graphs(m);
+        m->graphs.drop();
     }
     m->chain_rows = rows;
     return COCR_OK;
@@ -2360,8 +2265,9 @@ extern "C" int cocr_set_chain_rows(cocr_model *m, int rows) {
 
 extern "C" int cocr_get_chain_rows(cocr_model *m, int N, int W, int *rows) {
     if (!m || !rows) return fail(COCR_EINVAL, "null argument");
-    if (m->dtype < 0 || !m->blob) return fail(COCR_ESTATE, "model not finalized");
+    if (!m->w->blob) return fail(COCR_ESTATE, "model not finalized");
     if (N < 1 || W < 1) return fail(COCR_EINVAL, "empty batch");
+    { const int rc = adopt_layout(m); if (rc) return rc; }
     *rows = forward_form(m, N, W).chain_rows;
     return COCR_OK;
 }

@@ -185,7 +185,8 @@ extern "C" int cocr_train_adopt_decoder(cocr_model *dst, cocr_model *src, void *
     if (!dst || !src) return fail(COCR_EINVAL, "null argument");
     TrainState *t = dst->train;
     if (!t) return fail(COCR_ESTATE, "cocr_train_begin has not been called on the adopting model");
-    if (src->dtype < 0 || !src->blob) return fail(COCR_ESTATE, "the source model is not finalized");
+    if (!src->w->blob) return fail(COCR_ESTATE, "the source model is not finalized");
+    { const int rc = adopt_layout(src); if (rc) return rc; }
     if (src->device != dst->device) return fail(COCR_EINVAL, "the two models live on different devices (%d, %d)", src->device, dst->device);
     auto w = t->idx.find("decoder.weight"), b = t->idx.find("decoder.bias");
     if (w == t->idx.end() || b == t->idx.end()) return fail(COCR_ESTATE, "the training state has no output layer");
@@ -291,8 +292,9 @@ extern "C" int cocr_train_optim_step(cocr_model *m, const cocr_optim *o, void *s
 // kind, the step count (*k).
 static int decoder_step_begin(cocr_model *m, const float **grad_weight, const float *grad_bias, const cocr_optim *o, hipStream_t s, long *k) {
     if (!m || !*grad_weight || !grad_bias || !o) return fail(COCR_EINVAL, "null argument");
-    if (m->dtype < 0 || !m->blob) return fail(COCR_ESTATE, "model not finalized");
-    if (m->owner) return fail(COCR_ESTATE, "this model shares another model's weights: step the owner");
+    if (!m->w->blob) return fail(COCR_ESTATE, "model not finalized");
+    if (!m->w->owned_by(m)) return fail(COCR_ESTATE, "this model shares another model's weights: step the owner");
+    { const int rc = adopt_layout(m); if (rc) return rc; }
     { const int rc = optim_check(o); if (rc) return rc; }
     HIP_TRY(hipSetDevice(m->device));
     if (m->padded) {    // the caller's (ncls, rD) gradient embedded in the engine's zero-padded rows
@@ -321,9 +323,9 @@ extern "C" int cocr_decoder_optim_step(cocr_model *m, const float *grad_weight, 
     if (o->kind == COCR_OPT_ADAMW || o->kind == COCR_OPT_ADAM) { bc1 = 1.0f - powf(o->beta1, (float)k); bc2 = 1.0f - powf(o->beta2, (float)k); }
     float *p = m->tr_state, *s0 = p + n, *s1 = s0 + n;
     const bool bf = m->dtype == COCR_BF16;
-    int rc = launch_optim(s, o, p, grad_weight, s0, s1, nw, bc1, bc2, nullptr, bf ? (bf16_t *)(m->blob + m->plan.wdec) : nullptr, bf ? nullptr : (float *)(m->blob + m->plan.wdec));
+    int rc = launch_optim(s, o, p, grad_weight, s0, s1, nw, bc1, bc2, nullptr, bf ? (bf16_t *)(m->w->blob + m->w->plan.wdec) : nullptr, bf ? nullptr : (float *)(m->w->blob + m->w->plan.wdec));
     if (rc) return rc;
-    return launch_optim(s, o, p + nw, grad_bias, s0 + nw, s1 + nw, nb, bc1, bc2, nullptr, nullptr, (float *)(m->blob + m->plan.bdec));
+    return launch_optim(s, o, p + nw, grad_bias, s0 + nw, s1 + nw, nb, bc1, bc2, nullptr, nullptr, (float *)(m->w->blob + m->w->plan.bdec));
 }
 
 // torch.optim.AdamW on the same state through adamw_kernel (train.hip.h), the step every frozen-backbone AdamW fit has taken.  NOT
@@ -339,12 +341,12 @@ extern "C" int cocr_decoder_adamw(cocr_model *m, const float *grad_weight, const
     float *p = m->tr_state, *m1 = p + n, *m2 = m1 + n;
     if (m->dtype == COCR_BF16)
         hipLaunchKernelGGL((adamw_kernel<bf16_t>), dim3(ceil_div((int)nw, 256)), dim3(256), 0, s, p, grad_weight, m1, m2, nw, lr, beta1, beta2, eps, weight_decay, bc1, bc2s,
-                           (bf16_t *)(m->blob + m->plan.wdec), (float *)nullptr);
+                           (bf16_t *)(m->w->blob + m->w->plan.wdec), (float *)nullptr);
     else
         hipLaunchKernelGGL((adamw_kernel<float>), dim3(ceil_div((int)nw, 256)), dim3(256), 0, s, p, grad_weight, m1, m2, nw, lr, beta1, beta2, eps, weight_decay, bc1, bc2s,
-                           (float *)nullptr, (float *)(m->blob + m->plan.wdec));
+                           (float *)nullptr, (float *)(m->w->blob + m->w->plan.wdec));
     hipLaunchKernelGGL((adamw_kernel<float>), dim3(ceil_div((int)nb, 256)), dim3(256), 0, s, p + nw, grad_bias, m1 + nw, m2 + nw, nb, lr, beta1, beta2, eps, weight_decay, bc1, bc2s,
-                       (float *)nullptr, (float *)(m->blob + m->plan.bdec));
+                       (float *)nullptr, (float *)(m->w->blob + m->w->plan.bdec));
     LAUNCH_CHECK();
     return COCR_OK;
 }
@@ -371,7 +373,8 @@ extern "C" int cocr_train_optim_restore(cocr_model *m, int kind, int64_t step, i
 
 extern "C" int cocr_decoder_optim_state(cocr_model *m, int *kind, int64_t *step, void **state, size_t *n_floats) {
     if (!m || !kind || !step || !state || !n_floats) return fail(COCR_EINVAL, "null argument");
-    if (m->dtype < 0 || !m->blob) return fail(COCR_ESTATE, "model not finalized");
+    if (!m->w->blob) return fail(COCR_ESTATE, "model not finalized");
+    { const int rc = adopt_layout(m); if (rc) return rc; }
     *kind = m->tr_state ? m->tr_kind : -1;
     *step = m->tr_state ? m->tr_step : 0;
     *state = m->tr_state;
@@ -381,8 +384,9 @@ extern "C" int cocr_decoder_optim_state(cocr_model *m, int *kind, int64_t *step,
 
 extern "C" int cocr_decoder_optim_restore(cocr_model *m, int kind, int64_t step, const float *state_device, size_t n_floats, void *stream) {
     if (!m || !state_device) return fail(COCR_EINVAL, "null argument");
-    if (m->dtype < 0 || !m->blob) return fail(COCR_ESTATE, "model not finalized");
-    if (m->owner) return fail(COCR_ESTATE, "this model shares another model's weights: restore the owner");
+    if (!m->w->blob) return fail(COCR_ESTATE, "model not finalized");
+    if (!m->w->owned_by(m)) return fail(COCR_ESTATE, "this model shares another model's weights: restore the owner");
+    { const int rc = adopt_layout(m); if (rc) return rc; }
     const size_t nw = (size_t)m->ncls * m->D, nb = (size_t)m->ncls, n = nw + nb;
     if (n_floats != 3 * n) return fail(COCR_EINVAL, "the output layer's state has %zu floats, not %zu", 3 * n, n_floats);
     if (kind < -1 || kind > COCR_OPT_RMSPROP || step < 0 || (kind < 0 && step != 0)) return fail(COCR_EINVAL, "invalid kind %d / step %lld", kind, (long long)step);
@@ -392,9 +396,9 @@ extern "C" int cocr_decoder_optim_restore(cocr_model *m, int kind, int64_t step,
     HIP_TRY(hipMemcpyAsync(m->tr_state, state_device, 3 * n * 4, hipMemcpyDeviceToDevice, s));
     m->tr_kind = kind; m->tr_step = (long)step;
     const bool bf = m->dtype == COCR_BF16;
-    hipLaunchKernelGGL(k_serve_copy, dim3(64), dim3(256), 0, s, (const float *)m->tr_state, nw, bf ? (bf16_t *)(m->blob + m->plan.wdec) : (bf16_t *)nullptr,
-                       bf ? (float *)nullptr : (float *)(m->blob + m->plan.wdec));
-    hipLaunchKernelGGL(k_serve_copy, dim3(1), dim3(256), 0, s, (const float *)(m->tr_state + nw), nb, (bf16_t *)nullptr, (float *)(m->blob + m->plan.bdec));
+    hipLaunchKernelGGL(k_serve_copy, dim3(64), dim3(256), 0, s, (const float *)m->tr_state, nw, bf ? (bf16_t *)(m->w->blob + m->w->plan.wdec) : (bf16_t *)nullptr,
+                       bf ? (float *)nullptr : (float *)(m->w->blob + m->w->plan.wdec));
+    hipLaunchKernelGGL(k_serve_copy, dim3(1), dim3(256), 0, s, (const float *)(m->tr_state + nw), nb, (bf16_t *)nullptr, (float *)(m->w->blob + m->w->plan.bdec));
     LAUNCH_CHECK();
     return COCR_OK;
 }

@@ -101,7 +101,8 @@ int32_t cocr_out_len(int32_t in_len, int32_t subsampling_factor);
  * and keeps only a workspace and captured launch sequences of its own.  (Four private copies of the cfg2 model are 4 x ~100 MB, more than
  * the 256 MB Infinity Cache: every forward then streamed its weights from HBM, cycling four copies on one stream ran 30 % slower than one.)
  * `owner` must outlive `m` and must not itself share; weights are changed through the owner (set_tensor + finalize, blob import, the
- * training entry points), `m` sees them at its next forward; finalizing `m` gives it weights of its own again. */
+ * training entry points), `m` sees them at its next forward; finalizing `m` gives it weights of its own again.  Every entry point of
+ * a sharing model reads the owner's current weights, not only its next forward; one that outlives its owner is not finalized. */
 int cocr_share_weights(cocr_model *m, cocr_model *owner);
 
 /* Host-side collation of a line batch: what kraken's `collate_sequences` does for the reference's loaders (cli/test.py:186-189, the

@@ -117,3 +117,93 @@ def test_owner_finalized_again_in_another_compute_dtype():
     owner.compute_dtype = 'bf16'
     owner.finalize()
     assert np.array_equal(sharer.forward(x, lens)[0].cpu().numpy(), bf)
+
+
+# ---- every entry point of a sharing model reads the owner's CURRENT weights (csrc/weights.hip.h), not only its next forward ----------
+# one encoder layer, 2 lines of 300 px (75 frames): seconds per case
+_SMALL = [('bf16', {}), ('fp32', {}), ('bf16', dict(encoder_dim=144, num_attention_heads=4))]      # the last: a zero-padded model (tr_pad path)
+
+
+def _small(dtype, **override):
+    hp = synth.hparams('cfg2', num_encoder_layers=1, **override)
+    state = synth.make_state_dict(hp, seed=41, decoder_gain=4.0)
+    img, lens = synth.make_lines(2, hp.height, 300, seed=9)
+    return hp, state, torch.from_numpy(img[:, 0]).cuda(), lens
+
+
+def _engine(hp, dtype, state=None, owner=None):
+    eng = HipRecognizer(hp, torch.device('cuda', 0), dtype)
+    if owner is not None:
+        eng.share_weights(owner)
+    else:
+        eng.load_state(state)
+        eng.finalize()
+    return eng
+
+
+def _grad(hp, seed=5):
+    g = torch.Generator().manual_seed(seed)
+    return torch.randn((2, 75, hp.num_classes), generator=g, dtype=torch.float32).cuda()
+
+
+@pytest.mark.parametrize('dtype,override', _SMALL, ids=['bf16', 'fp32', 'bf16-padded144'])
+def test_decoder_backward_of_a_sharer_reads_the_owners_current_weights(dtype, override):
+    hp, state, x, lens = _small(dtype, **override)
+    owner, private = _engine(hp, dtype, state), _engine(hp, dtype, state)
+    sharer = _engine(hp, dtype, owner=owner)
+    for eng in (owner, sharer, private):
+        eng.forward(x, lens)
+    state2 = {k: (v * 1.01 if k == 'decoder.weight' else v) for k, v in state.items()}      # the encoder output `xn` of all three stays valid
+    owner.load_state(state2)
+    owner.finalize()                                     # the owner's buffers move
+    private.load_state(state2)
+    private.finalize()
+    g = _grad(hp)
+    got = sharer.decoder_backward(g, with_input_grad=True)          # no forward in between
+    want = private.decoder_backward(g, with_input_grad=True)
+    torch.cuda.synchronize()
+    for a, b in zip(got, want):
+        assert a.shape == b.shape and np.array_equal(a.cpu().numpy(), b.cpu().numpy())
+    assert float(want[2].abs().max()) > 0
+
+
+def test_a_sharer_follows_a_compute_dtype_change_before_its_next_forward():
+    hp, state, x, lens = _small('bf16')
+    owner = _engine(hp, 'bf16', state)
+    sharer = _engine(hp, 'bf16', owner=owner)
+    sharer.forward(x, lens)
+    owner.compute_dtype = 'fp32'
+    owner.finalize()
+    fresh = _engine(hp, 'fp32', owner=owner)
+    assert sharer.chain_rows(2, 300) == fresh.chain_rows(2, 300)
+    with pytest.raises(RuntimeError, match='no forward of shape'):          # its encoder output went with the bf16 workspace
+        sharer.decoder_backward(_grad(hp), with_input_grad=True)
+    p32 = _engine(hp, 'fp32', state)
+    want = p32.forward(x, lens)[0].cpu().numpy()
+    assert np.array_equal(sharer.forward(x, lens)[0].cpu().numpy(), want)
+    got = sharer.decoder_backward(_grad(hp), with_input_grad=True)
+    ref = p32.decoder_backward(_grad(hp), with_input_grad=True)
+    for a, b in zip(got, ref):
+        assert np.array_equal(a.cpu().numpy(), b.cpu().numpy())
+
+
+@pytest.mark.parametrize('dtype', ['bf16', 'fp32'])
+def test_owner_destroyed_before_its_sharer(dtype):
+    """cocr.h asks for the owner to outlive its sharers; a sharer left behind is not finalized, and says so at every entry point."""
+    hp, state, x, lens = _small(dtype)
+    owner = _engine(hp, dtype, state)
+    sharer = _engine(hp, dtype, owner=owner)
+    want = owner.forward(x, lens)[0].cpu().numpy()
+    sharer.forward(x, lens)
+    torch.cuda.synchronize()
+    sharer._weights_owner = None
+    del owner
+    with pytest.raises(RuntimeError, match='not finalized'):
+        sharer.forward(x, lens)
+    with pytest.raises(RuntimeError):
+        sharer.decoder_backward(_grad(hp), with_input_grad=True)
+    with pytest.raises(RuntimeError):
+        sharer.chain_rows(2, 300)
+    sharer.load_state(state)
+    sharer.finalize()                                    # weights of its own
+    assert np.array_equal(sharer.forward(x, lens)[0].cpu().numpy(), want)
