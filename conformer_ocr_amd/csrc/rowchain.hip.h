@@ -41,11 +41,6 @@
 #ifndef COCR_STAMP_WG
 #define COCR_STAMP_WG 7        // dev (stamps build): the workgroup whose phase boundaries are stamped
 #endif
-#ifndef COCR_RC_EXP
-#define COCR_RC_EXP 0          // dev: timing experiments (wrong results): 1 no stream load, 2 no stream store, 4 no partial read-back, 8 no depthwise FMAs, 16 no SiLU transcendentals,
-                               // 32 no LayerNorm statistics, 64 no matrix instructions, 128 no weight stream (the ring is loaded once), 256 one operand fragment set per step,
-                               // 512 no barriers, 1024 no q/k/v staging and copy-out, 2048 no depthwise prologue arithmetic at all, 4096 no SiLU tiles, 8192 no normalise, 16384 no SiLU in the depthwise prologue
-#endif
 
 // Lane-swap butterflies (gfx950).  v_permlane32_swap a, b: a <- [a.lo32, b.lo32], b <- [a.hi32, b.hi32]; v_permlane16_swap a, b (rows of 16
 // lanes r0..r3): a <- [a.r0, b.r0, a.r2, b.r2], b <- [a.r1, b.r1, a.r3, b.r3].  Inline asm: the builtin's two results come back as ONE register when
@@ -68,40 +63,28 @@ __device__ __forceinline__ int xcd_remap_rows(int bid, int nwg) {
     return (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + (bid >> 3);
 }
 
-// Dev build -DCOCR_RC_PAIR=1 (round 4; measured, NOT the default -- DESIGN section 4b): the 48-row form of the 256-wide
-// engine built to be CO-RESIDENT, two workgroups per CU (4 waves per SIMD: <= 128 registers, 80 512 B of LDS each), so that one workgroup's
-// prologue / epilogues / barriers run beside the other's k-steps.  Its weight ring holds 8 fragments (half a step ahead) instead of 16 and
-// its depthwise prologue takes 128 channels per pass.  Bit-identical to the other forms.  At 2 x 250 workgroups on 250 CUs a launch takes
-// 98 us against 77 us for 250 96-row workgroups: two 48-row workgroups stream every weight byte twice through the CU's L1 path, and that
-// costs more than the overlap returns.
-#ifndef COCR_RC_PAIR
-#define COCR_RC_PAIR 0
-#endif
-template <int D, int MT> constexpr bool rowchain_pair_form() { return COCR_RC_PAIR && D == 256 && MT == 3; }
-
 // slack behind the two hidden-chunk images (the q / k / v output tiles' padded rows reach into it)
-template <int D, int MT> constexpr size_t rowchain_slack_bytes() { return rowchain_pair_form<D, MT>() ? 2048 : 4096; }
+constexpr size_t ROWCHAIN_SLACK = 4096;
+// channels per pass of the depthwise prologue (window + taps of that many channels in LDS at a time)
+constexpr int ROWCHAIN_DW_PASS = 256;
 // operand image + hidden images + slack.  HEAD (the out-proj -> GLU head in front of the depthwise prologue): the head's operand image of
 // MT + 2 row tiles and, BEHIND it (the GLU epilogue writes window rows while other waves still read the image), the GLU window of the
 // same rows ([row][2 D bytes]) alias that area; where they need more (48 and 32 rows) the area grows.
 template <int D, int MT, bool HEAD = false> constexpr size_t rowchain_area_bytes() {
-    constexpr size_t imgx = (size_t)(D / 64) * 16 * MT * 128, area = imgx + 2 * 4 * (size_t)(16 * MT) * 128 + rowchain_slack_bytes<D, MT>();
+    constexpr size_t imgx = (size_t)(D / 64) * 16 * MT * 128, area = imgx + 2 * 4 * (size_t)(16 * MT) * 128 + ROWCHAIN_SLACK;
     constexpr size_t harea = (size_t)(D / 64) * 16 * (MT + 2) * 128 + (size_t)16 * (MT + 2) * 2 * D;
     return HEAD && harea > area ? harea : area;
 }
 template <int D, int MT, bool HEAD = false> constexpr size_t rowchain_lds_bytes() {
     return rowchain_area_bytes<D, MT, HEAD>() + 16 * (size_t)D + 12 * (size_t)(16 * MT) + 64;
 }
-// channels per pass of the depthwise prologue (window + taps of that many channels in LDS at a time): the co-resident form takes 128
-template <int D, int MT> constexpr int rowchain_dw_pass() { return rowchain_pair_form<D, MT>() ? 128 : 256; }
 // Where the depthwise taps of a channel pass ((DWK + 1) rows of floats) are staged in LDS: 1 = behind the window inside the hidden-image
 // area, 2 = in an area of their own behind everything else, 0 = nowhere (no room: every thread loads its own taps from global memory)
 template <int D, int MT, int DWK> constexpr int rowchain_taps_place() {
     if (DWK == 0 || (DWK + 1) % 8 != 0) return 0;
-    constexpr size_t cw = rowchain_dw_pass<D, MT>(), rpi = 64 / (cw / 8);
-    constexpr size_t hsb = 2 * 4 * (size_t)(16 * MT) * 128 + rowchain_slack_bytes<D, MT>(), win = ((16 * MT + DWK - 1 + rpi - 1) / rpi) * 1024, taps = (size_t)(DWK + 1) * cw * 4;
+    constexpr size_t cw = ROWCHAIN_DW_PASS, rpi = 64 / (cw / 8);
+    constexpr size_t hsb = 2 * 4 * (size_t)(16 * MT) * 128 + ROWCHAIN_SLACK, win = ((16 * MT + DWK - 1 + rpi - 1) / rpi) * 1024, taps = (size_t)(DWK + 1) * cw * 4;
     if (win + taps <= hsb) return 1;
-    if (rowchain_pair_form<D, MT>()) return 0;
     if (rowchain_lds_bytes<D, MT>() + taps <= 160 * 1024) return 2;
     return 0;
 }
@@ -119,20 +102,17 @@ template <int D, int MT, int DWK> constexpr int rowchain_taps_place() {
 // computed with the arithmetic of the stand-alone launch, whichever workgroup computes them: bit-identical.  Halo rows outside [0, M)
 // (clamped addresses, a clamped neighbour block) and frames of other lines hold values no tap reads (the tap range, `tpos`).
 template <int D, int MT, int DWK, int K0, int K1, int K2, int K3, bool TAPS, int KD = 8, int KL = 8, int H0 = -1, int H1 = -1>
-__global__ __launch_bounds__(512, (rowchain_pair_form<D, MT>() ? 4 : 2)) void rowchain_kernel(ChainArgs p) {
+__global__ __launch_bounds__(512, 2) void rowchain_kernel(ChainArgs p) {
     typedef bf16_t T;
     constexpr bool HEAD = H0 >= 0;
     constexpr int ME = MT + 2;                 // row tiles of the head
-    static_assert(!HEAD || (H0 == ST_ROWLN && H1 == ST_GLU && K0 == ST_ROWLN && DWK == 31 && D == 256 && ME <= 6 && !rowchain_pair_form<D, MT>()), "head: out-proj -> GLU in front of the 31-tap prologue, 256 wide, at most 6 row tiles");
+    static_assert(!HEAD || (H0 == ST_ROWLN && H1 == ST_GLU && K0 == ST_ROWLN && DWK == 31 && D == 256 && ME <= 6), "head: out-proj -> GLU in front of the 31-tap prologue, 256 wide, at most 6 row tiles");
     static_assert(D == 256 || D == 512, "encoder_dim of the row-chain kernels");
     static_assert(MT >= 2 && MT <= 6, "16-row tiles per workgroup");
     static_assert(KD >= 1 && KD <= 8 && KL >= 1 && KL <= 8 && (D == 256 || (KD == 8 && KL == 8)), "skipped k-steps: the 256-wide engine only");
     typedef std::integral_constant<int, 8> KK8;
     typedef std::integral_constant<int, KD> KKD;           // K = D products
     typedef std::integral_constant<int, KL> KKL;           // the second product of the FFN's last hidden chunk
-    typedef KKD KKQ;
-    typedef KKD KKG;
-    typedef KKD KKP1;
     // the ROWLN stage of the out-proj -> GLU chain multiplies the attention context, whose real columns sit in head slots all over the
     // padded width ([64 h, 64 h + d_head)): no k-step of it is all zeros
     typedef std::integral_constant<int, (K1 == ST_GLU) ? 8 : KD> KKR;
@@ -148,7 +128,7 @@ __global__ __launch_bounds__(512, (rowchain_pair_form<D, MT>() ? 4 : 2)) void ro
     constexpr int SLICE = 16 * 512;            // elements in one step's weight run (16 fragments)
     constexpr int PROW = 80;                   // LayerNorm partials: 8 waves x (sum, sum of squares) per row, padded 64 -> 80 bytes (the 16 rows a
                                                // ds_read_b128 lane group touches then fall on 16 different bank quads)
-    constexpr int HSB = 2 * IMGH + (int)rowchain_slack_bytes<D, MT>();       // hidden images + slack (output tiles, depthwise window, LayerNorm partials alias them)
+    constexpr int HSB = 2 * IMGH + (int)ROWCHAIN_SLACK;     // hidden images + slack (output tiles, depthwise window, LayerNorm partials alias them)
     constexpr int AREA = (int)rowchain_area_bytes<D, MT, HEAD>();            // = IMGX + HSB, or what the head's image + window need
     constexpr int PANELE = 16 * ME * 128, IMGE = (D / 64) * PANELE;          // head: its operand image (ME tiles) at xa
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
@@ -176,11 +156,11 @@ __global__ __launch_bounds__(512, (rowchain_pair_form<D, MT>() ? 4 : 2)) void ro
     RSTAMP()                                       // 0: start
     auto lds_fence_barrier = [&]() {
         asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-        if constexpr (!(COCR_RC_EXP & 512)) __builtin_amdgcn_s_barrier();
+        __builtin_amdgcn_s_barrier();
     };
 
     constexpr int DWPAD = DWK ? (DWK - 1) / 2 : 0, DWROWS = BMC + 2 * DWPAD;
-    constexpr int CW = rowchain_dw_pass<D, MT>();          // channels per pass of the depthwise prologue
+    constexpr int CW = ROWCHAIN_DW_PASS;                   // channels per pass of the depthwise prologue
     constexpr int WS = CW * 2;                 // bytes per window row
     constexpr int LPR = CW / 8, RPI = 64 / LPR;            // lanes per window row (16 B each), window rows per wave-instruction
     constexpr int WINB = ((DWROWS + RPI - 1) / RPI) * 1024;
@@ -276,16 +256,15 @@ __global__ __launch_bounds__(512, (rowchain_pair_form<D, MT>() ? 4 : 2)) void ro
     dw_taps(0);
     RSTAMP()                                       // taps requested
     // ---- weight ring: the first step's 16 fragments
-    // RING = 16: the ring holds the current step's 16 fragments, slot f refilled with fragment f of the next step's run as soon as its
-    // k-step is done.  RING = 8 (the co-resident form): slot f % 8 holds fragment f; after k-step kk < 4 its two slots take fragments
-    // 2 kk + 8 (+ 1) of the CURRENT run, after k-step kk >= 4 fragments 2 (kk - 4) (+ 1) of the next one -- half a step ahead.
-    constexpr int RING = rowchain_pair_form<D, MT>() ? 8 : 16;
+    // the ring holds the current step's 16 fragments, slot f refilled with fragment f of the next step's run as soon as its k-step is done
+    constexpr int RING = 16;
     bf16x8 ring[RING];
-    auto fill = [&](const T *slice, int f) { ring[f % RING] = *reinterpret_cast<const bf16x8 *>(slice + f * 512 + lane * 8); };
-    const T *cur_run = p.st[HEAD ? 4 : 0].W + (size_t)wave * (FRONT0 ? p.st[0].K / 256 : KS) * SLICE;      // the run whose fragments the ring holds (RING = 8)
+    auto fill = [&](const T *slice, int f) { ring[f] = *reinterpret_cast<const bf16x8 *>(slice + f * 512 + lane * 8); };
+    const T *cur_run;                          // (written by every step, read by nothing: without it the compiler schedules the 96-row chains differently)
     {
+        const T *run0 = p.st[HEAD ? 4 : 0].W + (size_t)wave * (FRONT0 ? p.st[0].K / 256 : KS) * SLICE;
 #pragma unroll
-        for (int f = 0; f < RING; ++f) fill(cur_run, f);
+        for (int f = 0; f < RING; ++f) fill(run0, f);
     }
     __builtin_amdgcn_sched_barrier(0);
     RSTAMP()                                       // ring requested
@@ -302,20 +281,14 @@ __global__ __launch_bounds__(512, (rowchain_pair_form<D, MT>() ? 4 : 2)) void ro
 #pragma unroll
             for (int i = 0; i < MT; ++i)
 #pragma unroll
-                for (int c = 0; c < NJ; ++c) {
-                    if constexpr (COCR_RC_EXP & 1) xs[i][c] = (f32x4){(float)r16, 1.f, (float)g, 0.5f};
-                    else xs[i][c] = *reinterpret_cast<const f32x4 *>(p.x + xblk + (i * NJ + c) * 256);
-                }
+                for (int c = 0; c < NJ; ++c) xs[i][c] = *reinterpret_cast<const f32x4 *>(p.x + xblk + (i * NJ + c) * 256);
             return;
         }
 #pragma unroll
         for (int i = 0; i < MT; ++i) {
             const float *xrow = p.x + (size_t)min(m0 + 16 * i + r16, mend - 1) * D + 32 * wave + 4 * g;
 #pragma unroll
-            for (int c = 0; c < NJ; ++c) {
-                if constexpr (COCR_RC_EXP & 1) xs[i][c] = (f32x4){(float)r16, 1.f, (float)g, 0.5f};
-                else xs[i][c] = *reinterpret_cast<const f32x4 *>(xrow + 256 * (c >> 1) + 16 * (c & 1));
-            }
+            for (int c = 0; c < NJ; ++c) xs[i][c] = *reinterpret_cast<const f32x4 *>(xrow + 256 * (c >> 1) + 16 * (c & 1));
         }
     };
     // head: the stream of the ME tiles (blocked layout: the last tile of row block rblk - 1, the own tiles, the first tile of block rblk + 1;
@@ -343,8 +316,8 @@ __global__ __launch_bounds__(512, (rowchain_pair_form<D, MT>() ? 4 : 2)) void ro
     // the operand DMAs (older than the ring and stream loads) have landed.  The count is the FEWEST loads that can be in flight behind them:
     // a first step that skips k-steps never reads its last ring slots and the compiler drops those loads (with 16 here and 10 loads issued the
     // wait let the depthwise window arrive late: wrong rows in the first launch on fresh LDS, right ones by luck afterwards)
-    constexpr int RING0 = HEAD ? 16 : RING == 16 ? 2 * (K0 == ST_ROWLN ? KKR::value : K0 == ST_FFN ? KKP1::value : 8)
-                                     : (2 * (K0 == ST_ROWLN ? KKR::value : K0 == ST_FFN ? KKP1::value : 8) < 8 ? 2 * (K0 == ST_ROWLN ? KKR::value : K0 == ST_FFN ? KKP1::value : 8) : 8);
+    constexpr int KK0 = HEAD ? 8 : K0 == ST_ROWLN ? KKR::value : K0 == ST_FFN ? KKD::value : 8;       // k-steps of the launch's first step
+    constexpr int RING0 = 2 * KK0;
     asm volatile("s_waitcnt vmcnt(%0)" :: "n"(RING0 + EARLY_XS) : "memory");
     lds_fence_barrier();
     RSTAMP()                                       // 2: operand tile / window landed
@@ -374,7 +347,7 @@ __global__ __launch_bounds__(512, (rowchain_pair_form<D, MT>() ? 4 : 2)) void ro
             const f32x2_t bias = dw_bias;
             // rows of this thread: group rq of the block, G at a time (a ragged last group re-does rows of the previous one)
 #pragma unroll 1
-            for (int r0 = RQ * rq; r0 < ((COCR_RC_EXP & 2048) ? RQ * rq : RQ * (rq + 1)); r0 += G) {
+            for (int r0 = RQ * rq; r0 < RQ * (rq + 1); r0 += G) {
                 const int rb = min(r0, RQ * (rq + 1) - G);
                 const int t0 = __builtin_amdgcn_readfirstlane(tpos[rb]);
                 f32x2_t acc[G];
@@ -389,7 +362,7 @@ __global__ __launch_bounds__(512, (rowchain_pair_form<D, MT>() ? 4 : 2)) void ro
 #pragma unroll
                         for (int i = 0; i < G; ++i) {
                             const int tau = rin - i;
-                            if (tau >= 0 && tau < DWK) { if constexpr (COCR_RC_EXP & 8) { if (tau == 0) acc[i] += xf; } else acc[i] = __builtin_elementwise_fma(dw_wt[tau], xf, acc[i]); }
+                            if (tau >= 0 && tau < DWK) acc[i] = __builtin_elementwise_fma(dw_wt[tau], xf, acc[i]);
                         }
                     }
                 } else if (__builtin_amdgcn_readfirstlane(tpos[rb + G - 1]) == t0 + G - 1) {
@@ -430,7 +403,7 @@ __global__ __launch_bounds__(512, (rowchain_pair_form<D, MT>() ? 4 : 2)) void ro
 #pragma unroll
                 for (int i = 0; i < G; ++i) {
                     const int row = rb + i, cc = h * CW + c;
-                    const bf16x2 o = (COCR_RC_EXP & 16384) ? (bf16x2){(T)acc[i][0], (T)acc[i][1]} : (bf16x2){(T)silu_f(acc[i][0]), (T)silu_f(acc[i][1])};
+                    const bf16x2 o = {(T)silu_f(acc[i][0]), (T)silu_f(acc[i][1])};
                     *reinterpret_cast<bf16x2 *>(xa + (cc >> 6) * PANEL + row * 128 + ((((cc & 63) >> 3) ^ (row & 7)) << 4) + (cc & 7) * 2) = o;
                     if constexpr (TAPS) {
                         if (p.tap_dw && m0 + row < mend) *reinterpret_cast<bf16x2 *>(p.tap_dw + (size_t)(m0 + row) * D + cc) = o;
@@ -460,36 +433,19 @@ __global__ __launch_bounds__(512, (rowchain_pair_form<D, MT>() ? 4 : 2)) void ro
             for (int h0 = 0; h0 < MTN; h0 += HT) {
                 bf16x8 a[HT];
 #pragma unroll
-                for (int i = 0; i < HT; ++i) {
-                    if constexpr (COCR_RC_EXP & 256) { if (kk == 0) a[i] = lds_frag_swz(img + (16 * (h0 + i) + r16) * 128, 0, g, swz, T()); else asm volatile("" : "+v"(a[i])); }
-                    else a[i] = lds_frag_swz(img + (kk >> 1) * PANELN + (16 * (h0 + i) + r16) * 128, kk & 1, g, swz, T());
-                }
+                for (int i = 0; i < HT; ++i) a[i] = lds_frag_swz(img + (kk >> 1) * PANELN + (16 * (h0 + i) + r16) * 128, kk & 1, g, swz, T());
 #pragma unroll
                 for (int j = 0; j < 2; ++j)
 #pragma unroll
-                    for (int i = 0; i < HT; ++i) {
-                        if constexpr (COCR_RC_EXP & 64) {
-                            if (fresh && kk == 0) acc[h0 + i][c0 + j] = (f32x4){0.f, 0.f, 0.f, 0.f};
-                            asm volatile("" : "+v"(acc[h0 + i][c0 + j]) : "v"(ring[2 * kk + j]), "v"(a[i]));
-                        } else acc[h0 + i][c0 + j] = mma16(ring[(2 * kk + j) % RING], a[i], (fresh && kk == 0) ? (f32x4){0.f, 0.f, 0.f, 0.f} : acc[h0 + i][c0 + j]);
-                    }
+                    for (int i = 0; i < HT; ++i)
+                        acc[h0 + i][c0 + j] = mma16(ring[2 * kk + j], a[i], (fresh && kk == 0) ? (f32x4){0.f, 0.f, 0.f, 0.f} : acc[h0 + i][c0 + j]);
             }
-            if constexpr (!(COCR_RC_EXP & 128)) {
-                if constexpr (RING == 16) {
-                    fill(nxt, 2 * kk);
-                    fill(nxt, 2 * kk + 1);
-                } else if (kk < 4 && kk + 4 < KK) {          // (compile-time: kk is an unrolled constant) this slot is read again at k-step kk + 4
-                    fill(cur_run, 2 * kk + 8);
-                    fill(cur_run, 2 * kk + 9);
-                } else {
-                    fill(nxt, 2 * (kk & 3));
-                    fill(nxt, 2 * (kk & 3) + 1);
-                }
-            }
+            fill(nxt, 2 * kk);
+            fill(nxt, 2 * kk + 1);
             side(kk);
             __builtin_amdgcn_sched_barrier(0);               // keep the refill (and the side work) here: the scheduler otherwise sinks all of it to the step's end
         }
-        if constexpr (KK < (RING == 16 ? 8 : 4) && !(COCR_RC_EXP & 128)) {
+        if constexpr (KK < 8) {
 #pragma unroll
             for (int f = 2 * KK; f < RING; ++f) fill(nxt, f);  // the skipped k-steps' ring slots: the next step's fragments all the same
             __builtin_amdgcn_sched_barrier(0);
@@ -500,6 +456,19 @@ __global__ __launch_bounds__(512, (rowchain_pair_form<D, MT>() ? 4 : 2)) void ro
     typedef std::integral_constant<int, ME> MEC;
     auto step = [&](const unsigned char *img, auto &acc, int c0, const T *nxt, auto &&side, auto FRESH, auto KKC) { step_n(MTC0{}, img, acc, c0, nxt, side, FRESH, KKC); };
     auto no_side = [](int) {};
+    // this wave's weight run of k slice `ks` of the 256-column step `n` of a product with K = D
+    auto wslice = [&](const T *W, int n, int ks) { return W + ((size_t)(n * 8 + wave) * KS + ks) * SLICE; };
+    // A K = D product from zero: acc[..][c0], acc[..][c0 + 1] = operand image . step `n` of W, over its KS slices; the ring then takes the run
+    // at `nxt()` (a callable, evaluated where the last slice's step begins: where the address arithmetic sits decides the compiler's schedule)
+    auto fresh_n = [&](auto MTC, auto &acc, int c0, const T *W, int n, auto &&nxt, auto KKC) {
+        constexpr int PANELN = 16 * decltype(MTC)::value * 128;
+#pragma unroll
+        for (int ks = 0; ks < KS; ++ks) {
+            const T *then = ks + 1 < KS ? wslice(W, n, ks + 1) : nxt();
+            if (ks == 0) step_n(MTC, xa, acc, c0, then, no_side, std::true_type{}, KKC);
+            else step_n(MTC, xa + ks * 4 * PANELN, acc, c0, then, no_side, std::false_type{}, KKC);
+        }
+    };
     // LayerNorm parameters of a stage -> LDS, requested at the stage's start by waves 0..3 (one array each); the epilogue's vmcnt(16) + barrier
     // publishes them (at least one step = 16 younger ring loads lies between)
     auto request_ln_params = [&](const ChainStage &st) {
@@ -533,7 +502,6 @@ __global__ __launch_bounds__(512, (rowchain_pair_form<D, MT>() ? 4 : 2)) void ro
     auto add_bias_to_stream = [&](const float *bias, float alpha) { add_bias_n(MTC0{}, xs, bias, alpha); };
     // fp32 stream -> global in the accumulator layout (16 bytes per lane, 64-byte row segments; once per launch and consumer)
     auto store_stream = [&](float *dst) {
-        if constexpr (COCR_RC_EXP & 2) { asm volatile("" :: "v"(xs[0][0][0])); return; }
         if (dst == p.x && p.x_out_blocked) {                  // (rows beyond M inside the last block carry finite values nobody uses)
 #pragma unroll
             for (int i = 0; i < MT; ++i)
@@ -555,7 +523,6 @@ __global__ __launch_bounds__(512, (rowchain_pair_form<D, MT>() ? 4 : 2)) void ro
     // One pass (E[x^2] - mean^2 in fp32 over D <= 512 values of magnitude ~1: the bf16 operand this feeds has 8 significant bits).
     auto row_stats_n = [&](auto MTC, auto &xs, unsigned char *pbuf, bool wait_params, auto &mean, auto &rstd) {
         constexpr int MTN = decltype(MTC)::value;
-        if constexpr (COCR_RC_EXP & 32) { for (int i = 0; i < MTN; ++i) { mean[i] = 0.f; rstd[i] = 1.f; } lds_fence_barrier(); return; }
         float s[MTN], ss[MTN];
 #pragma unroll
         for (int i = 0; i < MTN; ++i) {
@@ -575,7 +542,7 @@ __global__ __launch_bounds__(512, (rowchain_pair_form<D, MT>() ? 4 : 2)) void ro
             *reinterpret_cast<f32x2 *>(pbuf + (16 * tile + r16) * PROW + wave * 8) = (f32x2){ts, tss};
         }
         if (wait_params && wave < 4) {      // this stage's LayerNorm parameters have landed (requested before the stage's first step)
-            if constexpr (KD == 8 && KL == 8) asm volatile("s_waitcnt vmcnt(%0)" :: "n"(RING) : "memory");      // ... at least one step = 16 younger ring loads lies between (8 of them in flight at most with the short ring)
+            if constexpr (KD == 8 && KL == 8) asm volatile("s_waitcnt vmcnt(%0)" :: "n"(RING) : "memory");      // ... at least one step = 16 younger ring loads lies between
             else asm volatile("s_waitcnt vmcnt(0)" ::: "memory");                                    // (steps that skip k-steps issue fewer: the compiler drops the dead ones)
         }
         lds_fence_barrier();
@@ -584,10 +551,8 @@ __global__ __launch_bounds__(512, (rowchain_pair_form<D, MT>() ? 4 : 2)) void ro
         for (int i = 0; i < MTN; ++i) {
             const unsigned char *pr = pbuf + (16 * i + r16) * PROW;
             f32x4 v = *reinterpret_cast<const f32x4 *>(pr);
-            if constexpr (!(COCR_RC_EXP & 4)) {
 #pragma unroll
-                for (int w2 = 1; w2 < 4; ++w2) v += *reinterpret_cast<const f32x4 *>(pr + 16 * w2);
-            }
+            for (int w2 = 1; w2 < 4; ++w2) v += *reinterpret_cast<const f32x4 *>(pr + 16 * w2);
             const float S = v[0] + v[2], SS = v[1] + v[3];
             mean[i] = S * inv_d;
             const float ex2 = SS * inv_d;
@@ -600,7 +565,6 @@ __global__ __launch_bounds__(512, (rowchain_pair_form<D, MT>() ? 4 : 2)) void ro
     auto normalise_n = [&](auto MTC, auto &xs, int which, const auto &mean, const auto &rstd, auto IN_PLACE) {
         constexpr int MTN = decltype(MTC)::value, PANELN = 16 * MTN * 128;
         constexpr bool in_place = decltype(IN_PLACE)::value;
-        if constexpr (COCR_RC_EXP & 8192) return;
         const float *ga = lnp + which * 2 * D, *be = ga + D;
 #pragma unroll
         for (int c = 0; c < NJ; ++c) {
@@ -621,6 +585,14 @@ __global__ __launch_bounds__(512, (rowchain_pair_form<D, MT>() ? 4 : 2)) void ro
         }
     };
     auto normalise = [&](int which, const float (&mean)[MT], const float (&rstd)[MT], auto IN_PLACE) { normalise_n(MTC0{}, xs, which, mean, rstd, IN_PLACE); };
+    // Coalesced copy of a staged [BMC][D] bf16 tile to the workgroup's rows of the (M, D) matrix `dst`; `src(row, ch)`: where the tile
+    // holds the 16-byte chunk ch of its row
+    auto copy_out = [&](T *dst, auto &&src) {
+        for (int id = tid; id < BMC * (D / 8); id += 512) {
+            const int row = id / (D / 8), ch = id - row * (D / 8);
+            if (m0 + row < mend) copy16(dst + (size_t)(m0 + row) * D + ch * 8, reinterpret_cast<const T *>(src(row, ch)));
+        }
+    };
     // Residual + LayerNorm(s) of a stage whose product has left x_new in the stream registers.
     //   single:  x <- x_new ;            operand <- LN1(x)
     //   chained: x <- LN1(x_new) ;       operand <- LN2(x)          (block-final LayerNorm + the next block's first)
@@ -651,24 +623,30 @@ __global__ __launch_bounds__(512, (rowchain_pair_form<D, MT>() ? 4 : 2)) void ro
         }
     };
 
+    // GLU of step s2 of the pointwise conv's 2 D packed columns: wave w's pair acc[..][0], acc[..][1] = (value tile, gate tile) of channels
+    // 128 s2 + 16 w .. + 15 (bb.v[0]: value bias, v[1]: gate bias) -> bf16 [row][stride bytes] at `tile`
+    auto glu_n = [&](auto MTC, const auto &acc, const Bias2 &bb, unsigned char *tile, int stride, int s2) {
+#pragma unroll
+        for (int i = 0; i < decltype(MTC)::value; ++i) {
+            const int row = 16 * i + r16;
+            bf16x4 o;
+#pragma unroll
+            for (int q = 0; q < 4; ++q) o[q] = (T)((acc[i][0][q] + bb.v[0][q]) * sigmoid_f(acc[i][1][q] + bb.v[1][q]));
+            *reinterpret_cast<bf16x4 *>(tile + row * stride + (s2 * 128 + 16 * wave + 4 * g) * 2) = o;
+        }
+    };
+
     auto run_stage = [&](auto KIND, auto FIRST, const ChainStage &st, const T *after) {      // `after`: this wave's first slice of the next stage
         constexpr int kind = decltype(KIND)::value;
         if constexpr (kind == ST_ROWLN) {
             // x_new = x + bias + A W^T: NS column steps x KS k-slices
             request_ln_params(st);
-            auto slice = [&](int ns, int ks) { return st.W + ((size_t)(ns * 8 + wave) * KS + ks) * SLICE; };
             if constexpr (decltype(FIRST)::value) {
                 // first stage of a launch: the stream is still on its way -- the product starts from zero and the stream (+ bias) is
                 // added afterwards
                 f32x4 acc[MT][NJ];
 #pragma unroll
-                for (int ns = 0; ns < NS; ++ns)
-#pragma unroll
-                    for (int ks = 0; ks < KS; ++ks) {
-                        const T *nxt = ks + 1 < KS ? slice(ns, ks + 1) : (ns + 1 < NS ? slice(ns + 1, 0) : after);
-                        if (ks == 0) step(xa, acc, 2 * ns, nxt, no_side, std::true_type{}, KKR{});
-                        else step(xa + ks * 4 * PANEL, acc, 2 * ns, nxt, no_side, std::false_type{}, KKR{});
-                    }
+                for (int ns = 0; ns < NS; ++ns) fresh_n(MTC0{}, acc, 2 * ns, st.W, ns, [&] { return ns + 1 < NS ? wslice(st.W, ns + 1, 0) : after; }, KKR{});
                 add_bias_to_stream(st.bias, 1.0f);
 #pragma unroll
                 for (int i = 0; i < MT; ++i)
@@ -681,7 +659,7 @@ __global__ __launch_bounds__(512, (rowchain_pair_form<D, MT>() ? 4 : 2)) void ro
                 for (int ns = 0; ns < NS; ++ns)
 #pragma unroll
                     for (int ks = 0; ks < KS; ++ks)
-                        step(xa + ks * 4 * PANEL, xs, 2 * ns, ks + 1 < KS ? slice(ns, ks + 1) : (ns + 1 < NS ? slice(ns + 1, 0) : after), no_side, std::false_type{}, KKR{});
+                        step(xa + ks * 4 * PANEL, xs, 2 * ns, ks + 1 < KS ? wslice(st.W, ns, ks + 1) : (ns + 1 < NS ? wslice(st.W, ns + 1, 0) : after), no_side, std::false_type{}, KKR{});
             }
             RSTAMP()                               // product done
             rowln_epilogue(st, hs);
@@ -723,12 +701,11 @@ __global__ __launch_bounds__(512, (rowchain_pair_form<D, MT>() ? 4 : 2)) void ro
             //                                                      S(c):  bias + SiLU of hidden(c) -> LDS          (VALU, folded into P2(c-1)'s k-steps)
             // weight stream order: W1(0), W1(1), W2(0), W1(2), W2(1), ..., W2(last).
             const int FF = st.N, nchunks = FF / 256;
-            auto w1 = [&](int c, int ks) { return st.W + ((size_t)(c * 8 + wave) * KS + ks) * SLICE; };
+            auto w1 = [&](int c) { return wslice(st.W, c, 0); };        // the first slice of W1(c)
             auto w2 = [&](int c, int ns) { return st.W2 + ((size_t)(ns * 8 + wave) * (FF / 32) + c * 8) * 1024; };
             f32x4 acc1[MT][2];
             Bias2 bb;
             auto silu_tile = [&](int tIdx, unsigned char *hb, auto PIN) {  // tile t = (row tile t / 2, column tile t % 2) of acc1 -> hb
-                if constexpr (COCR_RC_EXP & 4096) return;
                 const int i = tIdx >> 1, j = tIdx & 1;
                 // PIN: called from a k-step -- the arithmetic below is pure, and instruction selection otherwise gathers all twelve tiles'
                 // worth of it in one block ahead of the product's first k-step (seen in the ISA: only the LDS stores stayed inside the
@@ -744,8 +721,8 @@ __global__ __launch_bounds__(512, (rowchain_pair_form<D, MT>() ? 4 : 2)) void ro
                 for (int h = 0; h < 2; ++h) {
                     const f32x2_t v = {v4[2 * h], v4[2 * h + 1]};
                     f32x2_t e = v * (f32x2_t){-1.44269504088896340736f, -1.44269504088896340736f};
-                    if constexpr (!(COCR_RC_EXP & 16)) e = (f32x2_t){__builtin_amdgcn_exp2f(e[0]), __builtin_amdgcn_exp2f(e[1])} + (f32x2_t){1.0f, 1.0f};
-                    const f32x2_t o = (COCR_RC_EXP & 16) ? v * e : v * (f32x2_t){__builtin_amdgcn_rcpf(e[0]), __builtin_amdgcn_rcpf(e[1])};
+                    e = (f32x2_t){__builtin_amdgcn_exp2f(e[0]), __builtin_amdgcn_exp2f(e[1])} + (f32x2_t){1.0f, 1.0f};
+                    const f32x2_t o = v * (f32x2_t){__builtin_amdgcn_rcpf(e[0]), __builtin_amdgcn_rcpf(e[1])};
                     packed[h] = __builtin_bit_cast(unsigned, __builtin_convertvector(o, bf16x2));
                 }
                 typedef unsigned u32x2_t __attribute__((ext_vector_type(2)));
@@ -757,16 +734,12 @@ __global__ __launch_bounds__(512, (rowchain_pair_form<D, MT>() ? 4 : 2)) void ro
                 // in the same kind of phase at the same time (without it the older wave always wins the matrix pipe: 3.0 k / 4.4 k cycles
                 // for this product, the partners then alone in a 2.4 k tail of the next; chunk iteration 10.7 k -> 9.9 k cycles)
                 if (wave >= 4) __builtin_amdgcn_s_setprio(1);
-#pragma unroll
-                for (int ks = 0; ks < KS; ++ks) {
-                    if (ks == 0) step(xa, acc1, 0, KS > 1 ? w1(c, 1) : then, no_side, std::true_type{}, KKP1{});
-                    else step(xa + ks * 4 * PANEL, acc1, 0, ks + 1 < KS ? w1(c, ks + 1) : then, no_side, std::false_type{}, KKP1{});
-                }
+                fresh_n(MTC0{}, acc1, 0, st.W, c, [&] { return then; }, KKD{});
                 if (wave >= 4) __builtin_amdgcn_s_setprio(0);
             };
             request_ln_params(st);
             bb = load_bias(st.bias);
-            p1(0, nchunks > 1 ? w1(1, 0) : w2(0, 0));                     // P1(0)
+            p1(0, nchunks > 1 ? w1(1) : w2(0, 0));                     // P1(0)
             RSTAMP()                                                      // P1(0) done
 #pragma unroll
             for (int t2 = 0; t2 < 2 * MT; ++t2) silu_tile(t2, hs, std::false_type{});       // S(0)
@@ -782,7 +755,7 @@ __global__ __launch_bounds__(512, (rowchain_pair_form<D, MT>() ? 4 : 2)) void ro
                 unsigned char *hb = hs + (c & 1) * IMGH;
 #pragma unroll
                 for (int ns = 0; ns < NS; ++ns)                           // P2(c-1) beside S(c): the 2 MT tiles spread over the NS x 8 k-steps
-                    step(hs + ((c - 1) & 1) * IMGH, xs, 2 * ns, ns + 1 < NS ? w2(c - 1, ns + 1) : (c + 1 < nchunks ? w1(c + 1, 0) : w2(c, 0)),
+                    step(hs + ((c - 1) & 1) * IMGH, xs, 2 * ns, ns + 1 < NS ? w2(c - 1, ns + 1) : (c + 1 < nchunks ? w1(c + 1) : w2(c, 0)),
                          [&](int kk) {
 #pragma unroll
                              for (int t2 = 0; t2 < 2 * MT; ++t2) if ((t2 * 8 * NS) / (2 * MT) == ns * 8 + kk) silu_tile(t2, hb, std::true_type{});
@@ -799,48 +772,34 @@ __global__ __launch_bounds__(512, (rowchain_pair_form<D, MT>() ? 4 : 2)) void ro
             RSTAMP()                                                      // epilogue done
         } else if constexpr (kind == ST_GLU) {
             // 2 D packed columns in steps of 256: wave w's pair = (value tile, gate tile) of channels 128 step + 16 w .. +15
-            EpiGLU<T> e{st.out, D, st.bias, 2 * D};
-            auto slice = [&](int s2, int ks) { return st.W + ((size_t)(s2 * 8 + wave) * KS + ks) * SLICE; };
             constexpr int NSTEP = 2 * D / 256;
 #pragma unroll 1
             for (int s2 = 0; s2 < NSTEP; ++s2) {
-                const Bias2 bb = load_bias(st.bias + s2 * 256);          // v[0]: value bias, v[1]: gate bias
+                const Bias2 bb = load_bias(st.bias + s2 * 256);
                 f32x4 acc[MT][2];
 #pragma unroll
-                for (int ks = 0; ks < KS; ++ks) {
-                    const T *nxt = ks + 1 < KS ? slice(s2, ks + 1) : (s2 + 1 < NSTEP ? slice(s2 + 1, 0) : after);
-                    if (ks == 0) step(xa, acc, 0, nxt, no_side, std::true_type{}, KKG{});
-                    else step(xa + ks * 4 * PANEL, acc, 0, nxt, no_side, std::false_type{}, KKG{});
+                for (int ks = 0; ks < KS; ++ks) {          // (not fresh_n: at D = 512 this loop compiles differently through it)
+                    const T *nxt = ks + 1 < KS ? wslice(st.W, s2, ks + 1) : (s2 + 1 < NSTEP ? wslice(st.W, s2 + 1, 0) : after);
+                    if (ks == 0) step(xa, acc, 0, nxt, no_side, std::true_type{}, KKD{});
+                    else step(xa + ks * 4 * PANEL, acc, 0, nxt, no_side, std::false_type{}, KKD{});
                 }
-#pragma unroll
-                for (int i = 0; i < MT; ++i) {
-                    const int row = 16 * i + r16;
-                    bf16x4 o;
-#pragma unroll
-                    for (int q = 0; q < 4; ++q) o[q] = (T)((acc[i][0][q] + bb.v[0][q]) * sigmoid_f(acc[i][1][q] + bb.v[1][q]));
-                    *reinterpret_cast<bf16x4 *>(hs + row * OSD + (s2 * 128 + 16 * wave + 4 * g) * 2) = o;
-                }
+                glu_n(MTC0{}, acc, bb, hs, OSD, s2);
             }
             lds_fence_barrier();
-            for (int id = tid; id < BMC * (D / 8); id += 512) {          // coalesced copy of the staged [BMC][D] tile
-                const int row = id / (D / 8), ch = id - row * (D / 8);
-                if (m0 + row < mend) e.store(m0 + row, ch * 8, reinterpret_cast<const T *>(hs + row * OSD + ch * 16), 8);
-            }
+            copy_out(st.out, [&](int row, int ch) { return hs + row * OSD + ch * 16; });
         } else if constexpr (kind == ST_QKV) {   // 3 D columns in steps of 256; step s3 lies inside one of q, k, v
-            auto slice = [&](int s3, int ks) { return st.W + ((size_t)(s3 * 8 + wave) * KS + ks) * SLICE; };
             constexpr int NSTEP = 3 * D / 256;
 #pragma unroll
             for (int s3 = 0; s3 < NSTEP; ++s3) {
                 const Bias2 bb = load_bias(st.bias + s3 * 256);
                 f32x4 acc[MT][2];
 #pragma unroll
-                for (int ks = 0; ks < KS; ++ks) {
-                    const T *nxt = ks + 1 < KS ? slice(s3, ks + 1) : (s3 + 1 < NSTEP ? slice(s3 + 1, 0) : after);
-                    if (ks == 0) step(xa, acc, 0, nxt, no_side, std::true_type{}, KKQ{});
-                    else step(xa + ks * 4 * PANEL, acc, 0, nxt, no_side, std::false_type{}, KKQ{});
+                for (int ks = 0; ks < KS; ++ks) {          // (not fresh_n: at D = 512 this loop compiles differently through it)
+                    const T *nxt = ks + 1 < KS ? wslice(st.W, s3, ks + 1) : (s3 + 1 < NSTEP ? wslice(st.W, s3 + 1, 0) : after);
+                    if (ks == 0) step(xa, acc, 0, nxt, no_side, std::true_type{}, KKD{});
+                    else step(xa + ks * 4 * PANEL, acc, 0, nxt, no_side, std::false_type{}, KKD{});
                 }
                 unsigned char *tile = hs + (s3 & 1) * (BMC * OS);
-                if constexpr (COCR_RC_EXP & 1024) { asm volatile("" :: "v"(acc[0][0]), "v"(acc[MT - 1][1])); continue; }
 #pragma unroll
                 for (int j = 0; j < 2; ++j)
 #pragma unroll
@@ -872,11 +831,10 @@ __global__ __launch_bounds__(512, (rowchain_pair_form<D, MT>() ? 4 : 2)) void ro
     // operand image of ME tiles at xa, the GLU values into the window.
     auto run_head = [&]() { if constexpr (HEAD) {
         const ChainStage &hr = p.st[4], &hg = p.st[5];
-        auto gslice = [&](int s2) { return hg.W + (size_t)(s2 * 8 + wave) * SLICE; };
         request_ln_params(hr);
         {   // x_new = x + bias + ctx Wo^T, as the first stage of a launch computes it: the product from zero, then stream + bias, then their sum
             f32x4 acc[ME][NJ];
-            step_n(MEC{}, xa, acc, 0, gslice(0), no_side, std::true_type{}, KK8{});
+            fresh_n(MEC{}, acc, 0, hr.W, 0, [&] { return wslice(hg.W, 0, 0); }, KK8{});
             add_bias_n(MEC{}, xe, hr.bias, 1.0f);
 #pragma unroll
             for (int i = 0; i < ME; ++i)
@@ -914,25 +872,11 @@ __global__ __launch_bounds__(512, (rowchain_pair_form<D, MT>() ? 4 : 2)) void ro
         for (int s2 = 0; s2 < 2; ++s2) {
             const Bias2 bb = load_bias(hg.bias + s2 * 256);
             f32x4 acc[ME][2];
-            step_n(MEC{}, xa, acc, 0, s2 == 0 ? gslice(1) : first_slice(0), no_side, std::true_type{}, KKG{});
-#pragma unroll
-            for (int i = 0; i < ME; ++i) {
-                const int row = 16 * i + r16;
-                bf16x4 o;
-#pragma unroll
-                for (int q = 0; q < 4; ++q) o[q] = (T)((acc[i][0][q] + bb.v[0][q]) * sigmoid_f(acc[i][1][q] + bb.v[1][q]));
-                *reinterpret_cast<bf16x4 *>(winx + row * WS + (s2 * 128 + 16 * wave + 4 * g) * 2) = o;
-            }
+            fresh_n(MEC{}, acc, 0, hg.W, s2, [&] { return s2 == 0 ? wslice(hg.W, 1, 0) : first_slice(0); }, KKD{});
+            glu_n(MEC{}, acc, bb, winx, WS, s2);
         }
         lds_fence_barrier();                       // window complete; every wave is done with the head's operand image
-        if constexpr (TAPS) {
-            if (hg.out) {                          // the GLU output, own rows
-                for (int id = tid; id < BMC * (D / 8); id += 512) {
-                    const int row = id / (D / 8), ch = id - row * (D / 8);
-                    if (m0 + row < mend) copy16(hg.out + (size_t)(m0 + row) * D + ch * 8, reinterpret_cast<const T *>(winx + (16 + row) * WS + ch * 16));
-                }
-            }
-        }
+        if constexpr (TAPS) { if (hg.out) copy_out(hg.out, [&](int row, int ch) { return winx + (16 + row) * WS + ch * 16; }); }      // the GLU output, own rows
         RSTAMP()                                   // head: GLU done
     } };
     run_head();
@@ -956,70 +900,67 @@ static inline hipError_t launch_rowchain_mt(hipStream_t s, const ChainArgs &a) {
     return hipGetLastError();
 }
 
-// HAS_TAPS: whether the debug instantiation exists for this chain shape (the shapes the default forward uses)
-template <int D, int DWK, int K0, int K1, int K2, int K3, bool HAS_TAPS>
-static inline hipError_t launch_rowchain_cfg(hipStream_t s, const ChainArgs &a, bool taps, int rows_hint) {
+// One chain shape at every instantiated number of row tiles (MTS: 2, 3, 4, 6 at D = 256; 2, 4 at D = 512; 2, 3, 4 behind the head), each in
+// up to three forms.  (Ascending: the compiler instantiates the fold's last operand first, so a unit's kernels are emitted tallest first, in
+// the order the code object has always had.)  HAS_TAPS: whether the debug instantiation exists for this chain shape (the shapes the default forward uses).
+// H0, H1: the out-proj -> GLU head (ChainArgs::nhead = 2), or -1.
+template <int... MTS> struct RowTiles {};
+template <int D, int DWK, int K0, int K1, int K2, int K3, bool HAS_TAPS, int H0, int H1, int... MTS>
+static inline hipError_t launch_rowchain_cfg(hipStream_t s, const ChainArgs &a, bool taps, int rows_hint, RowTiles<MTS...>) {
     const int mt = rowchain_pick_mt<D>(a.M, rows_hint);
     if (taps && !HAS_TAPS) return hipErrorInvalidValue;
     // the reference's default model in its zero-padded 256 / 768-wide form: 5 of 8 k-steps per K = D product, 2 of 8 in the FFN's last chunk
     // (no debug instantiation: taps run the full-depth kernels, which compute the same values -- the skipped products are exact zeros)
     const bool narrow = D == 256 && a.kd == 5 && a.kl == 2 && !taps;
-#define COCR_RC(MTV)                                                                                            \
-    if (mt == MTV) {                                                                                            \
-        if constexpr (HAS_TAPS) { if (taps) return launch_rowchain_mt<D, MTV, DWK, K0, K1, K2, K3, true>(s, a); } \
-        if constexpr (D == 256) { if (narrow) return launch_rowchain_mt<D, MTV, DWK, K0, K1, K2, K3, false, 5, 2>(s, a); } \
-        return launch_rowchain_mt<D, MTV, DWK, K0, K1, K2, K3, false>(s, a);                                     \
-    }
-    if constexpr (D == 256) { COCR_RC(6) COCR_RC(4) COCR_RC(3) } else { COCR_RC(4) }
-    COCR_RC(2)
-#undef COCR_RC
-    return hipErrorInvalidValue;
+    auto form = [&](auto MTV) {
+        constexpr int MT = decltype(MTV)::value;
+        if constexpr (HAS_TAPS) { if (taps) return launch_rowchain_mt<D, MT, DWK, K0, K1, K2, K3, true, 8, 8, H0, H1>(s, a); }
+        if constexpr (D == 256) { if (narrow) return launch_rowchain_mt<D, MT, DWK, K0, K1, K2, K3, false, 5, 2, H0, H1>(s, a); }
+        return launch_rowchain_mt<D, MT, DWK, K0, K1, K2, K3, false, 8, 8, H0, H1>(s, a);
+    };
+    hipError_t e = hipErrorInvalidValue;
+    (void)((mt == MTS && ((e = form(std::integral_constant<int, MTS>{})), true)) || ...);
+    return e;
+}
+
+// the kinds of a chain's (up to four) stages, -1 behind the last
+struct ChainKinds { int k0, k1, k2, k3; };
+static inline ChainKinds rowchain_kinds(const ChainArgs &a) {
+    return {a.st[0].kind, a.nstages > 1 ? a.st[1].kind : -1, a.nstages > 2 ? a.st[2].kind : -1, a.nstages > 3 ? a.st[3].kind : -1};
 }
 
 // The depthwise-prologue chains behind the out-proj -> GLU head (ChainArgs::nhead = 2), 256 wide: 64, 48 and 32 rows (the 96-row form would
-// hold 8 row tiles of accumulators and stream in the head: it keeps its two launches).  Debug taps and the narrow k-steps as above.
-template <int K2, int K3>
-static inline hipError_t launch_rowchain_head_cfg(hipStream_t s, const ChainArgs &a, bool taps, int rows_hint) {
-    const int mt = rowchain_pick_mt<256>(a.M, rows_hint);
-    const bool narrow = a.kd == 5 && a.kl == 2 && !taps;
-#define COCR_RC(MTV)                                                                                                                \
-    if (mt == MTV) {                                                                                                                \
-        if (taps) return launch_rowchain_mt<256, MTV, 31, ST_ROWLN, ST_FFN, K2, K3, true, 8, 8, ST_ROWLN, ST_GLU>(s, a);              \
-        if (narrow) return launch_rowchain_mt<256, MTV, 31, ST_ROWLN, ST_FFN, K2, K3, false, 5, 2, ST_ROWLN, ST_GLU>(s, a);           \
-        return launch_rowchain_mt<256, MTV, 31, ST_ROWLN, ST_FFN, K2, K3, false, 8, 8, ST_ROWLN, ST_GLU>(s, a);                       \
-    }
-    COCR_RC(4) COCR_RC(3) COCR_RC(2)
-#undef COCR_RC
-    return hipErrorInvalidValue;
-}
+// hold 8 row tiles of accumulators and stream in the head: it keeps its two launches).
 template <int D>      // (a template so that only the unit that calls it instantiates the kernels)
 static inline hipError_t launch_rowchain_head(hipStream_t s, const ChainArgs &a, bool taps, int rows_hint) {
     static_assert(D == 256, "the head: encoder_dim 256");
-    const int k0 = a.st[0].kind, k1 = a.nstages > 1 ? a.st[1].kind : -1, k2 = a.nstages > 2 ? a.st[2].kind : -1, k3 = a.nstages > 3 ? a.st[3].kind : -1;
+    const auto [k0, k1, k2, k3] = rowchain_kinds(a);
+    typedef RowTiles<2, 3, 4> Tiles;
     if (a.nhead != 2 || a.st[4].kind != ST_ROWLN || a.st[5].kind != ST_GLU || !a.dw_w || !a.A0 || !a.xh || a.xh == a.x || !a.x_in_blocked) return hipErrorInvalidValue;
-    if (k0 == ST_ROWLN && k1 == ST_FFN && k2 == ST_FFN && k3 == ST_QKV) return launch_rowchain_head_cfg<ST_FFN, ST_QKV>(s, a, taps, rows_hint);
-    if (k0 == ST_ROWLN && k1 == ST_FFN && k2 == -1) return launch_rowchain_head_cfg<-1, -1>(s, a, taps, rows_hint);
+    if (k0 == ST_ROWLN && k1 == ST_FFN && k2 == ST_FFN && k3 == ST_QKV) return launch_rowchain_cfg<D, 31, ST_ROWLN, ST_FFN, ST_FFN, ST_QKV, true, ST_ROWLN, ST_GLU>(s, a, taps, rows_hint, Tiles{});
+    if (k0 == ST_ROWLN && k1 == ST_FFN && k2 == -1) return launch_rowchain_cfg<D, 31, ST_ROWLN, ST_FFN, -1, -1, true, ST_ROWLN, ST_GLU>(s, a, taps, rows_hint, Tiles{});
     return hipErrorInvalidValue;
 }
 
 // the chain shapes the forward uses; stage weights point at the fragment-major copies
 template <int D>
 static inline hipError_t launch_rowchain(hipStream_t s, const ChainArgs &a, bool taps, int rows_hint) {
-    const int k0 = a.st[0].kind, k1 = a.nstages > 1 ? a.st[1].kind : -1, k2 = a.nstages > 2 ? a.st[2].kind : -1, k3 = a.nstages > 3 ? a.st[3].kind : -1;
+    const auto [k0, k1, k2, k3] = rowchain_kinds(a);
+    typedef std::conditional_t<D == 256, RowTiles<2, 3, 4, 6>, RowTiles<2, 4>> Tiles;
     if (a.nhead) return hipErrorInvalidValue;      // (launch_rowchain_head)
     if (a.dw_in) {                       // depthwise-conv prologue (kernel 31): the chains that follow the conv module's GLU
-        if (k0 == ST_ROWLN && k1 == ST_FFN && k2 == ST_FFN && k3 == ST_QKV) return launch_rowchain_cfg<D, 31, ST_ROWLN, ST_FFN, ST_FFN, ST_QKV, true>(s, a, taps, rows_hint);
-        if (k0 == ST_ROWLN && k1 == ST_FFN && k2 == -1) return launch_rowchain_cfg<D, 31, ST_ROWLN, ST_FFN, -1, -1, true>(s, a, taps, rows_hint);
+        if (k0 == ST_ROWLN && k1 == ST_FFN && k2 == ST_FFN && k3 == ST_QKV) return launch_rowchain_cfg<D, 31, ST_ROWLN, ST_FFN, ST_FFN, ST_QKV, true, -1, -1>(s, a, taps, rows_hint, Tiles{});
+        if (k0 == ST_ROWLN && k1 == ST_FFN && k2 == -1) return launch_rowchain_cfg<D, 31, ST_ROWLN, ST_FFN, -1, -1, true, -1, -1>(s, a, taps, rows_hint, Tiles{});
         return hipErrorInvalidValue;
     }
-    if (k0 == ST_FRONT && k1 == ST_FFN && k2 == ST_QKV && k3 == -1) return launch_rowchain_cfg<D, 0, ST_FRONT, ST_FFN, ST_QKV, -1, true>(s, a, taps, rows_hint);
-    if (k0 == ST_FFN && k1 == ST_QKV && k2 == -1) return launch_rowchain_cfg<D, 0, ST_FFN, ST_QKV, -1, -1, true>(s, a, taps, rows_hint);
+    if (k0 == ST_FRONT && k1 == ST_FFN && k2 == ST_QKV && k3 == -1) return launch_rowchain_cfg<D, 0, ST_FRONT, ST_FFN, ST_QKV, -1, true, -1, -1>(s, a, taps, rows_hint, Tiles{});
+    if (k0 == ST_FFN && k1 == ST_QKV && k2 == -1) return launch_rowchain_cfg<D, 0, ST_FFN, ST_QKV, -1, -1, true, -1, -1>(s, a, taps, rows_hint, Tiles{});
     // one feed-forward module alone (operand tile + stream in, LayerNorm epilogue, nothing else): the measurement probe of cocr_api.hip
     // (COCR_FFN_PROBE=1: matrix-pipe counters of the FFN products by themselves, tools/ffn_probe.py)
-    if (k0 == ST_FFN && k1 == -1) return launch_rowchain_cfg<D, 0, ST_FFN, -1, -1, -1, false>(s, a, false, rows_hint);
-    if (k0 == ST_ROWLN && k1 == ST_GLU && k2 == -1) return launch_rowchain_cfg<D, 0, ST_ROWLN, ST_GLU, -1, -1, true>(s, a, taps, rows_hint);
+    if (k0 == ST_FFN && k1 == -1) return launch_rowchain_cfg<D, 0, ST_FFN, -1, -1, -1, false, -1, -1>(s, a, false, rows_hint, Tiles{});
+    if (k0 == ST_ROWLN && k1 == ST_GLU && k2 == -1) return launch_rowchain_cfg<D, 0, ST_ROWLN, ST_GLU, -1, -1, true, -1, -1>(s, a, taps, rows_hint, Tiles{});
     // (without the depthwise prologue: conv kernels other than 31 -- the stand-alone depthwise kernel runs before the launch --, COCR_NO_DW_FUSE A/B runs)
-    if (k0 == ST_ROWLN && k1 == ST_FFN && k2 == ST_FFN && k3 == ST_QKV) return launch_rowchain_cfg<D, 0, ST_ROWLN, ST_FFN, ST_FFN, ST_QKV, true>(s, a, taps, rows_hint);
-    if (k0 == ST_ROWLN && k1 == ST_FFN && k2 == -1) return launch_rowchain_cfg<D, 0, ST_ROWLN, ST_FFN, -1, -1, true>(s, a, taps, rows_hint);
+    if (k0 == ST_ROWLN && k1 == ST_FFN && k2 == ST_FFN && k3 == ST_QKV) return launch_rowchain_cfg<D, 0, ST_ROWLN, ST_FFN, ST_FFN, ST_QKV, true, -1, -1>(s, a, taps, rows_hint, Tiles{});
+    if (k0 == ST_ROWLN && k1 == ST_FFN && k2 == -1) return launch_rowchain_cfg<D, 0, ST_ROWLN, ST_FFN, -1, -1, true, -1, -1>(s, a, taps, rows_hint, Tiles{});
     return hipErrorInvalidValue;
 }

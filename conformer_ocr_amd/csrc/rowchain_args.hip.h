@@ -1,5 +1,5 @@
-// Arguments of the row-chain kernels (rowchain.hip.h) and the entry points of their two translation units (rowchain_d256.hip,
-// rowchain_d512.hip: the template instantiations are compiled beside cocr_api.hip, in parallel).
+// Arguments of the row-chain kernels (rowchain.hip.h) and the entry points of their three translation units (rowchain_d256.hip,
+// rowchain_d256_head.hip, rowchain_d512.hip: the template instantiations are compiled beside cocr_api.hip, in parallel).
 #pragma once
 #include <hip/hip_runtime.h>
 
