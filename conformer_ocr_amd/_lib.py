@@ -71,6 +71,9 @@ SYMBOLS = {
     'cocr_train_adopt_decoder': (_I, [_P, _P, _P]),
     'cocr_train_optim_step': (_I, [_P, _P, _P]),
     'cocr_decoder_optim_step': (_I, [_P, _P, _P, _P, _P]),
+    'cocr_grad_accumulate': (_I, [_P, _P, C.c_size_t, C.c_float, _I, _I, _P]),
+    'cocr_grad_norm': (_I, [_P, C.c_size_t, _I, C.POINTER(C.c_double), _P]),
+    'cocr_train_optim_step_ex': (_I, [_P, _P, _P, C.c_float, _P]),
     'cocr_train_optim_state': (_I, [_P, C.POINTER(C.c_int), C.POINTER(C.c_int64), C.POINTER(C.c_int64), C.POINTER(_P), C.POINTER(_P), C.POINTER(C.c_size_t)]),
     'cocr_train_optim_restore': (_I, [_P, _I, C.c_int64, C.c_int64]),
     'cocr_decoder_optim_state': (_I, [_P, C.POINTER(C.c_int), C.POINTER(C.c_int64), C.POINTER(_P), C.POINTER(C.c_size_t)]),

@@ -228,8 +228,9 @@ static int optim_check(const cocr_optim *o) {
 }
 
 // n elements of (P, G, S0, S1); bc1 / bc2: the bias corrections of every element outside `ranges` (Adam kinds; null: no ranges)
+// grad_scale: every gradient element enters the step as fl(grad_scale g) (cocr_train_optim_step_ex; 1.0f: the gradient as it is)
 static int launch_optim(hipStream_t s, const cocr_optim *o, float *P, const float *G, float *S0, float *S1, size_t n, float bc1, float bc2, const AdamwRanges *ranges,
-                        bf16_t *serve_b, float *serve_f) {
+                        bf16_t *serve_b, float *serve_f, float grad_scale = 1.0f) {
     if (n == 0) return COCR_OK;
     // 16 bytes per lane where all four vectors are aligned at the same elements; otherwise (a slot that starts at an odd float offset of
     // its allocation) every element goes the scalar way
@@ -237,7 +238,7 @@ static int launch_optim(hipStream_t s, const cocr_optim *o, float *P, const floa
     for (const void *q : {(const void *)(P + head), (const void *)(G + head), (const void *)(S0 + head), (const void *)(S1 + head)})
         if ((uintptr_t)q & 15) head = n;
     const size_t nvec = (n - head) / 4;
-    const OptimArgs a = {o->lr, o->weight_decay, o->beta1, o->beta2, o->eps, o->momentum, o->alpha, bc1, bc2};
+    const OptimArgs a = {o->lr, o->weight_decay, o->beta1, o->beta2, o->eps, o->momentum, o->alpha, bc1, bc2, grad_scale};
     const AdamwRanges r = ranges ? *ranges : AdamwRanges{};
     const dim3 grid((unsigned)std::max<size_t>(1, std::min<size_t>((std::max(nvec, n - 4 * nvec) + 255) / 256, 2048))), block(256);
     const bool flag = (o->kind == COCR_OPT_ADAMW || o->kind == COCR_OPT_ADAM) ? ranges != nullptr : o->momentum > 0.f;
@@ -257,11 +258,14 @@ static int launch_optim(hipStream_t s, const cocr_optim *o, float *P, const floa
     return COCR_OK;
 }
 
-extern "C" int cocr_train_optim_step(cocr_model *m, const cocr_optim *o, void *stream) {
+// cocr_train_optim_step with the gradient read from `grad` (NULL: the state's own vector) and scaled by grad_scale on its way in
+extern "C" int cocr_train_optim_step_ex(cocr_model *m, const cocr_optim *o, const float *grad, float grad_scale, void *stream) {
     if (!m || !o) return fail(COCR_EINVAL, "null argument");
     TrainState *t = m->train;
     if (!t) return fail(COCR_ESTATE, "cocr_train_begin has not been called");
     { const int rc = optim_check(o); if (rc) return rc; }
+    // finite and >= 0, or NaN (what torch's clip makes of a NaN norm; the Trainer never passes one)
+    if (!std::isnan(grad_scale) && !(grad_scale >= 0.f && std::isfinite(grad_scale))) return fail(COCR_EINVAL, "invalid grad_scale %g", (double)grad_scale);
     if (t->kind >= 0 && t->kind != o->kind) return fail(COCR_ESTATE, "the optimizer state is %s's: a %s step cannot follow", optim_name(t->kind), optim_name(o->kind));
     HIP_TRY(hipSetDevice(m->device));
     t->kind = o->kind;
@@ -284,7 +288,56 @@ extern "C" int cocr_train_optim_step(cocr_model *m, const cocr_optim *o, void *s
             ranges = true;
         }
     }
-    return launch_optim((hipStream_t)stream, o, t->P, t->G, t->Mo, t->Vo, t->nparam, bc1, bc2, ranges ? &r : nullptr, nullptr, nullptr);
+    return launch_optim((hipStream_t)stream, o, t->P, grad ? grad : t->G, t->Mo, t->Vo, t->nparam, bc1, bc2, ranges ? &r : nullptr, nullptr, nullptr, grad_scale);
+}
+
+// = cocr_train_optim_step_ex(m, o, NULL, 1.0f, stream): fl(1.0f g) is g for every float, so the step keeps its bits
+extern "C" int cocr_train_optim_step(cocr_model *m, const cocr_optim *o, void *stream) { return cocr_train_optim_step_ex(m, o, nullptr, 1.0f, stream); }
+
+// ---- the gradient window on raw device vectors (kernels: train_enc.hip.h) ------------------------------------------------------------------------
+extern "C" int cocr_grad_accumulate(float *dst, const float *src, size_t n, float scale, int overwrite, int device, void *stream) {
+    if (n == 0) return COCR_OK;
+    if (!dst || !src) return fail(COCR_EINVAL, "null argument");
+    if (dst == src && !overwrite) return fail(COCR_EINVAL, "dst may be src only with overwrite (the in-place scale)");
+    HIP_TRY(hipSetDevice(device));
+    // 16 bytes per lane where both vectors are aligned at the same elements; otherwise every element goes the scalar way
+    size_t head = std::min<size_t>(n, (size_t)((16 - ((uintptr_t)dst & 15)) & 15) / 4);
+    if (((uintptr_t)(dst + head) & 15) || ((uintptr_t)(src + head) & 15)) head = n;
+    const size_t nvec = (n - head) / 4;
+    const dim3 grid((unsigned)std::max<size_t>(1, std::min<size_t>((std::max(nvec, n - 4 * nvec) + 255) / 256, 2048))), block(256);
+    hipLaunchKernelGGL(k_grad_accumulate, grid, block, 0, (hipStream_t)stream, dst, src, n, head, nvec, scale, overwrite ? 1 : 0);
+    LAUNCH_CHECK();
+    return COCR_OK;
+}
+
+// The norm's scratch, one per device, allocated on the first call there and kept for the life of the process: the chunk sums and the
+// result on the device, the result's pinned host twin.  One call at a time per device holds it from its launches to its wait.
+#define COCR_NORM_DEVICES 64
+struct NormScratch { double *dev = nullptr, *host = nullptr; std::mutex mu; };
+static NormScratch g_norm[COCR_NORM_DEVICES];
+
+extern "C" int cocr_grad_norm(const float *g, size_t n, int device, double *norm_out, void *stream) {
+    if (!norm_out) return fail(COCR_EINVAL, "null argument");
+    if (n == 0) { *norm_out = 0.0; return COCR_OK; }
+    if (!g) return fail(COCR_EINVAL, "null argument");
+    if ((uintptr_t)g & 3) return fail(COCR_EINVAL, "the vector is not aligned to a float");
+    if (device < 0 || device >= COCR_NORM_DEVICES) return fail(COCR_EINVAL, "device %d out of range", device);
+    HIP_TRY(hipSetDevice(device));
+    NormScratch &sc = g_norm[device];
+    std::lock_guard<std::mutex> lock(sc.mu);
+    if (!sc.dev) HIP_TRY(hipMalloc((void **)&sc.dev, (COCR_NORM_MAX_CHUNKS + 1) * sizeof(double)));
+    if (!sc.host) HIP_TRY(hipHostMalloc((void **)&sc.host, sizeof(double)));
+    // the chunk length depends on n only: a multiple of 4 floats, at least 4096, at most COCR_NORM_MAX_CHUNKS chunks
+    const size_t len = std::max<size_t>(4096, ((n + COCR_NORM_MAX_CHUNKS - 1) / COCR_NORM_MAX_CHUNKS + 3) / 4 * 4);
+    const int nchunk = (int)((n + len - 1) / len);
+    hipStream_t s = (hipStream_t)stream;
+    hipLaunchKernelGGL(k_sumsq_chunks, dim3(nchunk), dim3(256), 0, s, g, n, len, ((uintptr_t)g & 15) == 0 ? 1 : 0, sc.dev);
+    hipLaunchKernelGGL(k_sumsq_finish, dim3(1), dim3(256), 0, s, (const double *)sc.dev, nchunk, sc.dev + COCR_NORM_MAX_CHUNKS);
+    LAUNCH_CHECK();
+    HIP_TRY(hipMemcpyAsync(sc.host, sc.dev + COCR_NORM_MAX_CHUNKS, sizeof(double), hipMemcpyDeviceToHost, s));
+    HIP_TRY(hipStreamSynchronize(s));
+    *norm_out = *sc.host;
+    return COCR_OK;
 }
 
 // What a step on the output layer's own state (fp32 master copy [W | b], slot 0, slot 1: created on the first call; the frozen-backbone

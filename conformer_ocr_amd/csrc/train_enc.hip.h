@@ -1001,7 +1001,8 @@ __global__ static void k_adamw_flat_ranges(float *__restrict__ p, const float *_
 // momentum on.  Elements [head, head + 4 nvec) go 16 bytes per lane on all four vectors (the host picks `head` so that they are
 // aligned there, or head = n when the vectors' alignments differ); the few before and after go one by one.
 // serve_b / serve_f (either may be null): the value the serving forward reads (bf16 / fp32 copy of the output layer).
-struct OptimArgs { float lr, wd, b1, b2, eps, mu, alpha, bc1, bc2; };
+// gs (cocr_train_optim_step_ex's grad_scale): every gradient element enters the step as fl(gs g), rounded on its own; 1.0f leaves every float as it is.
+struct OptimArgs { float lr, wd, b1, b2, eps, mu, alpha, bc1, bc2, gs; };
 
 // Which products the compiler fuses into the following sum is its choice per kernel, and it chooses differently for the 16-byte form of
 // a loop than for the scalar one.  So this function takes no such choice: contraction is off, every operation is rounded on its own, and the
@@ -1009,8 +1010,9 @@ struct OptimArgs { float lr, wd, b1, b2, eps, mu, alpha, bc1, bc2; };
 // products and the final difference are not fused there).  That is what makes the AdamW instance equal cocr_train_adamw bit for bit
 // (tests/test_hip_optim.py holds the two against each other), and a vector lane equal the scalar path for every kind.
 template <int KIND, bool FLAG>
-__device__ __forceinline__ void optim_elem(float &p, const float g, float &s0, float &s1, const OptimArgs &a, const float c1, const float c2) {
+__device__ __forceinline__ void optim_elem(float &p, const float g_in, float &s0, float &s1, const OptimArgs &a, const float c1, const float c2) {
 #pragma clang fp contract(off)
+    const float g = a.gs * g_in;
     if constexpr (KIND == COCR_OPT_ADAMW) {
         float w = p * __builtin_fmaf(-a.lr, a.wd, 1.0f);
         const float gi = g, mi = __builtin_fmaf(1.0f - a.b1, gi, a.b1 * s0), vi = gi * ((1.0f - a.b2) * gi) + a.b2 * s1;
@@ -1088,6 +1090,76 @@ __global__ __launch_bounds__(256) static void k_optim_flat(float *__restrict__ P
         if constexpr (use1) S1[i] = s1e;
         if (serve_b) serve_b[i] = from_f32<bf16_t>(pe);
         if (serve_f) serve_f[i] = pe;
+    }
+}
+
+// ---- the gradient window on flat vectors (cocr_grad_accumulate / cocr_grad_norm) ---------------------------------------------------------------
+// dst[i] = overwrite ? fl(scale src[i]) : fl(dst[i] + fl(scale src[i])): two fp32 operations, each rounded on its own (contraction off, as in
+// optim_elem), which is torch's acc.add_(g * s) bit for bit.  dst may be src (overwrite: the in-place scale), so neither pointer is
+// __restrict__ and every element is read before it is written by the lane that owns it.  Elements [head, head + 4 nvec) go 16 bytes per
+// lane (the host picks `head` so that both vectors are aligned there, or head = n when their alignments differ); the rest one by one.
+__device__ __forceinline__ float accum_elem(const float d, const float s, const float scale, const bool overwrite) {
+#pragma clang fp contract(off)
+    const float t = scale * s;
+    return overwrite ? t : d + t;
+}
+__global__ __launch_bounds__(256) static void k_grad_accumulate(float *dst, const float *src, size_t n, size_t head, size_t nvec, float scale, int overwrite) {
+    const size_t tid = (size_t)blockIdx.x * blockDim.x + threadIdx.x, nthr = (size_t)gridDim.x * blockDim.x;
+    for (size_t q = tid; q < nvec; q += nthr) {
+        const size_t i = head + 4 * q;
+        const f32x4 s = *reinterpret_cast<const f32x4 *>(src + i);
+        f32x4 d = {0.f, 0.f, 0.f, 0.f};
+        if (!overwrite) d = *reinterpret_cast<const f32x4 *>(dst + i);
+#pragma unroll
+        for (int e = 0; e < 4; ++e) d[e] = accum_elem(d[e], s[e], scale, overwrite != 0);
+        *reinterpret_cast<f32x4 *>(dst + i) = d;
+    }
+    const size_t nscal = n - 4 * nvec;
+    for (size_t j = tid; j < nscal; j += nthr) {
+        const size_t i = j < head ? j : j + 4 * nvec;
+        dst[i] = accum_elem(overwrite ? 0.f : dst[i], src[i], scale, overwrite != 0);
+    }
+}
+
+// Sum of squares in double, stage one: chunk c of `nchunk` owns the elements [c len, min(n, (c + 1) len)), len a multiple of 4 that depends
+// on n only.  Within a chunk, group q (4 consecutive elements) belongs to thread q % 256; a thread adds its elements' squares in index
+// order (an fp32 x fp32 product is exact in double, so fusing it into the sum changes nothing), then the 256 thread sums are folded by a
+// fixed LDS tree.  Which element is added where depends on its index alone: a pointer that is not 16-byte aligned (vec = 0) loads the
+// same groups one float at a time.  No atomics; the chunk sums go to part[c].
+#define COCR_NORM_MAX_CHUNKS 1024
+__global__ __launch_bounds__(256) static void k_sumsq_chunks(const float *__restrict__ g, size_t n, size_t len, int vec, double *__restrict__ part) {
+    __shared__ double red[256];
+    const size_t lo = (size_t)blockIdx.x * len, hi = lo + len < n ? lo + len : n;
+    double acc = 0.0;
+    for (size_t i = lo + 4 * (size_t)threadIdx.x; i < hi; i += 4 * 256) {
+        if (i + 4 <= hi) {
+            float x[4];
+            if (vec) { const f32x4 v = *reinterpret_cast<const f32x4 *>(g + i); x[0] = v[0]; x[1] = v[1]; x[2] = v[2]; x[3] = v[3]; }
+            else { x[0] = g[i]; x[1] = g[i + 1]; x[2] = g[i + 2]; x[3] = g[i + 3]; }
+#pragma unroll
+            for (int e = 0; e < 4; ++e) acc += (double)x[e] * (double)x[e];
+        } else {
+            for (size_t j = i; j < hi; ++j) acc += (double)g[j] * (double)g[j];
+        }
+    }
+    red[threadIdx.x] = acc;
+    __syncthreads();
+    for (int w = 128; w > 0; w >>= 1) {
+        if ((int)threadIdx.x < w) red[threadIdx.x] += red[threadIdx.x + w];
+        __syncthreads();
+    }
+    if (threadIdx.x == 0) part[blockIdx.x] = red[0];
+}
+// stage two: the chunk sums in index order, the square root, one double (one workgroup; the sums come through LDS so that the serial
+// additions do not each wait for memory)
+__global__ __launch_bounds__(256) static void k_sumsq_finish(const double *__restrict__ part, int nchunk, double *__restrict__ out) {
+    __shared__ double s[COCR_NORM_MAX_CHUNKS];
+    for (int i = threadIdx.x; i < nchunk; i += 256) s[i] = part[i];
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        double t = 0.0;
+        for (int i = 0; i < nchunk; ++i) t += s[i];
+        *out = sqrt(t);
     }
 }
 

@@ -515,13 +515,47 @@ class HipRecognizer:
         return self._device_view(p.value, n.value)
 
     def train_optim_step(self, kind: str, lr: float, weight_decay: float = 0.0, betas=(0.9, 0.999), eps: float = 1e-8, momentum: float = 0.0,
-                         alpha: float = 0.99) -> None:
+                         alpha: float = 0.99, grad: Optional[torch.Tensor] = None, grad_scale: float = 1.0) -> None:
         """One step of torch.optim.{AdamW, Adam, SGD, RMSprop} (`kind`) on all parameters with the gradients of the last `train_step`;
         betas / eps reach the Adam kinds, momentum SGD and RMSprop, alpha / eps RMSprop (defaults are torch's).  The first step
-        fixes the kind: another kind afterwards raises."""
+        fixes the kind: another kind afterwards raises.  grad: another gradient vector in `train_grad_buffer()`'s layout (an
+        accumulation window); grad_scale: every gradient element enters the step as fl(grad_scale * g) (the clip coefficient)."""
         o = self._optim(kind, lr, weight_decay, betas, eps, momentum, alpha)
+        if grad is None and float(grad_scale) == 1.0:
+            with torch.cuda.device(self.device):
+                _lib.check(self.lib.cocr_train_optim_step(self._h, C.byref(o), _stream_ptr(self.device)))
+            return
+        if grad is not None:
+            self._check_flat(grad)
+            if grad.numel() != self.train_grad_buffer().numel():
+                raise ValueError(f'grad has {grad.numel()} floats, the gradient vector {self.train_grad_buffer().numel()}')
         with torch.cuda.device(self.device):
-            _lib.check(self.lib.cocr_train_optim_step(self._h, C.byref(o), _stream_ptr(self.device)))
+            _lib.check(self.lib.cocr_train_optim_step_ex(self._h, C.byref(o), C.c_void_p(grad.data_ptr()) if grad is not None else None,
+                                                         float(grad_scale), _stream_ptr(self.device)))
+
+    # ---- the gradient window on flat vectors (include/cocr.h: cocr_grad_accumulate / cocr_grad_norm) ------
+    def _check_flat(self, t: torch.Tensor) -> None:
+        if t.device != self.device or t.dtype != torch.float32 or t.dim() != 1 or not t.is_contiguous():
+            raise RuntimeError('expected a contiguous float32 vector on the model device')
+
+    def grad_accumulate(self, dst: torch.Tensor, src: torch.Tensor, scale: float, overwrite: bool = False) -> None:
+        """dst += fl(scale * src), or dst = fl(scale * src) with `overwrite` (then dst may be src: the in-place scale); float32 vectors
+        of one length on this device, stream-ordered.  Bit for bit torch's `dst.add_(src * scale)`."""
+        self._check_flat(dst)
+        self._check_flat(src)
+        if dst.numel() != src.numel():
+            raise ValueError(f'dst has {dst.numel()} floats, src {src.numel()}')
+        with torch.cuda.device(self.device):
+            _lib.check(self.lib.cocr_grad_accumulate(C.c_void_p(dst.data_ptr()), C.c_void_p(src.data_ptr()), dst.numel(), float(scale), int(bool(overwrite)),
+                                                     self.device.index or 0, _stream_ptr(self.device)))
+
+    def grad_norm(self, t: torch.Tensor) -> float:
+        """The L2 norm of a float32 vector on this device, squares and sums in double, the same bits on every call; waits for the stream."""
+        self._check_flat(t)
+        out = C.c_double()
+        with torch.cuda.device(self.device):
+            _lib.check(self.lib.cocr_grad_norm(C.c_void_p(t.data_ptr()), t.numel(), self.device.index or 0, C.byref(out), _stream_ptr(self.device)))
+        return float(out.value)
 
     def train_optim_state(self) -> Dict:
         """The whole-network optimizer state: {'kind': name or None before the first step, 'step', 'dec_steps', 'slot0', 'slot1'}; the

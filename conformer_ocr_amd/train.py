@@ -92,6 +92,31 @@ def reduce_gradients(tensors, group=None) -> None:
         off += t.numel()
 
 
+def clip_coef(norm: float, max_norm: float) -> float:
+    """The factor `torch.nn.utils.clip_grad_norm_(max_norm)` applies to a gradient of L2 norm `norm`, computed in float32 like torch's:
+    min(1, f32(max_norm) / (f32(norm) + f32(1e-6)))."""
+    import numpy as np
+    with np.errstate(over='ignore', invalid='ignore'):
+        c = np.float32(max_norm) / (np.float32(norm) + np.float32(1e-6))
+        return float(np.minimum(np.float32(1.0), c))                                                # (a NaN norm gives NaN, as torch's clamp does)
+
+
+# what a state written before the gradient window existed lacks, with the values that describe such a run
+WINDOW_HYPER = {'accumulate_grad_batches': 1, 'gradient_clip_val': None, 'skip_nonfinite': False}
+
+
+def upgrade_state(sd: Dict) -> Dict:
+    """`sd` (a `Trainer.state_dict()`, or the tensors and records of a state file) with the keys of the gradient window filled in where
+    an older writer left them out: the three arguments at their defaults, no skipped step, no open window, and -- every call having
+    been an optimizer step -- batches_seen = global_step, frozen_batches = frozen_steps.  `sd` itself is not changed."""
+    out = dict(sd)
+    out['hyper'] = dict(WINDOW_HYPER, **sd['hyper'])
+    c = sd['counters']
+    out['counters'] = dict({'batches_seen': c['global_step'], 'frozen_batches': c['frozen_steps'], 'skipped_steps': 0, '_window': 0,
+                            '_window_frozen': False}, **c)
+    return out
+
+
 class Trainer:
     """Training of the WHOLE network on the GPU: the reference's `training_step` + `configure_optimizers` + `optimizer_step` /
     `lr_scheduler_step` (reference conformer_ocr/model.py:147-152,238-321) behind one object.
@@ -119,7 +144,24 @@ class Trainer:
     on across both phases.  The frozen step and the hand-over work for every optimizer kind.
 
     `state_dict()` / `load_state_dict()` hold everything a step or an epoch end reads: `fit(save_state=True)` writes
-    them to a file, `fit(resume=...)` continues from one."""
+    them to a file, `fit(resume=...)` continues from one.
+
+    The gradient window (the names are Lightning's, under whose `Trainer` the reference trains).  With all three at
+    their defaults the step launches what it always launched: no norm, no extra wait.
+    `accumulate_grad_batches` = k > 1: `training_step` is still called once per batch and returns that batch's loss; each call adds
+    fl(1/k) g (1/k in float32) to an accumulation vector A, the k-th call takes the optimizer step on A and zeroes it.  `flush()` takes
+    the step on an incomplete window, still at 1/k (as Lightning steps on an epoch's last batch); `end_epoch` and `fit` call it.  This
+    is NOT one k-times larger batch: BatchNorm takes and updates its statistics per call, as torch does under accumulation.
+    `global_step`, the warm-up and `lr` count optimizer steps, `samples_seen` lines per call, `batches_seen` calls (the dropout seed
+    is seed * 1000003 + batches_seen).  Whether a window is frozen is decided at its start: the hand-over never splits one.  Data
+    parallel: ONE all-reduce per optimizer step, on A; every rank then holds the same bits, hence the same norm, coefficient and skip.
+    `gradient_clip_val`: the vector the step uses (A, or the gradient vector when k = 1; after the all-reduce) is clipped to that global
+    L2 norm: its norm is taken in double on the device (`last_grad_norm`; None while no norm is taken), `clip_coef` of it scales
+    every element on its way into the optimizer kernel (the frozen phase: in place, before its own step).
+    `skip_nonfinite`: a window whose norm is not finite takes no optimizer step -- no parameter, slot, step count or `global_step`
+    moves, A is zeroed, `skipped_steps` counts it, `log` gets a line.  Without it, with clipping on, such a window raises
+    FloatingPointError (the window is dropped, nothing else moves): a NaN coefficient never reaches the kernel.  With neither, the
+    gradient is used as it is."""
 
     SCHEDULES = ('constant', 'exponential', 'cosine', 'step', 'reduceonplateau')
 
@@ -127,9 +169,14 @@ class Trainer:
                  schedule: str = 'constant', gamma: float = 0.1, cos_t_max: int = 50, cos_min_lr: float = 1e-4, step_size: int = 10,
                  rop_factor: float = 0.1, rop_patience: int = 5, completed_epochs: int = 0, seed: int = 0, process_group=None,
                  distributed: Optional[bool] = None, matmul_precision: str = 'highest', freeze_backbone: int = 0, log=None,
-                 momentum: float = 0.9):
+                 momentum: float = 0.9, accumulate_grad_batches: int = 1, gradient_clip_val: Optional[float] = None,
+                 skip_nonfinite: bool = False):
         if optimizer not in OPTIMIZERS:
             raise ValueError(f'unknown optimizer {optimizer!r}: one of {", ".join(OPTIMIZERS)}')
+        if int(accumulate_grad_batches) < 1:
+            raise ValueError(f'accumulate_grad_batches must be at least 1, not {accumulate_grad_batches}')
+        if gradient_clip_val is not None and not float(gradient_clip_val) > 0.0:
+            raise ValueError(f'gradient_clip_val must be positive, not {gradient_clip_val}')
         if schedule not in self.SCHEDULES:
             raise ValueError(f'Unsupported learning rate scheduler {schedule}.')                      # model.py:309
         if not float(momentum) >= 0.0:
@@ -147,6 +194,14 @@ class Trainer:
         self.global_step = 0
         self.freeze_backbone, self.samples_seen, self.frozen_steps = int(freeze_backbone), 0, 0
         self._adopted = False                  # the frozen phase's output layer has moved into the whole-network state
+        self.accumulate_grad_batches = int(accumulate_grad_batches)
+        self.gradient_clip_val = None if gradient_clip_val is None else float(gradient_clip_val)
+        self.skip_nonfinite = bool(skip_nonfinite)
+        self.batches_seen, self.frozen_batches, self.skipped_steps = 0, 0, 0       # calls; calls of frozen windows; windows without a step
+        self._window, self._window_frozen = 0, False                                # calls in the open window; whether it is a frozen one
+        self._accum: Optional[torch.Tensor] = None                                  # A: the open window's accumulated gradient (k > 1)
+        self._pending = None                                                        # k = 1: the call's own gradient on its way to the step
+        self.last_grad_norm: Optional[float] = None
         self.log = log
         self.seed = int(seed)
         self.process_group = process_group
@@ -176,20 +231,6 @@ class Trainer:
         """Whether the next step is the frozen step."""
         return self.samples_seen < self.freeze_backbone
 
-    def _frozen_step(self, batch: Dict) -> float:
-        """`DecoderTrainer.training_step` at this Trainer's rate: only the output layer moves, on the serving engine."""
-        o = self.net.step(dict(batch, image=batch['image'].to(self.engine.device)), with_grad=True)
-        eng = self.net._engine
-        gw, gb, _ = eng.decoder_backward(o['grad_probits'])
-        if self.distributed:
-            reduce_gradients((gw, gb), self.process_group)
-        if self.optimizer == 'AdamW':
-            eng.decoder_adamw(gw, gb, self.lr, weight_decay=self.weight_decay)
-        else:
-            eng.decoder_optim_step(self.optimizer, gw, gb, self.lr, weight_decay=self.weight_decay, momentum=_momentum_of(self.optimizer, self.momentum))
-        self.frozen_steps += 1
-        return float(o['loss'])
-
     def _unfreeze(self) -> None:
         """The hand-over: the serving engine's output layer (fp32 master copy, moments, step count) into the whole-network state."""
         self.engine.train_adopt_decoder(self.net._engine)
@@ -197,33 +238,127 @@ class Trainer:
         if self.log is not None:
             self.log(f'backbone unfrozen after {self.samples_seen} samples ({self.frozen_steps} steps): training the whole network')
 
+    @property
+    def _norm_wanted(self) -> bool:
+        return self.gradient_clip_val is not None or self.skip_nonfinite
+
+    def _accumulate(self, parts) -> None:
+        """A += fl(1/k) g for the flat gradient pieces `parts`, which lie one behind the other in A."""
+        import numpy as np
+        n = sum(p.numel() for p in parts)
+        if self._accum is None or self._accum.numel() != n:
+            self._accum = torch.zeros(n, dtype=torch.float32, device=self.engine.device)
+        inv_k, off = float(np.float32(1.0) / np.float32(self.accumulate_grad_batches)), 0
+        for p in parts:
+            self.engine.grad_accumulate(self._accum[off:off + p.numel()], p, inv_k)
+            off += p.numel()
+
     def training_step(self, batch: Dict) -> float:
-        """One optimizer step on `batch`; returns the batch's summed CTC loss (this rank's lines)."""
+        """One call of the step on `batch`: its gradient joins the open window, and the call that completes the window takes the
+        optimizer step (every call, at accumulate_grad_batches = 1); returns the batch's summed CTC loss (this rank's lines)."""
         image = batch['image']
         if image.dim() != 4 or image.shape[1] != 1:
             raise ValueError(f'expected a (N,1,H,W) line batch, got {tuple(image.shape)}')
-        if self.frozen:                                   # (tested at the start of a step: a batch is never split)
-            self.samples_seen += int(image.shape[0])
-            loss = self._frozen_step(batch)
-            self._after_step()
-            return loss
-        if self.frozen_steps and not self._adopted:
-            self._unfreeze()
+        if self._window == 0:                             # (decided at the start of a window: neither a batch nor a window is split)
+            self._window_frozen = self.frozen
+            if not self._window_frozen and self.frozen_steps and not self._adopted:
+                self._unfreeze()
         self.samples_seen += int(image.shape[0])
-        x = image.squeeze(1).to(self.engine.device)
-        loss = self.engine.train_step(x, torch.as_tensor(batch['seq_lens']).cpu().numpy(), torch.as_tensor(batch['target']).cpu().numpy(),
-                                      torch.as_tensor(batch['target_lens']).cpu().numpy(), dropout=self.net.dropout_p,
-                                      seed=self.seed * 1000003 + self.global_step)
-        if self.distributed:
-            g = self.engine.train_grad_buffer()
-            torch.distributed.all_reduce(g, op=torch.distributed.ReduceOp.SUM, group=self.process_group)
-            g.div_(torch.distributed.get_world_size(self.process_group))
-        if self.optimizer == 'AdamW':
-            self.engine.train_adamw(self.lr, weight_decay=self.weight_decay)
+        k = self.accumulate_grad_batches
+        if self._window_frozen:
+            # `DecoderTrainer.training_step` at this Trainer's rate: only the output layer moves, on the serving engine
+            o = self.net.step(dict(batch, image=image.to(self.engine.device)), with_grad=True)
+            gw, gb, _ = self.net._engine.decoder_backward(o['grad_probits'])
+            loss = float(o['loss'])
+            self.frozen_batches += 1
+            if k > 1:
+                self._accumulate((gw.reshape(-1), gb))
+            else:
+                self._pending = (gw, gb)
         else:
-            self.engine.train_optim_step(self.optimizer, self.lr, weight_decay=self.weight_decay, momentum=_momentum_of(self.optimizer, self.momentum))
-        self._after_step()
+            x = image.squeeze(1).to(self.engine.device)
+            loss = self.engine.train_step(x, torch.as_tensor(batch['seq_lens']).cpu().numpy(), torch.as_tensor(batch['target']).cpu().numpy(),
+                                          torch.as_tensor(batch['target_lens']).cpu().numpy(), dropout=self.net.dropout_p,
+                                          seed=self.seed * 1000003 + self.batches_seen)
+            if k > 1:
+                self._accumulate((self.engine.train_grad_buffer(),))
+        self.batches_seen += 1
+        self._window += 1
+        if self._window >= k:
+            self._optimizer_step()
         return loss
+
+    def flush(self) -> None:
+        """The optimizer step on an incomplete window (its gradients still scaled by 1/k); nothing on an empty one."""
+        if self._window:
+            self._optimizer_step()
+
+    def _close_window(self) -> None:
+        if self._accum is not None:
+            self._accum.zero_()
+        self._window, self._pending = 0, None
+
+    def _optimizer_step(self) -> None:
+        """All-reduce, norm, clip or skip, and the optimizer step on the open window's gradient; closes the window."""
+        k, frozen = self.accumulate_grad_batches, self._window_frozen
+        eng = self.net._engine if frozen else self.engine
+        # ---- the vector the step uses, averaged over the ranks by one collective
+        if k > 1:
+            vec = self._accum
+            if self.distributed:
+                torch.distributed.all_reduce(vec, op=torch.distributed.ReduceOp.SUM, group=self.process_group)
+                vec.div_(torch.distributed.get_world_size(self.process_group))
+        elif frozen:
+            gw, gb = self._pending
+            if self.distributed:
+                reduce_gradients((gw, gb), self.process_group)
+            vec = torch.cat([gw.reshape(-1), gb]) if self._norm_wanted else None
+        else:
+            vec = self.engine.train_grad_buffer()
+            if self.distributed:
+                torch.distributed.all_reduce(vec, op=torch.distributed.ReduceOp.SUM, group=self.process_group)
+                vec.div_(torch.distributed.get_world_size(self.process_group))
+        # ---- norm, skip, coefficient
+        coef = 1.0
+        self.last_grad_norm = None
+        if self._norm_wanted:
+            import math
+            norm = self.last_grad_norm = self.engine.grad_norm(vec)
+            if not math.isfinite(norm):
+                self._close_window()
+                if not self.skip_nonfinite:
+                    raise FloatingPointError(f'the gradient norm of optimizer step {self.global_step} is {norm}: no step was taken '
+                                             '(skip_nonfinite=True skips such a window instead)')
+                self.skipped_steps += 1
+                if self.log is not None:
+                    self.log(f'optimizer step {self.global_step} skipped: the gradient norm is {norm} ({self.skipped_steps} skipped so far)')
+                return
+            if self.gradient_clip_val is not None:
+                coef = clip_coef(norm, self.gradient_clip_val)
+        # ---- the step
+        mom = _momentum_of(self.optimizer, self.momentum)
+        if frozen:
+            if vec is not None:
+                if coef != 1.0:
+                    eng.grad_accumulate(vec, vec, coef, overwrite=True)               # (ncls x D floats: the extra pass costs nothing)
+                nw = eng.hp.num_classes * eng.hp.encoder_dim
+                gw, gb = vec[:nw].view(eng.hp.num_classes, eng.hp.encoder_dim), vec[nw:]
+            if self.optimizer == 'AdamW':
+                eng.decoder_adamw(gw, gb, self.lr, weight_decay=self.weight_decay)
+            else:
+                eng.decoder_optim_step(self.optimizer, gw, gb, self.lr, weight_decay=self.weight_decay, momentum=mom)
+            self.frozen_steps += 1
+        elif k == 1 and coef == 1.0:
+            if self.optimizer == 'AdamW':
+                self.engine.train_adamw(self.lr, weight_decay=self.weight_decay)
+            else:
+                self.engine.train_optim_step(self.optimizer, self.lr, weight_decay=self.weight_decay, momentum=mom)
+        else:
+            # (AdamW through the general kernel: bit for bit cocr_train_adamw's step, with the scale fused in)
+            self.engine.train_optim_step(self.optimizer, self.lr, weight_decay=self.weight_decay, momentum=mom, grad=vec if k > 1 else None,
+                                         grad_scale=coef)
+        self._close_window()
+        self._after_step()
 
     def _after_step(self) -> None:
         if self.warmup and self.global_step < self.warmup:                                            # model.py:246-252
@@ -234,7 +369,8 @@ class Trainer:
 
     def end_epoch(self, metric: Optional[float] = None) -> float:
         """Epoch-wise scheduler step (model.py:254-265; not during warm-up); `metric` (validation accuracy, larger is better) drives
-        'reduceonplateau'.  Returns the learning rate of the next epoch."""
+        'reduceonplateau'.  Returns the learning rate of the next epoch.  An open accumulation window takes its step first."""
+        self.flush()
         self.epoch += 1
         if self.warmup and self.global_step < self.warmup:
             return self.lr
@@ -267,20 +403,22 @@ class Trainer:
         with torch.no_grad():
             for k, v in sd.items():
                 if k.endswith('num_batches_tracked'):
-                    v.add_(self.global_step - self.frozen_steps - int(v))                              # (train-mode forwards only)
+                    v.add_(self.batches_seen - self.frozen_batches - int(v))                           # (train-mode forwards only)
                     continue
                 v.copy_(torch.from_numpy(self.engine.train_value(k)).to(v.device).reshape(v.shape))
 
     # ---- everything a step or an epoch end reads, out and back in ------------------------------------------------
     HYPER = ('base_lr', 'weight_decay', 'optimizer', 'momentum', 'warmup', 'schedule', 'gamma', 'cos_t_max', 'cos_min_lr', 'step_size',
-             'rop_factor', 'rop_patience', 'seed', 'matmul_precision', 'freeze_backbone')
-    COUNTERS = ('epoch', 'global_step', 'samples_seen', 'frozen_steps', '_adopted', 'lr', '_sched_lr', '_best', '_bad')
+             'rop_factor', 'rop_patience', 'seed', 'matmul_precision', 'freeze_backbone', 'accumulate_grad_batches', 'gradient_clip_val',
+             'skip_nonfinite')
+    COUNTERS = ('epoch', 'global_step', 'samples_seen', 'frozen_steps', '_adopted', 'lr', '_sched_lr', '_best', '_bad', 'batches_seen',
+                'frozen_batches', 'skipped_steps', '_window', '_window_frozen')
 
     def state_dict(self) -> Dict:
         """{'values': the flat value vector (parameters, then BatchNorm statistics), 'slot0', 'slot1': the optimizer's two state vectors
         (device copies), 'optim': {kind, step, dec_steps}, 'counters', 'hyper'} and, while the frozen phase's output layer has not moved
         into the whole-network state, 'decoder_state' ([master | slot 0 | slot 1] of the serving engine) with 'decoder_optim'
-        {kind, step}."""
+        {kind, step}.  While an accumulation window is open (counters['_window'] calls in): 'accum', the vector A."""
         st = self.engine.train_optim_state()
         out = {'values': self.engine.train_value_buffer().clone(), 'slot0': st['slot0'].clone(), 'slot1': st['slot1'].clone(),
                'optim': {'kind': st['kind'], 'step': st['step'], 'dec_steps': st['dec_steps']},
@@ -289,10 +427,14 @@ class Trainer:
             d = self.net._engine.decoder_optim_state()
             out['decoder_state'] = d['state'].clone()
             out['decoder_optim'] = {'kind': d['kind'], 'step': d['step']}
+        if self._window and self.accumulate_grad_batches > 1:
+            out['accum'] = self._accum.clone()
         return out
 
     def load_state_dict(self, sd: Dict) -> None:
-        """Puts a `state_dict()` back into this trainer, its engine and `net.nn`; the model layout must be the one it was taken from."""
+        """Puts a `state_dict()` back into this trainer, its engine and `net.nn`; the model layout must be the one it was taken from.
+        A state from before the gradient window loads as `upgrade_state` describes."""
+        sd = upgrade_state(sd)
         values, st = self.engine.train_value_buffer(), self.engine.train_optim_state()
         for name, have in (('values', values), ('slot0', st['slot0']), ('slot1', st['slot1'])):
             if tuple(sd[name].shape) != tuple(have.shape):
@@ -305,6 +447,11 @@ class Trainer:
         st['slot0'].copy_(sd['slot0'].to(values.device))
         st['slot1'].copy_(sd['slot1'].to(values.device))
         self.engine.train_optim_restore(sd['optim']['kind'], sd['optim']['step'], sd['optim']['dec_steps'])
+        self._accum, self._pending, self.last_grad_norm = None, None, None
+        if self._window:
+            if self.accumulate_grad_batches < 2 or 'accum' not in sd:
+                raise ValueError('the state has an open accumulation window but no accumulated gradient')
+            self._accum = sd['accum'].to(values.device, torch.float32).contiguous().clone()
         self._sync_all()
         if 'decoder_state' in sd:
             # still in (or just out of) the frozen phase: the output layer and its optimizer state live on the serving engine
@@ -315,7 +462,7 @@ class Trainer:
 
 
 # ---- the state file of `fit(save_state=True)` ---------------------------------------------------------------------------------------
-STATE_TENSORS = ('values', 'slot0', 'slot1', 'decoder_state')
+STATE_TENSORS = ('values', 'slot0', 'slot1', 'decoder_state', 'accum')
 FINGERPRINT = ('n_train', 'n_val', 'seed', 'batch_size', 'edge', 'augment', 'height', 'pad')
 
 
@@ -394,6 +541,7 @@ def _resume_fit(path: str, net, data, log, **trainer_kw):
                 raise ValueError(f'the model is not the one the state was written with: {k} is {have["hyper_params"].get(k)!r}, was {v!r}')
         if json.loads(json.dumps(have['codec'])) != meta['codec']:
             raise ValueError('the model is not the one the state was written with: the codecs differ')
+    meta['trainer'] = upgrade_state(meta['trainer'])
     hyper = dict(meta['trainer']['hyper'])
     hyper['lr'] = hyper.pop('base_lr')
     trainer = Trainer(net, log=log, **hyper, **trainer_kw)
@@ -434,10 +582,11 @@ def fit(net: Optional[PytorchRecognitionModel], data, trainer: Optional[Trainer]
         best_epoch, best_cer, bad, history = -1, None, 0, []
     dev = trainer.engine.device
     for epoch in range(first, int(epochs)):
-        t0, loss, lines = time.perf_counter(), 0.0, 0
+        t0, loss, lines, skipped0 = time.perf_counter(), 0.0, 0, trainer.skipped_steps
         for batch in data.batches(epoch):
             loss += trainer.training_step(batch)
             lines += int(batch['image'].shape[0])
+        trainer.flush()                                   # (an epoch's last window may be incomplete)
         torch.cuda.synchronize(dev)
         rate = lines / max(time.perf_counter() - t0, 1e-9)
         trainer.sync_module()
@@ -458,7 +607,9 @@ def fit(net: Optional[PytorchRecognitionModel], data, trainer: Optional[Trainer]
             _save_fit_state(f'{output}_state.safetensors', net, data, trainer,
                             {'best_epoch': best_epoch, 'best_cer': best_cer, 'bad': bad, 'history': [list(h) for h in history]})
         if log is not None:
-            log(f'epoch {epoch}: loss {loss:.4f}  {rate:.1f} lines/s  val CER {cer:.4f}{"  (best)" if improved else ""}')
+            skipped = trainer.skipped_steps - skipped0
+            log(f'epoch {epoch}: loss {loss:.4f}  {rate:.1f} lines/s  val CER {cer:.4f}{f"  {skipped} steps skipped" if skipped else ""}'
+                f'{"  (best)" if improved else ""}')
         if quit == 'early' and bad >= int(lag) and epoch + 1 >= int(min_epochs):
             break
     return {'best_epoch': best_epoch, 'best_cer': best_cer, 'history': history, 'net': net, 'trainer': trainer}
@@ -521,6 +672,9 @@ def build_parser():
                          'the output layer (union), or make the codec exactly the training alphabet (new)')
     ap.add_argument('--freeze-backbone', type=int, default=0, help='number of samples to keep the backbone (everything but last layer) frozen')
     ap.add_argument('-c', '--codec', default=None, help='JSON codec file {grapheme: [labels]} for a new model, instead of the training alphabet')
+    ap.add_argument('--accumulate', type=int, default=1, metavar='K', help='optimizer step on the gradients of K batches (accumulate_grad_batches)')
+    ap.add_argument('--clip-norm', type=float, default=None, metavar='X', help='clip the gradient to this global L2 norm (gradient_clip_val)')
+    ap.add_argument('--skip-nonfinite', action='store_true', help='take no optimizer step on a gradient whose norm is Inf or NaN')
     ap.add_argument('-o', '--output', default='model', help='prefix of the written models')
     ap.add_argument('--device', default='cuda:0')
     ap.add_argument('--seed', type=int, default=0)
@@ -543,6 +697,10 @@ def check_args(ap, args) -> None:
         ap.error('--freeze-backbone is a number of samples')
     if args.momentum < 0:
         ap.error('-m/--momentum must not be negative')
+    if args.accumulate < 1:
+        ap.error('--accumulate is a number of batches, at least 1')
+    if args.clip_norm is not None and not args.clip_norm > 0:
+        ap.error('--clip-norm must be positive')
     if args.resume:
         for flag, given in (('-i/--load', args.load), ('-c/--codec', args.codec), ('--resize', args.resize != 'fail')):
             if given:
@@ -618,7 +776,8 @@ def main(argv=None) -> int:
     trainer = Trainer(net, lr=args.lrate, weight_decay=args.weight_decay, optimizer=args.optimizer, momentum=args.momentum, warmup=args.warmup,
                       schedule=args.schedule, gamma=args.gamma, step_size=args.step_size, rop_patience=args.sched_patience,
                       cos_t_max=args.cos_max, cos_min_lr=args.cos_min_lr, seed=args.seed, matmul_precision=args.precision,
-                      freeze_backbone=args.freeze_backbone, log=print)
+                      freeze_backbone=args.freeze_backbone, log=print, accumulate_grad_batches=args.accumulate,
+                      gradient_clip_val=args.clip_norm, skip_nonfinite=args.skip_nonfinite)
     res = fit(net, data, trainer, epochs=args.epochs, quit=args.quit, min_epochs=args.min_epochs, lag=args.lag, output=args.output,
               save_state=args.save_state)
     return _report(res, args.output)

@@ -365,6 +365,28 @@ typedef struct { int kind; float lr, weight_decay, beta1, beta2, eps, momentum, 
 int cocr_train_optim_step(cocr_model *m, const cocr_optim *o, void *stream);
 int cocr_decoder_optim_step(cocr_model *m, const float *grad_weight, const float *grad_bias, const cocr_optim *o, void *stream);
 
+/* The gradient window: accumulation over several cocr_train_step calls, the global L2 norm, and the clipped step.
+ * The first two work on raw DEVICE vectors of floats (any float offset of an allocation) on `device` and belong to no model: they serve
+ * the whole-network gradient vector and the frozen phase's two small output-layer gradients alike.
+ * cocr_grad_accumulate: per element t = fl(scale src[i]), then dst[i] = overwrite ? t : fl(dst[i] + t) -- two fp32 operations, each
+ * rounded on its own, torch's acc.add_(g * s) bit for bit.  dst == src is legal with overwrite: the in-place scale.  16 bytes per lane
+ * where dst and src are aligned alike, one float at a time before, behind and otherwise.  Stream-ordered, no synchronisation, no
+ * allocation.
+ * cocr_grad_norm: *norm_out (HOST) = sqrt(sum g[i]^2), every square formed and every sum taken in double: partial sums over a number of
+ * contiguous chunks that depends on n only, added in index order by a second small kernel -- no atomics, so the result is a function of
+ * the values and n alone, the same bits on every call and at every alignment of g.  Relative error <= n 2^-53.  IEEE on non-finite
+ * input: an Inf gives +Inf, a NaN (with or without an Inf) NaN.  n = 0 gives 0 and launches nothing.  Squares of 1e30 or 1e-30 neither
+ * overflow nor vanish.  The result comes back through pinned host memory; the call SYNCHRONISES `stream`.  Its scratch (8 KB per device)
+ * is allocated on the first call on a device and kept.
+ * cocr_train_optim_step_ex: cocr_train_optim_step with the gradient read from `grad` (DEVICE, the layout of cocr_train_grad_buffer; NULL:
+ * the state's own vector) and every gradient element entering the step as fl(grad_scale g).  cocr_train_optim_step IS
+ * cocr_train_optim_step_ex(m, o, NULL, 1.0f, stream): fl(1.0f g) == g for every float, so it keeps its bits.  grad_scale must be finite
+ * and >= 0 (else COCR_EINVAL), with one exception: NaN is taken, because torch's clip makes a NaN coefficient of a NaN norm; the
+ * Python Trainer never passes one (it skips or refuses a window whose norm is not finite).  Stream-ordered, no synchronisation. */
+int cocr_grad_accumulate(float *dst, const float *src, size_t n, float scale, int overwrite, int device, void *stream);
+int cocr_grad_norm(const float *g, size_t n, int device, double *norm_out, void *stream);
+int cocr_train_optim_step_ex(cocr_model *m, const cocr_optim *o, const float *grad, float grad_scale, void *stream);
+
 /* The optimizer state out of the library and back, for continuing an interrupted fit.
  * cocr_train_optim_state: the kind (-1 before the first step), the step count, the steps an adopted output layer is ahead, and DEVICE
  * pointers to the two slots (*n_floats each: the layout of cocr_train_grad_buffer).  The caller copies them out; to restore it writes

@@ -8,7 +8,12 @@ with HIP events next to the whole step -- `cocr_train_optim_step` of that kind a
 bytes per second the median implies (4 n x (vectors read + vectors written), n = the parameter count).  --dec-steps N: the output layer
 N steps ahead on both engines (`train_optim_restore`), the per-tensor bias corrections as after a frozen phase.
 --fit K: K steps on text lines (conformer_ocr_amd.synth.make_text_lines) from random weights, printing the loss and the greedy CER of
-the trained model against the ground truth every few steps (the inference path serves the trained weights after sync)."""
+the trained model against the ground truth every few steps (the inference path serves the trained weights after sync).
+--accumulate K / --clip-norm X: the Trainer's gradient window (DESIGN.md section 7h).  --steps then counts optimizer steps (K calls each);
+`ms_per_step` stays the time per call, `ms_per_optimizer_step` is K times that.  With --clip-norm the norm call ALONE is timed on the
+gradient vector of the last real step, next to one optimizer step at the same n on an engine of its own, alternating: per call the span
+between two HIP events around it and the host's wall time from the call to the end of its wait (the norm call waits for its result
+by itself, the optimizer call is followed by a wait on the second event); median / least / largest of --optim-rounds x 5 calls."""
 import argparse
 import json
 import os
@@ -38,6 +43,8 @@ ap.add_argument('--momentum', type=float, default=0.9)
 ap.add_argument('--dec-steps', type=int, default=0)
 ap.add_argument('--optim-reps', type=int, default=50)
 ap.add_argument('--optim-rounds', type=int, default=9)
+ap.add_argument('--accumulate', type=int, default=1)
+ap.add_argument('--clip-norm', type=float, default=None)
 ap.add_argument('--matmul', default='highest', help="'highest' (exact fp32 products) or 'medium' (bf16-rounded operands, the reference's training setting)")
 args = ap.parse_args()
 kw = {'num_encoder_layers': args.layers} if args.layers else {}
@@ -50,16 +57,52 @@ net = net.to('cuda:0').eval()
 image, lens, texts, _ = synth.make_text_lines(args.batch, hp.height, args.width, seed=3)
 batch = {'image': torch.from_numpy(image).cuda(), 'seq_lens': torch.from_numpy(lens), 'target': torch.tensor([c for t in texts for c in t]),
          'target_lens': torch.tensor([len(t) for t in texts])}
-tr = Trainer(net, lr=args.lr, weight_decay=1e-2, warmup=10, matmul_precision=args.matmul, optimizer=args.optimizer or 'AdamW', momentum=args.momentum)
+tr = Trainer(net, lr=args.lr, weight_decay=1e-2, warmup=10, matmul_precision=args.matmul, optimizer=args.optimizer or 'AdamW', momentum=args.momentum,
+             **({'accumulate_grad_batches': args.accumulate, 'gradient_clip_val': args.clip_norm} if args.accumulate != 1 or args.clip_norm is not None else {}))
 out = {'config': args.config, 'layers': hp.num_encoder_layers, 'batch': args.batch, 'width': args.width}
-tr.training_step(batch)
+for _ in range(args.accumulate):
+    tr.training_step(batch)
 torch.cuda.synchronize()
 t0 = time.perf_counter()
-for _ in range(args.steps):
+for _ in range(args.steps * args.accumulate):
     loss = tr.training_step(batch)
 torch.cuda.synchronize()
-dt = (time.perf_counter() - t0) / args.steps
+dt = (time.perf_counter() - t0) / (args.steps * args.accumulate)
 out.update(ms_per_step=round(dt * 1e3, 2), lines_per_s=round(args.batch / dt, 1), last_loss=loss)
+if args.accumulate != 1 or args.clip_norm is not None:
+    out.update(accumulate=args.accumulate, clip_norm=args.clip_norm, ms_per_optimizer_step=round(dt * args.accumulate * 1e3, 2),
+               last_grad_norm=tr.last_grad_norm)
+if args.clip_norm is not None:
+    from conformer_ocr_amd.engine import HipRecognizer
+    side = HipRecognizer(hp, torch.device('cuda', 0), 'fp32')
+    side.load_state(state)
+    side.train_begin()
+    side.train_grad_buffer().copy_(tr.engine.train_grad_buffer())
+    kind = args.optimizer or 'AdamW'
+    g = tr.engine.train_grad_buffer()
+    calls = {'grad_norm': lambda: tr.engine.grad_norm(g),
+             f'train_optim_step[{kind}]': lambda: side.train_optim_step(kind, args.lr, weight_decay=1e-2, momentum=args.momentum if kind in ('SGD', 'RMSprop') else 0.0)}
+    spans = {k: ([], []) for k in calls}
+    for fn in calls.values():
+        for _ in range(5):
+            fn()
+    torch.cuda.synchronize()
+    for _ in range(args.optim_rounds * 5):
+        for name, fn in calls.items():
+            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            e0.record()
+            h0 = time.perf_counter()
+            fn()
+            e1.record()
+            e1.synchronize()
+            spans[name][1].append((time.perf_counter() - h0) * 1e6)
+            spans[name][0].append(e0.elapsed_time(e1) * 1e3)
+    rep = {'floats': g.numel()}
+    for name, (dev, host) in spans.items():
+        dev, host = sorted(dev), sorted(host)
+        rep[name] = {'event_us_median': round(dev[len(dev) // 2], 2), 'event_us_min': round(dev[0], 2), 'event_us_max': round(dev[-1], 2),
+                     'host_us_median': round(host[len(host) // 2], 2), 'host_us_min': round(host[0], 2), 'host_us_max': round(host[-1], 2)}
+    out['norm_alone'] = rep
 if args.optimizer:
     from conformer_ocr_amd.engine import HipRecognizer
 
