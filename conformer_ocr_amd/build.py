@@ -67,7 +67,7 @@ def _compile(args):
 
 
 def build(force: bool = False, verbose: bool = True, out: str = None) -> str:
-    """One object per translation unit (cocr_api.hip and the row-chain instantiation units), compiled in parallel, one link.
+    """One object per translation unit (the host layer's units, csrc/model.hip.h, and the row-chain instantiation units), compiled in parallel, one link.
     `out`: write the library there instead (dev experiments: COCR_HIPCC_FLAGS=-D... builds loaded through COCR_LIB_PATH)."""
     if out is not None:
         return _build_to(out, verbose)

@@ -57,7 +57,6 @@ __device__ __forceinline__ void mfma_results_fence(f32x4 (&a)[4], f32x4 (&b)[4],
 #define COCR_ATT_EXP 0          // dev: timing experiments (wrong results): 1 no shift through LDS, 2 no positional products, 4 no exponentials,
                                // 8 no P.V products, 16 tiles staged once, 32 no content products, 64 no barriers
 #endif
-#define COCR_POS_MAXLEN 5000        // the reference's RelPositionalEncoding(max_len): 2 * max_len - 1 table rows, row max_len - 1 <-> relative position 0
 
 // V^T fragment of one k-chunk (32 keys) for head-dim row tile d: element e of quad g <-> key 16 (e>>2) + 4g + (e&3)
 // (the same permutation the exponentiated scores have in their accumulator registers).

@@ -12,6 +12,9 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include <mutex>
+#include <set>
+
 typedef __attribute__((address_space(3))) void *lds_ptr_t;            // operands of __builtin_amdgcn_global_load_lds (LDS-DMA)
 typedef __attribute__((address_space(1))) const void *gbl_ptr_t;
 
@@ -89,3 +92,20 @@ __device__ __forceinline__ float wave_max(float v) {
 
 static inline int ceil_div(int a, int b) { return (a + b - 1) / b; }
 static inline int round_up(int a, int b) { return ceil_div(a, b) * b; }
+
+// limits the host layer checks against (cocr_create; weights.hip.h)
+#define COCR_LN_MAX_D 1024          // widest LayerNorm row (norm.hip.h: NV = ceil(D / 256) <= 4)
+#define COCR_POS_MAXLEN 5000        // the reference's RelPositionalEncoding(max_len): 2 * max_len - 1 table rows, row max_len - 1 <-> relative position 0
+
+// A launch with more than `above` bytes of dynamic LDS needs the kernel's limit raised first, to `limit` (a kernel with static LDS
+// of its own passes figures that leave room for it).  Models on several threads launch at once: the set is locked.
+static inline hipError_t raise_lds_limit(const void *kern, size_t lds, size_t above = 64 * 1024, int limit = 160 * 1024) {
+    if (lds <= above) return hipSuccess;
+    static std::mutex mu;
+    static std::set<const void *> raised;      // per kernel instantiation, once
+    std::lock_guard<std::mutex> lock(mu);
+    if (raised.count(kern)) return hipSuccess;
+    hipError_t e = hipFuncSetAttribute(kern, hipFuncAttributeMaxDynamicSharedMemorySize, limit);
+    if (e == hipSuccess) raised.insert(kern);
+    return e;
+}

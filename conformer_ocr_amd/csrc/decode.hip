@@ -1,0 +1,260 @@
+// What follows the forward behind the C ABI (units of the host layer: model.hip.h): the CTC decoders (greedy, beam, beam with an
+// n-gram model), the n-gram model itself, the CTC criterion and forced alignment.
+#include "model.hip.h"
+#include "ctc.hip.h"
+#include "ctc_lm.hip.h"
+#include "ctc_loss.hip.h"
+#include "ctc_align.hip.h"
+
+// ------------------------------------------------------------------------------------ CTC
+// The per-line lengths reach the decode kernels through a PINNED host ring: an async copy from pageable memory goes through the
+// runtime's staging buffers, and a third such copy in flight (three batches on three streams, each copy queued behind its
+// forward) blocked the host until the first forward had finished -- 5.5 ms per run start.  `d_lens`: the lengths on the device.
+static int upload_lens(cocr_model *m, const int32_t *lens, int N, hipStream_t s, const int32_t *&d_lens) {
+    int32_t *h, *d;
+    HIP_TRY(m->dec.lens_ring.stage((size_t)N * 4, h, d));
+    memcpy(h, lens, (size_t)N * 4);
+    HIP_TRY(m->dec.lens_ring.commit((size_t)N * 4, s));
+    d_lens = d;
+    return COCR_OK;
+}
+
+int ensure_ctc_scratch(cocr_model *m, size_t rows) {
+    if (rows <= m->dec.ctc_lab.n && rows <= m->dec.ctc_val.n) return COCR_OK;
+    HIP_TRY(hipDeviceSynchronize());                          // (captured launches that point at the old scratch are dropped with it)
+    m->graphs.drop();
+    m->dec.amax_logits = nullptr;
+    HIP_TRY(m->dec.ctc_lab.grow(rows));
+    HIP_TRY(m->dec.ctc_val.grow(rows));
+    return COCR_OK;
+}
+
+extern "C" int cocr_ctc_greedy(cocr_model *m, const float *logits, int N, int T, int ncls, const int32_t *out_lens, int32_t *labels,
+                               int32_t *starts, int32_t *ends, float *conf, int32_t *counts, int max_per_line, void *stream) {
+    if (!m || !logits || !out_lens || !labels || !starts || !ends || !conf || !counts) return fail(COCR_EINVAL, "null argument");
+    if (N < 1 || T < 1 || ncls < 1 || max_per_line < 1) return fail(COCR_EINVAL, "empty problem");
+    if (T > 8000) return fail(COCR_EUNSUPPORTED, "more than 8000 frames per line");
+    HIP_TRY(hipSetDevice(m->device));
+    hipStream_t s = (hipStream_t)stream;
+    const int32_t *d_lens;
+    int rc = upload_lens(m, out_lens, N, s, d_lens);
+    if (rc) return rc;
+    const bool have_argmax = logits == m->dec.amax_logits && N * T == m->dec.amax_rows && ncls == m->ncls;      // the decoder's epilogue computed it for these logits
+    if (!have_argmax && (rc = ensure_ctc_scratch(m, (size_t)N * T))) return rc;
+    ProfScope ps(m, s, FAM_GREEDY);
+    if (!have_argmax) {
+        m->dec.amax_logits = nullptr;                             // the scratch no longer belongs to the last forward's logits
+        hipLaunchKernelGGL(ctc_argmax_kernel, dim3(ceil_div(N * T, 4)), dim3(256), 0, s, logits, T, ncls, N * T, d_lens, m->dec.ctc_lab.p, m->dec.ctc_val.p);
+        LAUNCH_CHECK();
+    }
+    hipLaunchKernelGGL(ctc_collapse_kernel, dim3(N), dim3(64), (size_t)T * 8, s, T, d_lens, m->dec.ctc_lab.p, m->dec.ctc_val.p, labels, starts, ends, conf, counts,
+                       max_per_line);
+    LAUNCH_CHECK();
+    return COCR_OK;
+}
+
+extern "C" int cocr_ctc_beam(cocr_model *m, const float *logits, int N, int T, int ncls, const int32_t *out_lens, int32_t *labels,
+                             int32_t *starts, int32_t *ends, float *conf, int32_t *counts, int max_per_line, int beam, void *stream) {
+    if (!m || !logits || !out_lens || !labels || !starts || !ends || !conf || !counts) return fail(COCR_EINVAL, "null argument");
+    if (N < 1 || T < 1 || ncls < 2 || max_per_line < 1) return fail(COCR_EINVAL, "empty problem");
+    if (beam < 1 || beam > COCR_BEAM_MAX) return fail(COCR_EINVAL, "beam must be in 1..%d", COCR_BEAM_MAX);
+    if (ncls > 65535) return fail(COCR_EUNSUPPORTED, "more than 65535 classes");
+    HIP_TRY(hipSetDevice(m->device));
+    hipStream_t s = (hipStream_t)stream;
+    const int32_t *d_lens;
+    int rc = upload_lens(m, out_lens, N, s, d_lens);
+    if (rc) return rc;
+    const bool fast = ncls <= 256 && !m->sw.beam_ref;            // ctc_beam_rank_kernel + ctc_beam_walk_kernel: frames ranked in parallel, a static pruned candidate set per frame
+    const int K = std::min(beam + 1, ncls - 1);
+    // scratch: back-pointers [N][T][COCR_BEAM_MAX] i32, then log Z [N][T] (exhaustive kernel) or the frame records (fast)
+    const size_t need = (size_t)N * T * ((size_t)COCR_BEAM_MAX * 4 + (fast ? (size_t)COCR_BEAM_REC : 4));
+    HIP_TRY(m->dec.beam_bp.grow(need));
+    int32_t *bp = reinterpret_cast<int32_t *>(m->dec.beam_bp.p);
+    ProfScope ps(m, s, FAM_BEAM);
+    if (fast) {
+        unsigned char *rec = reinterpret_cast<unsigned char *>(bp + (size_t)N * T * COCR_BEAM_MAX);
+        const size_t dyn = (size_t)T * ((size_t)beam * 4 + 8);                 // back-pointers + the label stack of the final walk, in LDS when they fit
+        const int bp_in_lds = dyn <= 96 * 1024;
+        hipLaunchKernelGGL(ctc_beam_rank_kernel, dim3(N * T), dim3(256), 0, s, logits, T, ncls, d_lens, K, rec);
+        auto walk = ctc_beam_walk_kernel<3>;                          // candidates per lane of a wave: <= 88 for beam <= 16, <= 184 for beam 32
+        if (beam <= 16) walk = ctc_beam_walk_kernel<2>;
+        // (the kernel also has ~12 KB of static LDS: the limit raised for the dynamic part stays below 160 KB - static)
+        if (bp_in_lds) HIP_TRY(raise_lds_limit((const void *)walk, dyn, 48 * 1024, 96 * 1024));
+        hipLaunchKernelGGL(walk, dim3(N), dim3(256), bp_in_lds ? dyn : 0, s, logits, T, ncls, d_lens, beam, K, labels, starts,
+                           ends, conf, counts, max_per_line, rec, bp, bp_in_lds, m->stamps ? m->stamps + 240 : nullptr);
+    } else {
+        float *logz = reinterpret_cast<float *>(bp + (size_t)N * T * COCR_BEAM_MAX);
+        const size_t lds = ((size_t)ncls + (size_t)beam * ncls) * 4 + COCR_BEAM_MAX * (11 * 4 + 2 * 8) + 64;
+        if (lds > 150 * 1024) return fail(COCR_EUNSUPPORTED, "beam x classes too large for the LDS candidate table");
+        HIP_TRY(raise_lds_limit((const void *)ctc_beam_kernel, lds));
+        hipLaunchKernelGGL(ctc_beam_kernel, dim3(N), dim3(64), lds, s, logits, T, ncls, d_lens, beam, labels, starts, ends, conf, counts,
+                           max_per_line, bp, logz);
+    }
+    LAUNCH_CHECK();
+    return COCR_OK;
+}
+
+// ------------------------------------------------------------------------------------ beam search with an n-gram model (ctc_lm.hip.h)
+struct cocr_lm {
+    int device = 0, order = 0, ncls = 0;
+    int64_t nslots = 0, cslots = 0;
+    DevBuf<float> unigram, nlogp, cbow;
+    DevBuf<unsigned long long> nkeys, ckeys;
+};
+
+static int lm_check_table(const char *what, const int64_t *keys, const float *vals, int64_t slots) {
+    if (slots < 2 || slots > (1ll << 30) || (slots & (slots - 1))) return fail(COCR_EINVAL, "%s: slot count %lld is not a power of two in 2..2^30", what, (long long)slots);
+    if (!keys || !vals) return fail(COCR_EINVAL, "%s: null table", what);
+    for (int64_t i = 0; i < slots; ++i)
+        if (keys[i] == 0) return COCR_OK;
+    return fail(COCR_EINVAL, "%s: no empty slot (a probe sequence would not end)", what);
+}
+
+extern "C" int cocr_lm_create(cocr_model *m, int order, int ncls, const float *unigram, const int64_t *ngram_keys, const float *ngram_logp,
+                              int64_t ngram_slots, const int64_t *ctx_keys, const float *ctx_bow, int64_t ctx_slots, cocr_lm **out) {
+    if (!m || !unigram || !out) return fail(COCR_EINVAL, "null argument");
+    if (order < 1 || order > COCR_LM_CTX + 1) return fail(COCR_EINVAL, "order must be in 1..%d", COCR_LM_CTX + 1);
+    if (ncls < 2 || ncls > 65535) return fail(COCR_EINVAL, "ncls must be in 2..65535");
+    int rc = lm_check_table("ngram table", ngram_keys, ngram_logp, ngram_slots);
+    if (rc) return rc;
+    if ((rc = lm_check_table("context table", ctx_keys, ctx_bow, ctx_slots))) return rc;
+    HIP_TRY(hipSetDevice(m->device));
+    cocr_lm *lm = new cocr_lm();
+    lm->device = m->device; lm->order = order; lm->ncls = ncls; lm->nslots = ngram_slots; lm->cslots = ctx_slots;
+    hipError_t e = lm->unigram.grow((size_t)ncls);
+    if (e == hipSuccess) e = lm->nkeys.grow((size_t)ngram_slots);
+    if (e == hipSuccess) e = lm->nlogp.grow((size_t)ngram_slots);
+    if (e == hipSuccess) e = lm->ckeys.grow((size_t)ctx_slots);
+    if (e == hipSuccess) e = lm->cbow.grow((size_t)ctx_slots);
+    if (e == hipSuccess) e = hipMemcpy(lm->unigram.p, unigram, (size_t)ncls * 4, hipMemcpyHostToDevice);
+    if (e == hipSuccess) e = hipMemcpy(lm->nkeys.p, ngram_keys, (size_t)ngram_slots * 8, hipMemcpyHostToDevice);
+    if (e == hipSuccess) e = hipMemcpy(lm->nlogp.p, ngram_logp, (size_t)ngram_slots * 4, hipMemcpyHostToDevice);
+    if (e == hipSuccess) e = hipMemcpy(lm->ckeys.p, ctx_keys, (size_t)ctx_slots * 8, hipMemcpyHostToDevice);
+    if (e == hipSuccess) e = hipMemcpy(lm->cbow.p, ctx_bow, (size_t)ctx_slots * 4, hipMemcpyHostToDevice);
+    if (e != hipSuccess) { delete lm; return fail(COCR_EHIP, "copying the language model to the device failed: %s", hipGetErrorString(e)); }
+    *out = lm;
+    return COCR_OK;
+}
+
+extern "C" void cocr_lm_destroy(cocr_lm *lm) {
+    if (!lm) return;
+    (void)hipSetDevice(lm->device);
+    delete lm;
+}
+
+extern "C" int cocr_ctc_beam_lm(cocr_model *m, cocr_lm *lm, const float *logits, int N, int T, int ncls, const int32_t *out_lens, int32_t *labels,
+                                int32_t *starts, int32_t *ends, float *conf, int32_t *counts, int max_per_line, int beam, int classes, float alpha,
+                                float beta, float *score, void *stream) {
+    if (!m || !lm || !logits || !out_lens || !labels || !starts || !ends || !conf || !counts) return fail(COCR_EINVAL, "null argument");
+    if (N < 1 || T < 1 || ncls < 2 || max_per_line < 1) return fail(COCR_EINVAL, "empty problem");
+    if (T > 8000) return fail(COCR_EUNSUPPORTED, "more than 8000 frames per line");
+    if (beam < 1 || beam > COCR_BEAM_MAX) return fail(COCR_EINVAL, "beam must be in 1..%d", COCR_BEAM_MAX);
+    if (classes < 1 || classes > COCR_LM_KMAX) return fail(COCR_EINVAL, "classes must be in 1..%d", COCR_LM_KMAX);
+    if (ncls != lm->ncls) return fail(COCR_EINVAL, "the logits have %d classes, the language model %d", ncls, lm->ncls);
+    if (lm->device != m->device) return fail(COCR_EINVAL, "the language model lives on device %d, the model on %d", lm->device, m->device);
+    if (!std::isfinite(alpha) || !std::isfinite(beta)) return fail(COCR_EINVAL, "alpha and beta must be finite");
+    HIP_TRY(hipSetDevice(m->device));
+    hipStream_t s = (hipStream_t)stream;
+    const int32_t *d_lens;
+    int rc = upload_lens(m, out_lens, N, s, d_lens);
+    if (rc) return rc;
+    const int K = std::min(classes, ncls - 1);
+    // scratch: back-pointers [N][T][COCR_BEAM_MAX] i32, then the frame records [N][T][COCR_LM_REC] f32
+    const size_t bp_bytes = (size_t)N * T * COCR_BEAM_MAX * 4;
+    HIP_TRY(m->dec.lm_scratch.grow(bp_bytes + (size_t)N * T * COCR_LM_REC * 4));
+    int32_t *bp = reinterpret_cast<int32_t *>(m->dec.lm_scratch.p);
+    float *rec = reinterpret_cast<float *>(m->dec.lm_scratch.p + bp_bytes);
+    const size_t dyn = (size_t)T * ((size_t)beam * 4 + 8);                     // back-pointers + the label stack of the final walk, in LDS when they fit
+    const int bp_in_lds = dyn <= 96 * 1024;
+    if (bp_in_lds) HIP_TRY(raise_lds_limit((const void *)ctc_lm_walk_kernel, dyn, 16 * 1024, 96 * 1024));      // (the kernel has ~30 KB of static LDS)
+    cocr_lm_tables L;
+    L.unigram = lm->unigram.p; L.nkeys = lm->nkeys.p; L.nlogp = lm->nlogp.p; L.ckeys = lm->ckeys.p; L.cbow = lm->cbow.p;
+    L.nmask = (unsigned)(lm->nslots - 1); L.cmask = (unsigned)(lm->cslots - 1); L.order = lm->order;
+    ProfScope ps(m, s, FAM_BEAM);
+    hipLaunchKernelGGL(ctc_lm_topk_kernel, dim3(ceil_div(N * T, 4)), dim3(256), 0, s, logits, T, ncls, N * T, d_lens, K, rec);
+    LAUNCH_CHECK();
+    hipLaunchKernelGGL(ctc_lm_walk_kernel, dim3(N), dim3(256), bp_in_lds ? dyn : 0, s, logits, T, ncls, d_lens, beam, K, L, alpha, beta, labels, starts,
+                       ends, conf, counts, score, max_per_line, rec, bp, bp_in_lds);
+    LAUNCH_CHECK();
+    return COCR_OK;
+}
+
+// ------------------------------------------------------------------------------------ CTC loss (ctc_loss.hip.h)
+// The targets of a batch on the device, and the kernel form for its longest line: sj 64-state columns per lane.
+struct CtcTargets { const int32_t *lens, *label_lens, *label_off, *labels; int sj; };
+
+// Loss and forced alignment: checks the per-line lengths and the labels, then sends [lens | label lens | label offsets | labels]
+// through the targets ring.  `outputs_ok`: the caller's per-label output pointers are set (asked for only where there are labels);
+// `too_long`: the status for a line of more than COCR_CTCL_MAX_LABELS labels.
+static int upload_targets(cocr_model *m, int N, int T, int ncls, const int32_t *out_lens, const int32_t *targets, const int32_t *label_lens,
+                          bool outputs_ok, int too_long, void *stream, CtcTargets &t) {
+    size_t total = 0;
+    int max_l = 0;
+    for (int n = 0; n < N; ++n) {
+        if (label_lens[n] < 0) return fail(COCR_EINVAL, "negative target length (line %d)", n);
+        if (label_lens[n] > COCR_CTCL_MAX_LABELS) return fail(too_long, "line %d has %d labels; the kernel holds at most %d", n, label_lens[n], COCR_CTCL_MAX_LABELS);
+        if (out_lens[n] < 0 || out_lens[n] > T) return fail(COCR_EINVAL, "input length %d outside [0, %d] (line %d)", out_lens[n], T, n);
+        max_l = std::max(max_l, (int)label_lens[n]);
+        total += (size_t)label_lens[n];
+    }
+    if (total && (!targets || !outputs_ok)) return fail(COCR_EINVAL, "null argument");
+    for (size_t i = 0; i < total; ++i)
+        if (targets[i] < 1 || targets[i] >= ncls) return fail(COCR_EINVAL, "target %d outside [1, %d) (blank is 0)", targets[i], ncls);
+    HIP_TRY(hipSetDevice(m->device));
+    const size_t ints = (size_t)3 * N + total;
+    int32_t *h, *d;
+    HIP_TRY(m->dec.target_ring.stage(ints * 4, h, d));
+    int32_t off = 0;
+    for (int n = 0; n < N; ++n) { h[n] = out_lens[n]; h[N + n] = label_lens[n]; h[2 * N + n] = off; off += label_lens[n]; }
+    if (total) memcpy(h + 3 * N, targets, total * 4);
+    HIP_TRY(m->dec.target_ring.commit(ints * 4, (hipStream_t)stream));
+    const int states = 2 * max_l + 1;
+    t = {d, d + N, d + 2 * N, d + 3 * N, states <= 64 ? 1 : states <= 128 ? 2 : states <= 256 ? 4 : 8};
+    return COCR_OK;
+}
+
+extern "C" int cocr_ctc_loss(cocr_model *m, const float *probits, int N, int T, int ncls, const int32_t *out_lens, const int32_t *targets,
+                             const int32_t *label_lens, float *nll, float *grad, void *stream) {
+    if (!m || !probits || !out_lens || !label_lens || !nll) return fail(COCR_EINVAL, "null argument");
+    if (N < 1 || T < 1 || ncls < 2) return fail(COCR_EINVAL, "empty problem");
+    if (ncls > 16384) return fail(COCR_EUNSUPPORTED, "more than 16384 classes");
+    CtcTargets t;
+    const int rc = upload_targets(m, N, T, ncls, out_lens, targets, label_lens, true, COCR_EUNSUPPORTED, stream, t);
+    if (rc) return rc;
+    hipStream_t s = (hipStream_t)stream;
+    const int sj = t.sj;
+    const size_t need = (size_t)N * T * ((size_t)ncls + 2 * 64 * sj);
+    HIP_TRY(m->dec.loss_ws.grow(need));
+    ProfScope ps(m, s, FAM_LOSS);
+    launch_ctc_loss(s, sj, (size_t)ncls * 4, probits, N, T, ncls, t.lens, t.label_lens, t.label_off, t.labels, nll, grad, m->dec.loss_ws.p, m->dec.loss_ws.p + (size_t)N * T * ncls);
+    LAUNCH_CHECK();
+    return COCR_OK;
+}
+
+// ------------------------------------------------------------------------------------ forced alignment (ctc_align.hip.h)
+extern "C" int cocr_ctc_align(cocr_model *m, const float *logits, int N, int T, int ncls, const int32_t *out_lens, const int32_t *targets,
+                              const int32_t *label_lens, int32_t *starts, int32_t *ends, float *conf, float *score, int32_t *counts, void *stream) {
+    if (!m || !logits || !out_lens || !label_lens || !score || !counts) return fail(COCR_EINVAL, "null argument");
+    if (N < 1 || T < 1 || ncls < 2) return fail(COCR_EINVAL, "empty problem");
+    if (T > 8000) return fail(COCR_EUNSUPPORTED, "more than 8000 frames per line");
+    CtcTargets t;
+    const int rc = upload_targets(m, N, T, ncls, out_lens, targets, label_lens, starts && ends && conf, COCR_EINVAL, stream, t);
+    if (rc) return rc;
+    hipStream_t s = (hipStream_t)stream;
+    const int sj = t.sj;
+    // the back-pointer table: in LDS beside lz when both fit (the kernel has ~5 KB of static LDS), else one region per line of the workspace
+    const size_t words = ctca_bp_words(T, sj), lds_all = ctca_lz_bytes(T) + words * 4;
+    if (lds_all <= 144 * 1024) {
+        auto kern = ctc_align_kernel<8, true>;
+        switch (sj) { case 1: kern = ctc_align_kernel<1, true>; break; case 2: kern = ctc_align_kernel<2, true>; break; case 4: kern = ctc_align_kernel<4, true>; break; }
+        // (the kernel also has ~5 KB of static LDS: the limit raised for the dynamic part stays below 160 KB - static)
+        HIP_TRY(raise_lds_limit((const void *)kern, lds_all, 48 * 1024, 150 * 1024));
+        launch_ctc_align<true>(s, sj, lds_all, logits, N, T, ncls, t.lens, t.label_lens, t.label_off, t.labels, starts, ends, conf, score, counts, nullptr, 0);
+    } else {
+        HIP_TRY(m->dec.align_ws.grow((size_t)N * words));
+        launch_ctc_align<false>(s, sj, ctca_lz_bytes(T), logits, N, T, ncls, t.lens, t.label_lens, t.label_off, t.labels, starts, ends, conf, score, counts,
+                                m->dec.align_ws.p, words);
+    }
+    LAUNCH_CHECK();
+    return COCR_OK;
+}

@@ -18,7 +18,7 @@
 #include "gemm.hip.h"
 #include "conv.hip.h"
 
-// ---- weight images built once per model (cocr_api: ensure_packed) -----------------------------------------------
+// ---- weight images built once per model (forward.hip: ensure_packed) -----------------------------------------------
 // w0f: conv.0 A-fragments [16 channel tiles][64 lanes][4 bf16]: lane (r, g) = w0[16 nt + r][dt = g][df = 0..2], 0
 // dwf: depthwise B-fragments [16 blocks][5 k-chunks][64 lanes][8 bf16]: lane (r, g), element i <-> k = 32 chunk + 8 g + i
 //      = (tap = 2 chunk + (g >> 1), c' = 8 (g & 1) + i); value w2[16 blk + r][tap] where c' == r and tap < 9, else 0

@@ -20,8 +20,6 @@
 // direct 8-byte-per-lane store of the accumulator layout -- 32-byte row fragments -- took 2/3 of the kernel.)
 #pragma once
 #include <algorithm>
-#include <mutex>
-#include <set>
 #include <type_traits>
 
 #include "common.hip.h"
@@ -754,19 +752,6 @@ __global__ __launch_bounds__(256) void gemm_stream_kernel(GemmArgs<T> p, Epi epi
 }
 
 // ---- host side ---------------------------------------------------------------------------------------
-// A launch with more than `above` bytes of dynamic LDS needs the kernel's limit raised first, to `limit` (a kernel with static LDS
-// of its own passes figures that leave room for it).  Models on several threads launch at once: the set is locked.
-static inline hipError_t raise_lds_limit(const void *kern, size_t lds, size_t above = 64 * 1024, int limit = 160 * 1024) {
-    if (lds <= above) return hipSuccess;
-    static std::mutex mu;
-    static std::set<const void *> raised;      // per kernel instantiation, once
-    std::lock_guard<std::mutex> lock(mu);
-    if (raised.count(kern)) return hipSuccess;
-    hipError_t e = hipFuncSetAttribute(kern, hipFuncAttributeMaxDynamicSharedMemorySize, limit);
-    if (e == hipSuccess) raised.insert(kern);
-    return e;
-}
-
 template <typename T, int BM, int BN, int NST, typename Epi>
 static inline hipError_t launch_ring_cfg(hipStream_t s, const GemmArgs<T> &a, const Epi &epi) {
     const size_t lds = std::max((size_t)NST * (BM + BN) * 128, epi_lds_bytes<Epi, BM, BN>());

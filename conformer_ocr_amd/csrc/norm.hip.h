@@ -11,8 +11,6 @@
 #pragma once
 #include "common.hip.h"
 
-#define COCR_LN_MAX_D 1024
-
 template <typename T, int NV>
 __global__ __launch_bounds__(256) void layernorm_kernel(const float *x, int M, int D, int Dn, float eps,      // Dn: LayerNorm width (columns [Dn, D): zero padding)
                                                         const float *__restrict__ g1, const float *__restrict__ b1,

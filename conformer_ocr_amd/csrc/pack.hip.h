@@ -1,4 +1,4 @@
-// Weight re-layout kernels run once per model (cocr_api.hip: ensure_packed).
+// Weight re-layout kernels run once per model (forward.hip: ensure_packed).
 #pragma once
 #include "common.hip.h"
 

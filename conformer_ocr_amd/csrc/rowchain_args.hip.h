@@ -1,5 +1,5 @@
 // Arguments of the row-chain kernels (rowchain.hip.h) and the entry points of their three translation units (rowchain_d256.hip,
-// rowchain_d256_head.hip, rowchain_d512.hip: the template instantiations are compiled beside cocr_api.hip, in parallel).
+// rowchain_d256_head.hip, rowchain_d512.hip: the template instantiations are compiled beside the host layer's units, in parallel).
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -54,7 +54,7 @@ static inline bool rowchain_supported(int D, int FF, int dh) { return (D == 256 
 
 // 16-row tiles per workgroup (MT) of the instantiated forms.  `rows_hint` > 0: the nearest form.  0: by the number of rows alone -- the most
 // rows the registers and LDS allow (the weight stream is read once per workgroup) from 50 workgroups on, else 32.  Which hint a forward
-// passes is cocr_api.hip's decision (chain_rows_for).
+// passes is forward.hip's decision (chain_rows_for).
 template <int D> static inline int rowchain_pick_mt(int M, int rows_hint) {
     constexpr int MAXMT = D == 256 ? 6 : 4;
     if (rows_hint > 0) {

@@ -1,4 +1,4 @@
-// Training step of the whole network behind the C ABI (included at the end of cocr_api.hip):
+// Training behind the C ABI: the output layer alone (cocr_decoder_*), and the training step of the whole network:
 //     cocr_train_begin      fp32 master copy of every parameter / buffer (reference state-dict names) on the device, zeroed AdamW state
 //     cocr_train_step       RecognitionModel.training_step (model.py:129-152): train-mode forward (batch-statistics BatchNorm, dropout at the
 //                           reference's six sites), CTC criterion, backward through decoder AND encoder -> the gradient of every parameter
@@ -16,11 +16,100 @@
 //                dW = dY^T X reads dY and X K-major (gemm_tn_kernel, no transposed copies), dX = dY W takes the kept W^T
 // The inference path (bf16 row chains, fused frontend) is not touched: training keeps its own activations (everything the backward needs is
 // stored; nothing is recomputed except dropout masks, which are regenerated from (seed, site, index)).
-#pragma once
+#include <mutex>
 
+#include "model.hip.h"
+#include "gemm.hip.h"
+#include "train.hip.h"
+#include "train_enc.hip.h"
 #include "train_step.hip.h"
 
-static void train_free(cocr_model *m) {
+// ------------------------------------------------------------------------------------ output-layer training step (train.hip.h)
+extern "C" int cocr_decoder_backward(cocr_model *m, const float *grad_probits, int N, int T, float *grad_weight, float *grad_bias, float *grad_output,
+                                     void *stream) {
+    if (!m || !grad_probits || !grad_weight || !grad_bias) return fail(COCR_EINVAL, "null argument");
+    if (!m->w->blob) return fail(COCR_ESTATE, "model not finalized");
+    { const int rc = adopt_layout(m); if (rc) return rc; }
+    if (N != m->ws.lastN || T != m->ws.lastT || !m->ws.xn) return fail(COCR_ESTATE, "no forward of shape (%d lines, %d frames) precedes this call (last forward: %d, %d)", N, T, m->ws.lastN, m->ws.lastT);
+    HIP_TRY(hipSetDevice(m->device));
+    hipStream_t s = (hipStream_t)stream;
+    const int M = N * T, C = m->ncls, D = m->D, chunks = ceil_div(M, COCR_TR_ROWS);
+    const size_t per = (size_t)C * D + C, need = per * chunks;
+    HIP_TRY(m->dtr.tr_part.grow(need));
+    float *part_w = m->dtr.tr_part.p, *part_b = m->dtr.tr_part.p + (size_t)chunks * C * D;
+    // A padded model (set_engine_dims): the kernels work on the engine's D-wide rows (the padded columns of the encoder output and of
+    // the weight are zero, so are their gradients); the caller's tensors have the model's own width rD: strided copies at the boundary.
+    const int rD = m->rD;
+    float *gw_dst = grad_weight, *go_dst = grad_output;
+    if (m->padded) {
+        const size_t need_pad = (size_t)C * D + (grad_output ? (size_t)M * D : 0);
+        HIP_TRY(m->dtr.tr_pad.grow(need_pad));
+        gw_dst = m->dtr.tr_pad.p;
+        if (grad_output) go_dst = m->dtr.tr_pad.p + (size_t)C * D;
+    }
+    const dim3 grid(chunks, ceil_div(C, COCR_TR_CT));
+    if (m->dtype == COCR_BF16) hipLaunchKernelGGL((decoder_wgrad_kernel<bf16_t>), grid, dim3(256), 0, s, grad_probits, (const bf16_t *)m->ws.xn, M, C, D, part_w, part_b);
+    else hipLaunchKernelGGL((decoder_wgrad_kernel<float>), grid, dim3(256), 0, s, grad_probits, (const float *)m->ws.xn, M, C, D, part_w, part_b);
+    LAUNCH_CHECK();
+    hipLaunchKernelGGL(chunk_reduce_kernel, dim3(ceil_div(C * D, 256)), dim3(256), 0, s, part_w, chunks, (size_t)C * D, gw_dst);
+    hipLaunchKernelGGL(chunk_reduce_kernel, dim3(ceil_div(C, 256)), dim3(256), 0, s, part_b, chunks, (size_t)C, grad_bias);
+    LAUNCH_CHECK();
+    if (grad_output) {
+        if (m->dtype == COCR_BF16) hipLaunchKernelGGL((decoder_igrad_kernel<bf16_t>), dim3(ceil_div(M, 16)), dim3(256), 0, s, grad_probits, (const bf16_t *)(m->w->blob + m->w->plan.wdec), M, C, D, go_dst);
+        else hipLaunchKernelGGL((decoder_igrad_kernel<float>), dim3(ceil_div(M, 16)), dim3(256), 0, s, grad_probits, (const float *)(m->w->blob + m->w->plan.wdec), M, C, D, go_dst);
+        LAUNCH_CHECK();
+    }
+    if (m->padded) {
+        HIP_TRY(hipMemcpy2DAsync(grad_weight, (size_t)rD * 4, gw_dst, (size_t)D * 4, (size_t)rD * 4, C, hipMemcpyDeviceToDevice, s));
+        if (grad_output) HIP_TRY(hipMemcpy2DAsync(grad_output, (size_t)rD * 4, go_dst, (size_t)D * 4, (size_t)rD * 4, M, hipMemcpyDeviceToDevice, s));
+    }
+    return COCR_OK;
+}
+
+// fp32 master copy [W | b] of the output layer + zeroed moments: the state-dict tensors when this rank has them, else (weights received by
+// broadcast) the blob's values
+static int decoder_master_init(cocr_model *m, hipStream_t s) {
+    const size_t nw = (size_t)m->ncls * m->D, nb = (size_t)m->ncls, n = nw + nb, nw_model = (size_t)m->ncls * m->rD;
+    const size_t row_e = (size_t)m->D * 4, row_m = (size_t)m->rD * 4;      // engine / model row bytes of the decoder weight (equal unless padded)
+    HIP_TRY(hipMalloc((void **)&m->dtr.tr_state, 3 * n * 4));
+    HIP_TRY(hipMemsetAsync(m->dtr.tr_state + n, 0, 2 * n * 4, s));
+    auto w = m->host.find("decoder.weight"), b = m->host.find("decoder.bias");
+    if (w != m->host.end() && w->second.set && w->second.data.size() == nw_model && b != m->host.end() && b->second.set && b->second.data.size() == nb) {
+        HIP_TRY(hipMemsetAsync(m->dtr.tr_state, 0, nw * 4, s));
+        HIP_TRY(hipMemcpy2DAsync(m->dtr.tr_state, row_e, w->second.data.data(), row_m, row_m, m->ncls, hipMemcpyHostToDevice, s));
+        HIP_TRY(hipMemcpyAsync(m->dtr.tr_state + nw, b->second.data.data(), nb * 4, hipMemcpyHostToDevice, s));
+        HIP_TRY(hipStreamSynchronize(s));                                   // pageable sources
+    } else {
+        blob_to_f32(m, m->w->plan.wdec, m->dtr.tr_state, nw, s);
+        HIP_TRY(hipMemcpyAsync(m->dtr.tr_state + nw, m->w->blob + m->w->plan.bdec, nb * 4, hipMemcpyDeviceToDevice, s));
+        LAUNCH_CHECK();
+    }
+    m->dtr.tr_step = 0;
+    m->dtr.tr_kind = -1;
+    return COCR_OK;
+}
+
+extern "C" int cocr_get_tensor(cocr_model *m, const char *name, float *host_out, int64_t max_elems, void *stream) {
+    if (!m || !name || !host_out) return fail(COCR_EINVAL, "null argument");
+    const bool is_w = !strcmp(name, "decoder.weight"), is_b = !strcmp(name, "decoder.bias");
+    if (!is_w && !is_b) return fail(COCR_EINVAL, "only decoder.weight / decoder.bias are trained by this library (got '%s')", name);
+    const size_t nw = (size_t)m->ncls * m->D, nb = (size_t)m->ncls, n = is_w ? (size_t)m->ncls * m->rD : nb;      // nw: the engine's (maybe padded) copy
+    if ((int64_t)n > max_elems) return fail(COCR_EINVAL, "%s has %zu elements, buffer %lld", name, n, (long long)max_elems);
+    auto it = m->host.find(name);
+    if (m->dtr.tr_state) {
+        HIP_TRY(hipSetDevice(m->device));
+        HIP_TRY(hipStreamSynchronize((hipStream_t)stream));
+        if (is_w) HIP_TRY(hipMemcpy2D(host_out, (size_t)m->rD * 4, m->dtr.tr_state, (size_t)m->D * 4, (size_t)m->rD * 4, m->ncls, hipMemcpyDeviceToHost));
+        else HIP_TRY(hipMemcpy(host_out, m->dtr.tr_state + nw, n * 4, hipMemcpyDeviceToHost));
+        if (it != m->host.end() && it->second.data.size() == n) memcpy(it->second.data.data(), host_out, n * 4);      // a later cocr_finalize keeps the trained values
+        return COCR_OK;
+    }
+    if (it == m->host.end() || !it->second.set || it->second.data.size() != n) return fail(COCR_ESTATE, "%s was never set on this model", name);
+    memcpy(host_out, it->second.data.data(), n * 4);
+    return COCR_OK;
+}
+
+void train_free(cocr_model *m) {
     TrainState *t = m->train;
     if (!t) return;
     for (void *p : {(void *)t->P, (void *)t->G, (void *)t->Mo, (void *)t->Vo})
@@ -192,21 +281,21 @@ extern "C" int cocr_train_adopt_decoder(cocr_model *dst, cocr_model *src, void *
     if (w == t->idx.end() || b == t->idx.end()) return fail(COCR_ESTATE, "the training state has no output layer");
     if (src->ncls != dst->ncls || src->rD != dst->rD || w->second.n != (size_t)src->ncls * src->rD || b->second.n != (size_t)src->ncls)
         return fail(COCR_EINVAL, "output layers differ: (%d, %d) into (%d, %d)", src->ncls, src->rD, dst->ncls, dst->rD);
-    if (src->tr_state && src->tr_kind >= 0 && t->kind >= 0 && src->tr_kind != t->kind)
-        return fail(COCR_EINVAL, "the two states have taken steps of different optimizer kinds (%s into %s)", optim_name(src->tr_kind), optim_name(t->kind));
+    if (src->dtr.tr_state && src->dtr.tr_kind >= 0 && t->kind >= 0 && src->dtr.tr_kind != t->kind)
+        return fail(COCR_EINVAL, "the two states have taken steps of different optimizer kinds (%s into %s)", optim_name(src->dtr.tr_kind), optim_name(t->kind));
     HIP_TRY(hipSetDevice(dst->device));
     hipStream_t s = (hipStream_t)stream;
-    if (!src->tr_state) { const int rc = decoder_master_init(src, s); if (rc) return rc; }
+    if (!src->dtr.tr_state) { const int rc = decoder_master_init(src, s); if (rc) return rc; }
     const size_t nw = (size_t)src->ncls * src->D, n = nw + (size_t)src->ncls;
     const size_t row_e = (size_t)src->D * 4, row_m = (size_t)src->rD * 4;
     float *dsts[3] = {t->P, t->Mo, t->Vo};
     for (int i = 0; i < 3; ++i) {
-        const float *from = src->tr_state + (size_t)i * n;
+        const float *from = src->dtr.tr_state + (size_t)i * n;
         HIP_TRY(hipMemcpy2DAsync(dsts[i] + w->second.off, row_m, from, row_e, row_m, src->ncls, hipMemcpyDeviceToDevice, s));
         HIP_TRY(hipMemcpyAsync(dsts[i] + b->second.off, from + nw, (size_t)src->ncls * 4, hipMemcpyDeviceToDevice, s));
     }
-    t->dec_steps = src->tr_step - t->step;        // (the layer's count is dst's own count + dec_steps: an adoption after dst has stepped keeps k exact)
-    if (t->kind < 0) t->kind = src->tr_kind;      // (slots and count mean what they meant in `src`; SGD / RMSprop read no count)
+    t->dec_steps = src->dtr.tr_step - t->step;        // (the layer's count is dst's own count + dec_steps: an adoption after dst has stepped keeps k exact)
+    if (t->kind < 0) t->kind = src->dtr.tr_kind;      // (slots and count mean what they meant in `src`; SGD / RMSprop read no count)
     return COCR_OK;
 }
 
@@ -352,16 +441,16 @@ static int decoder_step_begin(cocr_model *m, const float **grad_weight, const fl
     HIP_TRY(hipSetDevice(m->device));
     if (m->padded) {    // the caller's (ncls, rD) gradient embedded in the engine's zero-padded rows
         const size_t nw = (size_t)m->ncls * m->D, row_e = (size_t)m->D * 4, row_m = (size_t)m->rD * 4;
-        HIP_TRY(m->tr_pad.grow(nw));
-        HIP_TRY(hipMemsetAsync(m->tr_pad.p, 0, nw * 4, s));
-        HIP_TRY(hipMemcpy2DAsync(m->tr_pad.p, row_e, *grad_weight, row_m, row_m, m->ncls, hipMemcpyDeviceToDevice, s));
-        *grad_weight = m->tr_pad.p;
+        HIP_TRY(m->dtr.tr_pad.grow(nw));
+        HIP_TRY(hipMemsetAsync(m->dtr.tr_pad.p, 0, nw * 4, s));
+        HIP_TRY(hipMemcpy2DAsync(m->dtr.tr_pad.p, row_e, *grad_weight, row_m, row_m, m->ncls, hipMemcpyDeviceToDevice, s));
+        *grad_weight = m->dtr.tr_pad.p;
     }
-    if (!m->tr_state) { const int rc = decoder_master_init(m, s); if (rc) return rc; }
-    if (m->tr_kind >= 0 && m->tr_kind != o->kind)
-        return fail(COCR_ESTATE, "the output layer's optimizer state is %s's: a %s step cannot follow", optim_name(m->tr_kind), optim_name(o->kind));
-    m->tr_kind = o->kind;
-    *k = ++m->tr_step;
+    if (!m->dtr.tr_state) { const int rc = decoder_master_init(m, s); if (rc) return rc; }
+    if (m->dtr.tr_kind >= 0 && m->dtr.tr_kind != o->kind)
+        return fail(COCR_ESTATE, "the output layer's optimizer state is %s's: a %s step cannot follow", optim_name(m->dtr.tr_kind), optim_name(o->kind));
+    m->dtr.tr_kind = o->kind;
+    *k = ++m->dtr.tr_step;
     return COCR_OK;
 }
 
@@ -374,7 +463,7 @@ extern "C" int cocr_decoder_optim_step(cocr_model *m, const float *grad_weight, 
     const size_t nw = (size_t)m->ncls * m->D, nb = (size_t)m->ncls, n = nw + nb;
     float bc1 = 1.f, bc2 = 1.f;
     if (o->kind == COCR_OPT_ADAMW || o->kind == COCR_OPT_ADAM) { bc1 = 1.0f - powf(o->beta1, (float)k); bc2 = 1.0f - powf(o->beta2, (float)k); }
-    float *p = m->tr_state, *s0 = p + n, *s1 = s0 + n;
+    float *p = m->dtr.tr_state, *s0 = p + n, *s1 = s0 + n;
     const bool bf = m->dtype == COCR_BF16;
     int rc = launch_optim(s, o, p, grad_weight, s0, s1, nw, bc1, bc2, nullptr, bf ? (bf16_t *)(m->w->blob + m->w->plan.wdec) : nullptr, bf ? nullptr : (float *)(m->w->blob + m->w->plan.wdec));
     if (rc) return rc;
@@ -391,7 +480,7 @@ extern "C" int cocr_decoder_adamw(cocr_model *m, const float *grad_weight, const
     { const int rc = decoder_step_begin(m, &grad_weight, grad_bias, &o, s, &t); if (rc) return rc; }
     const size_t nw = (size_t)m->ncls * m->D, nb = (size_t)m->ncls, n = nw + nb;
     const float bc1 = 1.0f - (float)pow((double)beta1, (double)t), bc2s = (float)sqrt(1.0 - pow((double)beta2, (double)t));
-    float *p = m->tr_state, *m1 = p + n, *m2 = m1 + n;
+    float *p = m->dtr.tr_state, *m1 = p + n, *m2 = m1 + n;
     if (m->dtype == COCR_BF16)
         hipLaunchKernelGGL((adamw_kernel<bf16_t>), dim3(ceil_div((int)nw, 256)), dim3(256), 0, s, p, grad_weight, m1, m2, nw, lr, beta1, beta2, eps, weight_decay, bc1, bc2s,
                            (bf16_t *)(m->w->blob + m->w->plan.wdec), (float *)nullptr);
@@ -428,9 +517,9 @@ extern "C" int cocr_decoder_optim_state(cocr_model *m, int *kind, int64_t *step,
     if (!m || !kind || !step || !state || !n_floats) return fail(COCR_EINVAL, "null argument");
     if (!m->w->blob) return fail(COCR_ESTATE, "model not finalized");
     { const int rc = adopt_layout(m); if (rc) return rc; }
-    *kind = m->tr_state ? m->tr_kind : -1;
-    *step = m->tr_state ? m->tr_step : 0;
-    *state = m->tr_state;
+    *kind = m->dtr.tr_state ? m->dtr.tr_kind : -1;
+    *step = m->dtr.tr_state ? m->dtr.tr_step : 0;
+    *state = m->dtr.tr_state;
     *n_floats = 3 * ((size_t)m->ncls * m->D + (size_t)m->ncls);
     return COCR_OK;
 }
@@ -445,13 +534,13 @@ extern "C" int cocr_decoder_optim_restore(cocr_model *m, int kind, int64_t step,
     if (kind < -1 || kind > COCR_OPT_RMSPROP || step < 0 || (kind < 0 && step != 0)) return fail(COCR_EINVAL, "invalid kind %d / step %lld", kind, (long long)step);
     HIP_TRY(hipSetDevice(m->device));
     hipStream_t s = (hipStream_t)stream;
-    if (!m->tr_state) { const int rc = decoder_master_init(m, s); if (rc) return rc; }
-    HIP_TRY(hipMemcpyAsync(m->tr_state, state_device, 3 * n * 4, hipMemcpyDeviceToDevice, s));
-    m->tr_kind = kind; m->tr_step = (long)step;
+    if (!m->dtr.tr_state) { const int rc = decoder_master_init(m, s); if (rc) return rc; }
+    HIP_TRY(hipMemcpyAsync(m->dtr.tr_state, state_device, 3 * n * 4, hipMemcpyDeviceToDevice, s));
+    m->dtr.tr_kind = kind; m->dtr.tr_step = (long)step;
     const bool bf = m->dtype == COCR_BF16;
-    hipLaunchKernelGGL(k_serve_copy, dim3(64), dim3(256), 0, s, (const float *)m->tr_state, nw, bf ? (bf16_t *)(m->w->blob + m->w->plan.wdec) : (bf16_t *)nullptr,
+    hipLaunchKernelGGL(k_serve_copy, dim3(64), dim3(256), 0, s, (const float *)m->dtr.tr_state, nw, bf ? (bf16_t *)(m->w->blob + m->w->plan.wdec) : (bf16_t *)nullptr,
                        bf ? (float *)nullptr : (float *)(m->w->blob + m->w->plan.wdec));
-    hipLaunchKernelGGL(k_serve_copy, dim3(1), dim3(256), 0, s, (const float *)(m->tr_state + nw), nb, (bf16_t *)nullptr, (float *)(m->w->blob + m->w->plan.bdec));
+    hipLaunchKernelGGL(k_serve_copy, dim3(1), dim3(256), 0, s, (const float *)(m->dtr.tr_state + nw), nb, (bf16_t *)nullptr, (float *)(m->w->blob + m->w->plan.bdec));
     LAUNCH_CHECK();
     return COCR_OK;
 }

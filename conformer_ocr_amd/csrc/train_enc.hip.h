@@ -3,7 +3,7 @@
 // in fp32 unless told otherwise, cli/__init__.py:39-70): correctness-first kernels, one thread / one wave per output with fixed-order
 // reductions (no floating-point atomics: two runs of a step give the same bits).  The matrix products -- forward, input gradient and
 // weight gradient of every Linear / pointwise conv -- run on the exact-fp32 MFMA GEMM of gemm.hip.h through explicit transposes
-// (train_api.hip.h).  Train-mode semantics: BatchNorm1d with batch statistics over ALL (line, frame) positions of the padded batch
+// (train.hip).  Train-mode semantics: BatchNorm1d with batch statistics over ALL (line, frame) positions of the padded batch
 // (convolution.py:141; no masking anywhere) and running-statistics update (momentum 0.1, unbiased variance); dropout at the
 // reference's six sites (convolution.py:144,225; feed_forward.py:49,51; attention.py:98,151) from a counter-based generator, so
 // the backward regenerates the masks instead of storing them.

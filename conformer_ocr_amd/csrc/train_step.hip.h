@@ -1,4 +1,4 @@
-// What cocr_train_step (train_api.hip.h) is made of:
+// What cocr_train_step (train.hip) is made of:
 //     TrainW      the float offset of every tensor the step touches, resolved from the reference's state-dict names ONCE (train_resolve)
 //     TrainPlan   one shape's derived dimensions, every workspace offset (activations per stage / block, scratch grouped by role) and the
 //                 sizes of the three per-step arenas (train_plan)

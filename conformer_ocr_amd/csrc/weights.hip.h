@@ -1,5 +1,5 @@
 // One set of weights and everything derived from it (Weights), and a model's captured launch sequences (GraphCache): the host-side
-// bookkeeping of cocr_api.hip that is plain C++.  The two HIP calls it makes go through the macros below, so that
+// bookkeeping of the host layer (model.hip.h) that is plain C++.  The two HIP calls it makes go through the macros below, so that
 // tools/weights_lifecycle.cpp can drive it on the CPU under a sanitizer.
 #pragma once
 
@@ -78,7 +78,7 @@ struct Weights {
         invalidate();
         ++gen;
     }
-    // (cocr_api.hip; the layout's dimensions are the owner's)
+    // (the layout's dimensions are the owner's.  ensure_packed: forward.hip, the one unit that knows a Form; the positional tables: cocr_api.hip)
     int ensure_packed(const Form &f, hipStream_t s);
     int ensure_ptab(hipStream_t s);
     template <typename T> int compute_pos_tables(hipStream_t s);

@@ -1,4 +1,4 @@
-"""GPU: the pinned upload rings of the host layer (UploadRing in cocr_api.hip) -- per-line lengths of the decoders,
+"""GPU: the pinned upload rings of the host layer (UploadRing in model.hip.h) -- per-line lengths of the decoders,
 the targets of loss and forced alignment, the pair tables of the edit-distance alignment.  A ring has 16 slots; these tests keep more calls
 than that in flight behind other device work, make a ring regrow while earlier calls are pending, and alternate loss and alignment on the
 ring they share.  Every call has its own lengths / targets (all within the logits' shape: a stale slot can only give a wrong answer), and

@@ -104,6 +104,50 @@ def test_set_tensor_rejects_unknown_keys_and_compute_needs_finalize():
     lib.cocr_destroy(h)
 
 
+def test_every_unit_of_the_host_layer_reports_through_the_one_error_buffer():
+    """The host layer is several translation units over one thread-local error buffer (csrc/model.hip.h: fail).  One entry point
+    of each unit outside the core is called with an argument error it detects before its first HIP call and whose message no other
+    unit produces, directly after a different error of the core unit: cocr_last_error() reads the unit's own message.  The same
+    calls on a second thread leave their messages there and this thread's message as it was.  No GPU involved."""
+    import threading
+    lib = _lib.load()
+    h, none = C.c_void_p(), C.c_void_p()
+    assert lib.cocr_create(C.byref(_hp()), 0, C.byref(h)) == 0                  # (created, never finalized)
+    p, i32 = C.c_void_p(16), (C.c_int32 * 1)(4)                                 # non-null pointers nobody gets to read
+    i64, loss = (C.c_int64 * 2)(0, 0), C.c_float()
+    units = [
+        ('decode.hip', b'beam must be in 1..32', _lib.EINVAL, lambda: lib.cocr_ctc_beam(h, p, 1, 4, 5, i32, p, p, p, p, p, 4, 0, None)),
+        ('lines.hip', b'the output must be a buffer of its own', _lib.EINVAL, lambda: lib.cocr_augment_lines(h, p, p, 1, 16, 40, i32, p, p, 4, None)),
+        ('score.hip', b'-1 pairs', _lib.EINVAL, lambda: lib.cocr_edit_align(h, p, i64, p, i64, -1, p, p, p, None)),
+        ('train.hip', b'cocr_train_begin has not been called', _lib.ESTATE,
+         lambda: lib.cocr_train_step(h, p, _lib.F32, 1, 16, 40, i32, i32, i32, None, 0, C.byref(loss), None)),
+        ('forward.hip', b'rows per workgroup must be in 0..96', _lib.EINVAL, lambda: lib.cocr_set_chain_rows(h, 97)),
+    ]
+
+    def core_error():
+        assert lib.cocr_create(C.byref(_hp(subsampling_factor=3)), 0, C.byref(none)) == _lib.EINVAL
+        assert lib.cocr_last_error() == b'Sampling factor should be a power of 2.'
+
+    for unit, msg, code, call in units:
+        core_error()
+        assert call() == code, unit
+        assert lib.cocr_last_error() == msg, unit
+    core_error()
+    seen = []
+
+    def second_thread():
+        seen.append(lib.cocr_last_error())                                      # (a thread's buffer starts empty)
+        for unit, msg, code, call in units:
+            seen.append((call(), lib.cocr_last_error()))
+
+    t = threading.Thread(target=second_thread)
+    t.start()
+    t.join()
+    assert seen == [b''] + [(code, msg) for unit, msg, code, call in units]
+    assert lib.cocr_last_error() == b'Sampling factor should be a power of 2.'
+    lib.cocr_destroy(h)
+
+
 def test_codec_roundtrip_and_longest_match():
     c = PytorchCodec({'a': [1], 'b': [2], 'ch': [3, 4], 'c': [3]})
     assert c.max_label == 4 and len(c) == 4 and c.is_valid

@@ -1,7 +1,8 @@
 #!/usr/bin/env python3
-"""Prints a sha256 of the compiled gfx950 code of every kernel of the given .hip units (default: the three row-chain units).
+"""Prints a sha256 of the compiled gfx950 code of every kernel of the library, by kernel name (the default) or of the given .hip
+units, unit by unit.
 
-    tools/kernel_isa.py [--against OTHER_CSRC_DIR] [--json OUT] [unit.hip ...]
+    tools/kernel_isa.py [--against OTHER_CSRC_DIR] [--json OUT] [--by-name | unit.hip ...]
 
 Each unit is compiled with the flags of build.py (COCR_HIPCC_FLAGS included) plus --offload-device-only -S.  The assembly is
 normalised -- comment lines, trailing `;` comments, .file and .ident dropped, __hip_cuid_<hex> made a constant, the number of
@@ -10,7 +11,10 @@ number only counts the kernels emitted before this one, the block number that te
 piece holds one kernel, so no two labels fall together) -- and cut into one piece per kernel (code and kernel descriptor).
 --against: the units of the same names in another csrc directory (a checkout of another commit) are compiled too and the
 kernels that differ, or exist on one side only, are listed; the exit status is 1 if there are any.  A refactor that moves
-code verbatim leaves every hash as it is; one that merely looks equivalent usually does not."""
+code verbatim leaves every hash as it is; one that merely looks equivalent usually does not.
+--by-name (the default when no unit is named): every *.hip of each tree is compiled and {kernel name: hash} is compared over the
+union of a tree's units, for changes that move kernels between units.  A kernel compiled into several units of one tree (a
+template two units instantiate alike) must have one hash there; those kernels are listed."""
 import argparse
 import hashlib
 import json
@@ -23,7 +27,6 @@ from concurrent.futures import ThreadPoolExecutor
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 CSRC = os.path.join(ROOT, 'conformer_ocr_amd', 'csrc')
-UNITS = ['rowchain_d256.hip', 'rowchain_d256_head.hip', 'rowchain_d512.hip']
 
 
 def assembly(csrc, unit, tmp):
@@ -64,13 +67,57 @@ def demangle(names):
     return {n: re.sub(r'^void ', '', re.sub(r'\(.*', '', d)) for n, d in zip(names, res)}
 
 
+def by_name(dirs, json_out):
+    """Every unit of each tree; kernels compared by name over the union of a tree's units."""
+    units = {d: sorted(f for f in os.listdir(d) if f.endswith('.hip')) for d in dirs}
+    with tempfile.TemporaryDirectory() as tmp, ThreadPoolExecutor(max_workers=8) as pool:
+        jobs = {(d, u): pool.submit(assembly, d, u, tmp) for d in dirs for u in units[d]}
+        trees = []
+        for d in dirs:                    # {kernel: {hash: [units]}}
+            tree = {}
+            for u in units[d]:
+                for n, h in kernels(jobs[(d, u)].result()).items():
+                    tree.setdefault(n, {}).setdefault(h, []).append(u)
+            trees.append(tree)
+    new, old = trees[0], trees[1] if len(trees) > 1 else None
+    names = demangle(sorted(set(new) | set(old or {})))
+    one = lambda t, n: sorted(t[n])[0] if n in t else None
+    rows, bad = [], 0
+    for n in sorted(names, key=names.get):
+        row = {'name': names[n], 'sha256': one(new, n), 'units': sorted(u for us in new.get(n, {}).values() for u in us)}
+        split = len(new.get(n, {})) > 1 or (old is not None and len(old.get(n, {})) > 1)      # units of one tree disagree
+        if old is not None:
+            row['against'] = one(old, n)
+            row['against_units'] = sorted(u for us in old.get(n, {}).values() for u in us)
+        same = not split and (old is None or row['against'] == row['sha256'])
+        bad += not same
+        rows.append(row)
+        print('%s %s %s  [%s]' % ((row['sha256'] or '-' * 64)[:16], '  ' if same else '!=', names[n], ' '.join(u[:-4] for u in row['units'])))
+        if not same:
+            print('%s    (%s%s)' % ((row.get('against') or '-' * 64)[:16], 'against' if old is not None else '', ', units of one tree disagree' if split else ''))
+    dups = [r for r in rows if len(r['units']) > 1]
+    print('kernels compiled into several units (%d):' % len(dups))
+    for r in dups:
+        print('    %s  [%s]' % (r['name'], ' '.join(u[:-4] for u in r['units'])))
+    print('%d kernels in %d units' % (len(new), len(units[dirs[0]])) + ('' if old is None else ', %d in the %d units of the other tree, %d differ, are missing or are new'
+          % (len(old), len(units[dirs[1]]), bad)))
+    if json_out:
+        with open(json_out, 'w') as fp:
+            json.dump({'kernels': rows, 'several_units': [r['name'] for r in dups]}, fp, indent=1)
+            fp.write('\n')
+    return 1 if bad else 0
+
+
 def main():
     ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
     ap.add_argument('--against', help='csrc directory of another checkout to compare with')
     ap.add_argument('--json', help='write {unit: [{name, sha256[, against]}]} there')
-    ap.add_argument('units', nargs='*', default=UNITS)
+    ap.add_argument('--by-name', action='store_true', help='every unit of each tree, kernels compared by name (the default when no unit is named)')
+    ap.add_argument('units', nargs='*')
     a = ap.parse_args()
     dirs = [CSRC] + ([os.path.abspath(a.against)] if a.against else [])
+    if a.by_name or not a.units:
+        return by_name(dirs, a.json)
     with tempfile.TemporaryDirectory() as tmp, ThreadPoolExecutor(max_workers=6) as pool:
         jobs = {(d, u): pool.submit(assembly, d, os.path.basename(u), tmp) for d in dirs for u in a.units}
         hashes = {k: kernels(j.result()) for k, j in jobs.items()}

@@ -9,7 +9,7 @@ import tempfile
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 flags = ['/opt/rocm/bin/hipcc', '--offload-arch=gfx950', '-O3', '-std=c++17', '-fPIC', '-fno-gpu-rdc', '-mllvm', '-amdgpu-mfma-vgpr-form', '-I', ROOT + '/include',
          '-Rpass-analysis=kernel-resource-usage']
-# every translation unit of the library (cocr_api.hip and the row-chain instantiation units), compiled side by side
+# every translation unit of the library (the host layer's units and the row-chain instantiation units), compiled side by side
 with tempfile.TemporaryDirectory() as tmp:
     procs = [subprocess.Popen(flags + ['-c', u, '-o', os.path.join(tmp, os.path.basename(u) + '.o')], stderr=subprocess.PIPE, text=True)
              for u in sorted(glob.glob(ROOT + '/conformer_ocr_amd/csrc/*.hip'))]

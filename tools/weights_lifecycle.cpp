@@ -19,7 +19,7 @@ static void dev_free(void *p) { --g_live; free(p); }
 #define COCR_GRAPH_EXEC_DESTROY(e) dev_free(e)
 #include "../conformer_ocr_amd/csrc/weights.hip.h"
 
-// as much of a model as the lifecycle needs; create / finalize / share / destroy do what cocr_api.hip does with the set
+// as much of a model as the lifecycle needs; create / finalize / share / destroy do what cocr_api.hip does with the set (forward: forward.hip's sync_weights)
 struct cocr_model {
     WeightsRef w;
     unsigned long long seen_gen = 0;
