@@ -1,10 +1,11 @@
 // What follows the forward behind the C ABI (units of the host layer: model.hip.h): the CTC decoders (greedy, beam, beam with an
-// n-gram model), the n-gram model itself, the CTC criterion and forced alignment.
+// n-gram model), the n-gram model itself, the CTC criterion, forced alignment and keyword spotting.
 #include "model.hip.h"
 #include "ctc.hip.h"
 #include "ctc_lm.hip.h"
 #include "ctc_loss.hip.h"
 #include "ctc_align.hip.h"
+#include "ctc_spot.hip.h"
 
 // ------------------------------------------------------------------------------------ CTC
 // The per-line lengths reach the decode kernels through a PINNED host ring: an async copy from pageable memory goes through the
@@ -254,6 +255,58 @@ extern "C" int cocr_ctc_align(cocr_model *m, const float *logits, int N, int T, 
         HIP_TRY(m->dec.align_ws.grow((size_t)N * words));
         launch_ctc_align<false>(s, sj, ctca_lz_bytes(T), logits, N, T, ncls, t.lens, t.label_lens, t.label_off, t.labels, starts, ends, conf, score, counts,
                                 m->dec.align_ws.p, words);
+    }
+    LAUNCH_CHECK();
+    return COCR_OK;
+}
+
+// ------------------------------------------------------------------------------------ keyword spotting (ctc_spot.hip.h)
+extern "C" int cocr_ctc_spot(cocr_model *m, const float *logits, int N, int T, int ncls, const int32_t *out_lens, const int32_t *queries,
+                             const int32_t *query_lens, int Q, int hits, float min_score, int32_t *starts, int32_t *ends, float *score,
+                             int32_t *counts, void *stream) {
+    if (!m || !logits || !out_lens || !queries || !query_lens || !starts || !ends || !score || !counts) return fail(COCR_EINVAL, "null argument");
+    if (N < 1 || T < 1 || ncls < 2) return fail(COCR_EINVAL, "empty problem");
+    if (Q < 1) return fail(COCR_EINVAL, "no query");
+    if (hits < 1 || hits > COCR_SPOT_MAX_HITS) return fail(COCR_EINVAL, "hits must be in 1..%d", COCR_SPOT_MAX_HITS);
+    if (std::isnan(min_score)) return fail(COCR_EINVAL, "min_score is NaN");
+    if (T > 8000) return fail(COCR_EUNSUPPORTED, "more than 8000 frames per line");
+    if (N > 65535) return fail(COCR_EUNSUPPORTED, "more than 65535 lines in one call");
+    for (int n = 0; n < N; ++n)
+        if (out_lens[n] < 0 || out_lens[n] > T) return fail(COCR_EINVAL, "input length %d outside [0, %d] (line %d)", out_lens[n], T, n);
+    size_t total = 0;
+    int max_l = 0;
+    for (int q = 0; q < Q; ++q) {
+        if (query_lens[q] < 1 || query_lens[q] > COCR_SPOT_MAX_LABELS)
+            return fail(COCR_EINVAL, "query %d has %d labels; a query holds 1..%d", q, query_lens[q], COCR_SPOT_MAX_LABELS);
+        max_l = std::max(max_l, (int)query_lens[q]);
+        total += (size_t)query_lens[q];
+    }
+    for (size_t i = 0; i < total; ++i)
+        if (queries[i] < 1 || queries[i] >= ncls) return fail(COCR_EINVAL, "query label %d outside [1, %d) (blank is 0)", queries[i], ncls);
+    HIP_TRY(hipSetDevice(m->device));
+    hipStream_t s = (hipStream_t)stream;
+    const size_t ints = (size_t)N + 2 * (size_t)Q + total;
+    int32_t *h, *d;
+    HIP_TRY(m->dec.spot_ring.stage(ints * 4, h, d));
+    memcpy(h, out_lens, (size_t)N * 4);
+    int32_t off = 0;
+    for (int q = 0; q < Q; ++q) { h[N + q] = query_lens[q]; h[N + Q + q] = off; off += query_lens[q]; }
+    memcpy(h + N + 2 * Q, queries, total * 4);
+    HIP_TRY(m->dec.spot_ring.commit(ints * 4, s));
+    const int states = 2 * max_l - 1;
+    const int sj = states <= 64 ? 1 : states <= 128 ? 2 : states <= 256 ? 4 : 8;
+    // the candidate tables (e_t, sigma_t) of the workgroup's four pairs: in LDS beside mx when all fit (the kernel has 4 KB of static
+    // LDS), else one region per pair of the workspace
+    const size_t row = ctcs_row_bytes(T), lds_all = 9 * row;
+    if (lds_all <= 144 * 1024) {
+        auto kern = ctc_spot_kernel<8, true>;
+        switch (sj) { case 1: kern = ctc_spot_kernel<1, true>; break; case 2: kern = ctc_spot_kernel<2, true>; break; case 4: kern = ctc_spot_kernel<4, true>; break; }
+        HIP_TRY(raise_lds_limit((const void *)kern, lds_all, 48 * 1024, 150 * 1024));
+        launch_ctc_spot<true>(s, sj, lds_all, logits, N, T, ncls, d, d + N, d + N + Q, d + N + 2 * Q, Q, hits, min_score, starts, ends, score, counts, nullptr);
+    } else {
+        HIP_TRY(m->dec.spot_ws.grow((size_t)N * Q * ctcs_pair_words(T)));
+        launch_ctc_spot<false>(s, sj, row, logits, N, T, ncls, d, d + N, d + N + Q, d + N + 2 * Q, Q, hits, min_score, starts, ends, score, counts,
+                               m->dec.spot_ws.p);
     }
     LAUNCH_CHECK();
     return COCR_OK;

@@ -2,7 +2,7 @@
 // model (struct cocr_model, its state grouped by the unit that writes it) and the few functions that cross units.  The units:
 //     cocr_api.hip   error buffer, model lifetime, layout, finalize / share / blob, positional tables, workspace, taps, profiler
 //     forward.hip    the forward: its form, its stages, the graph cache's use, the entry point; the GEMM micro-benchmark
-//     decode.hip     CTC decoders, n-gram model, criterion, forced alignment
+//     decode.hip     CTC decoders, n-gram model, criterion, forced alignment, keyword spotting
 //     lines.hip      line collation, pre-processing, page extraction, augmentation
 //     score.hip      edit-distance alignment
 //     train.hip      output-layer training and the training step of the whole network
@@ -177,6 +177,8 @@ struct COCR_INTERNAL DecodeScratch {
     UploadRing target_ring;                 // cocr_ctc_loss, cocr_ctc_align: [lens | label lens | label offsets | labels] (upload_targets)
     DevBuf<float> loss_ws;                  // log-softmax + alpha / beta tables
     DevBuf<unsigned> align_ws;              // back-pointer tables of the lines too long for the LDS
+    UploadRing spot_ring;                   // cocr_ctc_spot: [lens | query lens | query offsets | queries]
+    DevBuf<unsigned> spot_ws;               // cocr_ctc_spot: per (line, query) the candidate scores and starts of lines too long for the LDS
 };
 
 // Written by lines.hip.

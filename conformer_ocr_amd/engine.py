@@ -353,6 +353,58 @@ class HipRecognizer:
     def ctc_align(self, logits: torch.Tensor, out_lens, targets, label_lens):
         return self.collect_align(self.ctc_align_async(logits, out_lens, targets, label_lens))
 
+    # ---- keyword spotting (include/cocr.h: cocr_ctc_spot) ----------
+    def ctc_spot_async(self, logits: torch.Tensor, out_lens, queries, hits: int = 1, min_score: float = -np.inf):
+        """Enqueues the search for every query in every line on the current stream, its outputs in pinned host memory; returns a
+        handle for `collect_spot`.  logits (N,T,ncls) float32 on this device; out_lens (N) valid frames; queries: Q label sequences
+        (1..255 labels each); hits: 1..8 per (line, query); min_score: the selection stops below it.  Does not touch the forward's
+        per-frame argmax: a `ctc_greedy` on the same logits afterwards still takes its shortcut."""
+        if logits.device != self.device or logits.dtype != torch.float32 or logits.dim() != 3:
+            raise RuntimeError('logits must be a float32 (N,T,num_classes) tensor on the model device')
+        cont = logits.contiguous()
+        N, T, ncls = cont.shape
+        lens = np.ascontiguousarray(np.asarray(out_lens, dtype=np.int32).reshape(-1))
+        if lens.shape[0] != N:
+            raise ValueError('out_lens needs one entry per line')
+        qs = [np.asarray(q, dtype=np.int32).reshape(-1) for q in queries]
+        Q, K = len(qs), int(hits)
+        ql = np.ascontiguousarray(np.asarray([q.shape[0] for q in qs], dtype=np.int32))
+        qv = np.ascontiguousarray(np.concatenate(qs + [np.zeros(0, dtype=np.int32)]), dtype=np.int32)
+        i32 = C.POINTER(C.c_int32)
+        with torch.cuda.device(self.device):
+            cap = max(N * Q, 1) * min(max(K, 1), 8)
+            key = ('spot', cap, max(N * Q, 1))
+            pool = self._pinned.setdefault(key, [])
+            host = pool.pop() if pool else (torch.empty((2, cap), dtype=torch.int32).pin_memory(),
+                                            torch.empty((cap,), dtype=torch.float32).pin_memory(),
+                                            torch.empty((key[2],), dtype=torch.int32).pin_memory())
+            ints, score, counts = host
+            try:
+                _lib.check(self.lib.cocr_ctc_spot(self._h, C.c_void_p(cont.data_ptr()), N, T, ncls, lens.ctypes.data_as(i32),
+                                                  qv.ctypes.data_as(i32), ql.ctypes.data_as(i32), Q, K, C.c_float(min_score),
+                                                  C.c_void_p(ints[0].data_ptr()), C.c_void_p(ints[1].data_ptr()), C.c_void_p(score.data_ptr()),
+                                                  C.c_void_p(counts.data_ptr()), _stream_ptr(self.device)))
+            except Exception:
+                pool.append(host)                                   # nothing was launched: the buffers go back
+                raise
+            ev = torch.cuda.Event()
+            ev.record(torch.cuda.current_stream(self.device))
+        return (key, host, ev, (cont, N, Q, K))
+
+    def collect_spot(self, handle) -> List[List[List[Tuple[int, int, float]]]]:
+        """Waits for a `ctc_spot_async` handle; per line, per query [(start, end, score)], best first."""
+        key, host, ev, (_, N, Q, K) = handle
+        ev.synchronize()
+        st, en = host[0].numpy()[:, :N * Q * K].reshape(2, N, Q, K).tolist()
+        sc = host[1].numpy()[:N * Q * K].reshape(N, Q, K).tolist()
+        cnt = host[2].numpy()[:N * Q].reshape(N, Q).tolist()
+        out = [[list(zip(st[n][q][:cnt[n][q]], en[n][q][:cnt[n][q]], sc[n][q][:cnt[n][q]])) for q in range(Q)] for n in range(N)]
+        self._pinned[key].append(host)
+        return out
+
+    def ctc_spot(self, logits: torch.Tensor, out_lens, queries, hits: int = 1, min_score: float = -np.inf):
+        return self.collect_spot(self.ctc_spot_async(logits, out_lens, queries, hits, min_score))
+
     # ---- output-layer training step (include/cocr.h: cocr_decoder_backward / cocr_decoder_adamw) ----------
     def decoder_backward(self, grad_probits: torch.Tensor, with_input_grad: bool = False):
         """Gradients of the decoder `nn.Linear` for the LAST forward on this engine: (grad_weight (ncls, D), grad_bias (ncls),

@@ -443,6 +443,68 @@ class PytorchRecognitionModel(nn.Module):
         'score': the path's log-probability, 'frames': the line's output length, 'skipped': the characters the codec cannot encode}."""
         return self.collect_align(self.align_async(line, lens, texts))
 
+    # ------------------------------------------------------------------ keyword spotting (conformer_ocr_amd/search.py, DESIGN.md section 7i)
+    def spot_labels_async(self, line: torch.Tensor, lens: torch.Tensor, queries, hits: int = 1, min_score: float = -np.inf):
+        """Forward + `cocr_ctc_spot` enqueued on the current stream; returns a handle for `collect_spot_labels`.  A query of more than
+        255 labels (the kernel's bound) is searched by `search.spot_host` on the lines' own logits when the handle is collected."""
+        from .search import MAX_DEVICE_HITS, MAX_DEVICE_LABELS
+        queries = [[int(l) for l in q] for q in queries]
+        if not queries or not all(queries):
+            raise ValueError('no query, or an empty one')
+        if not 1 <= int(hits) <= MAX_DEVICE_HITS:
+            raise ValueError(f'hits must lie in 1..{MAX_DEVICE_HITS}')
+        o, olens = self.forward(line, lens)
+        eng = self._engine             # (a re-pack may replace `self._engine` before the collect)
+        olens = olens.numpy()
+        short = [i for i, q in enumerate(queries) if len(q) <= MAX_DEVICE_LABELS]
+        handle = eng.ctc_spot_async(o, olens, [queries[i] for i in short], hits, min_score) if short else None
+        return eng, handle, o, olens, queries, short, int(hits), float(min_score)
+
+    def collect_spot_labels(self, pending):
+        """Waits for a `spot_labels_async` handle: (per line, per query [(start, end, score)], the lines' output lengths)."""
+        from .search import spot_host
+        eng, handle, o, olens, queries, short, hits, min_score = pending
+        out = [[[] for _ in queries] for _ in range(o.shape[0])]
+        if handle is not None:
+            for n, per_query in enumerate(eng.collect_spot(handle)):
+                for i, spots in zip(short, per_query):
+                    out[n][i] = spots
+        long_queries = sorted(set(range(len(queries))) - set(short))
+        if long_queries:
+            host = o.cpu().numpy()
+            for n in range(o.shape[0]):
+                x = host[n, :int(olens[n])].T
+                for i in long_queries:
+                    out[n][i] = spot_host(x, queries[i], hits, min_score)
+        return out, olens
+
+    def spot_labels(self, line: torch.Tensor, lens: torch.Tensor, queries, hits: int = 1, min_score: float = -np.inf):
+        """Keyword spotting of label sequences: forward pass on a (N, C, H, W) batch, then per line and per query up to `hits`
+        non-overlapping occurrences [(start, end, score)], best first (`search.spot_host` is the definition: score is the log-ratio
+        of the query's best path over frames start..end to the unconstrained best path there, 0 when the query is what is read
+        there).  `min_score`: occurrences below it are not reported."""
+        return self.collect_spot_labels(self.spot_labels_async(line, lens, queries, hits, min_score))[0]
+
+    def spot(self, line: torch.Tensor, lens: torch.Tensor, texts, hits: int = 1, min_score: float = -np.inf) -> Dict:
+        """Keyword spotting of strings: `texts` are encoded with `self.codec.encode`.  Returns {'hits': per line, per text
+        [(start, end, score)] -- empty for a text that is not searched --, 'frames': the lines' output lengths, 'skipped': per text the
+        characters the codec cannot encode ('' where the text was searched; a text with such characters, or one that encodes to
+        nothing, is not searched)}."""
+        from .align import encode_text
+        texts = list(texts)
+        enc = [encode_text(self.codec, t) for t in texts]
+        searched = [i for i, (lab, sk) in enumerate(enc) if lab and not sk]
+        skipped = ['' if lab and not sk else (sk or t) for t, (lab, sk) in zip(texts, enc)]
+        if not searched:
+            o, olens = self.forward(line, lens)
+            return {'hits': [[[] for _ in texts] for _ in range(o.shape[0])], 'frames': [int(l) for l in olens], 'skipped': skipped}
+        found, olens = self.collect_spot_labels(self.spot_labels_async(line, lens, [enc[i][0] for i in searched], hits, min_score))
+        out = [[[] for _ in texts] for _ in found]
+        for n, per_query in enumerate(found):
+            for i, spots in zip(searched, per_query):
+                out[n][i] = spots
+        return {'hits': out, 'frames': [int(l) for l in olens], 'skipped': skipped}
+
     @classmethod
     def load_safetensors(cls, path, **kwargs):
         """

@@ -190,6 +190,22 @@ int cocr_ctc_loss(cocr_model *m, const float *probits, int N, int T, int ncls, c
 int cocr_ctc_align(cocr_model *m, const float *logits, int N, int T, int ncls, const int32_t *out_lens, const int32_t *targets,
                    const int32_t *label_lens, int32_t *starts, int32_t *ends, float *conf, float *score, int32_t *counts, void *stream);
 
+/* Keyword spotting (the definition is conformer_ocr_amd/search.py spot_host): where each of Q label sequences
+ * occurs in each of N lines.  With r_t(c) = logits[t, c] - max_c' logits[t, c'], a candidate ending at frame t is the best path that
+ * spells the query over some window [start, t] -- first frame on the first label, last frame on the last label, blanks between labels
+ * optional except between equal ones -- and its score the sum of r over the window: the log-ratio to the unconstrained best path
+ * there, 0 exactly when the query's path is the frame-wise argmax.  Ties keep the earlier of (stay, from s-1, from s-2, fresh start).
+ * Up to `hits` non-overlapping candidates are selected per (line, query), best first (ties: the later end); the selection stops at
+ * the first candidate below min_score (-inf: none).
+ * logits DEVICE float32 (N,T,ncls); out_lens (N), queries (concatenated) and query_lens (Q) HOST, checked before any launch:
+ * COCR_EINVAL for a label outside [1, ncls), a query length outside 1..255, out_lens[n] outside [0, T], hits outside 1..8, Q < 1 or a
+ * NaN min_score; COCR_EUNSUPPORTED for T > 8000.  Outputs DEVICE or device-visible pinned host memory: starts / ends int32 and score
+ * float32 (N,Q,hits), counts int32 (N,Q); entries past the count are -1 / -1 / -inf.  Does not touch the greedy decoder's argmax
+ * scratch.  Deterministic (no atomics).  Stream-ordered, does not synchronise (ring or workspace growth does). */
+int cocr_ctc_spot(cocr_model *m, const float *logits, int N, int T, int ncls, const int32_t *out_lens, const int32_t *queries,
+                  const int32_t *query_lens, int Q, int hits, float min_score, int32_t *starts, int32_t *ends, float *score,
+                  int32_t *counts, void *stream);
+
 /* Training step of the output layer: the part of the reference's `training_step` (model.py:147-152, autograd through
  * `nn['decoder'] = nn.Linear(encoder_dim, num_classes)`, model.py:115) between the encoder output and the criterion, and the
  * reference's default optimizer (`torch.optim.AdamW`, model.py:47,283-284).  The encoder's backward is not in this library yet;
