@@ -56,12 +56,15 @@ SYMBOLS = {
     'cocr_lm_destroy': (None, [_P]),
     'cocr_ctc_beam_lm': (_I, [_P, _P, _P, _I, _I, _I, _I32P, _P, _P, _P, _P, _P, _I, _I, _I, C.c_float, C.c_float, _P, _P]),
     'cocr_ctc_loss': (_I, [_P, _P, _I, _I, _I, _I32P, _I32P, _I32P, _P, _P, _P]),
+    'cocr_distill_loss': (_I, [_P, _P, _P, _I, _I, _I, _I32P, C.c_float, _P, _P, C.c_float, C.c_float, _I, _P]),
     'cocr_ctc_align': (_I, [_P, _P, _I, _I, _I, _I32P, _I32P, _I32P, _P, _P, _P, _P, _P, _P]),
     'cocr_ctc_spot': (_I, [_P, _P, _I, _I, _I, _I32P, _I32P, _I32P, _I, _I, C.c_float, _P, _P, _P, _P, _P]),
     'cocr_decoder_backward':(_I, [_P, _P, _I, _I, _P, _P, _P, _P]),
     'cocr_decoder_adamw': (_I, [_P, _P, _P, C.c_float, C.c_float, C.c_float, C.c_float, C.c_float, _P]),
     'cocr_train_begin': (_I, [_P]),
     'cocr_train_step': (_I, [_P, _P, _I, _I, _I, _I, _I32P, _I32P, _I32P, C.POINTER(C.c_float), C.c_uint64, C.POINTER(C.c_float), _P]),
+    'cocr_train_step_distill': (_I, [_P, _P, _I, _I, _I, _I, _I32P, _I32P, _I32P, C.POINTER(C.c_float), C.c_uint64, _P, C.c_float, C.c_float,
+                                     C.POINTER(C.c_float), _P]),
     'cocr_train_get': (_I, [_P, C.c_char_p, _I, _P, C.c_int64, _P]),
     'cocr_train_adamw': (_I, [_P, C.c_float, C.c_float, C.c_float, C.c_float, C.c_float, _P]),
     'cocr_train_end': (_I, [_P]),

@@ -85,15 +85,23 @@ class TrainBridge:
 
 
 class _TrainStep(torch.autograd.Function):
-    """loss = CTC(train-mode forward(lines)); d loss / d every parameter comes from the same library call."""
+    """loss = CTC(train-mode forward(lines)), with teacher logits (1 - weight) CTC + weight KD; d loss / d every
+    parameter comes from the same library call."""
+    LEADING = 11                                          # arguments of `forward` in front of the parameters
 
     @staticmethod
-    def forward(ctx, bridge: TrainBridge, lines, lens, targets, target_lens, dropout, seed, names_p, *params):
+    def forward(ctx, bridge: TrainBridge, lines, lens, targets, target_lens, dropout, seed, names_p, teacher_logits, tau, weight, *params):
         eng = bridge.engine
         with torch.no_grad():
             dst = bridge.slices(bridge.P, names_p, list(params))
             torch._foreach_copy_(dst, [p.detach().to(device=eng.device, dtype=torch.float32) for p in params])
-        loss = eng.train_step(lines, lens, targets, target_lens, dropout=dropout, seed=seed)
+        if teacher_logits is None:
+            loss = eng.train_step(lines, lens, targets, target_lens, dropout=dropout, seed=seed)
+        else:
+            ctc, kd = eng.train_step(lines, lens, targets, target_lens, dropout=dropout, seed=seed, teacher_logits=teacher_logits.detach(), tau=tau,
+                                     distill_weight=weight)
+            bridge.last_ctc_loss, bridge.last_kd_loss = ctc, kd
+            loss = (1.0 - weight) * ctc + weight * kd
         grads = bridge.G.clone()                          # this step's gradients, owned by autograd from here on
         ctx.bridge, ctx.names_p = bridge, names_p
         ctx.shapes = [p.shape for p in params]
@@ -106,20 +114,22 @@ class _TrainStep(torch.autograd.Function):
         (grads,) = ctx.saved_tensors
         b = ctx.bridge
         out = []
-        for k, shp, dt, need in zip(ctx.names_p, ctx.shapes, ctx.dtypes, ctx.needs_input_grad[8:]):
+        for k, shp, dt, need in zip(ctx.names_p, ctx.shapes, ctx.dtypes, ctx.needs_input_grad[_TrainStep.LEADING:]):
             if not need:
                 out.append(None)
                 continue
             off, n, _ = b.layout[k]
             g = grads[off:off + n].view(shp)
             out.append((g * grad_loss).to(dt))
-        return (None,) * 8 + tuple(out)
+        return (None,) * _TrainStep.LEADING + tuple(out)
 
 
-def training_step(net, batch: Dict, seed: int = None) -> torch.Tensor:
+def training_step(net, batch: Dict, seed: int = None, teacher_logits: torch.Tensor = None, tau: float = 1.0, distill_weight: float = 0.0) -> torch.Tensor:
     """`RecognitionModel.training_step` (model.py:147-152) for `net` = a `PytorchRecognitionModel` in train mode: returns the batch's
     summed CTC loss as a differentiable 0-dim device tensor.  batch: {'image' (N,1,H,W), 'seq_lens' (N), 'target' (sum target_lens,),
-    'target_lens' (N)} -- the reference's batch dict (model.py:131-138)."""
+    'target_lens' (N)} -- the reference's batch dict (model.py:131-138).
+    teacher_logits (N,T,ncls) float32 on the model's device: the scalar is the weighted total (1 - distill_weight) CTC + distill_weight KD
+    at temperature tau, its gradient that of `cocr_train_step_distill`; no gradient reaches the teacher."""
     bridge = getattr(net, '_train_bridge', None)
     dev = next(net.nn.parameters()).device
     if bridge is None or bridge.engine.device != dev or bridge.matmul_precision != getattr(net, 'matmul_precision', 'highest'):
@@ -135,7 +145,8 @@ def training_step(net, batch: Dict, seed: int = None) -> torch.Tensor:
     if seed is None:
         seed = int(getattr(net, 'dropout_seed', 0)) * 1000003 + bridge.steps
     loss = _TrainStep.apply(bridge, lines, torch.as_tensor(batch['seq_lens']).cpu().numpy(), torch.as_tensor(batch['target']).cpu().numpy(),
-                            torch.as_tensor(batch['target_lens']).cpu().numpy(), tuple(net.dropout_p), int(seed), names_p, *params)
+                            torch.as_tensor(batch['target_lens']).cpu().numpy(), tuple(net.dropout_p), int(seed), names_p,
+                            None if teacher_logits is None else teacher_logits.to(dev), float(tau), float(distill_weight), *params)
     with torch.no_grad():                                 # what nn.BatchNorm1d.forward does to its buffers in train mode
         if bufs:
             torch._foreach_copy_(bufs, [s.to(b.dtype) for s, b in zip(bridge.slices(bridge.P, names_b, bufs), bufs)])

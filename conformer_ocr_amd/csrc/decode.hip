@@ -1,9 +1,10 @@
 // What follows the forward behind the C ABI (units of the host layer: model.hip.h): the CTC decoders (greedy, beam, beam with an
-// n-gram model), the n-gram model itself, the CTC criterion, forced alignment and keyword spotting.
+// n-gram model), the n-gram model itself, the CTC criterion, the distillation term, forced alignment and keyword spotting.
 #include "model.hip.h"
 #include "ctc.hip.h"
 #include "ctc_lm.hip.h"
 #include "ctc_loss.hip.h"
+#include "distill.hip.h"
 #include "ctc_align.hip.h"
 #include "ctc_spot.hip.h"
 
@@ -230,6 +231,39 @@ extern "C" int cocr_ctc_loss(cocr_model *m, const float *probits, int N, int T, 
     launch_ctc_loss(s, sj, (size_t)ncls * 4, probits, N, T, ncls, t.lens, t.label_lens, t.label_off, t.labels, nll, grad, m->dec.loss_ws.p, m->dec.loss_ws.p + (size_t)N * T * ncls);
     LAUNCH_CHECK();
     return COCR_OK;
+}
+
+// ------------------------------------------------------------------------------------ distillation term (distill.hip.h)
+// frame_ws: N T floats of the caller's for the per-frame values (the training step's planned workspace), or null: the model's own scratch
+int distill_loss_on(cocr_model *m, const float *student, const float *teacher, int N, int T, int ncls, const int32_t *out_lens, float tau, float *kd, float *grad,
+                    float ctc_weight, float kd_weight, int accumulate, float *frame_ws, hipStream_t s) {
+    if (!m || !student || !teacher || !out_lens || !kd) return fail(COCR_EINVAL, "null argument");
+    if (N < 1 || T < 1 || ncls < 2) return fail(COCR_EINVAL, "empty problem");
+    if ((size_t)N * T > (size_t)1 << 30) return fail(COCR_EUNSUPPORTED, "more than 2^30 frames in one call");
+    if (!std::isfinite(tau) || !(tau > 0.f)) return fail(COCR_EINVAL, "the temperature must be finite and positive, not %g", (double)tau);
+    if (!std::isfinite(ctc_weight) || ctc_weight < 0.f || !std::isfinite(kd_weight) || kd_weight < 0.f)
+        return fail(COCR_EINVAL, "the weights must be finite and not negative (%g, %g)", (double)ctc_weight, (double)kd_weight);
+    if (accumulate != 0 && accumulate != 1) return fail(COCR_EINVAL, "accumulate must be 0 or 1");
+    for (int n = 0; n < N; ++n)
+        if (out_lens[n] < 0 || out_lens[n] > T) return fail(COCR_EINVAL, "input length %d outside [0, %d] (line %d)", out_lens[n], T, n);
+    if (ncls > 16384) return fail(COCR_EUNSUPPORTED, "more than 16384 classes");
+    HIP_TRY(hipSetDevice(m->device));
+    if (!frame_ws) {
+        if ((size_t)N * T > m->dec.distill_ws.n) HIP_TRY(hipDeviceSynchronize());      // (launches in flight may still write the old scratch)
+        HIP_TRY(m->dec.distill_ws.grow((size_t)N * T));
+        frame_ws = m->dec.distill_ws.p;
+    }
+    const int32_t *d_lens;
+    const int rc = upload_lens(m, out_lens, N, s, d_lens);
+    if (rc) return rc;
+    launch_distill(s, student, teacher, N, T, ncls, d_lens, tau, frame_ws, kd, grad, ctc_weight, kd_weight, accumulate);
+    LAUNCH_CHECK();
+    return COCR_OK;
+}
+
+extern "C" int cocr_distill_loss(cocr_model *m, const float *student, const float *teacher, int N, int T, int ncls, const int32_t *out_lens, float tau, float *kd,
+                                 float *grad, float ctc_weight, float kd_weight, int accumulate, void *stream) {
+    return distill_loss_on(m, student, teacher, N, T, ncls, out_lens, tau, kd, grad, ctc_weight, kd_weight, accumulate, nullptr, (hipStream_t)stream);
 }
 
 // ------------------------------------------------------------------------------------ forced alignment (ctc_align.hip.h)

@@ -2,7 +2,7 @@
 // model (struct cocr_model, its state grouped by the unit that writes it) and the few functions that cross units.  The units:
 //     cocr_api.hip   error buffer, model lifetime, layout, finalize / share / blob, positional tables, workspace, taps, profiler
 //     forward.hip    the forward: its form, its stages, the graph cache's use, the entry point; the GEMM micro-benchmark
-//     decode.hip     CTC decoders, n-gram model, criterion, forced alignment, keyword spotting
+//     decode.hip     CTC decoders, n-gram model, criterion, distillation term, forced alignment, keyword spotting
 //     lines.hip      line collation, pre-processing, page extraction, augmentation
 //     score.hip      edit-distance alignment
 //     train.hip      output-layer training and the training step of the whole network
@@ -176,6 +176,7 @@ struct COCR_INTERNAL DecodeScratch {
     DevBuf<unsigned char> lm_scratch;       // cocr_ctc_beam_lm: back-pointers, then the frame records
     UploadRing target_ring;                 // cocr_ctc_loss, cocr_ctc_align: [lens | label lens | label offsets | labels] (upload_targets)
     DevBuf<float> loss_ws;                  // log-softmax + alpha / beta tables
+    DevBuf<float> distill_ws;               // cocr_distill_loss: the per-frame KL values
     DevBuf<unsigned> align_ws;              // back-pointer tables of the lines too long for the LDS
     UploadRing spot_ring;                   // cocr_ctc_spot: [lens | query lens | query offsets | queries]
     DevBuf<unsigned> spot_ws;               // cocr_ctc_spot: per (line, query) the candidate scores and starts of lines too long for the LDS
@@ -263,5 +264,7 @@ template <typename T> COCR_INTERNAL int tap(cocr_model *m, hipStream_t s, const 
 COCR_INTERNAL void blob_to_f32(const cocr_model *m, size_t off, float *dst, size_t n, hipStream_t s);      // owns to_f32_kernel with the taps
 // decode.hip
 COCR_INTERNAL int ensure_ctc_scratch(cocr_model *m, size_t rows);
+COCR_INTERNAL int distill_loss_on(cocr_model *m, const float *student, const float *teacher, int N, int T, int ncls, const int32_t *out_lens, float tau, float *kd,
+                                  float *grad, float ctc_weight, float kd_weight, int accumulate, float *frame_ws, hipStream_t s);
 // train.hip
 COCR_INTERNAL void train_free(cocr_model *m);

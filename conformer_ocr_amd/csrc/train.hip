@@ -2,6 +2,7 @@
 //     cocr_train_begin      fp32 master copy of every parameter / buffer (reference state-dict names) on the device, zeroed AdamW state
 //     cocr_train_step       RecognitionModel.training_step (model.py:129-152): train-mode forward (batch-statistics BatchNorm, dropout at the
 //                           reference's six sites), CTC criterion, backward through decoder AND encoder -> the gradient of every parameter
+//     cocr_train_step_distill    the same step with a teacher's logits: (1 - weight) CTC + weight KD (distill.hip.h)
 //     cocr_train_adamw      torch.optim.AdamW over all parameters (model.py:283-284)
 //     cocr_train_optim_step      one step of AdamW / Adam / SGD / RMSprop over all parameters (model.py:283-289); cocr_decoder_optim_step: on the output layer
 //     cocr_train_adopt_decoder   the output layer a frozen-backbone phase trained (cocr_decoder_adamw / _optim_step), with its optimizer state, into this state
@@ -546,8 +547,10 @@ extern "C" int cocr_decoder_optim_restore(cocr_model *m, int kind, int64_t step,
 }
 
 // dropout_p: {input, feed_forward, attention, conv} (the reference's four probabilities, encoder.py:144-147); loss_out (host): the summed CTC loss
-extern "C" int cocr_train_step(cocr_model *m, const void *lines, int line_dtype, int N, int H, int W, const int32_t *in_lens, const int32_t *targets,
-                               const int32_t *label_lens, const float *dropout_p, uint64_t seed, float *loss_out, void *stream) {
+// The body of both entries.  teacher null: cocr_train_step (loss_out[0] alone is written); else cocr_train_step_distill
+static int train_step_body(cocr_model *m, const void *lines, int line_dtype, int N, int H, int W, const int32_t *in_lens, const int32_t *targets,
+                           const int32_t *label_lens, const float *dropout_p, uint64_t seed, const float *teacher, float tau, float lambda, float *loss_out,
+                           void *stream) {
     if (!m || !lines || !in_lens || !label_lens || !loss_out) return fail(COCR_EINVAL, "null argument");
     TrainState *t = m->train;
     if (!t) return fail(COCR_ESTATE, "cocr_train_begin has not been called");
@@ -601,7 +604,7 @@ extern "C" int cocr_train_step(cocr_model *m, const void *lines, int line_dtype,
         if ((rc = c.ffn_fwd(l, 0)) || (rc = c.attn_fwd(l)) || (rc = c.conv_fwd(l)) || (rc = c.ffn_fwd(l, 1))) return rc;
         c.final_ln_fwd(l);
     }
-    if ((rc = c.decoder_criterion(in_lens, targets, label_lens, loss_out))) return rc;
+    if ((rc = c.decoder_criterion(in_lens, targets, label_lens, teacher, tau, lambda, loss_out))) return rc;
 
     if ((rc = c.decoder_bwd())) return rc;
     for (int l = c.L - 1; l >= 0; --l) {
@@ -611,4 +614,20 @@ extern "C" int cocr_train_step(cocr_model *m, const void *lines, int line_dtype,
     if ((rc = c.front_bwd()) || (rc = c.flush_finals())) return rc;
     LAUNCH_CHECK();
     return COCR_OK;
+}
+
+extern "C" int cocr_train_step(cocr_model *m, const void *lines, int line_dtype, int N, int H, int W, const int32_t *in_lens, const int32_t *targets,
+                               const int32_t *label_lens, const float *dropout_p, uint64_t seed, float *loss_out, void *stream) {
+    return train_step_body(m, lines, line_dtype, N, H, W, in_lens, targets, label_lens, dropout_p, seed, nullptr, 1.0f, 0.0f, loss_out, stream);
+}
+
+// cocr_train_step with the distillation term: teacher_logits DEVICE (N, T, ncls), T = the frames of a W px line;
+// the criterion is (1 - weight) sum CTC + weight sum KD at temperature tau; loss_out (host) [2]: the two sums, unweighted
+extern "C" int cocr_train_step_distill(cocr_model *m, const void *lines, int line_dtype, int N, int H, int W, const int32_t *in_lens, const int32_t *targets,
+                                       const int32_t *label_lens, const float *dropout_p, uint64_t seed, const float *teacher_logits, float tau, float weight,
+                                       float *loss_out, void *stream) {
+    if (!teacher_logits) return fail(COCR_EINVAL, "null argument");
+    if (!std::isfinite(tau) || !(tau > 0.f)) return fail(COCR_EINVAL, "the temperature must be finite and positive, not %g", (double)tau);
+    if (!(weight >= 0.f && weight <= 1.f)) return fail(COCR_EINVAL, "the distillation weight %g is outside [0, 1]", (double)weight);
+    return train_step_body(m, lines, line_dtype, N, H, W, in_lens, targets, label_lens, dropout_p, seed, teacher_logits, tau, weight, loss_out, stream);
 }

@@ -138,6 +138,8 @@ struct TrainPlan {
     // LayerNorm / frontend weight gradients when not deferred), Vec the BatchNorm sums, LinePart per-line partial sums (depthwise weight
     // gradient, d positional rows)
     struct { size_t Part, Vec, LinePart; } rd;
+    // The distillation term (cocr_train_step_distill): per-frame KL values (M) and the per-line sums (N), written by the criterion alone
+    struct { size_t Frame, Kd; } kd;
     size_t ws_bytes, parts_floats, xb_bytes;              // the sizes of TrainState::ws / parts / Xb for this shape
 };
 
@@ -199,6 +201,7 @@ static TrainPlan train_plan(const cocr_model *m, const TrainState *t, int N, int
         split_floats = std::max(split_floats, (size_t)train_wg_splits(nk.first, nk.second) * nk.first * nk.second);
     p.op.Split = rsv(split_floats);
     p.rd.LinePart = rsv((size_t)N * std::max((size_t)R * D, (size_t)ceil_div(T, COCR_DW_WC) * D * K));
+    p.kd.Frame = rsv(M); p.kd.Kd = rsv(N);
     p.ws_bytes = need;
     // deferred column-sum finals: at most 12 jobs per block + the frontend's and the decoder's, each up to ceil(M / 32) x (widest matrix) partial sums
     p.parts_floats = (size_t)(12 * L + 16) * (size_t)ceil_div(M, 32) * (size_t)std::max(wide, 2 * D) + 4096;
@@ -537,20 +540,31 @@ struct Train : TrainPlan {
     void final_ln_fwd(int l) {
         ln_fwd(WS(lay[l].f1.out), w.blocks[l].f_ln_g, w.blocks[l].f_ln_b, WS(l + 1 < L ? lay[l + 1].x_in : Xout), WS(lay[l].mu5), WS(lay[l].rs5));
     }
-    // decoder, then the criterion (model.py:119,136-142): summed CTC loss (read back: the stream is drained here) and d loss / d probits
-    int decoder_criterion(const int32_t *in_lens, const int32_t *targets, const int32_t *label_lens, float *loss_out) {
+    // decoder, then the criterion (model.py:119,136-142): summed CTC loss (read back: the stream is drained here) and d loss / d probits.
+    // teacher (DEVICE (N, T, ncls) logits, or null): the distillation term joins -- Dlog becomes
+    // (1 - lambda) dCTC + lambda tau (q - p) (untouched at lambda = 0), loss_out[1] the summed KD read back with the same wait.
+    int decoder_criterion(const int32_t *in_lens, const int32_t *targets, const int32_t *label_lens, const float *teacher, float tau, float lambda, float *loss_out) {
         int rc;
         if ((rc = lin_fwd(WS(Xout), w.dec, M, ncls, D, WS(Logits)))) return rc;
         LAUNCH_CHECK();
         std::vector<int32_t> out_lens(N);
         for (int i = 0; i < N; ++i) out_lens[i] = cocr_out_len(in_lens[i], m->hp.subsampling_factor);
         if ((rc = cocr_ctc_loss(m, WS(Logits), N, T, ncls, out_lens.data(), targets, label_lens, WS(Nll), WS(Dlog), (void *)s))) return rc;
-        std::vector<float> nll(N);
+        if (teacher && (rc = distill_loss_on(m, WS(Logits), teacher, N, T, ncls, out_lens.data(), tau, WS(kd.Kd), lambda > 0.f ? WS(Dlog) : nullptr, 1.0f - lambda, lambda, 1,
+                                             WS(kd.Frame), s)))
+            return rc;
+        std::vector<float> nll(N), kdv(teacher ? N : 0);
         HIP_TRY(hipMemcpyAsync(nll.data(), WS(Nll), (size_t)N * 4, hipMemcpyDeviceToHost, s));
+        if (teacher) HIP_TRY(hipMemcpyAsync(kdv.data(), WS(kd.Kd), (size_t)N * 4, hipMemcpyDeviceToHost, s));
         HIP_TRY(hipStreamSynchronize(s));
         double sum = 0.0;
         for (float v : nll) sum += v;
-        *loss_out = (float)sum;
+        loss_out[0] = (float)sum;
+        if (teacher) {
+            sum = 0.0;
+            for (float v : kdv) sum += v;
+            loss_out[1] = (float)sum;
+        }
         return COCR_OK;
     }
 

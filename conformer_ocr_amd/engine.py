@@ -300,6 +300,36 @@ class HipRecognizer:
                                               _stream_ptr(self.device)))
         return nll, grad
 
+    def distill_loss(self, student: torch.Tensor, teacher: torch.Tensor, out_lens, tau: float, grad: Optional[torch.Tensor] = None,
+                     ctc_weight: float = 1.0, kd_weight: float = 1.0, with_grad: bool = True):
+        """The distillation term of `distill.kd_loss_host` on the device (include/cocr.h: cocr_distill_loss).
+        student, teacher (N,T,ncls) float32 logits on this device; out_lens (N) valid frames; tau the temperature.  Returns (per-line
+        KD (N) float32 device tensor, gradient (N,T,ncls) or None).  grad=None: a new tensor kd_weight tau (q - p) (with_grad=False:
+        the loss only).  grad given (contiguous, float32, the logits' shape): updated IN PLACE to ctc_weight grad + kd_weight tau (q - p)
+        -- the two-term criterion on the gradient `ctc_loss` left there -- and returned.  Stream-ordered."""
+        for t in (student, teacher):
+            if t.device != self.device or t.dtype != torch.float32 or t.dim() != 3:
+                raise RuntimeError('student and teacher must be float32 (N,T,num_classes) tensors on the model device')
+        if student.shape != teacher.shape:
+            raise ValueError(f'student logits are {tuple(student.shape)}, teacher logits {tuple(teacher.shape)}')
+        student, teacher = student.contiguous(), teacher.contiguous()
+        N, T, ncls = student.shape
+        lens = np.ascontiguousarray(np.asarray(out_lens, dtype=np.int32).reshape(-1))
+        if lens.shape[0] != N:
+            raise ValueError('out_lens needs one entry per line')
+        accumulate = grad is not None
+        if accumulate and (grad.device != self.device or grad.dtype != torch.float32 or grad.shape != student.shape or not grad.is_contiguous()):
+            raise RuntimeError('grad must be a contiguous float32 tensor of the logits\' shape on the model device')
+        if not accumulate and with_grad:
+            grad = torch.empty_like(student)
+        kd = torch.empty((N,), dtype=torch.float32, device=self.device)
+        with torch.cuda.device(self.device):
+            _lib.check(self.lib.cocr_distill_loss(self._h, C.c_void_p(student.data_ptr()), C.c_void_p(teacher.data_ptr()), N, T, ncls,
+                                                  lens.ctypes.data_as(C.POINTER(C.c_int32)), float(tau), C.c_void_p(kd.data_ptr()),
+                                                  C.c_void_p(grad.data_ptr()) if grad is not None else None, float(ctc_weight), float(kd_weight),
+                                                  int(accumulate), _stream_ptr(self.device)))
+        return kd, grad
+
     # ---- forced alignment (include/cocr.h: cocr_ctc_align; DESIGN.md section 7d) ----------
     def ctc_align_async(self, logits: torch.Tensor, out_lens, targets, label_lens):
         """Enqueues the forced alignment of every line's label sequence on the current stream, its outputs in pinned host memory;
@@ -493,11 +523,14 @@ class HipRecognizer:
         _lib.check(self.lib.cocr_train_begin(self._h))
         _lib.check(self.lib.cocr_train_set_matmul(self._h, int(matmul_precision == 'medium')))
 
-    def train_step(self, lines: torch.Tensor, lens, targets, label_lens, dropout=(0.0, 0.0, 0.0, 0.0), seed: int = 0) -> float:
+    def train_step(self, lines: torch.Tensor, lens, targets, label_lens, dropout=(0.0, 0.0, 0.0, 0.0), seed: int = 0,
+                   teacher_logits: Optional[torch.Tensor] = None, tau: float = 1.0, distill_weight: float = 0.0):
         """`RecognitionModel.training_step` without the optimizer (reference model.py:129-152): train-mode forward, summed CTC loss,
         backward through decoder and encoder.  lines (N,H,W) float32 / uint8 on this device; lens pixel widths; targets the
         concatenated labels, label_lens their per-line counts; dropout = (input, feed_forward, attention, conv) probabilities.
-        Returns the loss; the gradients stay on the device (`train_grad`, `train_optim_step`)."""
+        Returns the loss; the gradients stay on the device (`train_grad`, `train_optim_step`).
+        teacher_logits (N,T,ncls) float32 on this device, T = out_len(W): the step with the distillation term,
+        criterion (1 - distill_weight) CTC + distill_weight KD at temperature tau; returns (summed CTC, summed KD), both unweighted."""
         if lines.device != self.device or lines.dim() != 3:
             raise ValueError('expected a (N,H,W) batch on the model device')
         ldt = _lib.U8 if lines.dtype == torch.uint8 else _lib.F32
@@ -510,6 +543,18 @@ class HipRecognizer:
         if il.shape[0] != N or tl.shape[0] != N or int(tl.sum()) != tg.shape[0]:
             raise ValueError('lens / label_lens need one entry per line and targets sum(label_lens) labels')
         dp = (C.c_float * 4)(*[float(x) for x in dropout])
+        if teacher_logits is not None:
+            tz = teacher_logits
+            if tz.device != self.device or tz.dtype != torch.float32 or tuple(tz.shape) != (N, self.out_len(W), self.hp.num_classes):
+                raise ValueError(f'teacher_logits must be a float32 {(N, self.out_len(W), self.hp.num_classes)} tensor on the model device')
+            tz = tz.contiguous()
+            both = (C.c_float * 2)()
+            with torch.cuda.device(self.device):
+                _lib.check(self.lib.cocr_train_step_distill(self._h, C.c_void_p(lines.data_ptr()), ldt, N, H, W, il.ctypes.data_as(i32),
+                                                            tg.ctypes.data_as(i32) if tg.shape[0] else None, tl.ctypes.data_as(i32), dp,
+                                                            C.c_uint64(int(seed)), C.c_void_p(tz.data_ptr()), float(tau), float(distill_weight), both,
+                                                            _stream_ptr(self.device)))
+            return float(both[0]), float(both[1])
         loss = C.c_float()
         with torch.cuda.device(self.device):
             _lib.check(self.lib.cocr_train_step(self._h, C.c_void_p(lines.data_ptr()), ldt, N, H, W, il.ctypes.data_as(i32),

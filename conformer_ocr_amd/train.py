@@ -108,12 +108,14 @@ WINDOW_HYPER = {'accumulate_grad_batches': 1, 'gradient_clip_val': None, 'skip_n
 def upgrade_state(sd: Dict) -> Dict:
     """`sd` (a `Trainer.state_dict()`, or the tensors and records of a state file) with the keys of the gradient window filled in where
     an older writer left them out: the three arguments at their defaults, no skipped step, no open window, and -- every call having
-    been an optimizer step -- batches_seen = global_step, frozen_batches = frozen_steps.  `sd` itself is not changed."""
+    been an optimizer step -- batches_seen = global_step, frozen_batches = frozen_steps; and 'distill' = None (no teacher) where a
+    writer from before distillation left it out.  `sd` itself is not changed."""
     out = dict(sd)
     out['hyper'] = dict(WINDOW_HYPER, **sd['hyper'])
     c = sd['counters']
     out['counters'] = dict({'batches_seen': c['global_step'], 'frozen_batches': c['frozen_steps'], 'skipped_steps': 0, '_window': 0,
                             '_window_frozen': False}, **c)
+    out['distill'] = sd.get('distill')                    # (a state without the key was written without a teacher)
     return out
 
 
@@ -161,7 +163,15 @@ class Trainer:
     `skip_nonfinite`: a window whose norm is not finite takes no optimizer step -- no parameter, slot, step count or `global_step`
     moves, A is zeroed, `skipped_steps` counts it, `log` gets a line.  Without it, with clipping on, such a window raises
     FloatingPointError (the window is dropped, nothing else moves): a NaN coefficient never reaches the kernel.  With neither, the
-    gradient is used as it is."""
+    gradient is used as it is.
+
+    `teacher`: a `PytorchRecognitionModel` on the same device with the same classes, height, subsampling and
+    codec (`distill.check_teacher`).  Every `training_step` runs its eval-mode forward (its own `compute_dtype`, no gradient) on the very
+    batch the student sees and hands the logits to the step: the criterion becomes (1 - distill_weight) CTC + distill_weight KD at
+    `distill_temperature` -- in the whole-network step inside `cocr_train_step_distill`, in the frozen phase by `cocr_distill_loss` on
+    the serving engine's CTC gradient ahead of the decoder backward.  `training_step` returns that weighted total; `last_ctc_loss` and
+    `last_kd_loss` keep the two sums.  The defaults 0.5 / 2.0 are placeholders, not tuned on real material.  Accumulation, clipping,
+    `skip_nonfinite` and the all-reduce work on the flat gradient and do not change; with teacher=None nothing new is launched."""
 
     SCHEDULES = ('constant', 'exponential', 'cosine', 'step', 'reduceonplateau')
 
@@ -170,7 +180,8 @@ class Trainer:
                  rop_factor: float = 0.1, rop_patience: int = 5, completed_epochs: int = 0, seed: int = 0, process_group=None,
                  distributed: Optional[bool] = None, matmul_precision: str = 'highest', freeze_backbone: int = 0, log=None,
                  momentum: float = 0.9, accumulate_grad_batches: int = 1, gradient_clip_val: Optional[float] = None,
-                 skip_nonfinite: bool = False):
+                 skip_nonfinite: bool = False, teacher: Optional[PytorchRecognitionModel] = None, distill_weight: float = 0.5,
+                 distill_temperature: float = 2.0):
         if optimizer not in OPTIMIZERS:
             raise ValueError(f'unknown optimizer {optimizer!r}: one of {", ".join(OPTIMIZERS)}')
         if int(accumulate_grad_batches) < 1:
@@ -181,6 +192,17 @@ class Trainer:
             raise ValueError(f'Unsupported learning rate scheduler {schedule}.')                      # model.py:309
         if not float(momentum) >= 0.0:
             raise ValueError(f'Invalid momentum value: {momentum}')                                   # torch.optim.SGD / RMSprop
+        self.teacher = teacher
+        self.distill_weight, self.distill_temperature = float(distill_weight), float(distill_temperature)
+        self.last_ctc_loss: Optional[float] = None
+        self.last_kd_loss: Optional[float] = None
+        if teacher is not None:
+            from .distill import check_teacher
+            if not 0.0 <= self.distill_weight <= 1.0:
+                raise ValueError(f'distill_weight must lie in [0, 1], not {distill_weight}')
+            if not self.distill_temperature > 0.0 or self.distill_temperature == float('inf'):
+                raise ValueError(f'distill_temperature must be positive and finite, not {distill_temperature}')
+            check_teacher(net, teacher)
         self.net = net
         self.optimizer, self.momentum, self.matmul_precision = optimizer, float(momentum), matmul_precision
         self.base_lr = self.lr = float(lr)
@@ -209,6 +231,8 @@ class Trainer:
             distributed = torch.distributed.is_available() and torch.distributed.is_initialized() and torch.distributed.get_world_size(process_group) > 1
         self.distributed = bool(distributed)
         dev = next(net.nn.parameters()).device
+        if teacher is not None and next(teacher.nn.parameters()).device != dev:
+            raise ValueError(f'the teacher lives on {next(teacher.nn.parameters()).device}, the model on {dev}')
         from .engine import HipRecognizer
         self.engine = HipRecognizer(net.hparams_record, dev, 'fp32')
         self.engine.load_state({k: v for k, v in net.nn.state_dict().items()}, strict=True)
@@ -255,7 +279,8 @@ class Trainer:
 
     def training_step(self, batch: Dict) -> float:
         """One call of the step on `batch`: its gradient joins the open window, and the call that completes the window takes the
-        optimizer step (every call, at accumulate_grad_batches = 1); returns the batch's summed CTC loss (this rank's lines)."""
+        optimizer step (every call, at accumulate_grad_batches = 1); returns the batch's summed CTC loss (this rank's lines) -- with a
+        teacher the weighted total (1 - distill_weight) CTC + distill_weight KD of the two sums in `last_ctc_loss` / `last_kd_loss`."""
         image = batch['image']
         if image.dim() != 4 or image.shape[1] != 1:
             raise ValueError(f'expected a (N,1,H,W) line batch, got {tuple(image.shape)}')
@@ -265,9 +290,17 @@ class Trainer:
                 self._unfreeze()
         self.samples_seen += int(image.shape[0])
         k = self.accumulate_grad_batches
+        lam, tau, kd, tz = self.distill_weight, self.distill_temperature, None, None
+        if self.teacher is not None:
+            with torch.no_grad():                         # the teacher's eval-mode forward on the batch the student sees
+                tz, _ = self.teacher.forward(image.to(self.engine.device), batch['seq_lens'])
         if self._window_frozen:
             # `DecoderTrainer.training_step` at this Trainer's rate: only the output layer moves, on the serving engine
             o = self.net.step(dict(batch, image=image.to(self.engine.device)), with_grad=True)
+            if tz is not None:                            # (1 - lambda) dCTC + lambda tau (q - p), in place, ahead of the decoder backward
+                kdv, _ = self.net._engine.distill_loss(o['probits'], tz, o['output_lens'].numpy(), tau, grad=o['grad_probits'], ctc_weight=1.0 - lam,
+                                                       kd_weight=lam)
+                kd = float(kdv.sum())
             gw, gb, _ = self.net._engine.decoder_backward(o['grad_probits'])
             loss = float(o['loss'])
             self.frozen_batches += 1
@@ -279,14 +312,17 @@ class Trainer:
             x = image.squeeze(1).to(self.engine.device)
             loss = self.engine.train_step(x, torch.as_tensor(batch['seq_lens']).cpu().numpy(), torch.as_tensor(batch['target']).cpu().numpy(),
                                           torch.as_tensor(batch['target_lens']).cpu().numpy(), dropout=self.net.dropout_p,
-                                          seed=self.seed * 1000003 + self.batches_seen)
+                                          seed=self.seed * 1000003 + self.batches_seen, teacher_logits=tz, tau=tau, distill_weight=lam)
+            if tz is not None:
+                loss, kd = loss
             if k > 1:
                 self._accumulate((self.engine.train_grad_buffer(),))
         self.batches_seen += 1
         self._window += 1
         if self._window >= k:
             self._optimizer_step()
-        return loss
+        self.last_ctc_loss, self.last_kd_loss = loss, kd
+        return loss if kd is None else (1.0 - lam) * loss + lam * kd
 
     def flush(self) -> None:
         """The optimizer step on an incomplete window (its gradients still scaled by 1/k); nothing on an empty one."""
@@ -418,7 +454,8 @@ class Trainer:
         """{'values': the flat value vector (parameters, then BatchNorm statistics), 'slot0', 'slot1': the optimizer's two state vectors
         (device copies), 'optim': {kind, step, dec_steps}, 'counters', 'hyper'} and, while the frozen phase's output layer has not moved
         into the whole-network state, 'decoder_state' ([master | slot 0 | slot 1] of the serving engine) with 'decoder_optim'
-        {kind, step}.  While an accumulation window is open (counters['_window'] calls in): 'accum', the vector A."""
+        {kind, step}.  While an accumulation window is open (counters['_window'] calls in): 'accum', the vector A.  'distill': None
+        without a teacher, else {'weight', 'temperature', 'teacher': the teacher's hyper-parameters, codec and compute_dtype}."""
         st = self.engine.train_optim_state()
         out = {'values': self.engine.train_value_buffer().clone(), 'slot0': st['slot0'].clone(), 'slot1': st['slot1'].clone(),
                'optim': {'kind': st['kind'], 'step': st['step'], 'dec_steps': st['dec_steps']},
@@ -429,12 +466,26 @@ class Trainer:
             out['decoder_optim'] = {'kind': d['kind'], 'step': d['step']}
         if self._window and self.accumulate_grad_batches > 1:
             out['accum'] = self._accum.clone()
+        out['distill'] = self._distill_record()
         return out
+
+    def _distill_record(self) -> Optional[Dict]:
+        if self.teacher is None:
+            return None
+        import json
+        return {'weight': self.distill_weight, 'temperature': self.distill_temperature, 'teacher': json.loads(json.dumps(_model_record(self.teacher)))}
 
     def load_state_dict(self, sd: Dict) -> None:
         """Puts a `state_dict()` back into this trainer, its engine and `net.nn`; the model layout must be the one it was taken from.
         A state from before the gradient window loads as `upgrade_state` describes."""
         sd = upgrade_state(sd)
+        was, now = sd['distill'], self._distill_record()
+        if (was is None) != (now is None):
+            raise ValueError('the state was written ' + ('with a teacher: give the teacher again' if now is None else 'without a teacher'))
+        for k in (() if was is None else ('weight', 'temperature', 'teacher')):
+            if was[k] != now[k]:
+                raise ValueError(f'the distillation is not the one the state was written with: {k} ' +
+                                 ('differs' if k == 'teacher' else f'is {now[k]!r}, was {was[k]!r}'))
         values, st = self.engine.train_value_buffer(), self.engine.train_optim_state()
         for name, have in (('values', values), ('slot0', st['slot0']), ('slot1', st['slot1'])):
             if tuple(sd[name].shape) != tuple(have.shape):
@@ -520,6 +571,8 @@ def _save_fit_state(path: str, net, data, trainer: 'Trainer', progress: Dict) ->
     sd = trainer.state_dict()
     meta = dict(_model_record(net), format=1, data=data_fingerprint(data), fit=progress,
                 trainer={k: sd[k] for k in ('optim', 'counters', 'hyper', 'decoder_optim') if k in sd})
+    if sd['distill'] is not None:
+        meta['distill'] = sd['distill']
     write_state_file(path, {k: sd[k] for k in STATE_TENSORS if k in sd}, meta)
 
 
@@ -541,9 +594,17 @@ def _resume_fit(path: str, net, data, log, **trainer_kw):
                 raise ValueError(f'the model is not the one the state was written with: {k} is {have["hyper_params"].get(k)!r}, was {v!r}')
         if json.loads(json.dumps(have['codec'])) != meta['codec']:
             raise ValueError('the model is not the one the state was written with: the codecs differ')
-    meta['trainer'] = upgrade_state(meta['trainer'])
+    meta['trainer'] = upgrade_state(dict(meta['trainer'], distill=meta.get('distill')))
     hyper = dict(meta['trainer']['hyper'])
     hyper['lr'] = hyper.pop('base_lr')
+    was = meta['trainer']['distill']
+    if was is not None:                                   # the two numbers come from the state unless given (then they must agree)
+        if trainer_kw.get('teacher') is None:
+            raise ValueError('the state was written with a teacher: give the teacher again')
+        for kw, k in (('distill_weight', 'weight'), ('distill_temperature', 'temperature')):
+            if trainer_kw.get(kw) is None:
+                trainer_kw[kw] = was[k]
+    trainer_kw = {k: v for k, v in trainer_kw.items() if v is not None}
     trainer = Trainer(net, log=log, **hyper, **trainer_kw)
     trainer.load_state_dict(dict(tensors, **meta['trainer']))
     return net, trainer, meta['fit']
@@ -554,7 +615,8 @@ def fit(net: Optional[PytorchRecognitionModel], data, trainer: Optional[Trainer]
         lag: int = 10, output: Optional[str] = 'model', log=print, save_state: bool = False, resume: Optional[str] = None, **trainer_kw) -> Dict:
     """Trains `net` on `data` (a `dataset.GroundTruthDataset`).  Per epoch: `training_step` on every batch of `data.batches(epoch)`,
     `sync_module`, validation CER (`data.validate`), `end_epoch(1 - CER)`, `{output}_{epoch}.safetensors` and, when the CER is the best
-    so far, `{output}_best.safetensors` (no files with output=None); one log line with the summed loss, lines/s and the CER.
+    so far, `{output}_best.safetensors` (no files with output=None); one log line with the summed loss (with a teacher: the weighted
+    total and its CTC and KD parts), lines/s and the CER.
     quit 'fixed': `epochs` epochs; 'early': stops once `lag` epochs in a row did not improve the best CER and at least `min_epochs`
     ran (`epochs` still bounds the run).  Returns {'best_epoch', 'best_cer', 'history': [(loss, lines/s, cer), ...], 'net', 'trainer'}.
 
@@ -583,9 +645,12 @@ def fit(net: Optional[PytorchRecognitionModel], data, trainer: Optional[Trainer]
     dev = trainer.engine.device
     for epoch in range(first, int(epochs)):
         t0, loss, lines, skipped0 = time.perf_counter(), 0.0, 0, trainer.skipped_steps
+        ctc, kd = 0.0, 0.0
         for batch in data.batches(epoch):
             loss += trainer.training_step(batch)
             lines += int(batch['image'].shape[0])
+            if trainer.teacher is not None:
+                ctc, kd = ctc + trainer.last_ctc_loss, kd + trainer.last_kd_loss
         trainer.flush()                                   # (an epoch's last window may be incomplete)
         torch.cuda.synchronize(dev)
         rate = lines / max(time.perf_counter() - t0, 1e-9)
@@ -608,7 +673,8 @@ def fit(net: Optional[PytorchRecognitionModel], data, trainer: Optional[Trainer]
                             {'best_epoch': best_epoch, 'best_cer': best_cer, 'bad': bad, 'history': [list(h) for h in history]})
         if log is not None:
             skipped = trainer.skipped_steps - skipped0
-            log(f'epoch {epoch}: loss {loss:.4f}  {rate:.1f} lines/s  val CER {cer:.4f}{f"  {skipped} steps skipped" if skipped else ""}'
+            parts = f' (CTC {ctc:.4f}, KD {kd:.4f})' if trainer.teacher is not None else ''
+            log(f'epoch {epoch}: loss {loss:.4f}{parts}  {rate:.1f} lines/s  val CER {cer:.4f}{f"  {skipped} steps skipped" if skipped else ""}'
                 f'{"  (best)" if improved else ""}')
         if quit == 'early' and bad >= int(lag) and epoch + 1 >= int(min_epochs):
             break
@@ -675,6 +741,13 @@ def build_parser():
     ap.add_argument('--accumulate', type=int, default=1, metavar='K', help='optimizer step on the gradients of K batches (accumulate_grad_batches)')
     ap.add_argument('--clip-norm', type=float, default=None, metavar='X', help='clip the gradient to this global L2 norm (gradient_clip_val)')
     ap.add_argument('--skip-nonfinite', action='store_true', help='take no optimizer step on a gradient whose norm is Inf or NaN')
+    ap.add_argument('--teacher', default=None, metavar='FILE',
+                    help='safetensors archive or checkpoint of a (larger) model of the same alphabet to distill from: the loss becomes '
+                         '(1 - weight) CTC + weight KD against its per-frame posteriors')
+    ap.add_argument('--distill-weight', type=float, default=None, metavar='L',
+                    help='weight of the distillation term, in [0, 1] (default 0.5: a placeholder, not tuned on real material)')
+    ap.add_argument('--distill-temperature', type=float, default=None, metavar='TAU',
+                    help='temperature both posteriors are softened with (default 2.0: a placeholder, not tuned on real material)')
     ap.add_argument('-o', '--output', default='model', help='prefix of the written models')
     ap.add_argument('--device', default='cuda:0')
     ap.add_argument('--seed', type=int, default=0)
@@ -701,6 +774,12 @@ def check_args(ap, args) -> None:
         ap.error('--accumulate is a number of batches, at least 1')
     if args.clip_norm is not None and not args.clip_norm > 0:
         ap.error('--clip-norm must be positive')
+    if not args.teacher and (args.distill_weight is not None or args.distill_temperature is not None):
+        ap.error('--distill-weight and --distill-temperature describe the distillation: give --teacher')
+    if args.distill_weight is not None and not 0.0 <= args.distill_weight <= 1.0:
+        ap.error('--distill-weight must lie in [0, 1]')
+    if args.distill_temperature is not None and not (args.distill_temperature > 0 and args.distill_temperature != float('inf')):
+        ap.error('--distill-temperature must be positive')
     if args.resume:
         for flag, given in (('-i/--load', args.load), ('-c/--codec', args.codec), ('--resize', args.resize != 'fail')):
             if given:
@@ -758,9 +837,10 @@ def main(argv=None) -> int:
         resize_output(net, data.codec, data.row_map, seed=args.seed)
         print(f'resize {args.resize}: {old_classes} -> {data.num_classes} classes; kept {len(was & now)}, added {len(now - was)} '
               f'({"".join(sorted(now - was))!r}), dropped {len(was - now)} characters')
+    teacher = load_model(args.teacher, device=args.device) if args.teacher else None
     if args.resume:
         res = fit(None, data, epochs=args.epochs, quit=args.quit, min_epochs=args.min_epochs, lag=args.lag, output=args.output, save_state=True,
-                  resume=args.resume)
+                  resume=args.resume, teacher=teacher, distill_weight=args.distill_weight, distill_temperature=args.distill_temperature)
         return _report(res, args.output)
     if net is None:
         from .pred import PytorchRecognitionModel
@@ -777,7 +857,9 @@ def main(argv=None) -> int:
                       schedule=args.schedule, gamma=args.gamma, step_size=args.step_size, rop_patience=args.sched_patience,
                       cos_t_max=args.cos_max, cos_min_lr=args.cos_min_lr, seed=args.seed, matmul_precision=args.precision,
                       freeze_backbone=args.freeze_backbone, log=print, accumulate_grad_batches=args.accumulate,
-                      gradient_clip_val=args.clip_norm, skip_nonfinite=args.skip_nonfinite)
+                      gradient_clip_val=args.clip_norm, skip_nonfinite=args.skip_nonfinite, teacher=teacher,
+                      distill_weight=0.5 if args.distill_weight is None else args.distill_weight,
+                      distill_temperature=2.0 if args.distill_temperature is None else args.distill_temperature)
     res = fit(net, data, trainer, epochs=args.epochs, quit=args.quit, min_epochs=args.min_epochs, lag=args.lag, output=args.output,
               save_state=args.save_state)
     return _report(res, args.output)

@@ -178,6 +178,23 @@ int cocr_ctc_beam_lm(cocr_model *m, cocr_lm *lm, const float *logits, int N, int
 int cocr_ctc_loss(cocr_model *m, const float *probits, int N, int T, int ncls, const int32_t *out_lens, const int32_t *targets,
                   const int32_t *label_lens, float *nll, float *grad, void *stream);
 
+/* Knowledge distillation (the definition is conformer_ocr_amd/distill.py kd_loss_host): the Kullback-Leibler term
+ * between a teacher's and a student's per-frame posteriors at temperature tau,
+ *     p = softmax(teacher / tau), q = softmax(student / tau) over the classes of a frame,
+ *     kd[n] = tau^2 sum_{t < out_lens[n]} sum_c p(c) (log p(c) - log q(c)),        d kd[n] / d student[n,t,:] = tau (q - p),
+ * i.e. tau^2 F.kl_div(log_softmax(student / tau), log_softmax(teacher / tau), reduction='sum', log_target=True) on the valid frames.
+ * student, teacher DEVICE float32 (N,T,ncls); out_lens HOST (N); kd (N) float32, DEVICE or pinned host (0 for a line of length 0);
+ * grad (N,T,ncls) DEVICE float32 or NULL (loss only).  accumulate = 0: grad = kd_weight tau (q - p), zero for frames >= out_lens[n];
+ * accumulate = 1: grad = ctc_weight grad + kd_weight tau (q - p), frames >= out_lens[n] multiplied by ctc_weight only (the two-term
+ * criterion on the gradient the CTC loss left there).  Log-probabilities come from log-softmax, so a teacher probability that underflows
+ * to 0 contributes exactly 0; equal student and teacher rows give exactly 0 in kd and grad.  The logits must be finite: anything else is
+ * unspecified.  Checked before any launch: N, T < 1, ncls < 2, out_lens[n] outside [0, T], a tau that is not finite and positive, a
+ * weight that is not finite or is negative, accumulate other than 0 / 1 (COCR_EINVAL); ncls > 16384 (COCR_EUNSUPPORTED).  Deterministic
+ * (no floating-point atomics: per-frame values, then each line's sum in index order in double).  Stream-ordered, does not synchronise
+ * (scratch growth does). */
+int cocr_distill_loss(cocr_model *m, const float *student, const float *teacher, int N, int T, int ncls, const int32_t *out_lens,
+                      float tau, float *kd, float *grad, float ctc_weight, float kd_weight, int accumulate, void *stream);
+
 /* Forced alignment (the definition is conformer_ocr_amd/align.py viterbi_align): the best path of each line's KNOWN
  * label sequence through log_softmax(logits) -- the CTC lattice with max in place of the sum; ties keep the earlier of (stay, from s-1,
  * from s-2); the path ends in the last label or the blank after it, the blank unless the label scores strictly higher.
@@ -336,6 +353,14 @@ int cocr_profile_read(cocr_model *m, char *names, size_t names_len, double *ms, 
 int cocr_train_begin(cocr_model *m);
 int cocr_train_step(cocr_model *m, const void *lines, int line_dtype, int N, int H, int W, const int32_t *in_lens, const int32_t *targets,
                     const int32_t *label_lens, const float *dropout_p, uint64_t seed, float *loss_out, void *stream);
+/* The step with a teacher: the criterion is (1 - weight) sum CTC + weight sum KD, KD as cocr_distill_loss defines
+ * it at temperature tau between the step's own logits and teacher_logits, DEVICE float32 (N, T, ncls) with T = cocr_out_len(W) -- the
+ * teacher's eval-mode forward on the same batch.  loss_out HOST [2]: the summed CTC loss and the summed KD, both unweighted.  Everything
+ * else is the step above, which keeps its launches and its bits; with weight = 0 the gradient is that step's gradient bit for bit and KD
+ * is still reported.  COCR_EINVAL: teacher_logits NULL, weight outside [0, 1], tau not finite and positive. */
+int cocr_train_step_distill(cocr_model *m, const void *lines, int line_dtype, int N, int H, int W, const int32_t *in_lens,
+                            const int32_t *targets, const int32_t *label_lens, const float *dropout_p, uint64_t seed,
+                            const float *teacher_logits, float tau, float weight, float *loss_out, void *stream);
 int cocr_train_get(cocr_model *m, const char *name, int kind, float *host_out, int64_t n_elems, void *stream);
 int cocr_train_adamw(cocr_model *m, float lr, float beta1, float beta2, float eps, float weight_decay, void *stream);
 int cocr_train_end(cocr_model *m);
