@@ -4,7 +4,7 @@
 // leave the GPU.  Integer outputs (labels, starts, ends, counts) are exact; conf is the max over a
 // run of the winning logit (greedy) / softmax probability (beam).
 #pragma once
-#include "common.hip.h"
+#include "ctc_lattice.hip.h"      // row_max / row_lse: the frame statistics every CTC kernel forms in the same order
 
 // ---- greedy: argmax per frame (first index on ties, like numpy), merge runs, drop blank ---------
 // Per frame: lanes stride the classes (coalesced), keep (value, index) with strict > so the lowest index wins
@@ -121,12 +121,7 @@ __global__ __launch_bounds__(64) void ctc_beam_kernel(const float *__restrict__ 
     int nb = 1;
     for (int t = 0; t < len; ++t) {
         // 1. log-softmax of the frame
-        float mx = -INFINITY;
-        for (int c = lane; c < C; c += 64) mx = fmaxf(mx, lg[(size_t)t * C + c]);
-        mx = wave_max(mx);
-        float sm = 0.f;
-        for (int c = lane; c < C; c += 64) sm += expf(lg[(size_t)t * C + c] - mx);
-        const float lz = mx + logf(wave_sum(sm));
+        const float mx = row_max(lg + (size_t)t * C, C, lane), lz = row_lse(lg + (size_t)t * C, C, lane, mx);
         for (int c = lane; c < C; c += 64) lp[c] = (lg[(size_t)t * C + c] - mx) - (lz - mx);
         if (lane == 0) logz[t] = lz;
         if (lane < COCR_BEAM_MAX) { mval[lane] = -INFINITY; mpos[lane] = 0x7fffffff; }
@@ -283,7 +278,8 @@ __global__ __launch_bounds__(256) void ctc_beam_rank_kernel(const float *__restr
     e_s[c] = x;
     if (c < 64) { tc_s[c] = 0; tl_s[c] = -INFINITY; }
     __syncthreads();
-    // the frame's maximum and sum in the lane-strided order of ctc_beam_kernel (every wave computes both: no second exchange)
+    // the frame's maximum and sum in the lane-strided order of row_max / row_lse (ctc_lattice.hip.h), here from LDS with four registers
+    // per lane (every wave computes both: no second exchange)
     float xs[4], mx = -INFINITY;
 #pragma unroll
     for (int j = 0; j < 4; ++j) { xs[j] = e_s[lane + 64 * j]; mx = fmaxf(mx, xs[j]); }

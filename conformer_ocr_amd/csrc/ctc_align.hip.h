@@ -7,8 +7,8 @@
 // Per line n (one workgroup of 4 waves):
 //   A  lz_t = logsumexp_c(logits[t, c]) of the valid frames (all 4 waves, one frame per wave at a time) -> LDS; lp_t(c) = logits[t, c] - lz_t
 //      is formed where it is needed, the log-softmax is never stored.
-//   B  the recursion on wave 0: state s on lane s & 63, register s >> 6, the neighbours s-1 and s-2 by two lane rotations per register,
-//      the next frames' values requested four steps ahead.  A step is a compare chain; its outcome (0 stay, 1 from s-1, 2 from s-2) is the
+//   B  the recursion on wave 0, on the shared machine of ctc_lattice.hip.h (DESIGN.md "The lattice kernels' shared pieces": states over
+//      the lanes, the neighbour exchange, the prefetch ring).  A step is a compare chain; its outcome (0 stay, 1 from s-1, 2 from s-2) is the
 //      back-pointer: 2 bits, a lane packing 16 consecutive frames of its state into one word, bp[(t >> 4) * 64 SJ + s] -- in LDS when
 //      the table fits (BP_LDS), else in the line's region of a global workspace (same code).
 //   C  traceback on wave 0: per block of 16 frames ONE wave-wide read (lane i takes the word of state s - i: a path moves at most 2 states
@@ -16,11 +16,9 @@
 //   D  confidences, thread k for label k: exp of the largest lp over its run; starts / ends / conf go out together.
 // Every loop is bounded by T, S or L; nothing waits on another workgroup; no atomics: results are reproducible run to run.
 #pragma once
-#include "common.hip.h"
-#include "ctc_loss.hip.h"
+#include "ctc_lattice.hip.h"
 
-// dynamic LDS of one line: lz (T floats, padded to 16 bytes), then the back-pointer table when it lives in LDS
-__host__ __device__ static inline size_t ctca_lz_bytes(int T) { return ((size_t)T * 4 + 15) & ~(size_t)15; }
+// dynamic LDS of one line: lz (lattice_row_bytes(T)), then the back-pointer table when it lives in LDS
 __host__ __device__ static inline size_t ctca_bp_words(int T, int sj) { return (size_t)((T + 15) / 16) * 64 * sj; }
 
 template <int SJ, bool BP_LDS>
@@ -31,7 +29,7 @@ __global__ __launch_bounds__(256) void ctc_align_kernel(const float *__restrict_
                                                         int32_t *__restrict__ counts, unsigned *__restrict__ ws, size_t ws_stride) {
     constexpr int SP = 64 * SJ;
     extern __shared__ __attribute__((aligned(16))) unsigned char ctca_smem[];
-    __shared__ int32_t lab[COCR_CTCL_MAX_LABELS + 1], run_st[COCR_CTCL_MAX_LABELS + 1], run_en[COCR_CTCL_MAX_LABELS + 1];
+    __shared__ int32_t lab[COCR_LATTICE_MAX_LABELS + 1], run_st[COCR_LATTICE_MAX_LABELS + 1], run_en[COCR_LATTICE_MAX_LABELS + 1];
     __shared__ float fin[64 * 8];
     __shared__ int sh_ok;
     const int n = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
@@ -40,20 +38,15 @@ __global__ __launch_bounds__(256) void ctc_align_kernel(const float *__restrict_
     const int S = 2 * L + 1;
     const float *x = logits + (size_t)n * T * C;
     float *lz = reinterpret_cast<float *>(ctca_smem);
-    unsigned *bp = BP_LDS ? reinterpret_cast<unsigned *>(ctca_smem + ctca_lz_bytes(T)) : ws + (size_t)n * ws_stride;
+    unsigned *bp = BP_LDS ? reinterpret_cast<unsigned *>(ctca_smem + lattice_row_bytes(T)) : ws + (size_t)n * ws_stride;
     const int off = label_off[n];
 
     for (int k = tid; k < L; k += 256) { lab[k] = labels[off + k]; run_st[k] = 0; run_en[k] = -1; }
     // ---- A: the per-frame normaliser
     for (int t = wave; t < len; t += 4) {
         const float *xt = x + (size_t)t * C;
-        float mx = -INFINITY;
-        for (int c = lane; c < C; c += 64) mx = fmaxf(mx, xt[c]);
-        mx = wave_max(mx);
-        float sum = 0.f;
-        for (int c = lane; c < C; c += 64) sum += expf(xt[c] - mx);
-        sum = wave_sum(sum);
-        if (lane == 0) lz[t] = mx + logf(sum);
+        const float l = row_lse(xt, C, lane, row_max(xt, C, lane));
+        if (lane == 0) lz[t] = l;
     }
     __syncthreads();
 
@@ -64,19 +57,8 @@ __global__ __launch_bounds__(256) void ctc_align_kernel(const float *__restrict_
         if (len > 0) {
             int cls[SJ];
             bool skip[SJ], live[SJ];
-#pragma unroll
-            for (int j = 0; j < SJ; ++j) {
-                const int s = lane + 64 * j;
-                live[j] = s < S;
-                const int k = (s - 1) >> 1;
-                cls[j] = (live[j] && (s & 1)) ? lab[k] : 0;
-                skip[j] = live[j] && (s & 1) && s >= 3 && lab[k] != lab[k - 1];
-            }
-            // The logits and normalisers of the next PF frames are requested PF steps ahead (a ring in registers; every lane loads, a
-            // dead state the blank's; beyond the line the last frame again) and subtracted only when their step begins: a step never
-            // waits for a load it has just issued.
-            constexpr int PF = 4;
-            float a[SJ], nx[PF][SJ], nz[PF];
+            lattice_states<SJ, 1>(lab, S, lane, false, cls, skip, live);
+            float a[SJ];
             unsigned acc[SJ];
 #pragma unroll
             for (int j = 0; j < SJ; ++j) {
@@ -84,24 +66,16 @@ __global__ __launch_bounds__(256) void ctc_align_kernel(const float *__restrict_
                 a[j] = (live[j] && s < 2) ? x[cls[j]] - lz[0] : -INFINITY;
                 acc[j] = 0u;
             }
-#pragma unroll
-            for (int u = 0; u < PF; ++u) {
-                const int tt = min(1 + u, len - 1);
-                nz[u] = lz[tt];
-#pragma unroll
-                for (int j = 0; j < SJ; ++j) nx[u][j] = x[(size_t)tt * C + cls[j]];
-            }
-            const int src1 = (lane + 63) & 63, src2 = (lane + 62) & 63;
-            auto step = [&](int t, float (&cur)[SJ]) {       // cur: lp_t(l'_s) of this lane's states
+            int src1, src2;
+            lattice_src_fwd(lane, src1, src2);
+            lattice_ring(x, C, lz, cls, 1, len, [&](int t, float (&cur)[SJ]) {       // cur: lp_t(l'_s) of this lane's states
                 float r1[SJ], r2[SJ];
-#pragma unroll
-                for (int j = 0; j < SJ; ++j) { r1[j] = __shfl(a[j], src1, 64); r2[j] = __shfl(a[j], src2, 64); }
+                lattice_rotate(a, r1, r2, src1, src2);
                 const int sh = 2 * (t & 15);
                 const bool flush = (t & 15) == 15 || t == len - 1;
 #pragma unroll
-                for (int j = 0; j < SJ; ++j) {      // lanes 0 (and 1) take the previous register's lanes 63 (and 62)
-                    const float n1 = lane >= 1 ? r1[j] : (j > 0 ? r1[j > 0 ? j - 1 : 0] : -INFINITY);
-                    const float n2 = lane >= 2 ? r2[j] : (j > 0 ? r2[j > 0 ? j - 1 : 0] : -INFINITY);
+                for (int j = 0; j < SJ; ++j) {
+                    const float n1 = lattice_seam_fwd(r1, j, lane, 1, -INFINITY), n2 = lattice_seam_fwd(r2, j, lane, 2, -INFINITY);
                     float best = a[j];
                     unsigned code = 0u;
                     if (n1 > best) { best = n1; code = 1u; }
@@ -114,30 +88,7 @@ __global__ __launch_bounds__(256) void ctc_align_kernel(const float *__restrict_
                     a[j] = cur[j];
                     if (flush) { bp[(size_t)(t >> 4) * SP + lane + 64 * j] = acc[j]; acc[j] = 0u; }
                 }
-            };
-            int t0 = 1;
-            for (; t0 + PF <= len; t0 += PF) {
-#pragma unroll
-                for (int u = 0; u < PF; ++u) {
-                    float cur[SJ];
-#pragma unroll
-                    for (int j = 0; j < SJ; ++j) cur[j] = nx[u][j] - nz[u];
-                    const int tt = min(t0 + u + PF, len - 1);
-                    nz[u] = lz[tt];
-#pragma unroll
-                    for (int j = 0; j < SJ; ++j) nx[u][j] = x[(size_t)tt * C + cls[j]];
-                    step(t0 + u, cur);
-                }
-            }
-#pragma unroll
-            for (int u = 0; u < PF - 1; ++u) {               // the last len - t0 < PF frames are in the ring already
-                if (t0 + u < len) {
-                    float cur[SJ];
-#pragma unroll
-                    for (int j = 0; j < SJ; ++j) cur[j] = nx[u][j] - nz[u];
-                    step(t0 + u, cur);
-                }
-            }
+            });
 #pragma unroll
             for (int j = 0; j < SJ; ++j) fin[lane + 64 * j] = a[j];
             if (!BP_LDS) __threadfence();                // the workspace words written above are read below by other lanes
@@ -191,15 +142,14 @@ __global__ __launch_bounds__(256) void ctc_align_kernel(const float *__restrict_
     }
 }
 
-template <bool BP_LDS>
-static inline void launch_ctc_align(hipStream_t s, int sj, size_t lds, const float *logits, int N, int T, int C, const int32_t *lens,
-                                    const int32_t *label_lens, const int32_t *label_off, const int32_t *labels, int32_t *starts, int32_t *ends,
-                                    float *conf, float *score, int32_t *counts, unsigned *ws, size_t ws_stride) {
-    dim3 grid(N), block(256);
-    switch (sj) {
-    case 1: hipLaunchKernelGGL((ctc_align_kernel<1, BP_LDS>), grid, block, lds, s, logits, T, C, lens, label_lens, label_off, labels, starts, ends, conf, score, counts, ws, ws_stride); break;
-    case 2: hipLaunchKernelGGL((ctc_align_kernel<2, BP_LDS>), grid, block, lds, s, logits, T, C, lens, label_lens, label_off, labels, starts, ends, conf, score, counts, ws, ws_stride); break;
-    case 4: hipLaunchKernelGGL((ctc_align_kernel<4, BP_LDS>), grid, block, lds, s, logits, T, C, lens, label_lens, label_off, labels, starts, ends, conf, score, counts, ws, ws_stride); break;
-    default: hipLaunchKernelGGL((ctc_align_kernel<8, BP_LDS>), grid, block, lds, s, logits, T, C, lens, label_lens, label_off, labels, starts, ends, conf, score, counts, ws, ws_stride); break;
-    }
+// bp_lds: the back-pointer table is in the `lds` bytes of dynamic LDS (then ws is not read)
+static inline hipError_t launch_ctc_align(hipStream_t s, int sj, bool bp_lds, size_t lds, const float *logits, int N, int T, int C, const int32_t *lens,
+                                          const int32_t *label_lens, const int32_t *label_off, const int32_t *labels, int32_t *starts, int32_t *ends,
+                                          float *conf, float *score, int32_t *counts, unsigned *ws, size_t ws_stride) {
+    return with_sj(sj, [&](auto SJ) {
+        auto go = [&](auto kern) {
+            return lattice_launch(kern, dim3(N), lds, s, logits, T, C, lens, label_lens, label_off, labels, starts, ends, conf, score, counts, ws, ws_stride);
+        };
+        return bp_lds ? go(ctc_align_kernel<decltype(SJ)::value, true>) : go(ctc_align_kernel<decltype(SJ)::value, false>);
+    });
 }

@@ -3,8 +3,8 @@
 // ctc_beam_kernel (ctc.hip.h); a frame's candidate classes are blank + its K best non-blank classes, every prefix carries
 // lmv = sum over its labels of alpha * lm(context, label) + beta, and candidates rank by logaddexp(p_b, p_nb) + lmv.  The static
 // pruning of ctc_beam_walk_kernel does not hold with a per-(prefix, class) term, so all beam x K extensions are scored.
-//   * ctc_lm_topk_kernel: one wave per frame of the whole batch, any class count: max / log Z in the lane-strided order of
-//     ctc_beam_kernel (so lp is bit-identical to the plain beam's), then K rounds of "largest key below the last one" for the
+//   * ctc_lm_topk_kernel: one wave per frame of the whole batch, any class count: max / log Z by the row_max / row_lse that
+//     ctc_beam_kernel calls (so lp is bit-identical to the plain beam's), then K rounds of "largest key below the last one" for the
 //     K best non-blank classes (ties: smaller class).  Record per frame: lp[blank], log Z, max, K x (class, lp).
 //   * ctc_lm_walk_kernel: one workgroup of 256 threads per line, prefix state double-buffered in LDS (the last 7 labels of each
 //     prefix as 16-bit values).  Per frame: extension candidate (i, r) -> one thread each (tid, tid + 256, ..): score, fold test,
@@ -102,12 +102,7 @@ __global__ __launch_bounds__(256) void ctc_lm_topk_kernel(const float *__restric
     if (t >= min(max(lens[n], 0), T)) return;
     const float *lg = logits + (size_t)f * C;
     float *rec = rec_all + (size_t)f * COCR_LM_REC;
-    float mx = -INFINITY;
-    for (int c = lane; c < C; c += 64) mx = fmaxf(mx, lg[c]);
-    mx = wave_max(mx);
-    float sm = 0.f;
-    for (int c = lane; c < C; c += 64) sm += expf(lg[c] - mx);
-    const float lz = mx + logf(wave_sum(sm));
+    const float mx = row_max(lg, C, lane), lz = row_lse(lg, C, lane, mx);
     if (lane == 0) { rec[0] = (lg[0] - mx) - (lz - mx); rec[1] = lz; rec[2] = mx; rec[3] = 0.f; }
     unsigned long long bound = ~0ull;                           // the last round's key: this round takes the largest key below it
     for (int r = 0; r < K; ++r) {

@@ -4,8 +4,9 @@
 //   A  log-softmax of the valid frames (all 4 waves, one frame per wave at a time) -> lp (scratch)
 //   B  the forward recursion alpha on wave 0 and the backward recursion beta on wave 1, AT THE SAME TIME (they are independent);
 //      the blank-extended label sequence l' (S = 2 L + 1 states) is spread over the lanes, state s on lane s & 63, register s >> 6,
-//      so the two neighbours s-1, s-2 (s+1, s+2) of a step arrive by two lane rotations per register and nothing is exchanged through
-//      memory inside the T-step dependent chain; the frame's lp values for the next step are requested one step ahead.
+//      and the two neighbours s-1, s-2 (s+1, s+2) of a step arrive by the exchange of ctc_lattice.hip.h (DESIGN.md "The lattice kernels'
+//      shared pieces"); the frame's lp values for the next step are requested one step ahead (a stored log-softmax walked in both
+//      directions: not the ring of the other two lattice kernels).
 //      alpha_t(s) = lse(alpha_{t-1}(s), alpha_{t-1}(s-1), [alpha_{t-1}(s-2) if l'_s != blank and l'_s != l'_{s-2}]) + lp_t(l'_s)
 //      nll = -lse(alpha_{len-1}(S-1), alpha_{len-1}(S-2));   beta mirrors it from the last valid frame.
 //   C  gradient (all 4 waves, one frame per wave at a time):  d nll / d probits[t, c] = softmax[t, c] - occ[t, c],
@@ -17,9 +18,7 @@
 // T = 300: the log-domain quantities reach 1e3, one ulp there is 1e-4).  Latency-bound by the T-step chain, not by bytes: algorithmic
 // bytes = N T C 4 read (+ N T C 4 written for the gradient).
 #pragma once
-#include "common.hip.h"
-
-#define COCR_CTCL_MAX_LABELS 255        // per line: S = 2 L + 1 <= 512 states = 8 registers of a wave
+#include "ctc_lattice.hip.h"
 
 __device__ __forceinline__ float ctcl_lse3(float a, float b, float c) {
     const float m = fmaxf(a, fmaxf(b, c));
@@ -35,7 +34,7 @@ __global__ __launch_bounds__(256) void ctc_loss_kernel(const float *__restrict__
     constexpr int SP = 64 * SJ;
     extern __shared__ __attribute__((aligned(16))) unsigned char ctcl_smem[];
     int32_t *first = reinterpret_cast<int32_t *>(ctcl_smem);                 // [C] first occurrence of class c in the label sequence, -1 if none
-    __shared__ int32_t lab[COCR_CTCL_MAX_LABELS + 1], nxt[COCR_CTCL_MAX_LABELS + 1];
+    __shared__ int32_t lab[COCR_LATTICE_MAX_LABELS + 1], nxt[COCR_LATTICE_MAX_LABELS + 1];
     __shared__ float fin[64 * 8];
     __shared__ float sh_nll;
     const int n = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
@@ -63,12 +62,7 @@ __global__ __launch_bounds__(256) void ctc_loss_kernel(const float *__restrict__
     // ---- A: log-softmax of the valid frames
     for (int t = wave; t < len; t += 4) {
         const float *x = pr + (size_t)t * C;
-        float mx = -INFINITY;
-        for (int c = lane; c < C; c += 64) mx = fmaxf(mx, x[c]);
-        mx = wave_max(mx);
-        float sum = 0.f;
-        for (int c = lane; c < C; c += 64) sum += expf(x[c] - mx);
-        const float lz = mx + logf(wave_sum(sum));
+        const float lz = row_lse(x, C, lane, row_max(x, C, lane));
         for (int c = lane; c < C; c += 64) lp[(size_t)t * C + c] = x[c] - lz;
     }
     __threadfence_block();
@@ -80,15 +74,7 @@ __global__ __launch_bounds__(256) void ctc_loss_kernel(const float *__restrict__
         int cls[SJ];            // class of state s = lane + 64 j
         bool skip[SJ];          // alpha: s-2 feeds s;  beta: s+2 feeds s
         bool live[SJ];
-#pragma unroll
-        for (int j = 0; j < SJ; ++j) {
-            const int s = lane + 64 * j;
-            live[j] = s < S;
-            const int k = (s - 1) >> 1;
-            cls[j] = (live[j] && (s & 1)) ? lab[k] : 0;
-            if (fwd) skip[j] = live[j] && (s & 1) && s >= 3 && lab[k] != lab[k - 1];
-            else skip[j] = (s & 1) && s + 2 < S && lab[k] != lab[k + 1];
-        }
+        lattice_states<SJ, 1>(lab, S, lane, !fwd, cls, skip, live);
         float a[SJ], nlp[SJ];
         const int t0 = fwd ? 0 : len - 1, dt = fwd ? 1 : -1;
 #pragma unroll
@@ -103,7 +89,9 @@ __global__ __launch_bounds__(256) void ctc_loss_kernel(const float *__restrict__
 #pragma unroll
             for (int j = 0; j < SJ; ++j) nlp[j] = live[j] ? lp[(size_t)(t0 + dt) * C + cls[j]] : -INFINITY;
         }
-        const int src1 = fwd ? ((lane + 63) & 63) : ((lane + 1) & 63), src2 = fwd ? ((lane + 62) & 63) : ((lane + 2) & 63);
+        int src1, src2;
+        if (fwd) lattice_src_fwd(lane, src1, src2);
+        else lattice_src_bwd(lane, src1, src2);
         for (int i = 1; i < len; ++i) {
             const int t = t0 + i * dt;
             float cur[SJ];
@@ -114,18 +102,12 @@ __global__ __launch_bounds__(256) void ctc_loss_kernel(const float *__restrict__
                 for (int j = 0; j < SJ; ++j) nlp[j] = live[j] ? lp[(size_t)(t + dt) * C + cls[j]] : -INFINITY;
             }
             float r1[SJ], r2[SJ];
-#pragma unroll
-            for (int j = 0; j < SJ; ++j) { r1[j] = __shfl(a[j], src1, 64); r2[j] = __shfl(a[j], src2, 64); }
+            lattice_rotate(a, r1, r2, src1, src2);
 #pragma unroll
             for (int j = 0; j < SJ; ++j) {
                 float n1, n2;
-                if (fwd) {     // lanes 0 (and 1) take the previous register's lanes 63 (and 62)
-                    n1 = lane >= 1 ? r1[j] : (j > 0 ? r1[j > 0 ? j - 1 : 0] : -INFINITY);
-                    n2 = lane >= 2 ? r2[j] : (j > 0 ? r2[j > 0 ? j - 1 : 0] : -INFINITY);
-                } else {       // lanes 63 (and 62) take the next register's lanes 0 (and 1)
-                    n1 = lane < 63 ? r1[j] : (j + 1 < SJ ? r1[j + 1 < SJ ? j + 1 : 0] : -INFINITY);
-                    n2 = lane < 62 ? r2[j] : (j + 1 < SJ ? r2[j + 1 < SJ ? j + 1 : 0] : -INFINITY);
-                }
+                if (fwd) { n1 = lattice_seam_fwd(r1, j, lane, 1, -INFINITY); n2 = lattice_seam_fwd(r2, j, lane, 2, -INFINITY); }
+                else { n1 = lattice_seam_bwd(r1, j, lane, 1, -INFINITY); n2 = lattice_seam_bwd(r2, j, lane, 2, -INFINITY); }
                 const float v = ctcl_lse3(a[j], n1, skip[j] ? n2 : -INFINITY) + cur[j];
                 cur[j] = live[j] ? v : -INFINITY;
             }
@@ -173,11 +155,7 @@ __global__ __launch_bounds__(256) void ctc_loss_kernel(const float *__restrict__
 
 static inline void launch_ctc_loss(hipStream_t s, int sj, size_t lds, const float *probits, int N, int T, int C, const int32_t *lens, const int32_t *label_lens,
                                    const int32_t *label_off, const int32_t *labels, float *nll, float *grad, float *lp_all, float *ab_all) {
-    dim3 grid(N), block(256);
-    switch (sj) {
-    case 1: hipLaunchKernelGGL((ctc_loss_kernel<1>), grid, block, lds, s, probits, T, C, lens, label_lens, label_off, labels, nll, grad, lp_all, ab_all); break;
-    case 2: hipLaunchKernelGGL((ctc_loss_kernel<2>), grid, block, lds, s, probits, T, C, lens, label_lens, label_off, labels, nll, grad, lp_all, ab_all); break;
-    case 4: hipLaunchKernelGGL((ctc_loss_kernel<4>), grid, block, lds, s, probits, T, C, lens, label_lens, label_off, labels, nll, grad, lp_all, ab_all); break;
-    default: hipLaunchKernelGGL((ctc_loss_kernel<8>), grid, block, lds, s, probits, T, C, lens, label_lens, label_off, labels, nll, grad, lp_all, ab_all); break;
-    }
+    with_sj(sj, [&](auto SJ) {
+        hipLaunchKernelGGL((ctc_loss_kernel<decltype(SJ)::value>), dim3(N), dim3(256), lds, s, probits, T, C, lens, label_lens, label_off, labels, nll, grad, lp_all, ab_all);
+    });
 }

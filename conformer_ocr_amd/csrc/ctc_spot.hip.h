@@ -11,22 +11,19 @@
 //   min_score, then every live candidate whose [sigma_u, u] intersects the hit's [sigma, t] dies.
 // One workgroup of 4 waves takes 4 queries of one line (grid (ceil(Q / 4), N)); one wave runs one (line, query) pair:
 //   A  mx_t = max_c logits[t, c] of the valid frames (all 4 waves, one frame per wave at a time) -> LDS: once per frame, not per state.
-//   B  the recursion: state s on lane s & 63, register s >> 6; delta AND sigma of the neighbours s-1 and s-2 by two lane rotations per
-//      register each; the next frames' gathered logits requested four steps ahead and subtracted only when their step begins.  The lane
-//      of state S-1 stores e_t and sigma_t: in LDS beside mx when the four waves' tables fit (ET_LDS), else in the pair's region of a
-//      global workspace (same code).
+//   B  the recursion, on the shared machine of ctc_lattice.hip.h (DESIGN.md "The lattice kernels' shared pieces": states over the lanes,
+//      the prefetch ring, and the neighbour exchange once for delta and once for sigma).  The lane of state S-1 stores e_t and sigma_t:
+//      in LDS beside mx when the four waves' tables fit (ET_LDS), else in the pair's region of a global workspace (same code).
 //   C  selection on the same wave: per round one pass for the wave-wide arg-max (lane i scans frames i, i + 64, ...) and one pass that
 //      kills the overlapping candidates (e_u = -inf).  Lane k keeps hit k; the records go out as ordinary vector stores.
 // Every loop is bounded by T, S or K; nothing waits on another workgroup; no atomics: results are reproducible run to run.
 #pragma once
-#include "common.hip.h"
+#include "ctc_lattice.hip.h"
 
-#define COCR_SPOT_MAX_LABELS 255
 #define COCR_SPOT_MAX_HITS 8
 
-// dynamic LDS: mx (T floats, padded to 16 bytes), then with ET_LDS per wave e (T floats) and sigma (T ints), each padded alike
-__host__ __device__ static inline size_t ctcs_row_bytes(int T) { return ((size_t)T * 4 + 15) & ~(size_t)15; }
-__host__ __device__ static inline size_t ctcs_pair_words(int T) { return 2 * (ctcs_row_bytes(T) / 4); }
+// dynamic LDS: mx (lattice_row_bytes(T)), then with ET_LDS per wave e (T floats) and sigma (T ints), each padded alike
+__host__ __device__ static inline size_t ctcs_pair_words(int T) { return 2 * (lattice_row_bytes(T) / 4); }
 
 template <int SJ, bool ET_LDS>
 __global__ __launch_bounds__(256) void ctc_spot_kernel(const float *__restrict__ logits, int T, int C, const int32_t *__restrict__ lens,
@@ -35,12 +32,12 @@ __global__ __launch_bounds__(256) void ctc_spot_kernel(const float *__restrict__
                                                        int32_t *__restrict__ starts, int32_t *__restrict__ ends, float *__restrict__ score,
                                                        int32_t *__restrict__ counts, unsigned *__restrict__ ws) {
     extern __shared__ __attribute__((aligned(16))) unsigned char ctcs_smem[];
-    __shared__ int32_t lab_all[4][COCR_SPOT_MAX_LABELS + 1];
+    __shared__ int32_t lab_all[4][COCR_LATTICE_MAX_LABELS + 1];
     const int n = blockIdx.y, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int q = blockIdx.x * 4 + wave;
     const int len = min(max(lens[n], 0), T);
     const float *x = logits + (size_t)n * T * C;
-    const size_t row = ctcs_row_bytes(T);
+    const size_t row = lattice_row_bytes(T);
     float *mx = reinterpret_cast<float *>(ctcs_smem);
     const int L = q < Q ? query_lens[q] : 0;
     int32_t *lab = lab_all[wave];
@@ -50,10 +47,7 @@ __global__ __launch_bounds__(256) void ctc_spot_kernel(const float *__restrict__
     }
     // ---- A: the per-frame maximum
     for (int t = wave; t < len; t += 4) {
-        const float *xt = x + (size_t)t * C;
-        float m = -INFINITY;
-        for (int c = lane; c < C; c += 64) m = fmaxf(m, xt[c]);
-        m = wave_max(m);
+        const float m = row_max(x + (size_t)t * C, C, lane);
         if (lane == 0) mx[t] = m;
     }
     __syncthreads();
@@ -68,46 +62,24 @@ __global__ __launch_bounds__(256) void ctc_spot_kernel(const float *__restrict__
     if (len > 0) {
         int cls[SJ];
         bool skip[SJ], live[SJ], last[SJ];
-#pragma unroll
-        for (int j = 0; j < SJ; ++j) {
-            const int s = lane + 64 * j;
-            live[j] = s < S;
-            last[j] = s == S - 1;
-            const int k = s >> 1;
-            const bool is_label = live[j] && !(s & 1);
-            cls[j] = is_label ? lab[k] : 0;
-            skip[j] = is_label && s >= 2 && lab[k] != lab[k - 1];
-        }
-        // The logits and row maxima of the next PF frames are requested PF steps ahead (a ring in registers; every lane loads, a dead
-        // state the blank's; beyond the line the last frame again) and subtracted only when their step begins.
-        constexpr int PF = 4;
-        float a[SJ], nx[PF][SJ], nz[PF];
+        lattice_states<SJ, 0>(lab, S, lane, false, cls, skip, live);
+        float a[SJ];
         int sg[SJ];
 #pragma unroll
-        for (int j = 0; j < SJ; ++j) { a[j] = -INFINITY; sg[j] = -1; }
-#pragma unroll
-        for (int u = 0; u < PF; ++u) {
-            const int tt = min(u, len - 1);
-            nz[u] = mx[tt];
-#pragma unroll
-            for (int j = 0; j < SJ; ++j) nx[u][j] = x[(size_t)tt * C + cls[j]];
-        }
-        const int src1 = (lane + 63) & 63, src2 = (lane + 62) & 63;
-        auto step = [&](int t, float (&cur)[SJ]) {            // cur: r_t(class(s)) of this lane's states
+        for (int j = 0; j < SJ; ++j) { last[j] = lane + 64 * j == S - 1; a[j] = -INFINITY; sg[j] = -1; }
+        int src1, src2;
+        lattice_src_fwd(lane, src1, src2);
+        lattice_ring(x, C, mx, cls, 0, len, [&](int t, float (&cur)[SJ]) {            // cur: r_t(class(s)) of this lane's states
             float r1[SJ], r2[SJ];
             int g1[SJ], g2[SJ], ns[SJ];
+            lattice_rotate(a, r1, r2, src1, src2);
+            lattice_rotate(sg, g1, g2, src1, src2);
 #pragma unroll
             for (int j = 0; j < SJ; ++j) {
-                r1[j] = __shfl(a[j], src1, 64); r2[j] = __shfl(a[j], src2, 64);
-                g1[j] = __shfl(sg[j], src1, 64); g2[j] = __shfl(sg[j], src2, 64);
-            }
-#pragma unroll
-            for (int j = 0; j < SJ; ++j) {          // lanes 0 (and 1) take the previous register's lanes 63 (and 62)
-                const int jp = j > 0 ? j - 1 : 0;
-                const float n1 = lane >= 1 ? r1[j] : (j > 0 ? r1[jp] : -INFINITY);
-                const float n2 = lane >= 2 ? r2[j] : (j > 0 ? r2[jp] : -INFINITY);
-                const int s1 = lane >= 1 ? g1[j] : g1[jp];
-                const int s2 = lane >= 2 ? g2[j] : g2[jp];
+                const float n1 = lattice_seam_fwd(r1, j, lane, 1, -INFINITY), n2 = lattice_seam_fwd(r2, j, lane, 2, -INFINITY);
+                // (below state 0 there is no path: its score is -inf and its start never taken, so any value does; the rotated one
+                // needs no select)
+                const int s1 = lattice_seam_fwd(g1, j, lane, 1, g1[0]), s2 = lattice_seam_fwd(g2, j, lane, 2, g2[0]);
                 float best = a[j];
                 int from = sg[j];
                 if (n1 > best) { best = n1; from = s1; }
@@ -121,30 +93,7 @@ __global__ __launch_bounds__(256) void ctc_spot_kernel(const float *__restrict__
                 a[j] = cur[j]; sg[j] = ns[j];
                 if (last[j]) { ev[t] = a[j]; sv[t] = sg[j]; }
             }
-        };
-        int t0 = 0;
-        for (; t0 + PF <= len; t0 += PF) {
-#pragma unroll
-            for (int u = 0; u < PF; ++u) {
-                float cur[SJ];
-#pragma unroll
-                for (int j = 0; j < SJ; ++j) cur[j] = nx[u][j] - nz[u];
-                const int tt = min(t0 + u + PF, len - 1);
-                nz[u] = mx[tt];
-#pragma unroll
-                for (int j = 0; j < SJ; ++j) nx[u][j] = x[(size_t)tt * C + cls[j]];
-                step(t0 + u, cur);
-            }
-        }
-#pragma unroll
-        for (int u = 0; u < PF - 1; ++u) {               // the last len - t0 < PF frames are in the ring already
-            if (t0 + u < len) {
-                float cur[SJ];
-#pragma unroll
-                for (int j = 0; j < SJ; ++j) cur[j] = nx[u][j] - nz[u];
-                step(t0 + u, cur);
-            }
-        }
+        });
         if (!ET_LDS) __threadfence();                // the workspace words written above are read below by other lanes
         __threadfence_block();
     }
@@ -180,15 +129,15 @@ __global__ __launch_bounds__(256) void ctc_spot_kernel(const float *__restrict__
     if (lane == 0) counts[pair] = count;
 }
 
-template <bool ET_LDS>
-static inline void launch_ctc_spot(hipStream_t s, int sj, size_t lds, const float *logits, int N, int T, int C, const int32_t *lens,
-                                   const int32_t *query_lens, const int32_t *query_off, const int32_t *queries, int Q, int K, float min_score,
-                                   int32_t *starts, int32_t *ends, float *score, int32_t *counts, unsigned *ws) {
-    dim3 grid((Q + 3) / 4, N), block(256);
-    switch (sj) {
-    case 1: hipLaunchKernelGGL((ctc_spot_kernel<1, ET_LDS>), grid, block, lds, s, logits, T, C, lens, query_lens, query_off, queries, Q, K, min_score, starts, ends, score, counts, ws); break;
-    case 2: hipLaunchKernelGGL((ctc_spot_kernel<2, ET_LDS>), grid, block, lds, s, logits, T, C, lens, query_lens, query_off, queries, Q, K, min_score, starts, ends, score, counts, ws); break;
-    case 4: hipLaunchKernelGGL((ctc_spot_kernel<4, ET_LDS>), grid, block, lds, s, logits, T, C, lens, query_lens, query_off, queries, Q, K, min_score, starts, ends, score, counts, ws); break;
-    default: hipLaunchKernelGGL((ctc_spot_kernel<8, ET_LDS>), grid, block, lds, s, logits, T, C, lens, query_lens, query_off, queries, Q, K, min_score, starts, ends, score, counts, ws); break;
-    }
+// et_lds: the candidate tables are in the `lds` bytes of dynamic LDS (then ws is not read)
+static inline hipError_t launch_ctc_spot(hipStream_t s, int sj, bool et_lds, size_t lds, const float *logits, int N, int T, int C, const int32_t *lens,
+                                         const int32_t *query_lens, const int32_t *query_off, const int32_t *queries, int Q, int K, float min_score,
+                                         int32_t *starts, int32_t *ends, float *score, int32_t *counts, unsigned *ws) {
+    return with_sj(sj, [&](auto SJ) {
+        auto go = [&](auto kern) {
+            return lattice_launch(kern, dim3((Q + 3) / 4, N), lds, s, logits, T, C, lens, query_lens, query_off, queries, Q, K, min_score, starts, ends, score, counts, ws);
+        };
+        return et_lds ? go(ctc_spot_kernel<decltype(SJ)::value, true>) : go(ctc_spot_kernel<decltype(SJ)::value, false>);
+    });
 }
+

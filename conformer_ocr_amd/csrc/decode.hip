@@ -21,6 +21,33 @@ static int upload_lens(cocr_model *m, const int32_t *lens, int N, hipStream_t s,
     return COCR_OK;
 }
 
+// Host prologues of the calls that read their per-line lengths and labels before anything is launched.
+static int check_out_lens(const int32_t *out_lens, int N, int T) {
+    for (int n = 0; n < N; ++n)
+        if (out_lens[n] < 0 || out_lens[n] > T) return fail(COCR_EINVAL, "input length %d outside [0, %d] (line %d)", out_lens[n], T, n);
+    return COCR_OK;
+}
+
+// `noun`: what a label is called in the message ("target", "query label")
+static int check_labels(const char *noun, const int32_t *labels, size_t total, int ncls) {
+    for (size_t i = 0; i < total; ++i)
+        if (labels[i] < 1 || labels[i] >= ncls) return fail(COCR_EINVAL, "%s %d outside [1, %d) (blank is 0)", noun, labels[i], ncls);
+    return COCR_OK;
+}
+
+// Where the per-line (per-pair) table of a lattice kernel lives: in dynamic LDS behind the frame statistics when all of it
+// (`lds_all` bytes) fits -- the kernels have ~5 KB of static LDS of their own -- else in `ws`, grown to `ws_words`, the statistics
+// (`lds_stats` bytes) alone in LDS.  `lds`: the dynamic LDS to launch with; `ws`: null for the LDS form.
+struct LatticeTable { bool in_lds; size_t lds; unsigned *ws; };
+static int place_lattice_table(size_t lds_stats, size_t lds_all, DevBuf<unsigned> &ws, size_t ws_words, LatticeTable &t) {
+    t = {lds_all <= 144 * 1024, lds_all, nullptr};
+    if (t.in_lds) return COCR_OK;
+    HIP_TRY(ws.grow(ws_words));
+    t.lds = lds_stats;
+    t.ws = ws.p;
+    return COCR_OK;
+}
+
 int ensure_ctc_scratch(cocr_model *m, size_t rows) {
     if (rows <= m->dec.ctc_lab.n && rows <= m->dec.ctc_val.n) return COCR_OK;
     HIP_TRY(hipDeviceSynchronize());                          // (captured launches that point at the old scratch are dropped with it)
@@ -187,21 +214,22 @@ struct CtcTargets { const int32_t *lens, *label_lens, *label_off, *labels; int s
 
 // Loss and forced alignment: checks the per-line lengths and the labels, then sends [lens | label lens | label offsets | labels]
 // through the targets ring.  `outputs_ok`: the caller's per-label output pointers are set (asked for only where there are labels);
-// `too_long`: the status for a line of more than COCR_CTCL_MAX_LABELS labels.
+// `too_long`: the status for a line of more than COCR_LATTICE_MAX_LABELS labels.
 static int upload_targets(cocr_model *m, int N, int T, int ncls, const int32_t *out_lens, const int32_t *targets, const int32_t *label_lens,
                           bool outputs_ok, int too_long, void *stream, CtcTargets &t) {
     size_t total = 0;
     int max_l = 0;
+    int rc = check_out_lens(out_lens, N, T);
+    if (rc) return rc;
     for (int n = 0; n < N; ++n) {
         if (label_lens[n] < 0) return fail(COCR_EINVAL, "negative target length (line %d)", n);
-        if (label_lens[n] > COCR_CTCL_MAX_LABELS) return fail(too_long, "line %d has %d labels; the kernel holds at most %d", n, label_lens[n], COCR_CTCL_MAX_LABELS);
-        if (out_lens[n] < 0 || out_lens[n] > T) return fail(COCR_EINVAL, "input length %d outside [0, %d] (line %d)", out_lens[n], T, n);
+        if (label_lens[n] > COCR_LATTICE_MAX_LABELS)
+            return fail(too_long, "line %d has %d labels; the kernel holds at most %d", n, label_lens[n], COCR_LATTICE_MAX_LABELS);
         max_l = std::max(max_l, (int)label_lens[n]);
         total += (size_t)label_lens[n];
     }
     if (total && (!targets || !outputs_ok)) return fail(COCR_EINVAL, "null argument");
-    for (size_t i = 0; i < total; ++i)
-        if (targets[i] < 1 || targets[i] >= ncls) return fail(COCR_EINVAL, "target %d outside [1, %d) (blank is 0)", targets[i], ncls);
+    if ((rc = check_labels("target", targets, total, ncls))) return rc;
     HIP_TRY(hipSetDevice(m->device));
     const size_t ints = (size_t)3 * N + total;
     int32_t *h, *d;
@@ -210,8 +238,7 @@ static int upload_targets(cocr_model *m, int N, int T, int ncls, const int32_t *
     for (int n = 0; n < N; ++n) { h[n] = out_lens[n]; h[N + n] = label_lens[n]; h[2 * N + n] = off; off += label_lens[n]; }
     if (total) memcpy(h + 3 * N, targets, total * 4);
     HIP_TRY(m->dec.target_ring.commit(ints * 4, (hipStream_t)stream));
-    const int states = 2 * max_l + 1;
-    t = {d, d + N, d + 2 * N, d + 3 * N, states <= 64 ? 1 : states <= 128 ? 2 : states <= 256 ? 4 : 8};
+    t = {d, d + N, d + 2 * N, d + 3 * N, sj_for_states(2 * max_l + 1)};
     return COCR_OK;
 }
 
@@ -244,8 +271,8 @@ int distill_loss_on(cocr_model *m, const float *student, const float *teacher, i
     if (!std::isfinite(ctc_weight) || ctc_weight < 0.f || !std::isfinite(kd_weight) || kd_weight < 0.f)
         return fail(COCR_EINVAL, "the weights must be finite and not negative (%g, %g)", (double)ctc_weight, (double)kd_weight);
     if (accumulate != 0 && accumulate != 1) return fail(COCR_EINVAL, "accumulate must be 0 or 1");
-    for (int n = 0; n < N; ++n)
-        if (out_lens[n] < 0 || out_lens[n] > T) return fail(COCR_EINVAL, "input length %d outside [0, %d] (line %d)", out_lens[n], T, n);
+    int rc = check_out_lens(out_lens, N, T);
+    if (rc) return rc;
     if (ncls > 16384) return fail(COCR_EUNSUPPORTED, "more than 16384 classes");
     HIP_TRY(hipSetDevice(m->device));
     if (!frame_ws) {
@@ -254,8 +281,7 @@ int distill_loss_on(cocr_model *m, const float *student, const float *teacher, i
         frame_ws = m->dec.distill_ws.p;
     }
     const int32_t *d_lens;
-    const int rc = upload_lens(m, out_lens, N, s, d_lens);
-    if (rc) return rc;
+    if ((rc = upload_lens(m, out_lens, N, s, d_lens))) return rc;
     launch_distill(s, student, teacher, N, T, ncls, d_lens, tau, frame_ws, kd, grad, ctc_weight, kd_weight, accumulate);
     LAUNCH_CHECK();
     return COCR_OK;
@@ -273,23 +299,14 @@ extern "C" int cocr_ctc_align(cocr_model *m, const float *logits, int N, int T, 
     if (N < 1 || T < 1 || ncls < 2) return fail(COCR_EINVAL, "empty problem");
     if (T > 8000) return fail(COCR_EUNSUPPORTED, "more than 8000 frames per line");
     CtcTargets t;
-    const int rc = upload_targets(m, N, T, ncls, out_lens, targets, label_lens, starts && ends && conf, COCR_EINVAL, stream, t);
+    int rc = upload_targets(m, N, T, ncls, out_lens, targets, label_lens, starts && ends && conf, COCR_EINVAL, stream, t);
     if (rc) return rc;
-    hipStream_t s = (hipStream_t)stream;
-    const int sj = t.sj;
-    // the back-pointer table: in LDS beside lz when both fit (the kernel has ~5 KB of static LDS), else one region per line of the workspace
-    const size_t words = ctca_bp_words(T, sj), lds_all = ctca_lz_bytes(T) + words * 4;
-    if (lds_all <= 144 * 1024) {
-        auto kern = ctc_align_kernel<8, true>;
-        switch (sj) { case 1: kern = ctc_align_kernel<1, true>; break; case 2: kern = ctc_align_kernel<2, true>; break; case 4: kern = ctc_align_kernel<4, true>; break; }
-        // (the kernel also has ~5 KB of static LDS: the limit raised for the dynamic part stays below 160 KB - static)
-        HIP_TRY(raise_lds_limit((const void *)kern, lds_all, 48 * 1024, 150 * 1024));
-        launch_ctc_align<true>(s, sj, lds_all, logits, N, T, ncls, t.lens, t.label_lens, t.label_off, t.labels, starts, ends, conf, score, counts, nullptr, 0);
-    } else {
-        HIP_TRY(m->dec.align_ws.grow((size_t)N * words));
-        launch_ctc_align<false>(s, sj, ctca_lz_bytes(T), logits, N, T, ncls, t.lens, t.label_lens, t.label_off, t.labels, starts, ends, conf, score, counts,
-                                m->dec.align_ws.p, words);
-    }
+    // the back-pointer table: beside lz, or one region per line of the workspace
+    const size_t words = ctca_bp_words(T, t.sj), row = lattice_row_bytes(T);
+    LatticeTable tab;
+    if ((rc = place_lattice_table(row, row + words * 4, m->dec.align_ws, (size_t)N * words, tab))) return rc;
+    HIP_TRY(launch_ctc_align((hipStream_t)stream, t.sj, tab.in_lds, tab.lds, logits, N, T, ncls, t.lens, t.label_lens, t.label_off, t.labels, starts, ends, conf, score,
+                             counts, tab.ws, tab.in_lds ? 0 : words));
     LAUNCH_CHECK();
     return COCR_OK;
 }
@@ -305,18 +322,17 @@ extern "C" int cocr_ctc_spot(cocr_model *m, const float *logits, int N, int T, i
     if (std::isnan(min_score)) return fail(COCR_EINVAL, "min_score is NaN");
     if (T > 8000) return fail(COCR_EUNSUPPORTED, "more than 8000 frames per line");
     if (N > 65535) return fail(COCR_EUNSUPPORTED, "more than 65535 lines in one call");
-    for (int n = 0; n < N; ++n)
-        if (out_lens[n] < 0 || out_lens[n] > T) return fail(COCR_EINVAL, "input length %d outside [0, %d] (line %d)", out_lens[n], T, n);
+    int rc = check_out_lens(out_lens, N, T);
+    if (rc) return rc;
     size_t total = 0;
     int max_l = 0;
     for (int q = 0; q < Q; ++q) {
-        if (query_lens[q] < 1 || query_lens[q] > COCR_SPOT_MAX_LABELS)
-            return fail(COCR_EINVAL, "query %d has %d labels; a query holds 1..%d", q, query_lens[q], COCR_SPOT_MAX_LABELS);
+        if (query_lens[q] < 1 || query_lens[q] > COCR_LATTICE_MAX_LABELS)
+            return fail(COCR_EINVAL, "query %d has %d labels; a query holds 1..%d", q, query_lens[q], COCR_LATTICE_MAX_LABELS);
         max_l = std::max(max_l, (int)query_lens[q]);
         total += (size_t)query_lens[q];
     }
-    for (size_t i = 0; i < total; ++i)
-        if (queries[i] < 1 || queries[i] >= ncls) return fail(COCR_EINVAL, "query label %d outside [1, %d) (blank is 0)", queries[i], ncls);
+    if ((rc = check_labels("query label", queries, total, ncls))) return rc;
     HIP_TRY(hipSetDevice(m->device));
     hipStream_t s = (hipStream_t)stream;
     const size_t ints = (size_t)N + 2 * (size_t)Q + total;
@@ -327,21 +343,12 @@ extern "C" int cocr_ctc_spot(cocr_model *m, const float *logits, int N, int T, i
     for (int q = 0; q < Q; ++q) { h[N + q] = query_lens[q]; h[N + Q + q] = off; off += query_lens[q]; }
     memcpy(h + N + 2 * Q, queries, total * 4);
     HIP_TRY(m->dec.spot_ring.commit(ints * 4, s));
-    const int states = 2 * max_l - 1;
-    const int sj = states <= 64 ? 1 : states <= 128 ? 2 : states <= 256 ? 4 : 8;
-    // the candidate tables (e_t, sigma_t) of the workgroup's four pairs: in LDS beside mx when all fit (the kernel has 4 KB of static
-    // LDS), else one region per pair of the workspace
-    const size_t row = ctcs_row_bytes(T), lds_all = 9 * row;
-    if (lds_all <= 144 * 1024) {
-        auto kern = ctc_spot_kernel<8, true>;
-        switch (sj) { case 1: kern = ctc_spot_kernel<1, true>; break; case 2: kern = ctc_spot_kernel<2, true>; break; case 4: kern = ctc_spot_kernel<4, true>; break; }
-        HIP_TRY(raise_lds_limit((const void *)kern, lds_all, 48 * 1024, 150 * 1024));
-        launch_ctc_spot<true>(s, sj, lds_all, logits, N, T, ncls, d, d + N, d + N + Q, d + N + 2 * Q, Q, hits, min_score, starts, ends, score, counts, nullptr);
-    } else {
-        HIP_TRY(m->dec.spot_ws.grow((size_t)N * Q * ctcs_pair_words(T)));
-        launch_ctc_spot<false>(s, sj, row, logits, N, T, ncls, d, d + N, d + N + Q, d + N + 2 * Q, Q, hits, min_score, starts, ends, score, counts,
-                               m->dec.spot_ws.p);
-    }
+    // the candidate tables (e_t, sigma_t) of the workgroup's four pairs: beside mx, or one region per pair of the workspace
+    const size_t row = lattice_row_bytes(T);
+    LatticeTable tab;
+    if ((rc = place_lattice_table(row, 9 * row, m->dec.spot_ws, (size_t)N * Q * ctcs_pair_words(T), tab))) return rc;
+    HIP_TRY(launch_ctc_spot(s, sj_for_states(2 * max_l - 1), tab.in_lds, tab.lds, logits, N, T, ncls, d, d + N, d + N + Q, d + N + 2 * Q, Q, hits, min_score, starts, ends,
+                            score, counts, tab.ws));
     LAUNCH_CHECK();
     return COCR_OK;
 }

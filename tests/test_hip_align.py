@@ -141,6 +141,31 @@ def test_planted_alignments(N, T, C, l_lo, l_hi, seed, gain):
     _log('align_planted', {'seed': seed, 'T': T, 'lines': N, 'min_runner_up_gap': min_gap})
 
 
+def _check_seam_lines(Ls):
+    from tests.test_hip_ctc_loss import seam_batch
+    logits, lines = seam_batch(Ls)
+    got = _run(logits, Ls, np.concatenate([lab for _, lab, _ in lines]), Ls)
+    for n, (L, (_, lab, lp)) in enumerate(zip(Ls, lines)):
+        own = lp[np.arange(L), lab]
+        records, score = got[n]
+        assert records is not None
+        assert [r[:3] for r in records] == [(int(lab[k]), k, k) for k in range(L)], L
+        assert abs(score - own.sum()) <= _tol(L, own.sum()), (L, score, own.sum())          # the bars of test_planted_alignments
+        np.testing.assert_allclose([r[3] for r in records], np.exp(own), atol=1e-5, rtol=0)
+
+
+@pytest.mark.parametrize('L', [32, 33, 64, 128, 255])
+def test_register_seams_on_the_single_path(L):
+    """tests/test_hip_ctc_loss.py `seam_line`: T = L frames for L labels, one path, label k on frame k -- every step crosses each
+    register seam through the skip edge.  Each L in a call of its own (the kernel form follows the longest line of a call)."""
+    _check_seam_lines([L])
+
+
+def test_register_seams_on_the_single_path_in_one_batch():
+    """All five lines at eight registers per lane."""
+    _check_seam_lines([32, 33, 64, 128, 255])
+
+
 # ---- 2. random logits: the score ----------------------------------------------------------------------------------------------------
 def _random_batches():
     d = np.load(GOLD)

@@ -59,6 +59,62 @@ def test_against_the_restatement_on_random_batches(N, T, C, max_l):
             assert np.abs(grad[n, :out_lens[n]].sum(axis=-1)).max() < 2e-3
 
 
+SEAM_L = [32, 33, 64, 128, 255]         # S = 2 L + 1 = 65, 67, 129, 257, 511 states: two, two, three, five and eight registers of a lane in use
+
+
+def seam_line(L, C=5):
+    """A line with a known answer that leans on the register seams: T = L frames for L labels without equal neighbours, so exactly one
+    path fits -- label k on frame k, no blank -- and every step of alpha and of beta moves two states up, across each seam between two
+    registers of a lane through the skip edge.  Returns logits (L, C) float32, the labels, and log-softmax in float64; then
+        nll = -sum_t lp_t(l_t),   d nll / d logits = softmax - onehot(l_t),   alignment: start = end = k, conf exp(lp_k(l_k)).
+    (The float64 values equal torch.nn.functional.ctc_loss's on the CPU: nll to 1e-15 relative, gradient to 1e-12.)"""
+    g = np.random.default_rng(7000 + L)
+    labels = np.empty(L, dtype=np.int64)
+    labels[0] = g.integers(1, C)
+    for k in range(1, L):
+        labels[k] = 1 + (labels[k - 1] - 1 + g.integers(1, C - 1)) % (C - 1)
+    assert (labels[1:] != labels[:-1]).all() and labels.min() >= 1 and labels.max() < C
+    logits = (g.standard_normal((L, C)) * 2.0).astype(np.float32)
+    x = logits.astype(np.float64)
+    m = x.max(axis=-1, keepdims=True)
+    lp = x - (m + np.log(np.exp(x - m).sum(axis=-1, keepdims=True)))
+    return logits, labels, lp
+
+
+def seam_batch(Ls):
+    """The lines of `Ls` in one batch of max(Ls) frames (a line's frames beyond its length are random and must not matter)."""
+    T, C = max(Ls), 5
+    probits = (np.random.default_rng(7999).standard_normal((len(Ls), T, C)) * 2.0).astype(np.float32)
+    lines = [seam_line(L, C) for L in Ls]
+    for n, (logits, _, _) in enumerate(lines):
+        probits[n, :Ls[n]] = logits
+    return probits, lines
+
+
+def _check_seam_lines(Ls):
+    probits, lines = seam_batch(Ls)
+    nll, grad = _run(probits, np.concatenate([lab for _, lab, _ in lines]), Ls, Ls)
+    for n, (L, (_, lab, lp)) in enumerate(zip(Ls, lines)):
+        want_nll = -lp[np.arange(L), lab].sum()
+        want_grad = np.exp(lp)
+        want_grad[np.arange(L), lab] -= 1.0
+        print(f'seam L {L}: nll {nll[n]:.6f} want {want_nll:.6f} |d grad| {np.abs(grad[n, :L] - want_grad).max():.3g}')
+        np.testing.assert_allclose(nll[n], want_nll, rtol=2e-6, atol=1e-3)            # the bars of the random batches above
+        np.testing.assert_allclose(grad[n, :L], want_grad, atol=2e-3)
+        assert not grad[n, L:].any()
+
+
+@pytest.mark.parametrize('L', SEAM_L)
+def test_register_seams_on_the_single_path(L):
+    """Each L in a call of its own: the kernel form (registers per lane) follows the longest line of a call."""
+    _check_seam_lines([L])
+
+
+def test_register_seams_on_the_single_path_in_one_batch():
+    """All five lines at eight registers per lane."""
+    _check_seam_lines(SEAM_L)
+
+
 def test_edge_lines():
     C = 5
     probits = np.random.default_rng(1).standard_normal((5, 6, C)).astype(np.float32)

@@ -1,0 +1,135 @@
+#!/usr/bin/env python3
+"""Digests of everything behind the forward -- the CTC criterion, forced alignment, keyword spotting, the beam searches, the greedy
+decoder -- for comparing two builds of the library bit for bit:   python tools/decode_digest.py [--out FILE]
+(the library is the tree's, or the one COCR_LIB_PATH names).  None of these kernels has floating-point atomics, so two builds that do
+the same arithmetic in the same order print the same JSON.  The sibling of tools/train_digest.py.
+
+The inputs are the seeded ones of the GPU tests, taken from the test modules themselves, and between them they reach every
+instantiation of the kernels:
+  loss, align   the batches of tests/test_hip_align.py `_random_batches()` (SJ 1, 2, 4, 8) and its two planted 5150-frame batches (the
+                workspace form of the back-pointer table at SJ 8 and SJ 1): nll and gradient; records and scores
+  spot          the five grid cases of tests/test_hip_search.py (SJ 1, 2, 8, the workspace form, lines without frames)
+  beam          the nine shapes of tests/test_hip_beam.py `test_beam_pruned_equals_exhaustive`, and again with COCR_BEAM_REF=1
+  beam_lm       the seven shapes of tests/test_hip_lm.py `test_without_the_model_every_field_equals_the_plain_beam` with alpha = beta
+                = 0, and the six of `test_equals_the_definition_with_a_real_model` with their models
+  greedy        the logits of the beam shapes
+A value is the sha256 of the outputs' bit patterns.  Each environment leg runs in a process of its own (the switch is read when the
+engine is made); this process only starts them and does not open the GPU."""
+import argparse
+import hashlib
+import json
+import os
+import struct
+import subprocess
+import sys
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+LEGS = {'default': {}, 'beam_ref': {'COCR_BEAM_REF': '1'}}
+
+
+def _feed(h, v):
+    """Nested lists / tuples of ints, floats, None, arrays and tensors, bit for bit."""
+    import numpy as np
+    import torch
+    if isinstance(v, torch.Tensor):
+        v = v.detach().cpu().numpy()
+    if isinstance(v, np.ndarray):
+        h.update(str((v.dtype.str, v.shape)).encode() + np.ascontiguousarray(v).tobytes())
+    elif isinstance(v, (list, tuple)):
+        h.update(b'[%d' % len(v))
+        for e in v:
+            _feed(h, e)
+    elif isinstance(v, (float, np.floating)):
+        h.update(b'f' + struct.pack('<d', float(v)))
+    elif v is None:
+        h.update(b'n')
+    else:
+        h.update(b'i' + struct.pack('<q', int(v)))
+
+
+def sha(*values):
+    h = hashlib.sha256()
+    _feed(h, values)
+    return h.hexdigest()
+
+
+def _params(test):
+    """The argument tuples of a parametrised test."""
+    return [tuple(p) for m in test.pytestmark if m.name == 'parametrize' for p in m.args[1]]
+
+
+def run_leg(leg):
+    sys.path.insert(0, ROOT)
+    import numpy as np
+    import torch
+    from conformer_ocr_amd.ctc_decoder import _scratch_engine
+    from tests import test_hip_align as TA, test_hip_beam as TB, test_hip_lm as TL, test_hip_search as TS
+    eng = _scratch_engine(torch.device('cuda', 0))
+    dev = lambda a: torch.from_numpy(np.ascontiguousarray(a, dtype=np.float32)).cuda()
+    out = {}
+    beam_cases = []
+    for C, T, beam, scale in _params(TB.test_beam_pruned_equals_exhaustive):      # the test's own recipe
+        g = np.random.default_rng(C * 7919 + T)
+        logits = (g.normal(size=(6, T, C)) * scale).astype(np.float32)
+        logits[:, :, 0] += 1.0
+        logits[1, :, 1:] = np.round(logits[1, :, 1:] * 2) / 2
+        beam_cases.append(((C, T, beam, scale), dev(logits), [T, T - 1, T // 2, 1, T, 7], beam))
+    for key, x, lens, beam in beam_cases:
+        out[f'{leg}/beam/{key}'] = sha(eng.ctc_beam(x, lens, beam))
+    if leg != 'default':
+        return out
+    for key, x, lens, beam in beam_cases:
+        out[f'greedy/{key}'] = sha(eng.ctc_greedy(x, lens))
+    batches = list(TA._random_batches())
+    for N, T, C, l_lo, l_hi, seed, gain in _params(TA.test_planted_alignments):
+        if T > 5000:
+            logits, labels, _ = TA._planted(N, T, C, l_lo, l_hi, seed, gain)
+            batches.append((f'planted{(N, T, C, l_lo, l_hi)}', logits, np.concatenate(labels), [T] * N, [len(l) for l in labels]))
+    for name, probits, targets, out_lens, label_lens in batches:
+        x = dev(probits)
+        nll, grad = eng.ctc_loss(x, out_lens, targets, label_lens)
+        out[f'loss/{name}'] = {'nll': sha(nll), 'grad': sha(grad), 'nll_only': sha(eng.ctc_loss(x, out_lens, targets, label_lens, with_grad=False)[0])}
+        out[f'align/{name}'] = sha(eng.ctc_align(x, out_lens, targets, label_lens))
+    for N, T, C, lens_q, K, out_lens, width in _params(TS.test_grid_logits_give_the_definition_exactly):
+        logits, queries = TS._grid_case(N, T, C, lens_q, 100 + T, out_lens, width)
+        h = eng.ctc_spot_async(dev(logits), out_lens, queries, K)
+        records = eng.collect_spot(h)
+        Q = len(queries)
+        raw = [h[1][0].numpy()[:, :N * Q * K], h[1][1].numpy()[:N * Q * K], h[1][2].numpy()[:N * Q]]      # entries past the count too
+        out[f'spot/{(N, T, C, K)}'] = {'records': sha(records), 'raw': sha(raw)}
+    for C, T, beam in _params(TL.test_without_the_model_every_field_equals_the_plain_beam):
+        lm = TL._chain_lm(C, 3, seed=C, n=20)
+        got, score = eng.ctc_beam_lm(dev(TL._logits(C, T, 5)), [T, T - 3, T // 2, 1, 0], lm, beam, min(C - 1, 64), 0.0, 0.0, return_scores=True)
+        out[f'beam_lm/off/{(C, T, beam)}'] = {'records': sha(got), 'score': sha(score)}
+    for C, T, beam, classes, order in [(5, 12, 4, 4, 2), (11, 40, 16, 8, 3), (32, 60, 16, 8, 5), (128, 48, 16, 8, 4), (93, 33, 8, 5, 8), (300, 20, 8, 8, 3)]:
+        lm = TL._chain_lm(C, order, seed=C * 31 + order)
+        got, score = eng.ctc_beam_lm(dev(TL._logits(C, T, 4)), [T, T - 3, max(1, T // 2), 1], lm, beam, classes, 0.7, 0.5, return_scores=True)
+        out[f'beam_lm/model/{(C, T, beam, classes, order)}'] = {'records': sha(got), 'score': sha(score)}
+    return out
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument('--leg', choices=sorted(LEGS))
+    ap.add_argument('--out')
+    args = ap.parse_args()
+    if args.leg:
+        print(json.dumps(run_leg(args.leg)))
+        return 0
+    out = {}
+    for leg, env in LEGS.items():
+        r = subprocess.run([sys.executable, os.path.abspath(__file__), '--leg', leg], env={**os.environ, **env}, stdout=subprocess.PIPE, text=True, timeout=300)
+        if r.returncode != 0:
+            print(f'leg {leg} ended with status {r.returncode}', file=sys.stderr)
+            return r.returncode or 1
+        out.update(json.loads(r.stdout.strip().splitlines()[-1]))
+    text = json.dumps(out, indent=1, sort_keys=True)
+    if args.out:
+        with open(args.out, 'w') as fp:
+            fp.write(text + '\n')
+    print(text)
+    return 0
+
+
+if __name__ == '__main__':
+    sys.exit(main())
