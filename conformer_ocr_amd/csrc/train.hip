@@ -23,6 +23,7 @@
 #include "gemm.hip.h"
 #include "train.hip.h"
 #include "train_enc.hip.h"
+#include "train_optim.hip.h"
 #include "train_step.hip.h"
 
 // ------------------------------------------------------------------------------------ output-layer training step (train.hip.h)
@@ -384,7 +385,7 @@ extern "C" int cocr_train_optim_step_ex(cocr_model *m, const cocr_optim *o, cons
 // = cocr_train_optim_step_ex(m, o, NULL, 1.0f, stream): fl(1.0f g) is g for every float, so the step keeps its bits
 extern "C" int cocr_train_optim_step(cocr_model *m, const cocr_optim *o, void *stream) { return cocr_train_optim_step_ex(m, o, nullptr, 1.0f, stream); }
 
-// ---- the gradient window on raw device vectors (kernels: train_enc.hip.h) ------------------------------------------------------------------------
+// ---- the gradient window on raw device vectors (kernels: train_optim.hip.h) ------------------------------------------------------------------------
 extern "C" int cocr_grad_accumulate(float *dst, const float *src, size_t n, float scale, int overwrite, int device, void *stream) {
     if (n == 0) return COCR_OK;
     if (!dst || !src) return fail(COCR_EINVAL, "null argument");

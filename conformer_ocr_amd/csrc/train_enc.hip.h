@@ -44,9 +44,6 @@ __global__ static void k_scale_drop(float *out, const float *in, float alpha, si
 __global__ static void k_axpy(float *y, const float *x, float alpha, size_t n) {          // y += alpha x
     for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (size_t)gridDim.x * blockDim.x) y[i] = fmaf(alpha, x[i], y[i]);
 }
-__global__ static void k_add3(float *y, const float *a, const float *b, float alpha, size_t n) {      // y = a + alpha b
-    for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (size_t)gridDim.x * blockDim.x) y[i] = fmaf(alpha, b[i], a[i]);
-}
 __global__ static void k_u8_to_f32(const uint8_t *in, float *out, size_t n) {
     for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (size_t)gridDim.x * blockDim.x) out[i] = (float)in[i] * (1.0f / 255.0f);
 }
@@ -57,32 +54,41 @@ __global__ static void k_f32_to_bf16(const float *__restrict__ in, bf16_t *__res
         reinterpret_cast<bf16x4 *>(out)[i] = (bf16x4){(bf16_t)v[0], (bf16_t)v[1], (bf16_t)v[2], (bf16_t)v[3]};
     }
 }
-// out[c * ldo + r] = in[r * C + c] for r < R, 0 for R <= r < ldo (grid.y covers ldo: no separate clearing of the tail)
+// ---- transposes through a [32][33] LDS tile: the two halves of k_transpose, k_transpose_bf16 and k_btranspose ---------------------------------
+// load: tile[j][tx] = elem(r0 + j, c0 + tx) inside the (R, C) matrix, 0 outside it (elem is called inside only: a kernel's dropout / row copy rides there)
+template <typename F> __device__ __forceinline__ void tile_load(float (&tile)[32][33], int r0, int c0, int R, int C, F &&elem) {
+    const int tx = threadIdx.x & 31, ty = threadIdx.x >> 5;
+    for (int j = ty; j < 32; j += 8) tile[j][tx] = (r0 + j < R && c0 + tx < C) ? elem(r0 + j, c0 + tx) : 0.f;
+}
+// store: out[c * ldo + r] = tile[r][c] for c < C and r < Rpad (rows R..Rpad-1 of the tile are the zeros of the load: no separate clearing of the tail)
+template <typename T> __device__ __forceinline__ void tile_store_T(const float (&tile)[32][33], T *__restrict__ out, long long ldo, int r0, int c0, int C, int Rpad) {
+    const int tx = threadIdx.x & 31, ty = threadIdx.x >> 5;
+    for (int j = ty; j < 32; j += 8)
+        if (c0 + j < C && r0 + tx < Rpad) out[(long long)(c0 + j) * ldo + r0 + tx] = (T)tile[tx][j];
+}
+// out[c * ldo + r] = in[r * C + c] for r < R, 0 for R <= r < ldo (grid.y covers ldo)
 __global__ static void k_transpose(const float *__restrict__ in, float *__restrict__ out, int R, int C, int ldo) {
     __shared__ float tile[32][33];
-    const int c0 = blockIdx.x * 32, r0 = blockIdx.y * 32, tx = threadIdx.x & 31, ty = threadIdx.x >> 5;
-    for (int j = ty; j < 32; j += 8) tile[j][tx] = (r0 + j < R && c0 + tx < C) ? in[(size_t)(r0 + j) * C + c0 + tx] : 0.f;
+    const int c0 = blockIdx.x * 32, r0 = blockIdx.y * 32;
+    tile_load(tile, r0, c0, R, C, [&](int r, int c) { return in[(size_t)r * C + c]; });
     __syncthreads();
-    for (int j = ty; j < 32; j += 8)
-        if (c0 + j < C && r0 + tx < ldo) out[(size_t)(c0 + j) * ldo + r0 + tx] = tile[tx][j];
+    tile_store_T(tile, out, ldo, r0, c0, C, ldo);
 }
 // 'medium' matmul precision (round 4): ONE pass over an fp32 (R, C) matrix for everything its weight-gradient and input-gradient products
 // need -- outT (C, ldo) = its transpose in bf16, zero beyond row R (the operand of dW = dY^T X; the separate k_transpose + k_f32_to_bf16
 // wrote and re-read the fp32 transpose); outR (R, C) = its bf16 copy (the operand of dX = dY W), or null; part[tile row][C] = the column sums
-// of each 32-row tile, rows added in order (the bias gradient's partial sums: k_colsum_final adds the tiles in a fixed order), or null.
+// of each 32-row tile, rows added in order (the bias gradient's partial sums: the deferred final adds the tiles in a fixed order), or null.
 __global__ __launch_bounds__(256) static void k_transpose_bf16(const float *__restrict__ in, bf16_t *__restrict__ outT, bf16_t *__restrict__ outR,
                                                               float *__restrict__ part, int R, int C, int ldo) {
     __shared__ float tile[32][33];
     const int c0 = blockIdx.x * 32, r0 = blockIdx.y * 32, tx = threadIdx.x & 31, ty = threadIdx.x >> 5;
-    for (int j = ty; j < 32; j += 8) {
-        const bool ok = r0 + j < R && c0 + tx < C;
-        const float v = ok ? in[(size_t)(r0 + j) * C + c0 + tx] : 0.f;
-        tile[j][tx] = v;
-        if (outR && ok) outR[(size_t)(r0 + j) * C + c0 + tx] = (bf16_t)v;
-    }
+    tile_load(tile, r0, c0, R, C, [&](int r, int c) {
+        const float v = in[(size_t)r * C + c];
+        if (outR) outR[(size_t)r * C + c] = (bf16_t)v;
+        return v;
+    });
     __syncthreads();
-    for (int j = ty; j < 32; j += 8)
-        if (c0 + j < C && r0 + tx < ldo) outT[(size_t)(c0 + j) * ldo + r0 + tx] = (bf16_t)tile[tx][j];
+    tile_store_T(tile, outT, ldo, r0, c0, C, ldo);
     if (part && ty == 0 && c0 + tx < C && r0 < R) {
         float sum = 0.f;
 #pragma unroll
@@ -90,6 +96,15 @@ __global__ __launch_bounds__(256) static void k_transpose_bf16(const float *__re
         part[(size_t)blockIdx.y * C + c0 + tx] = sum;
     }
 }
+// ---- column sums in a fixed order (bit-reproducible steps): the pieces ---------------------------------------------------------------------------
+// Every sum of a step's rows -- bias gradients, LayerNorm / BatchNorm parameter gradients, BatchNorm statistics -- is "partial": part[chunk][n]
+// over chunks of `rows` rows, then "final": out[n] = sum of the chunks.  A partial workgroup = 64 lanes of columns x 4 row groups: group g takes
+// every fourth row of the chunk in order, and the four group sums are added in order through LDS (colsum_fold4).  (One thread per column
+// walking all rows serially -- the first form -- left a (9600, 256) bias gradient to ONE workgroup for 28 us, 474 times per training step.)
+// Rows per chunk by the matrix height (colsum_chunk_rows): enough workgroups to fill the chip for the (9600, 256) bias gradients, not more
+// than ~1000 partial rows for the frontend's (230 k, 256) ones.
+static inline int colsum_chunk_rows(int M) { return M <= 16384 ? 32 : (M <= 65536 ? 64 : 256); }
+template <typename V> __device__ __forceinline__ V colsum_fold4(const V (&red)[4][64], int c) { return ((red[0][c] + red[1][c]) + red[2][c]) + red[3][c]; }
 // 'medium' matmul precision: the bf16 row-major copy of an fp32 (R, C) matrix with its rows padded by zeros to Rp (the K-major operand of the
 // weight-gradient product gemm_tn_kernel, whose depth is a multiple of 32 x the split count), and -- part != null -- the column sums of every
 // 32-row tile in a fixed order (the bias gradient's partial sums).  C % 4 == 0.  A thread = four columns x every fourth row of a 32-row tile.
@@ -107,7 +122,7 @@ __global__ __launch_bounds__(256) static void k_rows_bf16(const float *__restric
     if (part) {
         red4[rg][cq] = s;
         __syncthreads();
-        if (rg == 0 && n < C && r0 < R) *reinterpret_cast<f32x4 *>(part + (size_t)blockIdx.y * C + n) = ((red4[0][cq] + red4[1][cq]) + red4[2][cq]) + red4[3][cq];
+        if (rg == 0 && n < C && r0 < R) *reinterpret_cast<f32x4 *>(part + (size_t)blockIdx.y * C + n) = colsum_fold4(red4, cq);
     }
 }
 // out (M, ldo) <- in (M, C), columns C..ldo-1 zero
@@ -117,148 +132,103 @@ __global__ static void k_pad_cols(const float *__restrict__ in, float *__restric
         out[i] = c < C ? in[(i / ldo) * C + c] : 0.f;
     }
 }
-// column sums of a (M, N) matrix, optionally of the elementwise product a .* b: part[chunk][n] over chunks of `rows` rows, then
-// out[n] (+)= sum of chunks.  Fixed summation order (bit-reproducible steps): a workgroup = 64 columns x 4 row (chunk) groups, group g
-// takes every fourth row (chunk) in order, the four partial sums are added in order through LDS.  (One thread per column walking all
-// chunks serially -- the first form -- left a (9600, 256) bias gradient to ONE workgroup for 28 us, 474 times per training step.)
-// Rows per chunk by the matrix height (colsum_chunk_rows): enough workgroups to fill the chip for the (9600, 256) bias gradients, not more
-// than ~1000 partial rows for the frontend's (230 k, 256) ones.
-static inline int colsum_chunk_rows(int M) { return M <= 16384 ? 32 : (M <= 65536 ? 64 : 256); }
+// What a partial kernel sums.  CS_ONE: a, or (b not null) the elementwise product a .* b, N columns.  The others sum the (M, 2 N) pair
+// first | second, part[chunk][2 N]: CS_PAIR a | b (a LayerNorm's d gamma and d beta operands), CS_SQ a | a .* a (BatchNorm's batch statistics in
+// one pass), CS_AB a | a .* b (BatchNorm backward: sum dy = d beta, sum dy xhat = d gamma).  Sums are s += v, products fma(a, b, s).
+enum ColsumKind { CS_ONE, CS_PAIR, CS_SQ, CS_AB };
+// V = float: a thread = one column, a workgroup = 64 columns; V = f32x4 (N % 4 == 0, 16-byte aligned operands): a thread = four consecutive
+// columns (16-byte loads: a wave reads 1 KB of a row, where the scalar form's 256-byte pieces reached 0.55 TB/s), a workgroup = a 256-column stripe
+template <int KIND, typename V>
 __global__ __launch_bounds__(256) static void k_colsum_partial(const float *__restrict__ a, const float *__restrict__ b, float *__restrict__ part, int M, int N, int rows) {
-    __shared__ float red[4][64];
-    const int cl = threadIdx.x & 63, rg = threadIdx.x >> 6, n = blockIdx.x * 64 + cl, chunk = blockIdx.y;
+    constexpr int W = sizeof(V) / sizeof(float), WIDE = KIND == CS_ONE ? 1 : 2;
+    __shared__ V red[4][64];
+    const int cl = threadIdx.x & 63, rg = threadIdx.x >> 6, n = blockIdx.x * 64 * W + W * cl, chunk = blockIdx.y;      // n: column of the (M, WIDE N) matrix
     const int r0 = chunk * rows, r1 = min(M, r0 + rows);
-    float s = 0.f;
-    if (n < N) {
-        if (b) for (int r = r0 + rg; r < r1; r += 4) s = fmaf(a[(size_t)r * N + n], b[(size_t)r * N + n], s);
-        else for (int r = r0 + rg; r < r1; r += 4) s += a[(size_t)r * N + n];
+    V s = {};
+    if constexpr (KIND == CS_ONE) {
+        if (n < N) {
+            if (b) for (int r = r0 + rg; r < r1; r += 4) s = __builtin_elementwise_fma(*reinterpret_cast<const V *>(a + (size_t)r * N + n), *reinterpret_cast<const V *>(b + (size_t)r * N + n), s);
+            else for (int r = r0 + rg; r < r1; r += 4) s += *reinterpret_cast<const V *>(a + (size_t)r * N + n);
+        }
+    } else if constexpr (KIND == CS_PAIR) {
+        if (n < 2 * N) {
+            const float *p = n < N ? a + n : b + (n - N);
+            for (int r = r0 + rg; r < r1; r += 4) s += *reinterpret_cast<const V *>(p + (size_t)r * N);
+        }
+    } else {
+        if (n < N) { for (int r = r0 + rg; r < r1; r += 4) s += *reinterpret_cast<const V *>(a + (size_t)r * N + n); }
+        else if (n < 2 * N) {
+            for (int r = r0 + rg; r < r1; r += 4) {
+                const V v = *reinterpret_cast<const V *>(a + (size_t)r * N + n - N);
+                s = __builtin_elementwise_fma(v, KIND == CS_SQ ? v : *reinterpret_cast<const V *>(b + (size_t)r * N + n - N), s);
+            }
+        }
     }
     red[rg][cl] = s;
     __syncthreads();
-    if (rg == 0 && n < N) part[(size_t)chunk * N + n] = ((red[0][cl] + red[1][cl]) + red[2][cl]) + red[3][cl];
+    if (rg == 0 && n < WIDE * N) *reinterpret_cast<V *>(part + (size_t)chunk * WIDE * N + n) = colsum_fold4(red, cl);
 }
-// the same for N % 4 == 0: a thread = four consecutive columns (16-byte loads: a wave reads 1 KB of a row, where the scalar form's 256-byte
-// pieces reached 0.55 TB/s), a workgroup = a 256-column stripe x 4 row groups
-__global__ __launch_bounds__(256) static void k_colsum_partial4(const float *__restrict__ a, const float *__restrict__ b, float *__restrict__ part, int M, int N, int rows) {
-    __shared__ f32x4 red4[4][64];
-    const int cq = threadIdx.x & 63, rg = threadIdx.x >> 6, n = blockIdx.x * 256 + 4 * cq, chunk = blockIdx.y;
-    const int r0 = chunk * rows, r1 = min(M, r0 + rows);
-    f32x4 s = {0.f, 0.f, 0.f, 0.f};
-    if (n < N) {
-        if (b) for (int r = r0 + rg; r < r1; r += 4) s = __builtin_elementwise_fma(*reinterpret_cast<const f32x4 *>(a + (size_t)r * N + n), *reinterpret_cast<const f32x4 *>(b + (size_t)r * N + n), s);
-        else for (int r = r0 + rg; r < r1; r += 4) s += *reinterpret_cast<const f32x4 *>(a + (size_t)r * N + n);
-    }
-    red4[rg][cq] = s;
-    __syncthreads();
-    if (rg == 0 && n < N) *reinterpret_cast<f32x4 *>(part + (size_t)chunk * N + n) = ((red4[0][cq] + red4[1][cq]) + red4[2][cq]) + red4[3][cq];
-}
-// Two matrices at once (a LayerNorm's d gamma and d beta operands; N % 4 == 0): part[chunk][2 N] = column sums of a1 | of a2 over the
-// chunk's rows, the same arrangement as k_colsum_partial4; k_colsum_final_2 adds the chunks (16 chunk groups in order) into out1 / out2.
-__global__ __launch_bounds__(256) static void k_colsum_partial4_2(const float *__restrict__ a1, const float *__restrict__ a2, float *__restrict__ part, int M, int N, int rows) {
-    __shared__ f32x4 red4[4][64];
-    const int cq = threadIdx.x & 63, rg = threadIdx.x >> 6, n2 = blockIdx.x * 256 + 4 * cq, chunk = blockIdx.y;      // n2: column of the (M, 2 N) pair
-    const int r0 = chunk * rows, r1 = min(M, r0 + rows);
-    f32x4 s = {0.f, 0.f, 0.f, 0.f};
-    if (n2 < 2 * N) {
-        const float *a = n2 < N ? a1 + n2 : a2 + (n2 - N);
-        for (int r = r0 + rg; r < r1; r += 4) s += *reinterpret_cast<const f32x4 *>(a + (size_t)r * N);
-    }
-    red4[rg][cq] = s;
-    __syncthreads();
-    if (rg == 0 && n2 < 2 * N) *reinterpret_cast<f32x4 *>(part + (size_t)chunk * 2 * N + n2) = ((red4[0][cq] + red4[1][cq]) + red4[2][cq]) + red4[3][cq];
-}
-// part[chunk][2 N] = column sums of a | of a .* a over the chunk's rows (BatchNorm's batch statistics in one pass; N % 4 == 0)
-__global__ __launch_bounds__(256) static void k_colsum_partial4_sq(const float *__restrict__ a, float *__restrict__ part, int M, int N, int rows) {
-    __shared__ f32x4 red4[4][64];
-    const int cq = threadIdx.x & 63, rg = threadIdx.x >> 6, n2 = blockIdx.x * 256 + 4 * cq, chunk = blockIdx.y;
-    const int r0 = chunk * rows, r1 = min(M, r0 + rows);
-    f32x4 s = {0.f, 0.f, 0.f, 0.f};
-    if (n2 < N) { for (int r = r0 + rg; r < r1; r += 4) s += *reinterpret_cast<const f32x4 *>(a + (size_t)r * N + n2); }
-    else if (n2 < 2 * N) { for (int r = r0 + rg; r < r1; r += 4) { const f32x4 v = *reinterpret_cast<const f32x4 *>(a + (size_t)r * N + n2 - N); s = __builtin_elementwise_fma(v, v, s); } }
-    red4[rg][cq] = s;
-    __syncthreads();
-    if (rg == 0 && n2 < 2 * N) *reinterpret_cast<f32x4 *>(part + (size_t)chunk * 2 * N + n2) = ((red4[0][cq] + red4[1][cq]) + red4[2][cq]) + red4[3][cq];
-}
-// part[chunk][2 N] = column sums of a | of a .* b (BatchNorm backward: sum dy = d beta, sum dy xhat = d gamma; N % 4 == 0)
-__global__ __launch_bounds__(256) static void k_colsum_partial4_ab(const float *__restrict__ a, const float *__restrict__ b, float *__restrict__ part, int M, int N, int rows) {
-    __shared__ f32x4 red4[4][64];
-    const int cq = threadIdx.x & 63, rg = threadIdx.x >> 6, n2 = blockIdx.x * 256 + 4 * cq, chunk = blockIdx.y;
-    const int r0 = chunk * rows, r1 = min(M, r0 + rows);
-    f32x4 s = {0.f, 0.f, 0.f, 0.f};
-    if (n2 < N) { for (int r = r0 + rg; r < r1; r += 4) s += *reinterpret_cast<const f32x4 *>(a + (size_t)r * N + n2); }
-    else if (n2 < 2 * N) {
-        for (int r = r0 + rg; r < r1; r += 4)
-            s = __builtin_elementwise_fma(*reinterpret_cast<const f32x4 *>(a + (size_t)r * N + n2 - N), *reinterpret_cast<const f32x4 *>(b + (size_t)r * N + n2 - N), s);
-    }
-    red4[rg][cq] = s;
-    __syncthreads();
-    if (rg == 0 && n2 < 2 * N) *reinterpret_cast<f32x4 *>(part + (size_t)chunk * 2 * N + n2) = ((red4[0][cq] + red4[1][cq]) + red4[2][cq]) + red4[3][cq];
-}
-__global__ __launch_bounds__(256) static void k_colsum_final_2(const float *__restrict__ part, float *__restrict__ out1, float *__restrict__ out2, int chunks, int N) {
+// Finals over many chunks of 16-byte columns (N % 4 == 0): a workgroup = 16 column quads x 16 chunk groups.  Thread (kg, cq) adds chunks kg,
+// kg + 16, ... of its quad (`col`: the quad's first partial sum, chunks `stride` floats apart; live: the quad exists), then group 0 adds the
+// groups 0..15 in order and hands the total to `store`.
+template <typename F> __device__ __forceinline__ void colsum_final16(const float *__restrict__ col, size_t stride, int chunks, bool live, F &&store) {
     __shared__ f32x4 red4[16][16];
-    const int cq = threadIdx.x & 15, kg = threadIdx.x >> 4, n2 = blockIdx.x * 64 + 4 * cq;
+    const int cq = threadIdx.x & 15, kg = threadIdx.x >> 4;
     f32x4 s = {0.f, 0.f, 0.f, 0.f};
-    if (n2 < 2 * N) for (int k = kg; k < chunks; k += 16) s += *reinterpret_cast<const f32x4 *>(part + (size_t)k * 2 * N + n2);
+    if (live) for (int k = kg; k < chunks; k += 16) s += *reinterpret_cast<const f32x4 *>(col + (size_t)k * stride);
     red4[kg][cq] = s;
     __syncthreads();
-    if (kg == 0 && n2 < 2 * N) {
+    if (kg == 0 && live) {
         f32x4 tot = red4[0][cq];
 #pragma unroll
         for (int k = 1; k < 16; ++k) tot += red4[k][cq];
-        *reinterpret_cast<f32x4 *>(n2 < N ? out1 + n2 : out2 + (n2 - N)) = tot;
+        store(tot);
     }
+}
+// out[n] = sum over `chunks` of part[k][n]; stores 0 + sum (a sum of -0 leaves as +0)
+__global__ __launch_bounds__(256) static void k_colsum_final4(const float *__restrict__ part, float *__restrict__ out, int chunks, int N) {
+    const int n = blockIdx.x * 64 + 4 * (threadIdx.x & 15);
+    colsum_final16(part + n, (size_t)N, chunks, n < N, [&](const f32x4 &t) {
+#pragma unroll
+        for (int q = 0; q < 4; ++q) out[n + q] = 0.f + t[q];
+    });
+}
+// the final of a pair form: part[chunk][2 N] -> out1 | out2 (the sum as it is)
+__global__ __launch_bounds__(256) static void k_colsum_final_2(const float *__restrict__ part, float *__restrict__ out1, float *__restrict__ out2, int chunks, int N) {
+    const int n2 = blockIdx.x * 64 + 4 * (threadIdx.x & 15);
+    colsum_final16(part + n2, (size_t)2 * N, chunks, n2 < 2 * N, [&](const f32x4 &t) { *reinterpret_cast<f32x4 *>(n2 < N ? out1 + n2 : out2 + (n2 - N)) = t; });
 }
 // Round 4: the finals of a step's gradient column sums (bias gradients, LayerNorm d gamma / d beta) as ONE launch at the end of the backward
 // pass instead of one 4-workgroup launch each (330 of them, 7.6 us apiece: latency, not work).  A job = partial sums part[chunk * stride + n]
 // of `chunks` chunks for N columns (N % 4 == 0) -> out[n]; workgroup b of the launch serves job j with first_block[j] <= b < first_block[j + 1],
-// 64 columns each, 16 chunk groups added in a fixed order (bit-reproducible steps).
+// 64 columns each.
 #define COCR_MAX_COLSUM_JOBS 2048
 struct ColsumJob { const float *part; float *out; int stride, chunks, N, first_block; };
 __global__ __launch_bounds__(256) static void k_colsum_final_jobs(const ColsumJob *__restrict__ jobs, int njobs) {
-    __shared__ f32x4 red4[16][16];
     int lo = 0, hi = njobs - 1;                              // the last job whose first block is <= this block (uniform)
     while (lo < hi) {
         const int mid = (lo + hi + 1) >> 1;
         if (jobs[mid].first_block <= (int)blockIdx.x) lo = mid; else hi = mid - 1;
     }
     const ColsumJob j = jobs[lo];
-    const int cq = threadIdx.x & 15, kg = threadIdx.x >> 4, n = ((int)blockIdx.x - j.first_block) * 64 + 4 * cq;
-    f32x4 s = {0.f, 0.f, 0.f, 0.f};
-    if (n < j.N) for (int k = kg; k < j.chunks; k += 16) s += *reinterpret_cast<const f32x4 *>(j.part + (size_t)k * j.stride + n);
-    red4[kg][cq] = s;
-    __syncthreads();
-    if (kg == 0 && n < j.N) {
-        f32x4 tot = red4[0][cq];
-#pragma unroll
-        for (int k = 1; k < 16; ++k) tot += red4[k][cq];
-        *reinterpret_cast<f32x4 *>(j.out + n) = tot;
-    }
+    const int n = ((int)blockIdx.x - j.first_block) * 64 + 4 * (threadIdx.x & 15);
+    colsum_final16(j.part + n, (size_t)j.stride, j.chunks, n < j.N, [&](const f32x4 &t) { *reinterpret_cast<f32x4 *>(j.out + n) = t; });
 }
-// out[n] (+)= sum over `chunks` of part[k][n]: the same 64 x 4 arrangement over the chunks
-__global__ __launch_bounds__(256) static void k_colsum_final(const float *__restrict__ part, float *__restrict__ out, int chunks, int N, int accumulate) {
-    __shared__ float red[4][64];
-    const int cl = threadIdx.x & 63, kg = threadIdx.x >> 6, n = blockIdx.x * 64 + cl;
+// Finals over few chunks, any N: the partial kernels' 64 x 4 arrangement over the chunks.  colsum_chunks4 leaves the four group sums of column n
+// in red; how they are added is the kernel's own (k_colsum_final: one after the other; k_conv_w_final: in pairs).
+__device__ __forceinline__ void colsum_chunks4(float (&red)[4][64], const float *__restrict__ part, int chunks, int N, int n) {
+    const int kg = threadIdx.x >> 6;
     float s = 0.f;
     if (n < N) for (int k = kg; k < chunks; k += 4) s += part[(size_t)k * N + n];
-    red[kg][cl] = s;
+    red[kg][threadIdx.x & 63] = s;
     __syncthreads();
-    if (kg == 0 && n < N) out[n] = (accumulate ? out[n] : 0.f) + (((red[0][cl] + red[1][cl]) + red[2][cl]) + red[3][cl]);
 }
-// the same for many chunks of a narrow matrix (N % 4 == 0): a thread = four columns, a workgroup = 64 columns x 16 chunk groups
-__global__ __launch_bounds__(256) static void k_colsum_final4(const float *__restrict__ part, float *__restrict__ out, int chunks, int N, int accumulate) {
-    __shared__ f32x4 red4[16][16];
-    const int cq = threadIdx.x & 15, kg = threadIdx.x >> 4, n = blockIdx.x * 64 + 4 * cq;
-    f32x4 s = {0.f, 0.f, 0.f, 0.f};
-    if (n < N) for (int k = kg; k < chunks; k += 16) s += *reinterpret_cast<const f32x4 *>(part + (size_t)k * N + n);
-    red4[kg][cq] = s;
-    __syncthreads();
-    if (kg == 0 && n < N) {
-        f32x4 t = red4[0][cq];
-#pragma unroll
-        for (int g2 = 1; g2 < 16; ++g2) t += red4[g2][cq];
-#pragma unroll
-        for (int q = 0; q < 4; ++q) out[n + q] = (accumulate ? out[n + q] : 0.f) + t[q];
-    }
+// out[n] = 0 + sum over `chunks` of part[k][n]
+__global__ __launch_bounds__(256) static void k_colsum_final(const float *__restrict__ part, float *__restrict__ out, int chunks, int N) {
+    __shared__ float red[4][64];
+    const int cl = threadIdx.x & 63, n = blockIdx.x * 64 + cl;
+    colsum_chunks4(red, part, chunks, N, n);
+    if (threadIdx.x < 64 && n < N) out[n] = 0.f + colsum_fold4(red, cl);
 }
 
 // ---- LayerNorm (eps 1e-5): one wave per row -----------------------------------------------------------------------------------------------
@@ -300,9 +270,6 @@ __global__ static void k_ln_bwd(const float *__restrict__ dy, const float *__res
 
 // ---- activations -----------------------------------------------------------------------------------------------------------------------------------
 __device__ __forceinline__ float sigm(float x) { return 1.0f / (1.0f + expf(-x)); }
-__global__ static void k_silu_fwd(const float *__restrict__ h, float *__restrict__ a, size_t n) {
-    for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (size_t)gridDim.x * blockDim.x) a[i] = h[i] * sigm(h[i]);
-}
 // a = drop(silu(h)); d <- drop(d) * silu'(h): the feed-forward module's hidden dropout folded into its activation, forward and backward
 __global__ static void k_silu_fwd_drop(const float *__restrict__ h, float *__restrict__ a, size_t n, float p, unsigned long long seed, unsigned site) {
     const float sc = 1.0f / (1.0f - p);
@@ -521,20 +488,14 @@ __global__ static void k_btranspose(const float *__restrict__ in, float *__restr
     __shared__ float tile[32][33];
     const int z = blockIdx.z, zb = z / zdiv, zh = z - zb * zdiv;
     const float *src = in + zb * izb + zh * izh;
-    float *dst = out + (long long)z * oz;
-    const int r0 = blockIdx.x * 32, c0 = blockIdx.y * 32, tx = threadIdx.x & 31, ty = threadIdx.x >> 5;
+    const int r0 = blockIdx.x * 32, c0 = blockIdx.y * 32;      // (blockIdx.x walks the rows here, .y in the two transposes above)
     const float sc = p > 0.f ? 1.0f / (1.0f - p) : 1.0f;
-    for (int j = ty; j < 32; j += 8) {
-        float v = 0.f;
-        if (r0 + j < R && c0 + tx < C) {
-            v = src[(long long)(r0 + j) * ldi + c0 + tx];
-            if (drop_T > 0 && p > 0.f) v = drop_keep(seed, site, ((unsigned long long)z * drop_T + (r0 + j)) * drop_T + (c0 + tx), p) ? v * sc : 0.f;
-        }
-        tile[j][tx] = v;
-    }
+    tile_load(tile, r0, c0, R, C, [&](int r, int c) {
+        const float v = src[(long long)r * ldi + c];
+        return (drop_T > 0 && p > 0.f) ? (drop_keep(seed, site, ((unsigned long long)z * drop_T + r) * drop_T + c, p) ? v * sc : 0.f) : v;
+    });
     __syncthreads();
-    for (int j = ty; j < 32; j += 8)
-        if (c0 + j < C && r0 + tx < Rpad) dst[(long long)(c0 + j) * ldo + r0 + tx] = tile[tx][j];
+    tile_store_T(tile, out + (long long)z * oz, ldo, r0, c0, C, Rpad);
 }
 // attn row (z, i) <- softmax_j((S[j] + Rm[T-1-i+j]) scale), in place over S; columns T..Tk-1 zero; ad (nullable) <- the dropped weights
 __global__ static void k_attn_softmax(float *__restrict__ S, const float *__restrict__ Rm, float *__restrict__ ad, long long rows, int T, int Tk, int Rk,
@@ -694,15 +655,6 @@ __global__ static void k_bn_finalize(const float *__restrict__ sum, const float 
     rstd[c] = 1.0f / sqrtf(var + 1e-5f);
     running_mean[c] = (1.0f - momentum) * running_mean[c] + momentum * mu;
     running_var[c] = (1.0f - momentum) * running_var[c] + momentum * var * ((float)M / (float)max(M - 1, 1));
-}
-__global__ static void k_bn_apply(const float *__restrict__ x, const float *__restrict__ mean, const float *__restrict__ rstd, const float *__restrict__ g,
-                                  const float *__restrict__ b, float *__restrict__ xhat, float *__restrict__ y, int M, int D) {
-    for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < (size_t)M * D; i += (size_t)gridDim.x * blockDim.x) {
-        const int c = (int)(i % D);
-        const float xh = (x[i] - mean[c]) * rstd[c];
-        xhat[i] = xh;
-        y[i] = fmaf(xh, g[c], b[c]);
-    }
 }
 // the same with the SiLU behind it (convolution.py:141-142): xhat, y = BatchNorm output, a = silu(y) in one pass
 __global__ static void k_bn_apply_silu(const float *__restrict__ x, const float *__restrict__ mean, const float *__restrict__ rstd, const float *__restrict__ g,
@@ -916,13 +868,9 @@ __global__ __launch_bounds__(256) static void k_dw3_bwd_w(const float *__restric
 // partials [chunk][10][C] -> dw[c][9] and db[c]: a block per 64 (k, c) entries, its 4 waves take every fourth chunk; fixed order
 __global__ __launch_bounds__(256) static void k_conv_w_final(const float *__restrict__ part, int chunks, int C, float *__restrict__ dw, float *__restrict__ db) {
     __shared__ float red[4][64];
-    const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6, i = blockIdx.x * 64 + lane;      // i = k * C + c
-    float s = 0.f;
-    if (i < 10 * C)
-        for (int ch = wv; ch < chunks; ch += 4) s += part[(size_t)ch * 10 * C + i];
-    red[wv][lane] = s;
-    __syncthreads();
-    if (wv == 0 && i < 10 * C) {
+    const int lane = threadIdx.x & 63, i = blockIdx.x * 64 + lane;      // i = k * C + c
+    colsum_chunks4(red, part, chunks, 10 * C, i);
+    if (threadIdx.x < 64 && i < 10 * C) {
         const float tot = (red[0][lane] + red[1][lane]) + (red[2][lane] + red[3][lane]);
         const int k = i / C, c = i - k * C;
         if (k < 9) dw[c * 9 + k] = tot; else db[c] = tot;
@@ -952,221 +900,5 @@ __global__ static void k_tfc_to_tcf_flat(const float *__restrict__ in, float *__
         const int c = (int)(i % C), f = (int)((i / C) % F);
         const size_t nt = i / ((size_t)C * F), o = (nt * C + c) * F + f;
         if (reverse) out[i] = in[o]; else out[o] = in[i];
-    }
-}
-
-// ---- torch.optim.AdamW (model.py:283-284) on a flat parameter vector ------------------------------------------------------------------------------
-__global__ static void k_adamw_flat(float *__restrict__ p, const float *__restrict__ g, float *__restrict__ m, float *__restrict__ v, size_t n, float lr,
-                                    float b1, float b2, float eps, float wd, float bc1, float bc2) {
-    for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (size_t)gridDim.x * blockDim.x) {
-        float w = p[i] * (1.0f - lr * wd);
-        const float gi = g[i], mi = b1 * m[i] + (1.0f - b1) * gi, vi = b2 * v[i] + (1.0f - b2) * gi * gi;
-        m[i] = mi; v[i] = vi;
-        w -= lr / bc1 * mi / (sqrtf(vi) / sqrtf(bc2) + eps);
-        p[i] = w;
-    }
-}
-
-// The same step with PER-TENSOR step counts (torch keeps `state['step']` per parameter): the elements of up to COCR_ADAMW_RANGES ranges of
-// the flat vector take their own bias corrections -- an output layer adopted after k frozen-backbone steps (cocr_train_adopt_decoder)
-// continues at step k + 1 while every other tensor starts at 1.  Unused ranges are empty (lo == hi); the arithmetic per element is
-// k_adamw_flat's, so equal corrections give its result bit for bit.
-#define COCR_ADAMW_RANGES 4
-struct AdamwRanges { unsigned long long lo[COCR_ADAMW_RANGES], hi[COCR_ADAMW_RANGES]; float bc1[COCR_ADAMW_RANGES], bc2[COCR_ADAMW_RANGES]; };
-__global__ static void k_adamw_flat_ranges(float *__restrict__ p, const float *__restrict__ g, float *__restrict__ m, float *__restrict__ v, size_t n, float lr,
-                                           float b1, float b2, float eps, float wd, float bc1, float bc2, AdamwRanges r) {
-    for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (size_t)gridDim.x * blockDim.x) {
-        float c1 = bc1, c2 = bc2;
-#pragma unroll
-        for (int k = 0; k < COCR_ADAMW_RANGES; ++k)
-            if (i >= r.lo[k] && i < r.hi[k]) { c1 = r.bc1[k]; c2 = r.bc2[k]; }
-        float w = p[i] * (1.0f - lr * wd);
-        const float gi = g[i], mi = b1 * m[i] + (1.0f - b1) * gi, vi = b2 * v[i] + (1.0f - b2) * gi * gi;
-        m[i] = mi; v[i] = vi;
-        w -= lr / c1 * mi / (sqrtf(vi) / sqrtf(c2) + eps);
-        p[i] = w;
-    }
-}
-
-// ---- one optimizer step of any kind on a flat parameter vector (cocr_train_optim_step / cocr_decoder_optim_step) --------------------------------
-// Per element the definitions are torch's single-tensor implementations in fp32 (g' = g + wd p folds the L2 decay into the gradient for
-// every kind but AdamW, whose decay is decoupled):
-//   AdamW    p *= 1 - lr wd;  m = b1 m + (1 - b1) g;   v = b2 v + (1 - b2) g^2;    p -= lr / bc1 m / (sqrt(v) / sqrt(bc2) + eps)      (k_adamw_flat's expressions)
-//   Adam                      m = b1 m + (1 - b1) g';  v = b2 v + (1 - b2) g'^2;   p -= lr / bc1 m / (sqrt(v) / sqrt(bc2) + eps)
-//   SGD      buf = mu buf + g';  p -= lr buf            (mu = 0: p -= lr g', the slot is not touched; dampening 0, no Nesterov)
-//   RMSprop  sq = alpha sq + (1 - alpha) g'^2;  a = sqrt(sq) + eps;  mu > 0: buf = mu buf + g' / a, p -= lr buf;  else p -= lr g' / a     (not centered)
-// The two state vectors are slots whose meaning depends on the kind: AdamW / Adam (exp_avg, exp_avg_sq), SGD (momentum buffer, unused),
-// RMSprop (square_avg, momentum buffer).  Slots start zeroed: torch's "buf = g' on a tensor's first step" is mu 0 + g', no flag needed.
-// FLAG: Adam kinds -- per-range bias corrections (AdamwRanges, tested per element: a range starts at any float offset); SGD / RMSprop --
-// momentum on.  Elements [head, head + 4 nvec) go 16 bytes per lane on all four vectors (the host picks `head` so that they are
-// aligned there, or head = n when the vectors' alignments differ); the few before and after go one by one.
-// serve_b / serve_f (either may be null): the value the serving forward reads (bf16 / fp32 copy of the output layer).
-// gs (cocr_train_optim_step_ex's grad_scale): every gradient element enters the step as fl(gs g), rounded on its own; 1.0f leaves every float as it is.
-struct OptimArgs { float lr, wd, b1, b2, eps, mu, alpha, bc1, bc2, gs; };
-
-// Which products the compiler fuses into the following sum is its choice per kernel, and it chooses differently for the 16-byte form of
-// a loop than for the scalar one.  So this function takes no such choice: contraction is off, every operation is rounded on its own, and the
-// AdamW branch names the three fused operations k_adamw_flat compiles to (1 - lr wd, and (1 - b1) g onto the rounded b1 m; v's two
-// products and the final difference are not fused there).  That is what makes the AdamW instance equal cocr_train_adamw bit for bit
-// (tests/test_hip_optim.py holds the two against each other), and a vector lane equal the scalar path for every kind.
-template <int KIND, bool FLAG>
-__device__ __forceinline__ void optim_elem(float &p, const float g_in, float &s0, float &s1, const OptimArgs &a, const float c1, const float c2) {
-#pragma clang fp contract(off)
-    const float g = a.gs * g_in;
-    if constexpr (KIND == COCR_OPT_ADAMW) {
-        float w = p * __builtin_fmaf(-a.lr, a.wd, 1.0f);
-        const float gi = g, mi = __builtin_fmaf(1.0f - a.b1, gi, a.b1 * s0), vi = gi * ((1.0f - a.b2) * gi) + a.b2 * s1;
-        s0 = mi; s1 = vi;
-        w -= a.lr / c1 * mi / (sqrtf(vi) / sqrtf(c2) + a.eps);
-        p = w;
-    } else if constexpr (KIND == COCR_OPT_ADAM) {
-        float w = p;
-        const float gi = g + a.wd * w, mi = a.b1 * s0 + (1.0f - a.b1) * gi, vi = a.b2 * s1 + (1.0f - a.b2) * gi * gi;
-        s0 = mi; s1 = vi;
-        w -= a.lr / c1 * mi / (sqrtf(vi) / sqrtf(c2) + a.eps);
-        p = w;
-    } else if constexpr (KIND == COCR_OPT_SGD) {
-        const float gi = g + a.wd * p;
-        if constexpr (FLAG) { const float b = a.mu * s0 + gi; s0 = b; p -= a.lr * b; }
-        else p -= a.lr * gi;
-    } else {
-        const float gi = g + a.wd * p, sq = a.alpha * s0 + (1.0f - a.alpha) * gi * gi, d = sqrtf(sq) + a.eps;
-        s0 = sq;
-        if constexpr (FLAG) { const float b = a.mu * s1 + gi / d; s1 = b; p -= a.lr * b; }
-        else p -= a.lr * (gi / d);
-    }
-}
-
-template <int KIND, bool FLAG>
-__global__ __launch_bounds__(256) static void k_optim_flat(float *__restrict__ P, const float *__restrict__ G, float *__restrict__ S0, float *__restrict__ S1, size_t n,
-                                                           size_t head, size_t nvec, OptimArgs a, AdamwRanges r, bf16_t *__restrict__ serve_b, float *__restrict__ serve_f) {
-    constexpr bool adam = KIND == COCR_OPT_ADAMW || KIND == COCR_OPT_ADAM;
-    constexpr bool use0 = adam || KIND == COCR_OPT_RMSPROP || FLAG;            // SGD without momentum touches no slot,
-    constexpr bool use1 = adam || (KIND == COCR_OPT_RMSPROP && FLAG);          // RMSprop without momentum and SGD not the second
-    auto corr = [&](size_t i, float &c1, float &c2) {
-        c1 = a.bc1; c2 = a.bc2;
-        if constexpr (adam && FLAG) {
-#pragma unroll
-            for (int k = 0; k < COCR_ADAMW_RANGES; ++k)
-                if (i >= r.lo[k] && i < r.hi[k]) { c1 = r.bc1[k]; c2 = r.bc2[k]; }
-        }
-    };
-    const size_t tid = (size_t)blockIdx.x * blockDim.x + threadIdx.x, nthr = (size_t)gridDim.x * blockDim.x;
-    for (size_t q = tid; q < nvec; q += nthr) {
-        const size_t i = head + 4 * q;
-        f32x4 p = *reinterpret_cast<const f32x4 *>(P + i);
-        const f32x4 g = *reinterpret_cast<const f32x4 *>(G + i);
-        f32x4 s0 = {0.f, 0.f, 0.f, 0.f}, s1 = {0.f, 0.f, 0.f, 0.f};
-        if constexpr (use0) s0 = *reinterpret_cast<const f32x4 *>(S0 + i);
-        if constexpr (use1) s1 = *reinterpret_cast<const f32x4 *>(S1 + i);
-#pragma unroll
-        for (int e = 0; e < 4; ++e) {
-            float c1, c2, pe = p[e], s0e = s0[e], s1e = s1[e];
-            corr(i + e, c1, c2);
-            optim_elem<KIND, FLAG>(pe, g[e], s0e, s1e, a, c1, c2);
-            p[e] = pe; s0[e] = s0e; s1[e] = s1e;
-        }
-        *reinterpret_cast<f32x4 *>(P + i) = p;
-        if constexpr (use0) *reinterpret_cast<f32x4 *>(S0 + i) = s0;
-        if constexpr (use1) *reinterpret_cast<f32x4 *>(S1 + i) = s1;
-        if (serve_b)
-#pragma unroll
-            for (int e = 0; e < 4; ++e) serve_b[i + e] = from_f32<bf16_t>(p[e]);
-        if (serve_f)
-#pragma unroll
-            for (int e = 0; e < 4; ++e) serve_f[i + e] = p[e];
-    }
-    // the elements in front of the aligned part and behind it
-    const size_t nscal = n - 4 * nvec;
-    for (size_t j = tid; j < nscal; j += nthr) {
-        const size_t i = j < head ? j : j + 4 * nvec;
-        float c1, c2, pe = P[i], s0e = 0.f, s1e = 0.f;
-        if constexpr (use0) s0e = S0[i];
-        if constexpr (use1) s1e = S1[i];
-        corr(i, c1, c2);
-        optim_elem<KIND, FLAG>(pe, G[i], s0e, s1e, a, c1, c2);
-        P[i] = pe;
-        if constexpr (use0) S0[i] = s0e;
-        if constexpr (use1) S1[i] = s1e;
-        if (serve_b) serve_b[i] = from_f32<bf16_t>(pe);
-        if (serve_f) serve_f[i] = pe;
-    }
-}
-
-// ---- the gradient window on flat vectors (cocr_grad_accumulate / cocr_grad_norm) ---------------------------------------------------------------
-// dst[i] = overwrite ? fl(scale src[i]) : fl(dst[i] + fl(scale src[i])): two fp32 operations, each rounded on its own (contraction off, as in
-// optim_elem), which is torch's acc.add_(g * s) bit for bit.  dst may be src (overwrite: the in-place scale), so neither pointer is
-// __restrict__ and every element is read before it is written by the lane that owns it.  Elements [head, head + 4 nvec) go 16 bytes per
-// lane (the host picks `head` so that both vectors are aligned there, or head = n when their alignments differ); the rest one by one.
-__device__ __forceinline__ float accum_elem(const float d, const float s, const float scale, const bool overwrite) {
-#pragma clang fp contract(off)
-    const float t = scale * s;
-    return overwrite ? t : d + t;
-}
-__global__ __launch_bounds__(256) static void k_grad_accumulate(float *dst, const float *src, size_t n, size_t head, size_t nvec, float scale, int overwrite) {
-    const size_t tid = (size_t)blockIdx.x * blockDim.x + threadIdx.x, nthr = (size_t)gridDim.x * blockDim.x;
-    for (size_t q = tid; q < nvec; q += nthr) {
-        const size_t i = head + 4 * q;
-        const f32x4 s = *reinterpret_cast<const f32x4 *>(src + i);
-        f32x4 d = {0.f, 0.f, 0.f, 0.f};
-        if (!overwrite) d = *reinterpret_cast<const f32x4 *>(dst + i);
-#pragma unroll
-        for (int e = 0; e < 4; ++e) d[e] = accum_elem(d[e], s[e], scale, overwrite != 0);
-        *reinterpret_cast<f32x4 *>(dst + i) = d;
-    }
-    const size_t nscal = n - 4 * nvec;
-    for (size_t j = tid; j < nscal; j += nthr) {
-        const size_t i = j < head ? j : j + 4 * nvec;
-        dst[i] = accum_elem(overwrite ? 0.f : dst[i], src[i], scale, overwrite != 0);
-    }
-}
-
-// Sum of squares in double, stage one: chunk c of `nchunk` owns the elements [c len, min(n, (c + 1) len)), len a multiple of 4 that depends
-// on n only.  Within a chunk, group q (4 consecutive elements) belongs to thread q % 256; a thread adds its elements' squares in index
-// order (an fp32 x fp32 product is exact in double, so fusing it into the sum changes nothing), then the 256 thread sums are folded by a
-// fixed LDS tree.  Which element is added where depends on its index alone: a pointer that is not 16-byte aligned (vec = 0) loads the
-// same groups one float at a time.  No atomics; the chunk sums go to part[c].
-#define COCR_NORM_MAX_CHUNKS 1024
-__global__ __launch_bounds__(256) static void k_sumsq_chunks(const float *__restrict__ g, size_t n, size_t len, int vec, double *__restrict__ part) {
-    __shared__ double red[256];
-    const size_t lo = (size_t)blockIdx.x * len, hi = lo + len < n ? lo + len : n;
-    double acc = 0.0;
-    for (size_t i = lo + 4 * (size_t)threadIdx.x; i < hi; i += 4 * 256) {
-        if (i + 4 <= hi) {
-            float x[4];
-            if (vec) { const f32x4 v = *reinterpret_cast<const f32x4 *>(g + i); x[0] = v[0]; x[1] = v[1]; x[2] = v[2]; x[3] = v[3]; }
-            else { x[0] = g[i]; x[1] = g[i + 1]; x[2] = g[i + 2]; x[3] = g[i + 3]; }
-#pragma unroll
-            for (int e = 0; e < 4; ++e) acc += (double)x[e] * (double)x[e];
-        } else {
-            for (size_t j = i; j < hi; ++j) acc += (double)g[j] * (double)g[j];
-        }
-    }
-    red[threadIdx.x] = acc;
-    __syncthreads();
-    for (int w = 128; w > 0; w >>= 1) {
-        if ((int)threadIdx.x < w) red[threadIdx.x] += red[threadIdx.x + w];
-        __syncthreads();
-    }
-    if (threadIdx.x == 0) part[blockIdx.x] = red[0];
-}
-// stage two: the chunk sums in index order, the square root, one double (one workgroup; the sums come through LDS so that the serial
-// additions do not each wait for memory)
-__global__ __launch_bounds__(256) static void k_sumsq_finish(const double *__restrict__ part, int nchunk, double *__restrict__ out) {
-    __shared__ double s[COCR_NORM_MAX_CHUNKS];
-    for (int i = threadIdx.x; i < nchunk; i += 256) s[i] = part[i];
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        double t = 0.0;
-        for (int i = 0; i < nchunk; ++i) t += s[i];
-        *out = sqrt(t);
-    }
-}
-
-// master copy -> the serving copy of the output layer (cocr_decoder_optim_restore)
-__global__ static void k_serve_copy(const float *__restrict__ p, size_t n, bf16_t *__restrict__ serve_b, float *__restrict__ serve_f) {
-    for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (size_t)gridDim.x * blockDim.x) {
-        if (serve_b) serve_b[i] = from_f32<bf16_t>(p[i]);
-        if (serve_f) serve_f[i] = p[i];
     }
 }

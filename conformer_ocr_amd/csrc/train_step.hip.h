@@ -314,21 +314,41 @@ struct Train : TrainPlan {
         t->jobs.clear();
         return COCR_OK;
     }
-    void colsum(const float *a, const float *b, int Mr, int Nc, float *out, int accumulate) {
-        const int rows = colsum_chunk_rows(Mr), chunks = ceil_div(Mr, rows);
-        const bool vec = Nc % 4 == 0 && ((uintptr_t)a & 15) == 0 && ((uintptr_t)b & 15) == 0;
-        if (vec) hipLaunchKernelGGL(k_colsum_partial4, dim3(ceil_div(Nc, 256), chunks), dim3(256), 0, s, a, b, WS(rd.Part), Mr, Nc, rows);
-        else hipLaunchKernelGGL(k_colsum_partial, dim3(ceil_div(Nc, 64), chunks), dim3(256), 0, s, a, b, WS(rd.Part), Mr, Nc, rows);
-        if (vec && chunks > 32) hipLaunchKernelGGL(k_colsum_final4, dim3(ceil_div(Nc, 64)), dim3(256), 0, s, WS(rd.Part), out, chunks, Nc, accumulate);
-        else hipLaunchKernelGGL(k_colsum_final, dim3(ceil_div(Nc, 64)), dim3(256), 0, s, WS(rd.Part), out, chunks, Nc, accumulate);
+    // The final of partial sums part[chunk][Nc] at once: out[n] = sum over the chunks.  groups16 (and Nc % 4 == 0): 16 chunk groups, else 4 --
+    // the order of the additions differs, so who sums what keeps its form
+    void colsum_final(const float *part, int chunks, int Nc, float *out, bool groups16 = false) {
+        if (groups16 && Nc % 4 == 0) hipLaunchKernelGGL(k_colsum_final4, dim3(ceil_div(Nc, 64)), dim3(256), 0, s, part, out, chunks, Nc);
+        else hipLaunchKernelGGL(k_colsum_final, dim3(ceil_div(Nc, 64)), dim3(256), 0, s, part, out, chunks, Nc);
     }
-    // a gradient accumulator's column sums (bias gradients): the partial sums now, the final with the step's other finals
-    void colsum_grad(const float *a, int Mr, int Nc, float *out) {
-        const int rows = colsum_chunk_rows(Mr), chunks = ceil_div(Mr, rows);
-        float *gp = (Nc % 4 == 0 && ((uintptr_t)a & 15) == 0 && ((uintptr_t)out & 15) == 0) ? part_alloc((size_t)chunks * Nc) : nullptr;
-        if (!gp) { colsum(a, nullptr, Mr, Nc, out, 0); return; }
-        hipLaunchKernelGGL(k_colsum_partial4, dim3(ceil_div(Nc, 256), chunks), dim3(256), 0, s, a, (const float *)nullptr, gp, Mr, Nc, rows);
-        defer_final(gp, Nc, chunks, Nc, out);
+    // Column sums over the Mr rows of an (Mr, Nc) source (ColsumKind, train_enc.hip.h) -- CS_ONE: a, or a .* b, -> out; CS_PAIR a | b, CS_SQ
+    // a | a .* a, CS_AB a | a .* b -> out | out2.  Owns the chunk rule, the choice of the 16-byte forms (Nc % 4 == 0, aligned operands; a pair
+    // form and a deferred final store 16 bytes too) and where the final runs: at once (out is read next), or -- DEFER, gradients only -- with the
+    // step's other finals when the arena has room.  A pair the 16-byte forms cannot take is its two single sums, at once.
+    enum { NOW = 0, DEFER = 1 };
+    void colsum(ColsumKind kind, const float *a, const float *b, int Mr, int Nc, float *out, float *out2 = nullptr, int when = NOW) {
+        const int rows = colsum_chunk_rows(Mr), chunks = ceil_div(Mr, rows), wide = kind == CS_ONE ? 1 : 2;
+        const bool vec = Nc % 4 == 0 && (((uintptr_t)a | (uintptr_t)b) & 15) == 0, vec_out = (((uintptr_t)out | (uintptr_t)out2) & 15) == 0;
+        if (kind != CS_ONE && !(vec && vec_out)) {
+            colsum(CS_ONE, a, nullptr, Mr, Nc, out);
+            colsum(CS_ONE, kind == CS_PAIR ? b : a, kind == CS_PAIR ? nullptr : kind == CS_SQ ? a : b, Mr, Nc, out2);
+            return;
+        }
+        float *arena = (when == DEFER && vec && vec_out) ? part_alloc((size_t)chunks * wide * Nc) : nullptr, *part = arena ? arena : WS(rd.Part);
+        const auto partial = !vec ? k_colsum_partial<CS_ONE, float> : kind == CS_ONE ? k_colsum_partial<CS_ONE, f32x4> : kind == CS_PAIR ? k_colsum_partial<CS_PAIR, f32x4>
+                             : kind == CS_SQ ? k_colsum_partial<CS_SQ, f32x4> : k_colsum_partial<CS_AB, f32x4>;
+        hipLaunchKernelGGL(partial, dim3(ceil_div(wide * Nc, vec ? 256 : 64), chunks), dim3(256), 0, s, a, b, part, Mr, Nc, rows);
+        if (arena) {
+            defer_final(arena, wide * Nc, chunks, Nc, out);
+            if (out2) defer_final(arena + Nc, wide * Nc, chunks, Nc, out2);
+        } else if (kind != CS_ONE) hipLaunchKernelGGL(k_colsum_final_2, dim3(ceil_div(2 * Nc, 64)), dim3(256), 0, s, part, out, out2, chunks, Nc);
+        else colsum_final(part, chunks, Nc, out, vec && chunks > 32);
+    }
+    // A bias gradient whose partial sums another kernel writes on its way, a 32-row tile each (k_rows_bf16, k_transpose_bf16): where that kernel
+    // puts them, their final queued -- or null (32 rows are not this height's chunk, out is not 16-byte aligned, the arena is full): `colsum` then
+    float *defer_tile_sums(int rows, int Nc, float *out) {
+        float *part = (colsum_chunk_rows(rows) == 32 && ((uintptr_t)out & 15) == 0) ? part_alloc((size_t)ceil_div(rows, 32) * Nc) : nullptr;
+        if (part) defer_final(part, Nc, ceil_div(rows, 32), Nc, out);
+        return part;
     }
     // Y (rows, Nc) = X (rows, Kr) W(Nc, Kr)^T + b
     int lin_fwd(const float *X, const TrainLin &ln, int rows, int Nc, int Kr, float *Y) {
@@ -360,7 +380,7 @@ struct Train : TrainPlan {
         const bool has_b = ln.b != TRAIN_NONE;
         bf16_t *dYR = reinterpret_cast<bf16_t *>(WS(op.TA));
         const bf16_t *WT = reinterpret_cast<const bf16_t *>(t->WTb.p + ln.w * 4);          // written by lin_fwd of this step
-        float *bpart = (has_b && colsum_chunk_rows(rows) == 32 && ((uintptr_t)G(ln.b) & 15) == 0) ? part_alloc((size_t)ceil_div(rows, 32) * Nc) : nullptr;
+        float *bpart = has_b ? defer_tile_sums(rows, Nc, G(ln.b)) : nullptr;
         if (t->no_tn) {
             // COCR_TRAIN_NO_TN=1 (A/B of the test): the weight-gradient product on transposed bf16 copies, as before gemm_tn_kernel existed
             bf16_t *dYT = reinterpret_cast<bf16_t *>(t->ws.p + op.BfA), *XT = reinterpret_cast<bf16_t *>(t->ws.p + op.BfW);
@@ -378,9 +398,8 @@ struct Train : TrainPlan {
             hipLaunchKernelGGL(k_rows_bf16, dim3(ceil_div(Nc, 256), ceil_div(rp, 32)), dim3(256), 0, s, dY, dYR, bpart, rows, Nc, rp);
             GEMM_TRY(launch_gemm_tn(s, dYR, Nc, XR, Kr, Nc, Kr, rp, splits, splits == 1 ? G(ln.w) : WS(op.Split)));
         }
-        if (splits > 1) hipLaunchKernelGGL(k_colsum_final, dim3(ceil_div(Nc * Kr, 64)), dim3(256), 0, s, WS(op.Split), G(ln.w), splits, Nc * Kr, 0);
-        if (bpart) defer_final(bpart, Nc, ceil_div(rows, 32), Nc, G(ln.b));
-        else if (has_b) colsum_grad(dY, rows, Nc, G(ln.b));
+        if (splits > 1) colsum_final(WS(op.Split), splits, Nc * Kr, G(ln.w));
+        if (has_b && !bpart) colsum(CS_ONE, dY, nullptr, rows, Nc, G(ln.b), nullptr, DEFER);
         if (dX) {
             EpiStoreF32 e{dX, Kr, nullptr, Kr};
             GEMM_TRY(launch_gemm<bf16_t>(s, dYR, Nc, WT, Nc, rows, Kr, Nc, e));
@@ -404,9 +423,9 @@ struct Train : TrainPlan {
             } else {
                 GEMM_TRY(launch_gemm_splitk<float>(s, WS(op.TA), rp, WS(op.TB), rp, Nc, Kr, rp, splits, WS(op.Split)));
             }
-            hipLaunchKernelGGL(k_colsum_final, dim3(ceil_div(Nc * Kr, 64)), dim3(256), 0, s, WS(op.Split), G(ln.w), splits, Nc * Kr, 0);
+            colsum_final(WS(op.Split), splits, Nc * Kr, G(ln.w));
         }
-        if (ln.b != TRAIN_NONE) colsum_grad(dY, rows, Nc, G(ln.b));
+        if (ln.b != TRAIN_NONE) colsum(CS_ONE, dY, nullptr, rows, Nc, G(ln.b), nullptr, DEFER);
         if (dX) {
             const int np = round_up(Nc, 4);
             const float *dYp = dY;
@@ -421,18 +440,8 @@ struct Train : TrainPlan {
     }
     // dx (+)= LayerNorm backward of dy; d gamma, d beta.  (Its dy * xhat product goes through g.wide2.)
     void ln_bwd(const float *dy, const float *x, const float *mu, const float *rs, size_t gamma, size_t beta, float *dxo, int accumulate) {
-        float *gg = G(gamma), *gb = G(beta);
         hipLaunchKernelGGL(k_ln_bwd, dim3(ceil_div(M, 4)), dim3(256), 0, s, dy, x, mu, rs, P(gamma), dxo, WS(g.wide2), M, D, accumulate);
-        if (D % 4 == 0 && ((uintptr_t)dy & 15) == 0 && ((uintptr_t)gg & 15) == 0 && ((uintptr_t)gb & 15) == 0) {      // d gamma and d beta in one pair of launches
-            const int rows = colsum_chunk_rows(M), chunks = ceil_div(M, rows);
-            float *lp = part_alloc((size_t)chunks * 2 * D);
-            hipLaunchKernelGGL(k_colsum_partial4_2, dim3(ceil_div(2 * D, 256), chunks), dim3(256), 0, s, WS(g.wide2), dy, lp ? lp : WS(rd.Part), M, D, rows);
-            if (lp) { defer_final(lp, 2 * D, chunks, D, gg); defer_final(lp + D, 2 * D, chunks, D, gb); }
-            else hipLaunchKernelGGL(k_colsum_final_2, dim3(ceil_div(2 * D, 64)), dim3(256), 0, s, WS(rd.Part), gg, gb, chunks, D);
-            return;
-        }
-        colsum(WS(g.wide2), nullptr, M, D, gg, 0);
-        colsum(dy, nullptr, M, D, gb, 0);
+        colsum(CS_PAIR, WS(g.wide2), dy, M, D, G(gamma), G(beta), DEFER);
     }
     void dropout(float *x, size_t n, float p, unsigned site) {
         if (p > 0.f) hipLaunchKernelGGL(k_dropout, grid1(n), dim3(256), 0, s, x, n, p, seed, site);
@@ -522,14 +531,7 @@ struct Train : TrainPlan {
         if (K == 31) hipLaunchKernelGGL((k_dw1d_rows<false, 31>), gr, dim3(256), 0, s, WS(a.g), P(b.dww), WS(a.dwo), N, T, D, K);
         else if (K <= 32) hipLaunchKernelGGL((k_dw1d_rows<false, 0>), gr, dim3(256), 0, s, WS(a.g), P(b.dww), WS(a.dwo), N, T, D, K);
         else hipLaunchKernelGGL(k_dw1d_fwd_flat, grid1(MD), dim3(256), 0, s, WS(a.g), P(b.dww), WS(a.dwo), N, T, D, K, 0);
-        if (D % 4 == 0) {                                  // sum x and sum x^2 in one pass
-            const int rows = colsum_chunk_rows(M), chunks = ceil_div(M, rows);
-            hipLaunchKernelGGL(k_colsum_partial4_sq, dim3(ceil_div(2 * D, 256), chunks), dim3(256), 0, s, WS(a.dwo), WS(rd.Part), M, D, rows);
-            hipLaunchKernelGGL(k_colsum_final_2, dim3(ceil_div(2 * D, 64)), dim3(256), 0, s, WS(rd.Part), WS(rd.Vec), WS(rd.Vec) + D, chunks, D);
-        } else {
-            colsum(WS(a.dwo), nullptr, M, D, WS(rd.Vec), 0);
-            colsum(WS(a.dwo), WS(a.dwo), M, D, WS(rd.Vec) + D, 0);
-        }
+        colsum(CS_SQ, WS(a.dwo), nullptr, M, D, WS(rd.Vec), WS(rd.Vec) + D);      // sum x | sum x^2
         hipLaunchKernelGGL(k_bn_finalize, dim3(ceil_div(D, 256)), dim3(256), 0, s, WS(rd.Vec), WS(rd.Vec) + D, M, D, WS(a.bnm), WS(a.bnr), P(b.bn_mean), P(b.bn_var), 0.1f);
         hipLaunchKernelGGL(k_bn_apply_silu, grid1(MD), dim3(256), 0, s, WS(a.dwo), WS(a.bnm), WS(a.bnr), P(b.bn_g), P(b.bn_b), WS(a.xhat), WS(a.bny), WS(a.sact), M, D);
         if ((rc = lin_fwd(WS(a.sact), b.pw2, M, D, D, WS(g.a)))) return rc;
@@ -597,29 +599,20 @@ struct Train : TrainPlan {
         if ((rc = lin_bwd(WS(g.a), WS(a.sact), b.pw2, M, D, D, WS(g.c)))) return rc;
         hipLaunchKernelGGL(k_silu_bwd, grid1(MD), dim3(256), 0, s, WS(a.bny), WS(g.c), MD);               // d bn_y
         float *gbeta = G(b.bn_b), *ggamma = G(b.bn_g);
-        if (D % 4 == 0 && ((uintptr_t)gbeta & 15) == 0 && ((uintptr_t)ggamma & 15) == 0) {
-            // sum dy (= d beta) and sum dy xhat (= d gamma) in one pass, straight into the gradient vector; the input gradient reads them there
-            const int rows = colsum_chunk_rows(M), chunks = ceil_div(M, rows);
-            hipLaunchKernelGGL(k_colsum_partial4_ab, dim3(ceil_div(2 * D, 256), chunks), dim3(256), 0, s, WS(g.c), WS(a.xhat), WS(rd.Part), M, D, rows);
-            hipLaunchKernelGGL(k_colsum_final_2, dim3(ceil_div(2 * D, 64)), dim3(256), 0, s, WS(rd.Part), gbeta, ggamma, chunks, D);
-        } else {
-            colsum(WS(g.c), nullptr, M, D, WS(rd.Vec), 0);                                                      // sum dy   = d beta
-            colsum(WS(g.c), WS(a.xhat), M, D, WS(rd.Vec) + D, 0);                                               // sum dy xhat = d gamma
-            if ((rc = copy(gbeta, WS(rd.Vec), D)) || (rc = copy(ggamma, WS(rd.Vec) + D, D))) return rc;
-        }
+        // sum dy (= d beta) | sum dy xhat (= d gamma), straight into the gradient vector; the input gradient reads them there
+        colsum(CS_AB, WS(g.c), WS(a.xhat), M, D, gbeta, ggamma);
         hipLaunchKernelGGL(k_bn_bwd, grid1(MD), dim3(256), 0, s, WS(g.c), WS(a.xhat), P(b.bn_g), WS(a.bnr), gbeta, ggamma, WS(g.e), M, D);      // d dwo
         if (K <= 32) {
             const int nch = ceil_div(T, COCR_DW_WC);
             const dim3 gw(ceil_div(D, 256), nch, N), gr(ceil_div(D, 256), ceil_div(T, COCR_DW_TC), N);
             if (K == 31) hipLaunchKernelGGL(k_dw1d_bwd_w<31>, gw, dim3(256), 0, s, WS(g.e), WS(a.g), WS(rd.LinePart), N, T, D, K);
             else hipLaunchKernelGGL(k_dw1d_bwd_w<0>, gw, dim3(256), 0, s, WS(g.e), WS(a.g), WS(rd.LinePart), N, T, D, K);
-            if ((D * K) % 4 == 0) hipLaunchKernelGGL(k_colsum_final4, dim3(ceil_div(D * K, 64)), dim3(256), 0, s, WS(rd.LinePart), G(b.dww), N * nch, D * K, 0);
-            else hipLaunchKernelGGL(k_colsum_final, dim3(ceil_div(D * K, 64)), dim3(256), 0, s, WS(rd.LinePart), G(b.dww), N * nch, D * K, 0);
+            colsum_final(WS(rd.LinePart), N * nch, D * K, G(b.dww), true);
             if (K == 31) hipLaunchKernelGGL((k_dw1d_rows<true, 31>), gr, dim3(256), 0, s, WS(g.e), P(b.dww), WS(g.c), N, T, D, K);   // d g
             else hipLaunchKernelGGL((k_dw1d_rows<true, 0>), gr, dim3(256), 0, s, WS(g.e), P(b.dww), WS(g.c), N, T, D, K);
         } else {
             hipLaunchKernelGGL(k_dw1d_bwd_w_flat, dim3(ceil_div(D, 64), K, N), dim3(64), 0, s, WS(g.e), WS(a.g), WS(rd.LinePart), N, T, D, K);
-            hipLaunchKernelGGL(k_colsum_final, dim3(ceil_div(D * K, 64)), dim3(256), 0, s, WS(rd.LinePart), G(b.dww), N, D * K, 0);
+            colsum_final(WS(rd.LinePart), N, D * K, G(b.dww));
             hipLaunchKernelGGL(k_dw1d_fwd_flat, grid1(MD), dim3(256), 0, s, WS(g.e), P(b.dww), WS(g.c), N, T, D, K, 1);   // d g
         }
         hipLaunchKernelGGL(k_glu_bwd, grid1(MD), dim3(256), 0, s, WS(a.ga), WS(g.c), WS(g.wide), M, D);                  // d a (M, 2D)
@@ -678,9 +671,9 @@ struct Train : TrainPlan {
             hipLaunchKernelGGL(k_attn_bwd_pos, dim3(ceil_div(R * Hh, 4), N), dim3(256), 0, s, WS(a.q), P(b.vb), WS(at.Dsb), WS(rd.LinePart), N, T, Hh, dh);
         }
         HIP_TRY(hipMemsetAsync(WS(at.DP), 0, (size_t)Rp * D * 4, s));
-        hipLaunchKernelGGL(k_colsum_final, dim3(ceil_div(R * D, 64)), dim3(256), 0, s, WS(rd.LinePart), WS(at.DP), N, R * D, 0);
-        colsum_grad(du_part, M, D, G(b.ub));
-        colsum_grad(dvb_part, M, D, G(b.vb));
+        colsum_final(WS(rd.LinePart), N, R * D, WS(at.DP));
+        colsum(CS_ONE, du_part, nullptr, M, D, G(b.ub), nullptr, DEFER);
+        colsum(CS_ONE, dvb_part, nullptr, M, D, G(b.vb), nullptr, DEFER);
         hipLaunchKernelGGL(k_axpy, grid1(MD), dim3(256), 0, s, du_part, dvb_part, 1.0f, MD);                 // d q
         // pos_proj weight: P = PE Wpos^T  ->  d Wpos = dP^T PE
         if ((rc = lin_bwd(WS(at.DP), t->pe.p, b.pos, R, D, D, nullptr))) return rc;

@@ -237,7 +237,7 @@ CASES = {
     'cfg2x2_1000': dict(hp=lambda: synth.hparams('cfg2', num_encoder_layers=2), seed=5, lines_seed=23, n=3, W=1000, widths=[1000, 612, 333],
                         targets=[[5, 9, 9, 3], [17, 2], [2, 40, 7]]),
     # M = 2096 > 2048 (Mp = 4096; rp = 4096 over 32 splits: 128 rows each, the 17th holds 48 rows and padding, splits 18..32 are empty -- a last
-    # split that holds rows is 'rows_full' below; 66 column-sum chunks of 32 rows: k_colsum_final4), frontend rows 8 x 524 x 16 = 67072 > 65536 (256-row chunks) and 8 x 262 x 8 = 16768 > 16384 (64-row chunks)
+    # split that holds rows is 'rows_full' below; 66 column-sum chunks of 32 rows: k_colsum_final4 / the deferred finals, both colsum_final16), frontend rows 8 x 524 x 16 = 67072 > 65536 (256-row chunks) and 8 x 262 x 8 = 16768 > 16384 (64-row chunks)
     'rows': dict(hp=lambda: synth.hparams('cfg2', num_encoder_layers=1, height=32), seed=31, lines_seed=32, n=8, W=1048,
                  widths=[1048, 700, 333, 1043, 64, 900, 517, 1000],
                  targets=[[5, 9, 9, 3], [17], [2, 2], [40, 7, 7], [1], [3, 1, 4, 1], [59, 26], [5, 35, 8]]),
@@ -277,7 +277,7 @@ SHAPE_CASES = {
     # D = 512: two column blocks in the depthwise / column-sum / BatchNorm kernels, 8 heads of 64, 8 splits in the feed-forward weight gradients
     'd512k7': dict(hp=lambda: synth.hparams('cfg4', num_encoder_layers=1, conv_kernel_size=7, height=32), seed=48, n=2, W=140, widths=[140, 93],
                    targets=[[5, 9, 3], [17]]),
-    # the full-step feed-forward residual (ffr = 1), expansion 2 (ff = 512), 97 classes (nclp = 100: k_pad_cols, scalar column sums, `gemm`'s own
+    # the full-step feed-forward residual (ffr = 1), expansion 2 (ff = 512), 97 classes (nclp = 100: k_pad_cols, scalar column sums k_colsum_partial<CS_ONE, float>, `gemm`'s own
     # rounding rule under 'medium')
     'nohalf97ff2': dict(hp=lambda: synth.hparams('cfg2', num_encoder_layers=1, half_step_residual=False, num_classes=97,
                                                  feed_forward_expansion_factor=2, height=32), seed=49, n=2, W=140, widths=[140, 93],
@@ -315,7 +315,7 @@ def shape_facts(name) -> Dict[str, int]:
 # What each case exists for, as a predicate over `shape_facts`: asserted by the GPU test before it runs and by tests/test_train_ref_host.py
 # without a GPU, so that a later change of shapes cannot silently lose the branch.  The code lines: p.attn_gemm = dh % 32 == 0 and
 # train_wg_splits (train_step.hip.h), `d += 64` / `(dh & 3) == 0` (k_attn_* of train_enc.hip.h), K == 31 / K <= 32 / else (conv_fwd, conv_bwd),
-# ceil_div(D, 256) column blocks, the LDS test of `tfc`, ffr, `Nc % 4` (lin_bwd, colsum).
+# ceil_div(D, 256) column blocks, the LDS test of `tfc`, ffr, `Nc % 4` (lin_bwd; `Train::colsum`, which picks k_colsum_partial's float / f32x4 form).
 SHAPE_PRE = {
     'cfg1_1': lambda f: f['dh'] == 36 and f['dh'] % 32 != 0 and f['dh'] % 4 == 0 and f['T'] > 64 and f['K'] == 31 and f['D'] < 256
     and all(x % 128 != 0 for x in (f['D'], f['ff'], 2 * f['D'])) and all(x % 8 == 0 for x in (f['D'], f['ff'], f['C'], f['C'] * f['F'], f['ncls']))
