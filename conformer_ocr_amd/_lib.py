@@ -55,6 +55,7 @@ SYMBOLS = {
     'cocr_lm_create': (_I, [_P, _I, _I, _P, _P, _P, C.c_int64, _P, _P, C.c_int64, C.POINTER(_P)]),
     'cocr_lm_destroy': (None, [_P]),
     'cocr_ctc_beam_lm': (_I, [_P, _P, _P, _I, _I, _I, _I32P, _P, _P, _P, _P, _P, _I, _I, _I, C.c_float, C.c_float, _P, _P]),
+    'cocr_ctc_beam_nbest': (_I, [_P, _P, _P, _I, _I, _I, _I32P, _I, _I, _I, C.c_float, C.c_float, _P, _P, _P, _P, _P, _P, _P, _I, _P]),
     'cocr_ctc_loss': (_I, [_P, _P, _I, _I, _I, _I32P, _I32P, _I32P, _P, _P, _P]),
     'cocr_distill_loss': (_I, [_P, _P, _P, _I, _I, _I, _I32P, C.c_float, _P, _P, C.c_float, C.c_float, _I, _P]),
     'cocr_ctc_align': (_I, [_P, _P, _I, _I, _I, _I32P, _I32P, _I32P, _P, _P, _P, _P, _P, _P]),

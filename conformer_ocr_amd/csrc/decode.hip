@@ -1,8 +1,9 @@
 // What follows the forward behind the C ABI (units of the host layer: model.hip.h): the CTC decoders (greedy, beam, beam with an
-// n-gram model), the n-gram model itself, the CTC criterion, the distillation term, forced alignment and keyword spotting.
+// n-gram model, n-best output of both), the n-gram model itself, the CTC criterion, the distillation term, forced alignment and keyword spotting.
 #include "model.hip.h"
 #include "ctc.hip.h"
 #include "ctc_lm.hip.h"
+#include "ctc_nbest.hip.h"
 #include "ctc_loss.hip.h"
 #include "distill.hip.h"
 #include "ctc_align.hip.h"
@@ -82,28 +83,39 @@ extern "C" int cocr_ctc_greedy(cocr_model *m, const float *logits, int N, int T,
     return COCR_OK;
 }
 
-extern "C" int cocr_ctc_beam(cocr_model *m, const float *logits, int N, int T, int ncls, const int32_t *out_lens, int32_t *labels,
-                             int32_t *starts, int32_t *ends, float *conf, int32_t *counts, int max_per_line, int beam, void *stream) {
-    if (!m || !logits || !out_lens || !labels || !starts || !ends || !conf || !counts) return fail(COCR_EINVAL, "null argument");
-    if (N < 1 || T < 1 || ncls < 2 || max_per_line < 1) return fail(COCR_EINVAL, "empty problem");
-    if (beam < 1 || beam > COCR_BEAM_MAX) return fail(COCR_EINVAL, "beam must be in 1..%d", COCR_BEAM_MAX);
-    if (ncls > 65535) return fail(COCR_EUNSUPPORTED, "more than 65535 classes");
-    HIP_TRY(hipSetDevice(m->device));
-    hipStream_t s = (hipStream_t)stream;
-    const int32_t *d_lens;
-    int rc = upload_lens(m, out_lens, N, s, d_lens);
-    if (rc) return rc;
+// What a beam search leaves in its scratch for the n-best pass (ctc_nbest.hip.h): the back-pointers [N][T][COCR_BEAM_MAX], log Z of
+// frame (n, t) at lz[(n T + t) lz_stride], and `extra` bytes of the caller's behind both (16-byte aligned).
+struct BeamTrail { const int32_t *bp; const float *lz; int lz_stride; unsigned char *extra; };
+
+// The walk kernel's own 1-best outputs of an n-best call, one record per line (max_per_line 1: it is asked for no more), at the head of
+// `extra`.
+static size_t walk_out_bytes(int N) { return ((size_t)N * 5 * 4 + 15) / 16 * 16; }
+static void walk_out_at(unsigned char *p, int N, int32_t *&labels, int32_t *&starts, int32_t *&ends, float *&conf, int32_t *&counts) {
+    int32_t *q = reinterpret_cast<int32_t *>(p);
+    labels = q; starts = q + N; ends = q + 2 * N; conf = reinterpret_cast<float *>(q + 3 * N); counts = q + 4 * N;
+}
+
+// The launches of cocr_ctc_beam behind its checks.  `trail`: null for the 1-best call; else the back-pointers go to global memory over
+// a region filled with 0xFF bytes (-1: the rank was not alive in that frame), `extra` >= walk_out_bytes(N) bytes are kept behind the
+// scratch, and the kernel's 1-best outputs go to their head (the caller passes max_per_line 1 and no output pointers).
+static int beam_launch(cocr_model *m, const float *logits, int N, int T, int ncls, const int32_t *d_lens, int32_t *labels, int32_t *starts, int32_t *ends,
+                       float *conf, int32_t *counts, int max_per_line, int beam, hipStream_t s, size_t extra, BeamTrail *trail) {
     const bool fast = ncls <= 256 && !m->sw.beam_ref;            // ctc_beam_rank_kernel + ctc_beam_walk_kernel: frames ranked in parallel, a static pruned candidate set per frame
     const int K = std::min(beam + 1, ncls - 1);
     // scratch: back-pointers [N][T][COCR_BEAM_MAX] i32, then log Z [N][T] (exhaustive kernel) or the frame records (fast)
+    const size_t bp_bytes = (size_t)N * T * COCR_BEAM_MAX * 4;
     const size_t need = (size_t)N * T * ((size_t)COCR_BEAM_MAX * 4 + (fast ? (size_t)COCR_BEAM_REC : 4));
-    HIP_TRY(m->dec.beam_bp.grow(need));
+    HIP_TRY(m->dec.beam_bp.grow(trail ? (need + 15) / 16 * 16 + extra : need));
     int32_t *bp = reinterpret_cast<int32_t *>(m->dec.beam_bp.p);
-    ProfScope ps(m, s, FAM_BEAM);
+    if (trail) {
+        HIP_TRY(hipMemsetAsync(bp, 0xFF, bp_bytes, s));
+        *trail = {bp, nullptr, 1, m->dec.beam_bp.p + (need + 15) / 16 * 16};
+        walk_out_at(trail->extra, N, labels, starts, ends, conf, counts);
+    }
     if (fast) {
         unsigned char *rec = reinterpret_cast<unsigned char *>(bp + (size_t)N * T * COCR_BEAM_MAX);
         const size_t dyn = (size_t)T * ((size_t)beam * 4 + 8);                 // back-pointers + the label stack of the final walk, in LDS when they fit
-        const int bp_in_lds = dyn <= 96 * 1024;
+        const int bp_in_lds = !trail && dyn <= 96 * 1024;
         hipLaunchKernelGGL(ctc_beam_rank_kernel, dim3(N * T), dim3(256), 0, s, logits, T, ncls, d_lens, K, rec);
         auto walk = ctc_beam_walk_kernel<3>;                          // candidates per lane of a wave: <= 88 for beam <= 16, <= 184 for beam 32
         if (beam <= 16) walk = ctc_beam_walk_kernel<2>;
@@ -111,6 +123,7 @@ extern "C" int cocr_ctc_beam(cocr_model *m, const float *logits, int N, int T, i
         if (bp_in_lds) HIP_TRY(raise_lds_limit((const void *)walk, dyn, 48 * 1024, 96 * 1024));
         hipLaunchKernelGGL(walk, dim3(N), dim3(256), bp_in_lds ? dyn : 0, s, logits, T, ncls, d_lens, beam, K, labels, starts,
                            ends, conf, counts, max_per_line, rec, bp, bp_in_lds, m->stamps ? m->stamps + 240 : nullptr);
+        if (trail) { trail->lz = reinterpret_cast<const float *>(rec + COCR_BEAM_REC_LZ); trail->lz_stride = COCR_BEAM_REC / 4; }
     } else {
         float *logz = reinterpret_cast<float *>(bp + (size_t)N * T * COCR_BEAM_MAX);
         const size_t lds = ((size_t)ncls + (size_t)beam * ncls) * 4 + COCR_BEAM_MAX * (11 * 4 + 2 * 8) + 64;
@@ -118,9 +131,30 @@ extern "C" int cocr_ctc_beam(cocr_model *m, const float *logits, int N, int T, i
         HIP_TRY(raise_lds_limit((const void *)ctc_beam_kernel, lds));
         hipLaunchKernelGGL(ctc_beam_kernel, dim3(N), dim3(64), lds, s, logits, T, ncls, d_lens, beam, labels, starts, ends, conf, counts,
                            max_per_line, bp, logz);
+        if (trail) trail->lz = logz;
     }
     LAUNCH_CHECK();
     return COCR_OK;
+}
+
+static int beam_check(int N, int T, int ncls, int max_per_line, int beam) {
+    if (N < 1 || T < 1 || ncls < 2 || max_per_line < 1) return fail(COCR_EINVAL, "empty problem");
+    if (beam < 1 || beam > COCR_BEAM_MAX) return fail(COCR_EINVAL, "beam must be in 1..%d", COCR_BEAM_MAX);
+    if (ncls > 65535) return fail(COCR_EUNSUPPORTED, "more than 65535 classes");
+    return COCR_OK;
+}
+
+extern "C" int cocr_ctc_beam(cocr_model *m, const float *logits, int N, int T, int ncls, const int32_t *out_lens, int32_t *labels,
+                             int32_t *starts, int32_t *ends, float *conf, int32_t *counts, int max_per_line, int beam, void *stream) {
+    if (!m || !logits || !out_lens || !labels || !starts || !ends || !conf || !counts) return fail(COCR_EINVAL, "null argument");
+    int rc = beam_check(N, T, ncls, max_per_line, beam);
+    if (rc) return rc;
+    HIP_TRY(hipSetDevice(m->device));
+    hipStream_t s = (hipStream_t)stream;
+    const int32_t *d_lens;
+    if ((rc = upload_lens(m, out_lens, N, s, d_lens))) return rc;
+    ProfScope ps(m, s, FAM_BEAM);
+    return beam_launch(m, logits, N, T, ncls, d_lens, labels, starts, ends, conf, counts, max_per_line, beam, s, 0, nullptr);
 }
 
 // ------------------------------------------------------------------------------------ beam search with an n-gram model (ctc_lm.hip.h)
@@ -171,10 +205,7 @@ extern "C" void cocr_lm_destroy(cocr_lm *lm) {
     delete lm;
 }
 
-extern "C" int cocr_ctc_beam_lm(cocr_model *m, cocr_lm *lm, const float *logits, int N, int T, int ncls, const int32_t *out_lens, int32_t *labels,
-                                int32_t *starts, int32_t *ends, float *conf, int32_t *counts, int max_per_line, int beam, int classes, float alpha,
-                                float beta, float *score, void *stream) {
-    if (!m || !lm || !logits || !out_lens || !labels || !starts || !ends || !conf || !counts) return fail(COCR_EINVAL, "null argument");
+static int beam_lm_check(cocr_model *m, cocr_lm *lm, int N, int T, int ncls, int max_per_line, int beam, int classes, float alpha, float beta) {
     if (N < 1 || T < 1 || ncls < 2 || max_per_line < 1) return fail(COCR_EINVAL, "empty problem");
     if (T > 8000) return fail(COCR_EUNSUPPORTED, "more than 8000 frames per line");
     if (beam < 1 || beam > COCR_BEAM_MAX) return fail(COCR_EINVAL, "beam must be in 1..%d", COCR_BEAM_MAX);
@@ -182,28 +213,87 @@ extern "C" int cocr_ctc_beam_lm(cocr_model *m, cocr_lm *lm, const float *logits,
     if (ncls != lm->ncls) return fail(COCR_EINVAL, "the logits have %d classes, the language model %d", ncls, lm->ncls);
     if (lm->device != m->device) return fail(COCR_EINVAL, "the language model lives on device %d, the model on %d", lm->device, m->device);
     if (!std::isfinite(alpha) || !std::isfinite(beta)) return fail(COCR_EINVAL, "alpha and beta must be finite");
-    HIP_TRY(hipSetDevice(m->device));
-    hipStream_t s = (hipStream_t)stream;
-    const int32_t *d_lens;
-    int rc = upload_lens(m, out_lens, N, s, d_lens);
-    if (rc) return rc;
-    const int K = std::min(classes, ncls - 1);
-    // scratch: back-pointers [N][T][COCR_BEAM_MAX] i32, then the frame records [N][T][COCR_LM_REC] f32
-    const size_t bp_bytes = (size_t)N * T * COCR_BEAM_MAX * 4;
-    HIP_TRY(m->dec.lm_scratch.grow(bp_bytes + (size_t)N * T * COCR_LM_REC * 4));
-    int32_t *bp = reinterpret_cast<int32_t *>(m->dec.lm_scratch.p);
-    float *rec = reinterpret_cast<float *>(m->dec.lm_scratch.p + bp_bytes);
-    const size_t dyn = (size_t)T * ((size_t)beam * 4 + 8);                     // back-pointers + the label stack of the final walk, in LDS when they fit
-    const int bp_in_lds = dyn <= 96 * 1024;
-    if (bp_in_lds) HIP_TRY(raise_lds_limit((const void *)ctc_lm_walk_kernel, dyn, 16 * 1024, 96 * 1024));      // (the kernel has ~30 KB of static LDS)
+    return COCR_OK;
+}
+
+static cocr_lm_tables lm_tables(const cocr_lm *lm) {
     cocr_lm_tables L;
     L.unigram = lm->unigram.p; L.nkeys = lm->nkeys.p; L.nlogp = lm->nlogp.p; L.ckeys = lm->ckeys.p; L.cbow = lm->cbow.p;
     L.nmask = (unsigned)(lm->nslots - 1); L.cmask = (unsigned)(lm->cslots - 1); L.order = lm->order;
-    ProfScope ps(m, s, FAM_BEAM);
+    return L;
+}
+
+// The launches of cocr_ctc_beam_lm behind its checks; `extra` and `trail` as in beam_launch.
+static int beam_lm_launch(cocr_model *m, cocr_lm *lm, const float *logits, int N, int T, int ncls, const int32_t *d_lens, int32_t *labels, int32_t *starts,
+                          int32_t *ends, float *conf, int32_t *counts, int max_per_line, int beam, int classes, float alpha, float beta, float *score,
+                          hipStream_t s, size_t extra, BeamTrail *trail) {
+    const int K = std::min(classes, ncls - 1);
+    // scratch: back-pointers [N][T][COCR_BEAM_MAX] i32, then the frame records [N][T][COCR_LM_REC] f32
+    const size_t bp_bytes = (size_t)N * T * COCR_BEAM_MAX * 4;
+    const size_t need = bp_bytes + (size_t)N * T * COCR_LM_REC * 4;
+    HIP_TRY(m->dec.lm_scratch.grow(trail ? (need + 15) / 16 * 16 + extra : need));
+    int32_t *bp = reinterpret_cast<int32_t *>(m->dec.lm_scratch.p);
+    float *rec = reinterpret_cast<float *>(m->dec.lm_scratch.p + bp_bytes);
+    if (trail) {
+        HIP_TRY(hipMemsetAsync(bp, 0xFF, bp_bytes, s));
+        *trail = {bp, rec + 1, COCR_LM_REC, m->dec.lm_scratch.p + (need + 15) / 16 * 16};
+        walk_out_at(trail->extra, N, labels, starts, ends, conf, counts);
+    }
+    const size_t dyn = (size_t)T * ((size_t)beam * 4 + 8);                     // back-pointers + the label stack of the final walk, in LDS when they fit
+    const int bp_in_lds = !trail && dyn <= 96 * 1024;
+    if (bp_in_lds) HIP_TRY(raise_lds_limit((const void *)ctc_lm_walk_kernel, dyn, 16 * 1024, 96 * 1024));      // (the kernel has ~30 KB of static LDS)
+    const cocr_lm_tables L = lm_tables(lm);
     hipLaunchKernelGGL(ctc_lm_topk_kernel, dim3(ceil_div(N * T, 4)), dim3(256), 0, s, logits, T, ncls, N * T, d_lens, K, rec);
     LAUNCH_CHECK();
     hipLaunchKernelGGL(ctc_lm_walk_kernel, dim3(N), dim3(256), bp_in_lds ? dyn : 0, s, logits, T, ncls, d_lens, beam, K, L, alpha, beta, labels, starts,
                        ends, conf, counts, score, max_per_line, rec, bp, bp_in_lds);
+    LAUNCH_CHECK();
+    return COCR_OK;
+}
+
+extern "C" int cocr_ctc_beam_lm(cocr_model *m, cocr_lm *lm, const float *logits, int N, int T, int ncls, const int32_t *out_lens, int32_t *labels,
+                                int32_t *starts, int32_t *ends, float *conf, int32_t *counts, int max_per_line, int beam, int classes, float alpha,
+                                float beta, float *score, void *stream) {
+    if (!m || !lm || !logits || !out_lens || !labels || !starts || !ends || !conf || !counts) return fail(COCR_EINVAL, "null argument");
+    int rc = beam_lm_check(m, lm, N, T, ncls, max_per_line, beam, classes, alpha, beta);
+    if (rc) return rc;
+    HIP_TRY(hipSetDevice(m->device));
+    hipStream_t s = (hipStream_t)stream;
+    const int32_t *d_lens;
+    if ((rc = upload_lens(m, out_lens, N, s, d_lens))) return rc;
+    ProfScope ps(m, s, FAM_BEAM);
+    return beam_lm_launch(m, lm, logits, N, T, ncls, d_lens, labels, starts, ends, conf, counts, max_per_line, beam, classes, alpha, beta, score, s, 0, nullptr);
+}
+
+// ------------------------------------------------------------------------------------ n-best output (ctc_nbest.hip.h)
+extern "C" int cocr_ctc_beam_nbest(cocr_model *m, cocr_lm *lm, const float *logits, int N, int T, int ncls, const int32_t *out_lens, int beam, int nbest,
+                                   int classes, float alpha, float beta, int32_t *labels, int32_t *starts, int32_t *ends, float *conf, int32_t *counts,
+                                   int32_t *nhyp, float *scores, int max_per_line, void *stream) {
+    if (!m || !logits || !out_lens || !labels || !starts || !ends || !conf || !counts || !nhyp || !scores) return fail(COCR_EINVAL, "null argument");
+    int rc = lm ? beam_lm_check(m, lm, N, T, ncls, max_per_line, beam, classes, alpha, beta) : beam_check(N, T, ncls, max_per_line, beam);
+    if (rc) return rc;
+    if (nbest < 1 || nbest > beam) return fail(COCR_EINVAL, "nbest must be in 1..beam (%d)", beam);
+    if (T > 8000) return fail(COCR_EUNSUPPORTED, "more than 8000 frames per line");
+    if ((rc = check_out_lens(out_lens, N, T))) return rc;
+    const int cap = std::max(1, (int)*std::max_element(out_lens, out_lens + N));        // frames of the longest line
+    HIP_TRY(hipSetDevice(m->device));
+    hipStream_t s = (hipStream_t)stream;
+    const int32_t *d_lens;
+    if ((rc = upload_lens(m, out_lens, N, s, d_lens))) return rc;
+    // behind the search's scratch: the walk kernel's own 1-best outputs, then the chains' label stacks [N][nbest][T] of a call whose
+    // lines do not fit the LDS
+    const bool in_lds = nbest_lds_bytes(cap, beam, nbest, true) <= 144 * 1024;
+    const size_t walk_out = walk_out_bytes(N), extra = walk_out + (in_lds ? 0 : (size_t)N * nbest * T * 4);
+    ProfScope ps(m, s, FAM_BEAM);
+    BeamTrail tr;
+    if (lm) rc = beam_lm_launch(m, lm, logits, N, T, ncls, d_lens, nullptr, nullptr, nullptr, nullptr, nullptr, 1, beam, classes, alpha, beta, nullptr, s, extra, &tr);
+    else rc = beam_launch(m, logits, N, T, ncls, d_lens, nullptr, nullptr, nullptr, nullptr, nullptr, 1, beam, s, extra, &tr);
+    if (rc) return rc;
+    unsigned *stk_ws = in_lds ? nullptr : reinterpret_cast<unsigned *>(tr.extra + walk_out);
+    const cocr_lm_tables L = lm ? lm_tables(lm) : cocr_lm_tables{};
+    HIP_TRY(launch_ctc_nbest(s, sj_for_states(2 * std::min(cap, COCR_LATTICE_MAX_LABELS) + 1), in_lds, lm != nullptr, nbest_lds_bytes(cap, beam, nbest, in_lds), N, logits, T, ncls,
+                             d_lens, beam, nbest, tr.bp, tr.lz, tr.lz_stride, L, labels, starts, ends, conf, counts, nhyp, scores, max_per_line,
+                             stk_ws, cap));
     LAUNCH_CHECK();
     return COCR_OK;
 }

@@ -280,6 +280,64 @@ class HipRecognizer:
         recs = self.collect(self.ctc_beam_lm_async(logits, out_lens, lm, beam, classes, alpha, beta, score))
         return (recs, score.numpy().copy()) if return_scores else recs
 
+    def ctc_beam_nbest_async(self, logits: torch.Tensor, out_lens, beam: int = 16, nbest: int = 4, lm=None, classes: int = 8, alpha: float = 0.5,
+                             beta: float = 0.0):
+        """`cocr_ctc_beam_nbest` (include/cocr.h) enqueued on the current stream: the first `nbest` prefixes of the
+        final beam of `ctc_beam` (or, with `lm`, of `ctc_beam_lm`), each with its exact CTC log-probability and its raw n-gram sum.
+        The records and scores land in pinned host memory, like `_decode_async`'s.  Returns a handle for `collect_nbest`."""
+        if logits.device != self.device or logits.dtype != torch.float32 or logits.dim() != 3:
+            raise RuntimeError('logits must be a float32 (N,T,num_classes) tensor on the model device')
+        logits = logits.contiguous()
+        N, T, ncls = logits.shape
+        nbest = int(nbest)
+        lens = np.ascontiguousarray(np.asarray(out_lens, dtype=np.int32).reshape(-1))
+        if lens.shape[0] != N:
+            raise ValueError('one output length per line')
+        dlm = lm.to_device(self) if lm is not None else None
+        with torch.cuda.device(self.device):
+            key = ('nbest', N, T, max(nbest, 1))
+            pool = self._pinned.setdefault(key, [])
+            host = pool.pop() if pool else (torch.empty((3, N, key[3], T), dtype=torch.int32).pin_memory(),
+                                            torch.empty((N, key[3], T), dtype=torch.float32).pin_memory(),
+                                            torch.empty((N, key[3]), dtype=torch.int32).pin_memory(),
+                                            torch.empty((N,), dtype=torch.int32).pin_memory(),
+                                            torch.empty((N, key[3], 2), dtype=torch.float32).pin_memory())
+            ints, conf, counts, nhyp, scores = host
+            vp = lambda t: C.c_void_p(t.data_ptr())
+            try:
+                _lib.check(self.lib.cocr_ctc_beam_nbest(self._h, dlm.handle if dlm is not None else None, vp(logits), N, T, ncls,
+                                                        lens.ctypes.data_as(C.POINTER(C.c_int32)), int(beam), nbest, int(classes), C.c_float(alpha),
+                                                        C.c_float(beta), vp(ints[0]), vp(ints[1]), vp(ints[2]), vp(conf), vp(counts), vp(nhyp), vp(scores),
+                                                        T, _stream_ptr(self.device)))
+            except Exception:
+                pool.append(host)
+                raise
+            ev = torch.cuda.Event()
+            ev.record(torch.cuda.current_stream(self.device))
+        return (key, host, ev, (logits, dlm))
+
+    def collect_nbest(self, handle) -> List[List[Tuple[List[Tuple[int, int, int, float]], float, float]]]:
+        """Waits for a `ctc_beam_nbest_async` handle; per line its hypotheses in beam order, each (records, logp, lm_logp)."""
+        key, host, ev, _keep = handle
+        ev.synchronize()
+        ints, conf, counts, nhyp, scores = (h.numpy() for h in host)
+        out = []
+        for n, nh in enumerate(nhyp.tolist()):
+            hyps = []
+            for j in range(nh):
+                c = int(counts[n, j])
+                lab, st, en = ints[:, n, j, :c].tolist()
+                hyps.append((list(zip(lab, st, en, conf[n, j, :c].tolist())), float(scores[n, j, 0]), float(scores[n, j, 1])))
+            out.append(hyps)
+        self._pinned[key].append(host)
+        return out
+
+    def ctc_beam_nbest(self, logits: torch.Tensor, out_lens, beam: int = 16, nbest: int = 4, lm=None, classes: int = 8, alpha: float = 0.5,
+                       beta: float = 0.0):
+        """Per line a list of hypotheses (records, logp, lm_logp): `nbest.nbest_host` on the device for the whole batch.  logp is NaN for
+        a hypothesis of more than 255 labels."""
+        return self.collect_nbest(self.ctc_beam_nbest_async(logits, out_lens, beam, nbest, lm, classes, alpha, beta))
+
     def ctc_loss(self, probits: torch.Tensor, out_lens, targets, label_lens, with_grad: bool = True):
         """nn.CTCLoss(reduction='sum', zero_infinity=True) on log_softmax(probits) (reference model.py:119,136-142) on the device.
         probits (N,T,ncls) float32 on this device; out_lens (N) valid frames; targets: the batch's concatenated 1-D label vector,

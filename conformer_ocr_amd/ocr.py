@@ -2,10 +2,12 @@
 image plus its baseline segmentation:
 
     python -m conformer_ocr_amd.ocr -m MODEL [-f page|alto] -i IN.xml OUT.txt [-i IN2.xml OUT2.txt ...] [--device cuda:0] [--batch-size 32]
-                                    [--pad 16] [--edge 200] [--beam N] [--lm FILE [--lm-weight A] [--lm-bonus B] [--lm-classes K]]
+                                    [--pad 16] [--edge 200] [--beam N] [--lm FILE [--lm-weight A] [--lm-bonus B] [--lm-classes K]] [--nbest K]
 
 IN is a PAGE XML or ALTO file; the image it names is resolved relative to it.  MODEL is a safetensors archive (`save_safetensors`) or a
-Lightning checkpoint.  OUT receives one line of text per TextLine, in document order (the reference's "native" serializer)."""
+Lightning checkpoint.  OUT receives one line of text per TextLine, in document order (the reference's "native" serializer).  With --nbest K (needs --beam or
+--lm) OUT.nbest.json also holds, per line id, the K best readings of the beam: [{text, logp, lm_logp, conf: [...]}], logp the exact
+CTC log-probability of the reading (null beyond 255 labels), lm_logp the raw n-gram sum, conf the per-character confidences."""
 from __future__ import annotations
 
 import argparse
@@ -31,6 +33,20 @@ def add_decoder_arguments(ap) -> None:
                                                                  'not tuned on real material; `python -m conformer_ocr_amd.lm tune` finds yours)')
     ap.add_argument('--lm-bonus', type=float, default=0.0, help='bonus per decoded label (default 0: a placeholder, see --lm-weight)')
     ap.add_argument('--lm-classes', type=int, default=8, help='candidate classes per frame of the LM beam search, 1..64 (default 8: a placeholder)')
+
+
+def add_nbest_argument(ap) -> None:
+    """--nbest of the `ocr` and `test` commands (beside `add_decoder_arguments`)."""
+    ap.add_argument('--nbest', type=int, default=0, metavar='K', help='also report the K best readings of the beam per line (needs --beam or --lm); '
+                                                                      '0 = the best reading only (default)')
+
+
+def check_nbest(args) -> None:
+    """ValueError: --nbest without a beam, negative, or beyond the beam width."""
+    if args.nbest < 0 or (args.nbest and not (args.beam or args.lm)):
+        raise ValueError('--nbest needs a beam: give --beam or --lm' if args.nbest > 0 else '--nbest must not be negative')
+    if args.nbest > (args.beam or 16):
+        raise ValueError('--nbest cannot exceed the beam width')
 
 
 def set_decoder(net, args) -> None:
@@ -69,6 +85,7 @@ def main(argv=None) -> int:
     ap.add_argument('--pad', type=int, default=16, help='zero columns left and right of every scaled line (the model\'s training form)')
     ap.add_argument('--edge', type=int, default=200, help='width bucket edge: lines are padded to a multiple of it')
     add_decoder_arguments(ap)
+    add_nbest_argument(ap)
     args = ap.parse_args(argv)
     from .page import read_alto, read_page_xml, recognize_pages
     reader = read_alto if args.format == 'alto' else read_page_xml
@@ -81,15 +98,24 @@ def main(argv=None) -> int:
         docs.append((img, page.lines, dst))
     net = load_model(args.model, device=args.device)
     try:
+        check_nbest(args)
         set_decoder(net, args)
     except ValueError as e:
         raise SystemExit(f'error: {e}')
     results = recognize_pages(net, [(img, lines) for img, lines, _ in docs], batch_size=args.batch_size, edge=args.edge, pad=args.pad,
-                              device=args.device)
+                              device=args.device, nbest=args.nbest)
     for (_, _, dst), lines in zip(docs, results):
         with open(dst, 'w', encoding='utf-8') as fp:
             for rec in lines:
                 fp.write(rec['text'] + '\n')
+        if args.nbest:
+            import json
+            import math
+            doc = {rec['id']: [{'text': text, 'logp': None if math.isnan(logp) else logp, 'lm_logp': lmv, 'conf': [r[3] for r in recs]}
+                               for text, logp, lmv, recs in rec['nbest']] for rec in lines}
+            with open(dst + '.nbest.json', 'w', encoding='utf-8') as fp:
+                json.dump(doc, fp, ensure_ascii=False, indent=1)
+                fp.write('\n')
         print(f'{dst}: {len(lines)} lines', file=sys.stderr)
     return 0
 

@@ -296,9 +296,11 @@ def _check_image(image) -> np.ndarray:
 
 
 def recognize_pages(net, pages: Sequence[Tuple[np.ndarray, Sequence[Line]]], batch_size: int = 32, edge: int = 200, pad: int = 16,
-                    fill: int = 0, device: str = 'cuda:0') -> List[List[Dict]]:
+                    fill: int = 0, device: str = 'cuda:0', nbest: int = 0) -> List[List[Dict]]:
     """Text of every line of `pages` ((image, lines) pairs: (H, W) gray or (H, W, 3) RGB uint8 images, `Line`s).  Returns per page, in
-    the order of its lines, {'id', 'text', 'cuts': [(char, quad, conf)]} with quads in page pixels.
+    the order of its lines, {'id', 'text', 'cuts': [(char, quad, conf)]} with quads in page pixels.  nbest > 0 (a beam decoder is
+    required): every record also has 'nbest', `net.predict_nbest`'s [(text, logp, lm_logp, label records)]; 'text' and 'cuts' are
+    those of its first entry, which is the 1-best reading.
 
     All lines of all pages are bucketed together by the widths they have after scaling (`make_batches`, like `recognize_crops`), so a
     line's string is the one `recognize_crops` gives for its strip.  Per batch: `cocr_extract_lines` cuts the strips out of the pages
@@ -328,19 +330,25 @@ def recognize_pages(net, pages: Sequence[Tuple[np.ndarray, Sequence[Line]]], bat
     def finish(pend):
         idx, handle, lens = pend
         kind, h, e = handle
-        records = e.collect(h) if kind == 'device' else h
+        hyps = h if kind == 'nbest' else None
+        records = [hs[0][3] for hs in hyps] if hyps else e.collect(h) if kind == 'device' else h
         for n, (i, recs) in enumerate(zip(idx, records)):
             p, j, g = flat[i]
             chars = codec.decode(recs)
             W_in = int(lens[n])
             cuts = cut_quads(g, chars, W_in, int(lib.cocr_out_len(W_in, net.hparams_record.subsampling_factor)), pad)
             results[p][j] = {'id': g.id, 'text': ''.join(c[0] for c in chars), 'cuts': cuts}
+            if hyps:
+                results[p][j]['nbest'] = hyps[n]
 
     pending = None
     for width, idx in batches:
         strips, offs, hs, ws = eng.extract_lines(d_pages, [(flat[i][0], flat[i][2]) for i in idx], fill=fill)
         im, lens = eng.preprocess_device(strips, offs, hs, ws, height=height, pad=pad, width=width)
-        handle = net.predict_string_async(im.unsqueeze(1), torch.from_numpy(lens))
+        if nbest > 0:
+            handle = ('nbest', net.predict_nbest(im.unsqueeze(1), torch.from_numpy(lens), nbest), None)
+        else:
+            handle = net.predict_string_async(im.unsqueeze(1), torch.from_numpy(lens))
         if pending is not None:
             finish(pending)
         pending = (idx, handle, lens)

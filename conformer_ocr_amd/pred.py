@@ -309,6 +309,19 @@ class PytorchRecognitionModel(nn.Module):
             return [''.join(lut[np.minimum(lab, size - 1)].tolist()) for lab in eng.collect_labels(h)]
         return [''.join(x[0] for x in self.codec.decode(locs)) for locs in self._label_records(line, lens)]
 
+    def predict_nbest(self, line: torch.Tensor, seq_lens: torch.Tensor, nbest: int) -> List[List[Tuple[str, float, float, List[Tuple[int, int, int, float]]]]]:
+        """Forward pass + n-best decoding: per line the first `nbest` hypotheses of the beam of `ctc_decoder` (a
+        `BeamDecoder`, or an `LMDecoder` with its model and weights), each (text, logp, lm_logp, label records) -- text through the codec
+        as `predict_string`'s, logp the exact CTC log-probability of the label sequence (NaN beyond 255 labels), lm_logp the raw
+        n-gram sum (0 without a language model).  Entry 0 is the reading `predict_string` returns.  Any other decoder: ValueError."""
+        dec = self.ctc_decoder
+        if not isinstance(dec, (BeamDecoder, LMDecoder)):
+            raise ValueError('n-best output needs a beam: set ctc_decoder to a BeamDecoder or an LMDecoder (--beam / --lm)')
+        o, olens = self.forward(line, seq_lens)
+        kw = dict(lm=dec.lm, classes=dec.classes, alpha=dec.alpha, beta=dec.beta) if isinstance(dec, LMDecoder) else {}
+        hyps = self._engine.ctc_beam_nbest(o, olens.numpy(), dec.beam_size, min(int(nbest), dec.beam_size), **kw)
+        return [[(''.join(x[0] for x in self.codec.decode(recs)), logp, lmv, recs) for recs, logp, lmv in hs] for hs in hyps]
+
     def _codec_lut(self):
         """label -> character table of a 1:1, non-strict codec ('' for labels the codec does not know: skipped, as `decode` skips them;
         last entry: every label beyond the table); None for codecs with multi-label graphemes."""

@@ -2,14 +2,15 @@
 
     python -m conformer_ocr_amd.test -m MODEL [-m MODEL2 ...] [-f path|page|alto|xml] [-e LIST ...] [-B 32] [--pad 16] [-u NFD|NFC|NFKD|NFKC]
                                      [--no-normalize-whitespace] [--device cuda:0] [--edge 200] [--scorer device|host]
-                                     [--beam N] [--lm FILE [--lm-weight A] [--lm-bonus B] [--lm-classes K]] FILES...
+                                     [--beam N] [--lm FILE [--lm-weight A] [--lm-bonus B] [--lm-classes K]] [--nbest K] FILES...
 
 FILES (globs allowed) and the names listed in the -e manifests (one per line) are PAGE / ALTO documents or, with `-f path`, line images
 `foo.png` beside `foo.gt.txt`.  Every line with text and usable geometry is recognized (pages in bounded groups, so a test set larger
 than device memory runs) and compared with its ground truth: per model the report of cli/test.py:214-224 (characters, errors, character
 and word accuracy, insertions / deletions / substitutions, per-script counts, the most frequent confusions), then the average
 accuracies over the models.  The ground truth is not encoded, so the model's alphabet need not cover it.  The alignments behind the
-report run on the GPU (`--scorer host`: the Python functions, same output).
+report run on the GPU (`--scorer host`: the Python functions, same output).  With --nbest K (needs --beam or --lm) one more line per
+model: `oracle CER in the K-best: x (1-best: y)`, the error rate a perfect ranker would reach on the beam's K best readings.
 
 Not built: `-f binary` (Arrow datasets), `--reorder` / `--base-dir` (python-bidi is absent: text is compared in logical order),
 `--workers`, `--threads`."""
@@ -42,8 +43,9 @@ def parser() -> argparse.ArgumentParser:
     ap.add_argument('-d', '--device', default='cuda:0')
     ap.add_argument('--edge', type=int, default=200, help='width bucket edge: lines are padded to a multiple of it')
     ap.add_argument('--scorer', choices=('device', 'host'), default='device', help='where the alignments of the report are computed')
-    from .ocr import add_decoder_arguments
+    from .ocr import add_decoder_arguments, add_nbest_argument
     add_decoder_arguments(ap)
+    add_nbest_argument(ap)
     return ap
 
 
@@ -69,13 +71,15 @@ def gather_files(args) -> List[str]:
     return expand_globs(args.test_set) + expand_manifests(args.evaluation_files)
 
 
-def recognize_ground_truth(net, gt: Sequence, batch_size: int = 32, edge: int = 200, pad: int = 16, device: str = 'cuda:0') -> List[str]:
+def recognize_ground_truth(net, gt: Sequence, batch_size: int = 32, edge: int = 200, pad: int = 16, device: str = 'cuda:0', nbest: int = 0):
     """The model's string for every `dataset.GTLine` of `gt`, in order: page lines through `page.recognize_pages` in groups of
-    PAGE_GROUP pages, line images through `evaluate.recognize_crops` in groups of CROP_GROUP."""
-    from .evaluate import recognize_crops
+    PAGE_GROUP pages, line images through `evaluate.recognize_crops` in groups of CROP_GROUP.  nbest > 0: (the strings, per line the
+    texts of its `nbest` best readings), through `net.predict_nbest` over the same batches."""
+    from .evaluate import make_batches, recognize_crops
     from .ocr import load_image
     from .page import Line, recognize_pages
     out: List[Optional[str]] = [None] * len(gt)
+    alts: List[List[str]] = [[] for _ in gt]
     by_page: Dict[str, List[int]] = {}
     crops: List[int] = []
     for i, ln in enumerate(gt):
@@ -87,15 +91,27 @@ def recognize_ground_truth(net, gt: Sequence, batch_size: int = 32, edge: int = 
     for k in range(0, len(images), PAGE_GROUP):
         group = images[k:k + PAGE_GROUP]
         pages = [(load_image(image), [Line(gt[i].id, gt[i].geom.points, gt[i].geom.verts) for i in by_page[image]]) for image in group]
-        for image, recs in zip(group, recognize_pages(net, pages, batch_size=batch_size, edge=edge, pad=pad, device=device)):
+        for image, recs in zip(group, recognize_pages(net, pages, batch_size=batch_size, edge=edge, pad=pad, device=device, nbest=nbest)):
             for i, rec in zip(by_page[image], recs):
                 out[i] = rec['text']
+                alts[i] = [h[0] for h in rec.get('nbest', ())]
     for k in range(0, len(crops), CROP_GROUP):
         group = crops[k:k + CROP_GROUP]
-        strings = recognize_crops(net, [load_image(gt[i].image) for i in group], batch_size=batch_size, edge=edge, pad=pad, device=device)
-        for n, i in enumerate(group):
-            out[i] = strings[n]
-    return out
+        images = [load_image(gt[i].image) for i in group]
+        if not nbest:
+            strings = recognize_crops(net, images, batch_size=batch_size, edge=edge, pad=pad, device=device)
+            for n, i in enumerate(group):
+                out[i] = strings[n]
+            continue
+        from . import _lib
+        lib = _lib.load()
+        widths = [int(lib.cocr_preproc_width(int(c.shape[0]), int(c.shape[1]), int(net.height), int(pad))) for c in images]
+        for _, idx in make_batches(widths, batch_size, edge):            # `recognize_crops`' batches
+            im, lens = net.transform_lines([images[n] for n in idx], pad=pad, bucket_edge=edge, device=device)
+            for n, hyps in zip(idx, net.predict_nbest(im, lens, nbest)):
+                out[group[n]] = hyps[0][0]
+                alts[group[n]] = [h[0] for h in hyps]
+    return (out, alts) if nbest else out
 
 
 def main(argv=None) -> int:
@@ -120,21 +136,31 @@ def main(argv=None) -> int:
         return usage('no usable line in the evaluation data')
     import numpy as np
     from .evaluate import score_strings
-    from .ocr import load_model, set_decoder
+    from .ocr import check_nbest, load_model, set_decoder
     truths = [ln.text for ln in gt]
     cer_list, wer_list = [], []
     for model in args.model:
         net = load_model(model, device=args.device)
         try:
+            check_nbest(args)
             set_decoder(net, args)
         except ValueError as e:
             return usage(f'{model}: {e}')
         print(f'Evaluating {model}', flush=True)
-        preds = recognize_ground_truth(net, gt, args.batch_size, args.edge, args.pad, args.device)
+        preds = recognize_ground_truth(net, gt, args.batch_size, args.edge, args.pad, args.device, args.nbest)
+        alts = None
+        if args.nbest:
+            preds, alts = preds
         res = score_strings(net, preds, truths, report=True, model_name=model, scorer=args.scorer)
         cer_list.append(1.0 - res['cer'])
         wer_list.append(1.0 - res['wer'])
         print(res['report'], flush=True)
+        if alts is not None:
+            from .nbest import oracle_errors
+            chars = max(sum(len(t) for t in truths), 1)
+            best = sum(oracle_errors(alts, truths, getattr(net, '_engine', None), args.scorer))
+            first = sum(oracle_errors([a[:1] for a in alts], truths, getattr(net, '_engine', None), args.scorer))
+            print(f'oracle CER in the {args.nbest}-best: {best / chars:.4f} (1-best: {first / chars:.4f})', flush=True)
     print('Average character accuracy: {:0.2f}%, (stddev: {:0.2f})'.format(np.mean(cer_list) * 100, np.std(cer_list) * 100))
     print('Average word accuracy: {:0.2f}%, (stddev: {:0.2f})'.format(np.mean(wer_list) * 100, np.std(wer_list) * 100))
     return 0

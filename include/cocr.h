@@ -167,6 +167,23 @@ int cocr_ctc_beam_lm(cocr_model *m, cocr_lm *lm, const float *logits, int N, int
                      int32_t *labels, int32_t *starts, int32_t *ends, float *conf, int32_t *counts, int max_per_line,
                      int beam, int classes, float alpha, float beta, float *score, void *stream);
 
+/* N-best output (the definition is conformer_ocr_amd/nbest.py nbest_host): the search of cocr_ctc_beam (lm NULL;
+ * classes, alpha, beta ignored) or of cocr_ctc_beam_lm, returning the first min(nbest, live) prefixes of the final beam in beam order,
+ * live = the prefixes alive after the last frame (a line of length 0: the empty prefix alone).  labels / starts / ends / conf:
+ * (N, nbest, max_per_line), records as the 1-best decoders write them; counts (N, nbest): the full label count of each hypothesis
+ * (rows truncated at max_per_line); nhyp (N): min(nbest, live); scores (N, nbest, 2) float32:
+ *     [0] the exact CTC log-probability of the label sequence over ALL alignments (the forward recursion of the criterion on
+ *         log_softmax(logits), float32) -- not the beam's pruned logaddexp(p_b, p_nb); NaN for a hypothesis of more than 255 labels
+ *         (COCR_LATTICE_MAX_LABELS, the criterion's limit); 0 for the empty hypothesis of a line of length 0;
+ *     [1] the float32 sum, in label order, of lm(context, label): raw, without alpha or beta, so that a caller can re-weight; 0 without lm.
+ * Slots j >= nhyp[n] have counts 0 and both scores -inf.  Hypothesis 0 of every line is what cocr_ctc_beam (cocr_ctc_beam_lm) writes
+ * for it, bit for bit.  All outputs DEVICE or pinned host, like the other decoders'.  Errors and limits: those of cocr_ctc_beam /
+ * cocr_ctc_beam_lm, 1 <= nbest <= beam (COCR_EINVAL), out_lens within [0, T] (COCR_EINVAL), T <= 8000 (COCR_EUNSUPPORTED).
+ * Deterministic (no atomics).  Stream-ordered, does not synchronise (workspace growth does). */
+int cocr_ctc_beam_nbest(cocr_model *m, cocr_lm *lm /* may be NULL */, const float *logits, int N, int T, int ncls, const int32_t *out_lens,
+                        int beam, int nbest, int classes, float alpha, float beta, int32_t *labels, int32_t *starts, int32_t *ends,
+                        float *conf, int32_t *counts, int32_t *nhyp, float *scores, int max_per_line, void *stream);
+
 /* The loss of the reference's training / validation step, RecognitionModel._step (model.py:119,136-142):
  *     nn.CTCLoss(reduction='sum', zero_infinity=True)(log_softmax(probits, -1).transpose(0, 1), target, encoder_lens, label_lens)
  * and its gradient with respect to `probits` (what autograd hands to the decoder's backward).  probits DEVICE float32 (N,T,ncls), the
