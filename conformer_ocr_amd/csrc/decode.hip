@@ -1,5 +1,5 @@
 // What follows the forward behind the C ABI (units of the host layer: model.hip.h): the CTC decoders (greedy, beam, beam with an
-// n-gram model, n-best output of both), the n-gram model itself, the CTC criterion, the distillation term, forced alignment and keyword spotting.
+// n-gram model, n-best output of both), the n-gram model itself, the CTC criterion, the distillation term, forced alignment, keyword spotting and the search index's pack / unpack.
 #include "model.hip.h"
 #include "ctc.hip.h"
 #include "ctc_lm.hip.h"
@@ -8,6 +8,7 @@
 #include "distill.hip.h"
 #include "ctc_align.hip.h"
 #include "ctc_spot.hip.h"
+#include "ctc_index.hip.h"
 
 // ------------------------------------------------------------------------------------ CTC
 // The per-line lengths reach the decode kernels through a PINNED host ring: an async copy from pageable memory goes through the
@@ -440,5 +441,38 @@ extern "C" int cocr_ctc_spot(cocr_model *m, const float *logits, int N, int T, i
     HIP_TRY(launch_ctc_spot(s, sj_for_states(2 * max_l - 1), tab.in_lds, tab.lds, logits, N, T, ncls, d, d + N, d + N + Q, d + N + 2 * Q, Q, hits, min_score, starts, ends,
                             score, counts, tab.ws));
     LAUNCH_CHECK();
+    return COCR_OK;
+}
+
+// ------------------------------------------------------------------------------------ search index (ctc_index.hip.h)
+extern "C" int cocr_posterior_pack(cocr_model *m, const float *logits, int N, int T, int ncls, const int32_t *out_lens, int keep, float inv_step,
+                                   uint16_t *classes, uint8_t *codes, void *stream) {
+    if (!m || !logits || !out_lens || !classes || !codes) return fail(COCR_EINVAL, "null argument");
+    if (N < 1 || T < 1 || ncls < 1) return fail(COCR_EINVAL, "empty problem");
+    if (ncls > 65535) return fail(COCR_EUNSUPPORTED, "more than 65535 classes");
+    if (N > 65535) return fail(COCR_EUNSUPPORTED, "more than 65535 lines in one call");
+    if ((size_t)N * T > (size_t)INT_MAX) return fail(COCR_EUNSUPPORTED, "more than 2^31 - 1 frames in one call");
+    if (keep < 1 || keep > std::min(ncls, COCR_INDEX_MAX_KEEP)) return fail(COCR_EINVAL, "keep must be in 1..%d", std::min(ncls, COCR_INDEX_MAX_KEEP));
+    if (!std::isfinite(inv_step) || !(inv_step > 0.f)) return fail(COCR_EINVAL, "inv_step must be finite and positive, not %g", (double)inv_step);
+    int rc = check_out_lens(out_lens, N, T);
+    if (rc) return rc;
+    HIP_TRY(hipSetDevice(m->device));
+    hipStream_t s = (hipStream_t)stream;
+    const int32_t *d_lens;
+    if ((rc = upload_lens(m, out_lens, N, s, d_lens))) return rc;
+    HIP_TRY(launch_posterior_pack(s, logits, N, T, ncls, d_lens, keep, inv_step, classes, codes));
+    return COCR_OK;
+}
+
+extern "C" int cocr_posterior_unpack(cocr_model *m, const uint16_t *classes, const uint8_t *codes, int N, int T, int keep, int ncls, float step,
+                                     float *logits_out, void *stream) {
+    if (!m || !classes || !codes || !logits_out) return fail(COCR_EINVAL, "null argument");
+    if (N < 1 || T < 1 || ncls < 1) return fail(COCR_EINVAL, "empty problem");
+    if (ncls > 65535) return fail(COCR_EUNSUPPORTED, "more than 65535 classes");
+    if ((size_t)N * T > (size_t)INT_MAX) return fail(COCR_EUNSUPPORTED, "more than 2^31 - 1 frames in one call");
+    if (keep < 1 || keep > std::min(ncls, COCR_INDEX_MAX_KEEP)) return fail(COCR_EINVAL, "keep must be in 1..%d", std::min(ncls, COCR_INDEX_MAX_KEEP));
+    if (!std::isfinite(step) || !(step > 0.f)) return fail(COCR_EINVAL, "step must be finite and positive, not %g", (double)step);
+    HIP_TRY(hipSetDevice(m->device));
+    HIP_TRY(launch_posterior_unpack((hipStream_t)stream, classes, codes, N, T, keep, ncls, step, logits_out));
     return COCR_OK;
 }

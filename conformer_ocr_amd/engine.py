@@ -493,6 +493,45 @@ class HipRecognizer:
     def ctc_spot(self, logits: torch.Tensor, out_lens, queries, hits: int = 1, min_score: float = -np.inf):
         return self.collect_spot(self.ctc_spot_async(logits, out_lens, queries, hits, min_score))
 
+    # ---- search index (include/cocr.h: cocr_posterior_pack / cocr_posterior_unpack) ----------
+    def posterior_pack(self, logits: torch.Tensor, out_lens, keep: int = 8, step: float = 0.125) -> Tuple[torch.Tensor, torch.Tensor]:
+        """Enqueues `index.pack_host` of every line on the current stream: (classes uint16, codes uint8), device tensors (N,T,keep);
+        frames at or beyond out_lens[n] hold class 0 / code 255.  logits (N,T,ncls) float32 on this device.  Does not touch the
+        forward's per-frame argmax."""
+        from .index import inv_step
+        if logits.device != self.device or logits.dtype != torch.float32 or logits.dim() != 3:
+            raise RuntimeError('logits must be a float32 (N,T,num_classes) tensor on the model device')
+        cont = logits.contiguous()
+        N, T, ncls = cont.shape
+        lens = np.ascontiguousarray(np.asarray(out_lens, dtype=np.int32).reshape(-1))
+        if lens.shape[0] != N:
+            raise ValueError('out_lens needs one entry per line')
+        inv = inv_step(step)
+        K = max(int(keep), 0)
+        classes = torch.empty((N, T, K), dtype=torch.uint16, device=self.device)
+        codes = torch.empty((N, T, K), dtype=torch.uint8, device=self.device)
+        with torch.cuda.device(self.device):
+            _lib.check(self.lib.cocr_posterior_pack(self._h, C.c_void_p(cont.data_ptr()), N, T, ncls, lens.ctypes.data_as(C.POINTER(C.c_int32)),
+                                                    int(keep), C.c_float(inv), C.c_void_p(classes.data_ptr()), C.c_void_p(codes.data_ptr()),
+                                                    _stream_ptr(self.device)))
+        return classes, codes
+
+    def posterior_unpack(self, classes: torch.Tensor, codes: torch.Tensor, ncls: int, step: float = 0.125) -> torch.Tensor:
+        """Enqueues `index.expand_host` on the current stream: packed (N,T,keep) device tensors -> the (N,T,ncls) float32 table
+        `ctc_spot` takes.  An entry whose class is >= ncls is ignored."""
+        if classes.device != self.device or codes.device != self.device or classes.dtype != torch.uint16 or codes.dtype != torch.uint8:
+            raise RuntimeError('classes (uint16) and codes (uint8) must be tensors on the model device')
+        if classes.dim() != 3 or classes.shape != codes.shape:
+            raise ValueError('classes and codes must be (N,T,keep) tensors of one shape')
+        classes, codes = classes.contiguous(), codes.contiguous()
+        N, T, K = classes.shape
+        step32 = float(np.float32(step))
+        out = torch.empty((N, T, max(int(ncls), 0)), dtype=torch.float32, device=self.device)
+        with torch.cuda.device(self.device):
+            _lib.check(self.lib.cocr_posterior_unpack(self._h, C.c_void_p(classes.data_ptr()), C.c_void_p(codes.data_ptr()), N, T, K, int(ncls),
+                                                      C.c_float(step32), C.c_void_p(out.data_ptr()), _stream_ptr(self.device)))
+        return out
+
     # ---- output-layer training step (include/cocr.h: cocr_decoder_backward / cocr_decoder_adamw) ----------
     def decoder_backward(self, grad_probits: torch.Tensor, with_input_grad: bool = False):
         """Gradients of the decoder `nn.Linear` for the LAST forward on this engine: (grad_weight (ncls, D), grad_bias (ncls),

@@ -518,6 +518,31 @@ class PytorchRecognitionModel(nn.Module):
                 out[n][i] = spots
         return {'hits': out, 'frames': [int(l) for l in olens], 'skipped': skipped}
 
+    # ------------------------------------------------------------------ search index (conformer_ocr_amd/index.py)
+    def pack_posteriors_async(self, line: torch.Tensor, lens: torch.Tensor, keep: int = 8, step: float = 0.125):
+        """Forward + `cocr_posterior_pack` + the read-back into pinned host memory enqueued on the current stream; returns a handle
+        for `collect_packed`."""
+        o, olens = self.forward(line, lens)
+        classes, codes = self._engine.posterior_pack(o, olens.numpy(), keep, step)
+        host = (torch.empty(classes.shape, dtype=classes.dtype).pin_memory(), torch.empty(codes.shape, dtype=codes.dtype).pin_memory())
+        host[0].copy_(classes, non_blocking=True)
+        host[1].copy_(codes, non_blocking=True)
+        ev = torch.cuda.Event()
+        ev.record(torch.cuda.current_stream(o.device))
+        return host, ev, olens.numpy(), (o, classes, codes)
+
+    def collect_packed(self, handle):
+        """Waits for a `pack_posteriors_async` handle: per line (classes (out_len, keep) uint16, codes (out_len, keep) uint8)."""
+        host, ev, olens, _ = handle
+        ev.synchronize()
+        cls, cod = host[0].numpy(), host[1].numpy()
+        return [(cls[n, :int(l)].copy(), cod[n, :int(l)].copy()) for n, l in enumerate(olens)]
+
+    def pack_posteriors(self, line: torch.Tensor, lens: torch.Tensor, keep: int = 8, step: float = 0.125):
+        """The pruned, quantised posteriors of a (N, C, H, W) batch (`index.pack_host` is the definition): forward pass, then per
+        line (classes, codes) cut to the line's output length.  keep and step are placeholders, not tuned on real material."""
+        return self.collect_packed(self.pack_posteriors_async(line, lens, keep, step))
+
     @classmethod
     def load_safetensors(cls, path, **kwargs):
         """

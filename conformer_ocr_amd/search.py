@@ -12,7 +12,7 @@ One summary line per file goes to stderr.  No confidence threshold is set by def
 no such operation: the definition is this build's own.
 
 Not built: whole-word matching (a query also matches inside a longer word), regular expressions or lexicon tries, case folding, bidi
-reordering (queries are matched in logical order), queries by example, an on-disk index of posteriors."""
+reordering (queries are matched in logical order), queries by example.  An on-disk index of posteriors: `conformer_ocr_amd.index`."""
 from __future__ import annotations
 
 import argparse
@@ -178,7 +178,7 @@ def search_pages(net, pages, queries: Sequence[str], hits: int = 1, min_conf: fl
 def parser() -> argparse.ArgumentParser:
     ap = argparse.ArgumentParser(prog='python -m conformer_ocr_amd.search', description='Finds query strings on the lines of pages.',
                                  epilog='Not built: whole-word matching, regular expressions or lexicon tries, case folding, bidi '
-                                        'reordering, queries by example, an on-disk index of posteriors.')
+                                        'reordering, queries by example.  Many queries of the same pages: python -m conformer_ocr_amd.index.')
     ap.add_argument('-m', '--model', default=None, help='safetensors archive or checkpoint')
     ap.add_argument('-q', '--query', action='append', default=[], metavar='WORD', help='string to search for (repeatable)')
     ap.add_argument('-Q', '--query-file', default=None, metavar='FILE', help='file with one query per line')

@@ -240,6 +240,28 @@ int cocr_ctc_spot(cocr_model *m, const float *logits, int N, int T, int ncls, co
                   const int32_t *query_lens, int Q, int hits, float min_score, int32_t *starts, int32_t *ends, float *score,
                   int32_t *counts, void *stream);
 
+/* The search index (the definition is conformer_ocr_amd/index.py pack_host / expand_host): pruned, quantised
+ * frame posteriors that cocr_ctc_spot can be run on later, without the model.
+ * cocr_posterior_pack: per frame the `keep` classes of the largest logit, ties to the lower class, stored in that order (entry 0 is the
+ * frame's argmax), each with code = min(255, ceil(float32(float32(max - logit) * inv_step))): one float32 subtraction, one float32
+ * multiply (never fused), ceil -- so code == 0 exactly where the logit equals the frame's maximum; a difference of +inf codes as 255.
+ * Logits are finite, or -inf beside a finite row maximum; NaN is outside the contract.
+ * logits DEVICE float32 (N,T,ncls); out_lens (N) HOST, checked before any launch: COCR_EINVAL for out_lens[n] outside [0, T], keep
+ * outside 1..min(ncls, 32) or an inv_step that is not finite and positive; COCR_EUNSUPPORTED for ncls > 65535, N > 65535 or more than
+ * 2^31 - 1 frames.  classes uint16 and codes uint8 (N,T,keep): DEVICE or device-visible pinned host memory; the entries of frames at
+ * or beyond out_lens[n] are written as class 0 / code 255, so the buffers are fully defined.  Does not touch the greedy decoder's
+ * argmax scratch.  Deterministic (no atomics).  Stream-ordered, does not synchronise (ring growth does).
+ * cocr_posterior_unpack: classes / codes DEVICE (N,T,keep) -> logits_out DEVICE float32 (N,T,ncls), the table cocr_ctc_spot takes:
+ * -(float32(code) * step) for the stored classes (one float32 multiply), -(255 * step) for every other class; each row's maximum is
+ * 0 when entry 0 has code 0, as cocr_posterior_pack writes it.  A frame of all-255 codes comes out as a row of floors.  The stored
+ * classes cannot be checked on the host without a copy: an entry whose class is >= ncls is IGNORED by the kernel (no store leaves the
+ * row); of two entries of one class the later one wins.  COCR_EINVAL for keep outside 1..min(ncls, 32) or a step that is not finite
+ * and positive; COCR_EUNSUPPORTED for ncls > 65535 or more than 2^31 - 1 frames.  Deterministic.  Stream-ordered, does not synchronise. */
+int cocr_posterior_pack(cocr_model *m, const float *logits, int N, int T, int ncls, const int32_t *out_lens, int keep, float inv_step,
+                        uint16_t *classes, uint8_t *codes, void *stream);
+int cocr_posterior_unpack(cocr_model *m, const uint16_t *classes, const uint8_t *codes, int N, int T, int keep, int ncls, float step,
+                          float *logits_out, void *stream);
+
 /* Training step of the output layer: the part of the reference's `training_step` (model.py:147-152, autograd through
  * `nn['decoder'] = nn.Linear(encoder_dim, num_classes)`, model.py:115) between the encoder output and the criterion, and the
  * reference's default optimizer (`torch.optim.AdamW`, model.py:47,283-284).  The encoder's backward is not in this library yet;
