@@ -1,5 +1,5 @@
 // What follows the forward behind the C ABI (units of the host layer: model.hip.h): the CTC decoders (greedy, beam, beam with an
-// n-gram model, n-best output of both), the n-gram model itself, the CTC criterion, the distillation term, forced alignment, keyword spotting and the search index's pack / unpack.
+// n-gram model, n-best output of both), the n-gram model itself, the CTC criterion, the distillation term, forced alignment, keyword and pattern spotting and the search index's pack / unpack.
 #include "model.hip.h"
 #include "ctc.hip.h"
 #include "ctc_lm.hip.h"
@@ -8,6 +8,7 @@
 #include "distill.hip.h"
 #include "ctc_align.hip.h"
 #include "ctc_spot.hip.h"
+#include "ctc_spot_graph.hip.h"
 #include "ctc_index.hip.h"
 
 // ------------------------------------------------------------------------------------ CTC
@@ -440,6 +441,78 @@ extern "C" int cocr_ctc_spot(cocr_model *m, const float *logits, int N, int T, i
     if ((rc = place_lattice_table(row, 9 * row, m->dec.spot_ws, (size_t)N * Q * ctcs_pair_words(T), tab))) return rc;
     HIP_TRY(launch_ctc_spot(s, sj_for_states(2 * max_l - 1), tab.in_lds, tab.lds, logits, N, T, ncls, d, d + N, d + N + Q, d + N + 2 * Q, Q, hits, min_score, starts, ends,
                             score, counts, tab.ws));
+    LAUNCH_CHECK();
+    return COCR_OK;
+}
+
+// ------------------------------------------------------------------------------------ pattern spotting (ctc_spot_graph.hip.h)
+extern "C" int cocr_ctc_spot_pattern(cocr_model *m, const float *logits, int N, int T, int ncls, const int32_t *out_lens, const int32_t *state_counts,
+                                     const int32_t *classes, const int32_t *flags, const int32_t *pred_off, const int32_t *preds, int Q, int hits,
+                                     float min_score, int32_t *starts, int32_t *ends, float *score, int32_t *finals, int32_t *counts, void *stream) {
+    if (!m || !logits || !out_lens || !state_counts || !classes || !flags || !pred_off || !starts || !ends || !score || !finals || !counts)
+        return fail(COCR_EINVAL, "null argument");
+    if (N < 1 || T < 1 || ncls < 2) return fail(COCR_EINVAL, "empty problem");
+    if (Q < 1) return fail(COCR_EINVAL, "no pattern");
+    if (hits < 1 || hits > COCR_GRAPH_MAX_HITS) return fail(COCR_EINVAL, "hits must be in 1..%d", COCR_GRAPH_MAX_HITS);
+    if (std::isnan(min_score)) return fail(COCR_EINVAL, "min_score is NaN");
+    if (T > 8000) return fail(COCR_EUNSUPPORTED, "more than 8000 frames per line");
+    if (N > 65535) return fail(COCR_EUNSUPPORTED, "more than 65535 lines in one call");
+    int rc = check_out_lens(out_lens, N, T);
+    if (rc) return rc;
+    size_t states = 0, edges = 0;
+    int max_p = 0;
+    for (int q = 0; q < Q; ++q) {
+        const int P = state_counts[q];
+        if (P < 1 || P > COCR_GRAPH_MAX_STATES) return fail(COCR_EINVAL, "pattern %d has %d label states; a pattern holds 1..%d", q, P, COCR_GRAPH_MAX_STATES);
+        const int32_t *off = pred_off + states + q, *fl = flags + states;
+        if (off[0] != 0) return fail(COCR_EINVAL, "pattern %d: its predecessor offsets do not begin at 0", q);
+        for (int p = 0; p < P; ++p)
+            if (off[p + 1] < off[p]) return fail(COCR_EINVAL, "pattern %d: predecessor offsets descend at state %d", q, p);
+        const int E = off[P];
+        if (E > COCR_GRAPH_MAX_EDGES) return fail(COCR_EINVAL, "pattern %d has %d edges; a pattern holds at most %d", q, E, COCR_GRAPH_MAX_EDGES);
+        if (E && !preds) return fail(COCR_EINVAL, "null argument");
+        bool any_first = false, any_last = false;
+        for (int p = 0; p < P; ++p) {
+            if (fl[p] & ~3) return fail(COCR_EINVAL, "pattern %d: flags %d of state %d (1 = first, 2 = last)", q, fl[p], p);
+            any_first |= (fl[p] & 1) != 0; any_last |= (fl[p] & 2) != 0;
+            for (int e = off[p]; e < off[p + 1]; ++e) {
+                const int32_t pr = preds[edges + e];
+                if (pr < 0 || pr >= P) return fail(COCR_EINVAL, "pattern %d: predecessor %d of state %d outside [0, %d)", q, pr, p, P);
+                if (e > off[p] && pr <= preds[edges + e - 1]) return fail(COCR_EINVAL, "pattern %d: the predecessors of state %d do not ascend strictly", q, p);
+            }
+        }
+        if (!any_first || !any_last) return fail(COCR_EINVAL, "pattern %d has no %s state", q, any_first ? "last" : "first");
+        max_p = std::max(max_p, P);
+        states += (size_t)P;
+        edges += (size_t)E;
+    }
+    if ((rc = check_labels("pattern class", classes, states, ncls))) return rc;
+    HIP_TRY(hipSetDevice(m->device));
+    hipStream_t s = (hipStream_t)stream;
+    const size_t ints = (size_t)N + 3 * (size_t)Q + 2 * states + (states + Q) + edges;
+    int32_t *h, *d;
+    HIP_TRY(m->dec.pattern_ring.stage(ints * 4, h, d));
+    memcpy(h, out_lens, (size_t)N * 4);
+    int32_t so = 0, eo = 0;
+    for (int q = 0; q < Q; ++q) {
+        h[N + q] = state_counts[q]; h[N + Q + q] = so; h[N + 2 * Q + q] = eo;
+        eo += pred_off[so + q + state_counts[q]];
+        so += state_counts[q];
+    }
+    int32_t *hc = h + N + 3 * Q;
+    memcpy(hc, classes, states * 4);
+    memcpy(hc + states, flags, states * 4);
+    memcpy(hc + 2 * states, pred_off, (states + Q) * 4);
+    if (edges) memcpy(hc + 3 * states + Q, preds, edges * 4);
+    HIP_TRY(m->dec.pattern_ring.commit(ints * 4, s));
+    // the candidate tables (e_t, sigma_t, final_t) of the workgroup's four pairs: beside mx and the blank's row, or one region per pair of
+    // the workspace.  The kernel's static graph and exchange arrays count towards what fits.
+    const size_t row = lattice_row_bytes(T);
+    LatticeTable tab;
+    if ((rc = place_lattice_table(2 * row, COCR_GRAPH_STATIC_LDS + 14 * row, m->dec.pattern_ws, (size_t)N * Q * ctcg_pair_words(T), tab))) return rc;
+    const int32_t *dc = d + N + 3 * Q;
+    HIP_TRY(launch_ctc_spot_graph(s, sj_for_states(max_p), tab.in_lds, tab.in_lds ? 14 * row : 2 * row, logits, N, T, ncls, d, d + N, d + N + Q, d + N + 2 * Q, dc, dc + states,
+                                  dc + 2 * states, dc + 3 * states + Q, Q, hits, min_score, starts, ends, score, finals, counts, tab.ws));
     LAUNCH_CHECK();
     return COCR_OK;
 }

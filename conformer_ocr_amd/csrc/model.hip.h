@@ -180,6 +180,8 @@ struct COCR_INTERNAL DecodeScratch {
     DevBuf<unsigned> align_ws;              // back-pointer tables of the lines too long for the LDS
     UploadRing spot_ring;                   // cocr_ctc_spot: [lens | query lens | query offsets | queries]
     DevBuf<unsigned> spot_ws;               // cocr_ctc_spot: per (line, query) the candidate scores and starts of lines too long for the LDS
+    UploadRing pattern_ring;                // cocr_ctc_spot_pattern: [lens | state counts | state offsets | edge offsets | classes | flags | predecessor offsets | predecessors]
+    DevBuf<unsigned> pattern_ws;            // cocr_ctc_spot_pattern: per (line, pattern) the candidate scores, starts and final states of lines too long for the LDS
 };
 
 // Written by lines.hip.

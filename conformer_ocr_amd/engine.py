@@ -493,6 +493,64 @@ class HipRecognizer:
     def ctc_spot(self, logits: torch.Tensor, out_lens, queries, hits: int = 1, min_score: float = -np.inf):
         return self.collect_spot(self.ctc_spot_async(logits, out_lens, queries, hits, min_score))
 
+    # ---- pattern spotting (include/cocr.h: cocr_ctc_spot_pattern) ----------
+    def ctc_spot_pattern_async(self, logits: torch.Tensor, out_lens, graphs, hits: int = 1, min_score: float = -np.inf):
+        """Enqueues the search for every pattern in every line on the current stream, its outputs in pinned host memory; returns a
+        handle for `collect_spot_pattern`.  logits (N,T,ncls) float32 on this device; out_lens (N) valid frames; graphs: Q
+        `pattern.PatternGraph`s (1..256 label states, at most 4096 edges each; a chain is run as a graph like any other); hits: 1..8
+        per (line, pattern); min_score: the selection stops below it.  Does not touch the forward's per-frame argmax."""
+        if logits.device != self.device or logits.dtype != torch.float32 or logits.dim() != 3:
+            raise RuntimeError('logits must be a float32 (N,T,num_classes) tensor on the model device')
+        cont = logits.contiguous()
+        N, T, ncls = cont.shape
+        lens = np.ascontiguousarray(np.asarray(out_lens, dtype=np.int32).reshape(-1))
+        if lens.shape[0] != N:
+            raise ValueError('out_lens needs one entry per line')
+        tabs = [g.tables() for g in graphs]
+        Q, K = len(tabs), int(hits)
+        empty = [np.zeros(0, dtype=np.int32)]
+        counts_in = np.ascontiguousarray(np.asarray([t[0].shape[0] for t in tabs], dtype=np.int32))
+        cls, flags, off, preds = (np.ascontiguousarray(np.concatenate([t[i] for t in tabs] + empty), dtype=np.int32) for i in range(4))
+        i32 = C.POINTER(C.c_int32)
+        with torch.cuda.device(self.device):
+            cap = max(N * Q, 1) * min(max(K, 1), 8)
+            key = ('spot_pattern', cap, max(N * Q, 1))
+            pool = self._pinned.setdefault(key, [])
+            host = pool.pop() if pool else (torch.empty((3, cap), dtype=torch.int32).pin_memory(),
+                                            torch.empty((cap,), dtype=torch.float32).pin_memory(),
+                                            torch.empty((key[2],), dtype=torch.int32).pin_memory())
+            ints, score, counts = host
+            try:
+                _lib.check(self.lib.cocr_ctc_spot_pattern(self._h, C.c_void_p(cont.data_ptr()), N, T, ncls, lens.ctypes.data_as(i32),
+                                                          counts_in.ctypes.data_as(i32), cls.ctypes.data_as(i32), flags.ctypes.data_as(i32),
+                                                          off.ctypes.data_as(i32), preds.ctypes.data_as(i32), Q, K, C.c_float(min_score),
+                                                          C.c_void_p(ints[0].data_ptr()), C.c_void_p(ints[1].data_ptr()), C.c_void_p(score.data_ptr()),
+                                                          C.c_void_p(ints[2].data_ptr()), C.c_void_p(counts.data_ptr()), _stream_ptr(self.device)))
+            except Exception:
+                pool.append(host)                                   # nothing was launched: the buffers go back
+                raise
+            ev = torch.cuda.Event()
+            ev.record(torch.cuda.current_stream(self.device))
+        return (key, host, ev, (cont, N, Q, K))
+
+    def collect_spot_pattern(self, handle, raw: bool = False):
+        """Waits for a `ctc_spot_pattern_async` handle; per line, per pattern [(start, end, score, final state)], best first.  `raw`:
+        the output arrays themselves, copies of (starts, ends, scores, finals (N,Q,hits), counts (N,Q))."""
+        key, host, ev, (_, N, Q, K) = handle
+        ev.synchronize()
+        ints = host[0].numpy()[:, :N * Q * K].reshape(3, N, Q, K).copy()
+        score = host[1].numpy()[:N * Q * K].reshape(N, Q, K).copy()
+        counts = host[2].numpy()[:N * Q].reshape(N, Q).copy()
+        self._pinned[key].append(host)
+        if raw:
+            return ints[0], ints[1], score, ints[2], counts
+        st, en, fi = ints.tolist()
+        sc, cnt = score.tolist(), counts.tolist()
+        return [[list(zip(st[n][q][:cnt[n][q]], en[n][q][:cnt[n][q]], sc[n][q][:cnt[n][q]], fi[n][q][:cnt[n][q]])) for q in range(Q)] for n in range(N)]
+
+    def ctc_spot_pattern(self, logits: torch.Tensor, out_lens, graphs, hits: int = 1, min_score: float = -np.inf):
+        return self.collect_spot_pattern(self.ctc_spot_pattern_async(logits, out_lens, graphs, hits, min_score))
+
     # ---- search index (include/cocr.h: cocr_posterior_pack / cocr_posterior_unpack; DESIGN.md section 7l) ----------
     def posterior_pack(self, logits: torch.Tensor, out_lens, keep: int = 8, step: float = 0.125) -> Tuple[torch.Tensor, torch.Tensor]:
         """Enqueues `index.pack_host` of every line on the current stream: (classes uint16, codes uint8), device tensors (N,T,keep);

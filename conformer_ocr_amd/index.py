@@ -2,20 +2,22 @@
 
     python -m conformer_ocr_amd.index build  -m MODEL -i IN.xml [IN.xml ...] -o CORPUS.cidx [--keep 8] [--step 0.125] [-f page|alto|xml]
                                              [--device cuda:0] [--batch-size 32] [--pad 16] [--edge 200]
-    python -m conformer_ocr_amd.index search --index CORPUS.cidx -q WORD [-q WORD ...] [-Q FILE] [--hits K] [--min-conf X]
-                                             [-u NFD|NFC|NFKD|NFKC] [--no-normalize-whitespace] [--device cuda:0] [--batch-size 256] OUT.json
+    python -m conformer_ocr_amd.index search --index CORPUS.cidx [-q WORD ...] [-Q FILE] [-e REGEX ...] [-E FILE] [--ignore-case] [--hits K]
+                                             [--min-conf X] [-u NFD|NFC|NFKD|NFKC] [--no-normalize-whitespace] [--device cuda:0]
+                                             [--batch-size 256] OUT.json
     python -m conformer_ocr_amd.index info   --index CORPUS.cidx
 
 `build` runs extraction, pre-processing and the forward of `search` once and keeps, per frame, the `keep` classes of the largest logit
 with r_t(c) = logits[t, c] - max_c' logits[t, c'] quantised to steps of `step` (`pack_host` is the definition, `cocr_posterior_pack`
 the device form).  `search` needs no model and no images: the file's lines are expanded on the GPU (`cocr_posterior_unpack`) and
-handed to the unchanged `cocr_ctc_spot`; OUT.json receives the records of `search.search_pages`, 'page' being the input file the line
+handed to the unchanged `cocr_ctc_spot` (regular expressions, `-e` / `-E` / `--ignore-case` as in `search`: `cocr_ctc_spot_pattern`,
+DESIGN.md section 7m); OUT.json receives the records of `search.search_pages`, 'page' being the input file the line
 came from.  `info` prints what the file holds.
 
 keep = 8 and step = 1/8 (a floor of -31.875 for every class not kept) are placeholders, not tuned: recall against keep / step has not
 been measured on real material.
 
-Not built: recall measurements, whole-word matching, regular expressions and case folding, incremental append to an existing index,
+Not built: recall measurements, whole-word matching, anchors, lexicon tries that share prefixes, incremental append to an existing index,
 sharded indexes and multi-GPU search, a spot kernel that reads the packed rows directly."""
 from __future__ import annotations
 
@@ -322,7 +324,8 @@ def _batch_arrays(index: Index, lines: Sequence[int]) -> Tuple[np.ndarray, np.nd
     return classes, codes, lens
 
 
-def search_index(index, queries: Sequence[str], hits: int = 1, min_conf: float = None, batch_size: int = 256, device: str = 'cuda:0') -> List[Dict]:
+def search_index(index, queries: Sequence[str] = (), hits: int = 1, min_conf: float = None, batch_size: int = 256, device: str = 'cuda:0',
+                 patterns=(), ignore_case: bool = False) -> List[Dict]:
     """`search.search_pages` on an index file (or a loaded `Index`): every query string on every stored line, without model, images or
     forward.  Returns the same records in the same order -- by page, line, query, then best first: {'page': index into the file's
     pages, 'line', 'query', 'start', 'end', 'score', 'conf', 'quad'}, the quad from the stored line geometry -- with the same handling
@@ -332,19 +335,31 @@ def search_index(index, queries: Sequence[str], hits: int = 1, min_conf: float =
     the same (start, end) for every leading hit of score 0.  Lines are sorted by frame count and batched to the
     batch's longest line: uploaded, expanded by `cocr_posterior_unpack` and searched by `cocr_ctc_spot` on a model-less engine;
     frames past a line's end do not exist for the spotter, so the result does not depend on `batch_size`.  Queries of more than 255
-    labels, and everything with device='cpu', go through `spot_host` (float32, the type the device computes in) on `expand_host`."""
+    labels, and everything with device='cpu', go through `spot_host` (float32, the type the device computes in) on `expand_host`.
+
+    `patterns` (regular expressions over the stored codec, compiled with `ignore_case`, or `pattern.PatternGraph`s) are searched as
+    `search_pages` searches them: records with 'pattern' and 'match' in place of 'query', after the line's
+    query hits.  Chains go through `cocr_ctc_spot`, every other graph through `cocr_ctc_spot_pattern`, with device='cpu' through
+    `pattern.spot_pattern_host` (float32); the matched text is `pattern.match_host` on `expand_host` of the line either way."""
     from .align import encode_text
     from .page import cut_quads
+    from .pattern import PatternGraph, compile_pattern, labels_text, match_host, spot_pattern_host
     from .search import MAX_DEVICE_HITS, MAX_DEVICE_LABELS, spot_host
     index = _loaded(index)
     codec = index.codec()
     queries = list(queries)
     enc = [encode_text(codec, q) for q in queries]
     bad = [q for q, (lab, sk) in zip(queries, enc) if sk or not lab]
-    if bad or not queries:
+    graphs = [p if isinstance(p, PatternGraph) else compile_pattern(p, codec, ignore_case) for p in patterns]
+    bad += [g.text for g in graphs if g.skipped or not g.P]
+    if bad or not (queries or graphs):
         raise ValueError(f'queries the codec cannot encode: {bad}' if bad else 'no query')
-    labels = [lab for lab, _ in enc]
-    if any(l >= index.ncls for lab in labels for l in lab):
+    nq = len(queries)
+    # what is searched: the queries' label strings, then the patterns -- a chain as its label string, any other graph as itself
+    labels = [lab for lab, _ in enc] + [g.labels if g.is_chain else None for g in graphs]
+    if any(int(c) >= index.ncls for g in graphs for c in g.cls):
+        raise ValueError(f'the stored codec uses labels beyond the index\'s {index.ncls} classes')
+    if any(l >= index.ncls for lab in labels[:nq] for l in lab):
         raise ValueError(f'the stored codec uses labels beyond the index\'s {index.ncls} classes')
     if not 1 <= int(hits) <= MAX_DEVICE_HITS:
         raise ValueError(f'hits must lie in 1..{MAX_DEVICE_HITS}')
@@ -352,28 +367,35 @@ def search_index(index, queries: Sequence[str], hits: int = 1, min_conf: float =
         raise ValueError('batch_size must be positive')
     hits = int(hits)
     min_score = -np.inf
-    if min_conf is not None:
-        if not 0.0 < min_conf <= 1.0:
-            raise ValueError('min_conf must lie in (0, 1]')
-        # (search_pages' bound: the loosest any query needs, rounded away from zero; `conf` itself is held to min_conf below)
+    if min_conf is not None and not 0.0 < min_conf <= 1.0:
+        raise ValueError('min_conf must lie in (0, 1]')
+    if min_conf is not None and not graphs:
+        # (search_pages' bound: the loosest any query needs, rounded away from zero; `conf` itself is held to min_conf below.  With
+        # patterns the matched length is not known in advance: `conf` alone decides)
         min_score = max(len(l) for l in labels) * math.log(min_conf) * (1.0 + 1e-6) - 1e-6
     L = len(index)
-    spots: List[List[List[Tuple[int, int, float]]]] = [[[] for _ in queries] for _ in range(L)]
+    spots: List[List[List[Tuple]]] = [[[] for _ in labels] for _ in range(L)]           # (start, end, score[, final state])
     on_host = str(device) == 'cpu'
-    short = [] if on_host else [i for i, lab in enumerate(labels) if len(lab) <= MAX_DEVICE_LABELS]
-    slow = [i for i in range(len(queries)) if i not in short]
+    short = [] if on_host else [i for i, lab in enumerate(labels) if lab is not None and len(lab) <= MAX_DEVICE_LABELS]
+    wide = [] if on_host else [i for i, lab in enumerate(labels) if lab is None]             # the graph kernel's
+    slow = [i for i in range(len(labels)) if i not in short and i not in wide]
     order = sorted((i for i in range(L) if index.frames(i) > 0), key=lambda i: (index.frames(i), i))
-    if short and order:
+    if (short or wide) and order:
         import torch
         from .ctc_decoder import _scratch_engine
         dev = torch.device(device)
         eng = _scratch_engine(torch.device('cuda', dev.index if dev.index is not None else torch.cuda.current_device()))
 
         def finish(pend):
-            lines, handle = pend
-            for i, per_query in zip(lines, eng.collect_spot(handle)):
-                for qi, found in zip(short, per_query):
-                    spots[i][qi] = found
+            lines, handle, handle_wide = pend
+            if handle is not None:
+                for i, per_query in zip(lines, eng.collect_spot(handle)):
+                    for qi, found in zip(short, per_query):
+                        spots[i][qi] = found
+            if handle_wide is not None:
+                for i, per_pattern in zip(lines, eng.collect_spot_pattern(handle_wide)):
+                    for qi, found in zip(wide, per_pattern):
+                        spots[i][qi] = found
 
         pending = None
         with torch.cuda.device(eng.device):
@@ -381,32 +403,46 @@ def search_index(index, queries: Sequence[str], hits: int = 1, min_conf: float =
                 lines = order[at:at + int(batch_size)]
                 classes, codes, lens = _batch_arrays(index, lines)
                 table = eng.posterior_unpack(torch.from_numpy(classes).to(eng.device), torch.from_numpy(codes).to(eng.device), index.ncls, index.step)
-                handle = eng.ctc_spot_async(table, lens, [labels[qi] for qi in short], hits, min_score)
+                handle = eng.ctc_spot_async(table, lens, [labels[qi] for qi in short], hits, min_score) if short else None
+                handle_wide = eng.ctc_spot_pattern_async(table, lens, [graphs[qi - nq] for qi in wide], hits, min_score) if wide else None
                 if pending is not None:
                     finish(pending)
-                pending = (lines, handle)
+                pending = (lines, handle, handle_wide)
             finish(pending)
     if slow:
         for i in order:
             table = expand_host(*index.line(i), index.ncls, index.step)
             for qi in slow:
-                spots[i][qi] = spot_host(table, labels[qi], hits, min_score, dtype=np.float32)
+                if labels[qi] is not None:
+                    spots[i][qi] = spot_host(table, labels[qi], hits, min_score, dtype=np.float32)
+                else:
+                    spots[i][qi] = spot_pattern_host(table, graphs[qi - nq], hits, min_score, dtype=np.float32)
     out: List[Dict] = []
     by_page = sorted(range(L), key=lambda i: int(index.header['lines'][i]['page']))          # (stable: the stored order within a page)
     for i in by_page:
         ln = index.header['lines'][i]
-        recs = []                                            # (query, start, end, score, conf) of the line's hits
+        recs = []                                            # (query, start, end, score, conf, matched labels) of the line's hits
+        table = None
         for qi, found in enumerate(spots[i]):
-            for start, end, score in found:
-                conf = math.exp(score / len(labels[qi]))
+            for start, end, score, *final in found:
+                matched = labels[qi]
+                if matched is None:
+                    if table is None:
+                        table = expand_host(*index.line(i), index.ncls, index.step)
+                    matched = match_host(table, graphs[qi - nq], start, end, final[0])
+                conf = math.exp(score / max(len(matched), 1))
                 if min_conf is not None and conf < min_conf:
-                    break
-                recs.append((qi, start, end, score, conf))
+                    if qi < nq:
+                        break
+                    continue                                 # (a pattern's matches differ in length: a later one may pass)
+                recs.append((qi, start, end, score, conf, matched))
         # one call places all of the line's hits (`cut_quads` works element by element: the quads are those of one call per hit)
         quads = cut_quads(index.geometry(i), [(0, r[1], r[2], r[4]) for r in recs], int(ln['seq_len']), index.frames(i), int(index.header['pad']))
-        for (qi, start, end, score, conf), (_, quad, _) in zip(recs, quads):
-            out.append({'page': int(ln['page']), 'line': ln['id'], 'query': queries[qi], 'start': start, 'end': end, 'score': score, 'conf': conf,
-                        'quad': quad})
+        for (qi, start, end, score, conf, matched), (_, quad, _) in zip(recs, quads):
+            rec = {'page': int(ln['page']), 'line': ln['id'], 'query': queries[qi]} if qi < nq else \
+                {'page': int(ln['page']), 'line': ln['id'], 'pattern': graphs[qi - nq].text, 'match': labels_text(codec, matched)}
+            rec.update({'start': start, 'end': end, 'score': score, 'conf': conf, 'quad': quad})
+            out.append(rec)
     return out
 
 
@@ -427,7 +463,7 @@ def index_info(index) -> Dict:
 
 
 # ---- command ------------------------------------------------------------------------------------------------------------------------
-NOT_BUILT = ('Not built: recall measurements against keep / step, whole-word matching, regular expressions and case folding, incremental '
+NOT_BUILT = ('Not built: recall measurements against keep / step, whole-word matching, anchors, lexicon tries that share prefixes, incremental '
              'append, sharded indexes and multi-GPU search, a spot kernel that reads the packed rows directly.')
 
 
@@ -452,6 +488,8 @@ def parser() -> argparse.ArgumentParser:
     s.add_argument('--index', default=None, metavar='CORPUS.cidx')
     s.add_argument('-q', '--query', action='append', default=[], metavar='WORD', help='string to search for (repeatable)')
     s.add_argument('-Q', '--query-file', default=None, metavar='FILE', help='file with one query per line')
+    from .search import add_pattern_arguments
+    add_pattern_arguments(s)
     s.add_argument('output', nargs='?', default=None, metavar='OUT.json')
     s.add_argument('--hits', type=int, default=1, metavar='K', help=f'hits per line and query (1..{MAX_DEVICE_HITS})')
     s.add_argument('--min-conf', type=float, default=None, metavar='X', help='drops hits below this per-label confidence (default: none)')
@@ -509,11 +547,11 @@ def _search_command(ap, args, usage) -> int:
         return usage(f'--hits must lie in 1..{MAX_DEVICE_HITS}')
     if args.min_conf is not None and not 0.0 < args.min_conf <= 1.0:
         return usage('--min-conf must lie in (0, 1]')
-    missing = [f for f in [args.index, args.query_file] if f and not os.path.exists(f)]
+    missing = [f for f in [args.index, args.query_file, args.pattern_file] if f and not os.path.exists(f)]
     if missing:
         return usage(f'no such file: {", ".join(missing)}')
-    from .align import encode_text
     from .dataset import normalize_text
+    from .search import compile_for_command, read_patterns
     raw = list(args.query)
     if args.query_file:
         with open(args.query_file, encoding='utf-8') as fp:
@@ -523,25 +561,19 @@ def _search_command(ap, args, usage) -> int:
         q = normalize_text(q, args.normalization, args.normalize_whitespace)
         if q and q not in queries:
             queries.append(q)
-    if not queries:
-        return usage('No query given. Use `-q WORD` or `-Q FILE`.')
+    regexes = read_patterns(args)
+    if not queries and not regexes:
+        return usage('No query given. Use `-q WORD`, `-Q FILE`, `-e REGEX` or `-E FILE`.')
     index = load_index(args.index)
-    codec = index.codec()
-    searchable = []
-    for q in queries:
-        lab, skipped = encode_text(codec, q)
-        if skipped or not lab:
-            print(f'{ap.prog}: query {q!r} skipped: the index\'s codec cannot encode {skipped!r}', file=sys.stderr)
-        else:
-            searchable.append(q)
-    if not searchable:
+    searchable, graphs = compile_for_command(ap.prog, index.codec(), queries, regexes, args.ignore_case, whose='index\'s codec')
+    if not searchable and not graphs:
         return usage('no query the index\'s codec can encode')
-    found = search_index(index, searchable, hits=args.hits, min_conf=args.min_conf, batch_size=args.batch_size, device=args.device)
+    found = search_index(index, searchable, hits=args.hits, min_conf=args.min_conf, batch_size=args.batch_size, device=args.device, patterns=graphs)
     names = index.header['pages']
     per_page = [sum(1 for ln in index.header['lines'] if ln['page'] == p) for p in range(len(names))]
     for p, src in enumerate(names):
         mine = [h for h in found if h['page'] == p]
-        print(f'{src}: {len(mine)} hits of {len({h["query"] for h in mine})} of {len(searchable)} queries on '
+        print(f'{src}: {len(mine)} hits of {len({h.get("query", h.get("pattern")) for h in mine})} of {len(searchable) + len(graphs)} queries on '
               f'{len({h["line"] for h in mine})} of {per_page[p]} lines', file=sys.stderr)
     for h in found:
         h['page'] = names[h['page']]

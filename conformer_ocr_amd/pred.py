@@ -518,6 +518,58 @@ class PytorchRecognitionModel(nn.Module):
                 out[n][i] = spots
         return {'hits': out, 'frames': [int(l) for l in olens], 'skipped': skipped}
 
+    # ------------------------------------------------------------------ pattern spotting (conformer_ocr_amd/pattern.py)
+    def spot_patterns_async(self, line: torch.Tensor, lens: torch.Tensor, patterns, hits: int = 1, min_score: float = -np.inf,
+                            ignore_case: bool = False):
+        """Forward + the pattern search enqueued on the current stream; returns a handle for `collect_spot_patterns`.  `patterns`:
+        regular expressions (compiled with `pattern.compile_pattern` over `self.codec`) or `pattern.PatternGraph`s.  A pattern whose
+        graph is a plain chain goes through `cocr_ctc_spot` (the same result, at a string's cost), every other one through
+        `cocr_ctc_spot_pattern`.  ValueError: a pattern the codec cannot express, or one `compile_pattern` refuses."""
+        from .pattern import PatternGraph, compile_pattern
+        from .search import MAX_DEVICE_HITS, MAX_DEVICE_LABELS
+        graphs = [p if isinstance(p, PatternGraph) else compile_pattern(p, self.codec, ignore_case) for p in patterns]
+        bad = [g.text for g in graphs if g.skipped or not g.P]
+        if bad or not graphs:
+            raise ValueError(f'patterns the codec cannot express: {bad}' if bad else 'no pattern')
+        if not 1 <= int(hits) <= MAX_DEVICE_HITS:
+            raise ValueError(f'hits must lie in 1..{MAX_DEVICE_HITS}')
+        o, olens = self.forward(line, lens)
+        eng = self._engine             # (a re-pack may replace `self._engine` before the collect)
+        olens = olens.numpy()
+        chains = [i for i, g in enumerate(graphs) if g.is_chain and g.P <= MAX_DEVICE_LABELS]
+        rest = [i for i in range(len(graphs)) if i not in set(chains)]
+        h_chain = eng.ctc_spot_async(o, olens, [graphs[i].labels for i in chains], hits, min_score) if chains else None
+        h_graph = eng.ctc_spot_pattern_async(o, olens, [graphs[i] for i in rest], hits, min_score) if rest else None
+        return eng, h_chain, h_graph, o, olens, graphs, chains, rest
+
+    def collect_spot_patterns(self, pending):
+        """Waits for a `spot_patterns_async` handle: (per line, per pattern [(start, end, score, labels)] -- `labels`: the label
+        sequence the hit matched (`pattern.match_host` on the line's own logits) --, the lines' output lengths, the graphs)."""
+        from .pattern import match_host
+        eng, h_chain, h_graph, o, olens, graphs, chains, rest = pending
+        out = [[[] for _ in graphs] for _ in range(o.shape[0])]
+        if h_chain is not None:
+            for n, per_query in enumerate(eng.collect_spot(h_chain)):
+                for i, spots in zip(chains, per_query):
+                    out[n][i] = [(st, en, sc, graphs[i].labels) for st, en, sc in spots]
+        if h_graph is not None:
+            found = eng.collect_spot_pattern(h_graph)
+            host = o.cpu().numpy() if any(spots for per in found for spots in per) else None
+            for n, per_pattern in enumerate(found):
+                for i, spots in zip(rest, per_pattern):
+                    out[n][i] = [(st, en, sc, match_host(host[n, :int(olens[n])].T, graphs[i], st, en, fin)) for st, en, sc, fin in spots]
+        return out, olens, graphs
+
+    def spot_patterns(self, line: torch.Tensor, lens: torch.Tensor, patterns, hits: int = 1, min_score: float = -np.inf,
+                      ignore_case: bool = False) -> Dict:
+        """Pattern spotting: forward pass on a (N, C, H, W) batch, then per line and per pattern up to `hits` non-overlapping matches
+        (`pattern.spot_pattern_host` is the definition).  Returns {'hits': per line, per pattern [(start, end, score, matched text)],
+        'frames': the lines' output lengths}."""
+        from .pattern import labels_text
+        found, olens, _ = self.collect_spot_patterns(self.spot_patterns_async(line, lens, patterns, hits, min_score, ignore_case))
+        return {'hits': [[[(st, en, sc, labels_text(self.codec, lab)) for st, en, sc, lab in spots] for spots in per] for per in found],
+                'frames': [int(l) for l in olens]}
+
     # ------------------------------------------------------------------ search index (conformer_ocr_amd/index.py, DESIGN.md section 7l)
     def pack_posteriors_async(self, line: torch.Tensor, lens: torch.Tensor, keep: int = 8, step: float = 0.125):
         """Forward + `cocr_posterior_pack` + the read-back into pinned host memory enqueued on the current stream; returns a handle

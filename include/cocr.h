@@ -240,6 +240,24 @@ int cocr_ctc_spot(cocr_model *m, const float *logits, int N, int T, int ncls, co
                   const int32_t *query_lens, int Q, int hits, float min_score, int32_t *starts, int32_t *ends, float *score,
                   int32_t *counts, void *stream);
 
+/* Pattern spotting (the definition is conformer_ocr_amd/pattern.py spot_pattern_host): where each of Q patterns
+ * -- graphs of label states, compiled from regular expressions by pattern.compile_pattern -- matches in each of N lines.  Pattern i has
+ * state_counts[i] = P label states; state p has class classes[p] in [1, ncls), flags[p] (1: a match may begin in it, 2: a match may end
+ * in it) and the strictly ascending predecessors preds[pred_off[p] .. pred_off[p + 1]) (a state may precede itself); a blank state
+ * follows every label state.  The tables of the patterns are concatenated: classes and flags sum(P) entries, pred_off P + 1 entries per
+ * pattern, each list beginning at 0, preds sum(edges).  Scores, ties within a state (stay, the predecessors in list order -- blank
+ * state first, then the label state if the classes differ --, fresh start) and the selection are cocr_ctc_spot's; among the last
+ * states of equal score the lowest wins and is reported in `finals`.  A pattern that is a plain chain gives cocr_ctc_spot's results.
+ * logits DEVICE float32 (N,T,ncls); out_lens and the tables HOST, checked before any launch: COCR_EINVAL for a class outside
+ * [1, ncls), P outside 1..256, more than 4096 edges, a predecessor outside [0, P) or a list not strictly ascending, a pattern without a
+ * first or without a last state, out_lens[n] outside [0, T], hits outside 1..8, Q < 1 or a NaN min_score; COCR_EUNSUPPORTED for
+ * T > 8000 or more than 65535 lines.  Outputs DEVICE or device-visible pinned host memory: starts / ends / finals int32 and score
+ * float32 (N,Q,hits), counts int32 (N,Q); entries past the count are -1 / -1 / -1 / -inf.  Does not touch the greedy decoder's argmax
+ * scratch.  Deterministic (no atomics).  Stream-ordered, does not synchronise (ring or workspace growth does). */
+int cocr_ctc_spot_pattern(cocr_model *m, const float *logits, int N, int T, int ncls, const int32_t *out_lens, const int32_t *state_counts,
+                          const int32_t *classes, const int32_t *flags, const int32_t *pred_off, const int32_t *preds, int Q, int hits,
+                          float min_score, int32_t *starts, int32_t *ends, float *score, int32_t *finals, int32_t *counts, void *stream);
+
 /* The search index (the definition is conformer_ocr_amd/index.py pack_host / expand_host): pruned, quantised
  * frame posteriors that cocr_ctc_spot can be run on later, without the model.
  * cocr_posterior_pack: per frame the `keep` classes of the largest logit, ties to the lower class, stored in that order (entry 0 is the

@@ -1,6 +1,6 @@
 #!/usr/bin/env python3
-"""Digests of everything behind the forward -- the CTC criterion, forced alignment, keyword spotting, the beam searches, the greedy
-decoder -- for comparing two builds of the library bit for bit:   python tools/decode_digest.py [--out FILE]
+"""Digests of everything behind the forward -- the CTC criterion, forced alignment, keyword and pattern spotting, the beam searches, the
+greedy decoder -- for comparing two builds of the library bit for bit:   python tools/decode_digest.py [--out FILE]
 (the library is the tree's, or the one COCR_LIB_PATH names).  None of these kernels has floating-point atomics, so two builds that do
 the same arithmetic in the same order print the same JSON.  The sibling of tools/train_digest.py.
 
@@ -9,6 +9,8 @@ instantiation of the kernels:
   loss, align   the batches of tests/test_hip_align.py `_random_batches()` (SJ 1, 2, 4, 8) and its two planted 5150-frame batches (the
                 workspace form of the back-pointer table at SJ 8 and SJ 1): nll and gradient; records and scores
   spot          the five grid cases of tests/test_hip_search.py (SJ 1, 2, 8, the workspace form, lines without frames)
+  spot_pattern  the chain cases (SJ 1, 2, 4) and the grid cases of tests/test_hip_pattern.py (in-degree 10 across a register seam, K 1
+                and 3): cocr_ctc_spot_pattern's raw outputs
   beam          the nine shapes of tests/test_hip_beam.py `test_beam_pruned_equals_exhaustive`, and again with COCR_BEAM_REF=1
   beam_lm       the seven shapes of tests/test_hip_lm.py `test_without_the_model_every_field_equals_the_plain_beam` with alpha = beta
                 = 0, and the six of `test_equals_the_definition_with_a_real_model` with their models
@@ -63,7 +65,8 @@ def run_leg(leg):
     import numpy as np
     import torch
     from conformer_ocr_amd.ctc_decoder import _scratch_engine
-    from tests import test_hip_align as TA, test_hip_beam as TB, test_hip_lm as TL, test_hip_search as TS
+    from tests import test_hip_align as TA, test_hip_beam as TB, test_hip_lm as TL, test_hip_pattern as TP, test_hip_search as TS
+    from conformer_ocr_amd import pattern as PT
     eng = _scratch_engine(torch.device('cuda', 0))
     dev = lambda a: torch.from_numpy(np.ascontiguousarray(a, dtype=np.float32)).cuda()
     out = {}
@@ -97,6 +100,14 @@ def run_leg(leg):
         Q = len(queries)
         raw = [h[1][0].numpy()[:, :N * Q * K], h[1][1].numpy()[:N * Q * K], h[1][2].numpy()[:N * Q]]      # entries past the count too
         out[f'spot/{(N, T, C, K)}'] = {'records': sha(records), 'raw': sha(raw)}
+    raw_pattern = lambda x, lens, graphs, K: sha(list(eng.collect_spot_pattern(eng.ctc_spot_pattern_async(dev(x), lens, graphs, K), raw=True)))
+    for N, T, C, lens_q, K, out_lens, width in _params(TP.test_literal_chains_equal_the_string_kernel):
+        logits, queries = TS._grid_case(N, T, C, lens_q, 100 + T, out_lens, width)
+        out[f'spot_pattern/chains/{(N, T, C, K)}'] = raw_pattern(logits, out_lens, [PT.chain_graph(q) for q in queries], K)
+    for N, T, C, out_lens, width in TP.GRID_SHAPES:
+        logits, graphs = TP._pattern_case(N, T, C, out_lens, 300 + T, width)
+        for K in (1, 3):
+            out[f'spot_pattern/grid/{(N, T, C, K)}'] = raw_pattern(logits, out_lens, graphs, K)
     for C, T, beam in _params(TL.test_without_the_model_every_field_equals_the_plain_beam):
         lm = TL._chain_lm(C, 3, seed=C, n=20)
         got, score = eng.ctc_beam_lm(dev(TL._logits(C, T, 5)), [T, T - 3, T // 2, 1, 0], lm, beam, min(C - 1, 64), 0.0, 0.0, return_scores=True)

@@ -1,6 +1,6 @@
 #!/usr/bin/env python3
 """Prints VGPR / scratch / occupancy / LDS per kernel of libcocr_hip (hipcc -Rpass-analysis); an argument filters by kernel name
-(`ctc_align`, `ctc_spot`, ...: every instantiation of the kernel template is listed)."""
+(`ctc_align`, `ctc_spot`, `ctc_spot_graph`, ...: every instantiation of the kernel template is listed)."""
 import glob
 import os
 import re
