@@ -195,10 +195,10 @@ __global__ __launch_bounds__(64) void ctc_beam_kernel(const float *__restrict__ 
         __syncthreads();
     }
     // ---- best prefix: walk the back-pointers (one lane), then ends / confidences in parallel over the labels
-    __shared__ int s_cnt;
+    __shared__ int s_cnt, s_next;                                    // s_next: the start of the first label a truncated row leaves out (else len)
     int32_t *olab = labels + (size_t)n * max_per_line, *ost = starts + (size_t)n * max_per_line;
     if (lane == 0) {
-        int cnt = 0, e = 0;
+        int cnt = 0, e = 0, nx = len;
         for (int t = len - 1; t >= 0; --t) {
             const int v = bp[(size_t)t * COCR_BEAM_MAX + e];
             if (v & 0xffff) ++cnt;
@@ -209,16 +209,17 @@ __global__ __launch_bounds__(64) void ctc_beam_kernel(const float *__restrict__ 
         e = 0;
         for (int t = len - 1; t >= 0; --t) {
             const int v = bp[(size_t)t * COCR_BEAM_MAX + e];
-            if (v & 0xffff) { --k; if (k < max_per_line) { olab[k] = v & 0xffff; ost[k] = t; } }
+            if (v & 0xffff) { --k; if (k < max_per_line) { olab[k] = v & 0xffff; ost[k] = t; } else if (k == max_per_line) nx = t; }
             e = v >> 16;
         }
+        s_next = nx;
         counts[n] = cnt;
     }
     __syncthreads();
     __threadfence_block();
     const int cnt = min(s_cnt, max_per_line);
     for (int k = lane; k < cnt; k += 64) {
-        const int c = olab[k], s = ost[k], limit = k + 1 < cnt ? ost[k + 1] : len;
+        const int c = olab[k], s = ost[k], limit = k + 1 < cnt ? ost[k + 1] : s_next;
         int e = s;
         while (e + 1 < limit && lg[(size_t)(e + 1) * C + c] > lg[(size_t)(e + 1) * C]) ++e;
         float mxp = -INFINITY;
@@ -357,7 +358,7 @@ __global__ __launch_bounds__(256) void ctc_beam_walk_kernel(const float *__restr
     __shared__ __attribute__((aligned(16))) unsigned long long ckey[STAY0 + NB];                 // extensions [0, nep), stays [nep, nep + beam), zeros between
     __shared__ __attribute__((aligned(16))) unsigned long long hash[NB], phash[NB], hx[NB];
     __shared__ __attribute__((aligned(16))) float pb[NB], tot[NB], spb[NB], spnb[NB], lpl[NB];
-    __shared__ __attribute__((aligned(16))) int last[NB], pair_s[NB], live_s[4], off_s[KM + 1], rank_s[64 * SL], s_cnt;
+    __shared__ __attribute__((aligned(16))) int last[NB], pair_s[NB], live_s[4], off_s[KM + 1], rank_s[64 * SL], s_cnt, s_next;
     extern __shared__ __attribute__((aligned(16))) unsigned char beam_dyn[];
     const int n = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int len = min(max(lens[n], 0), T);
@@ -547,13 +548,14 @@ __global__ __launch_bounds__(256) void ctc_beam_walk_kernel(const float *__restr
                 e = v >> 16;
             }
             s_cnt = cnt;
+            s_next = cnt > max_per_line ? stk[2 * (cnt - 1 - max_per_line) + 1] : len;      // the start of the first label a truncated row leaves out
             counts[n] = cnt;
         }
         __syncthreads();
         const int cnt = s_cnt;
         for (int k2 = tid; k2 < min(cnt, max_per_line); k2 += 256) { olab[k2] = stk[2 * (cnt - 1 - k2)]; ost[k2] = stk[2 * (cnt - 1 - k2) + 1]; }
     } else if (tid == 0) {
-        int cnt = 0, e = 0;
+        int cnt = 0, e = 0, nx = len;
         for (int t = len - 1; t >= 0; --t) {
             const int v = bpg[(size_t)t * NB + e];
             if (v & 0xffff) ++cnt;
@@ -564,16 +566,17 @@ __global__ __launch_bounds__(256) void ctc_beam_walk_kernel(const float *__restr
         e = 0;
         for (int t = len - 1; t >= 0; --t) {
             const int v = bpg[(size_t)t * NB + e];
-            if (v & 0xffff) { --k2; if (k2 < max_per_line) { olab[k2] = v & 0xffff; ost[k2] = t; } }
+            if (v & 0xffff) { --k2; if (k2 < max_per_line) { olab[k2] = v & 0xffff; ost[k2] = t; } else if (k2 == max_per_line) nx = t; }
             e = v >> 16;
         }
+        s_next = nx;
         counts[n] = cnt;
     }
     __threadfence_block();
     __syncthreads();
     const int cnt = min(s_cnt, max_per_line);
     for (int k2 = tid; k2 < cnt; k2 += 256) {
-        const int c = olab[k2], s0 = ost[k2], limit = k2 + 1 < cnt ? ost[k2 + 1] : len;
+        const int c = olab[k2], s0 = ost[k2], limit = k2 + 1 < cnt ? ost[k2 + 1] : s_next;
         int e = s0;
         while (e + 1 < limit && lg[(size_t)(e + 1) * C + c] > lg[(size_t)(e + 1) * C]) ++e;
         float mxp = -INFINITY;

@@ -147,7 +147,7 @@ __global__ __launch_bounds__(256) void ctc_lm_walk_kernel(const float *__restric
     __shared__ __attribute__((aligned(16))) unsigned long long ckey[COCR_LM_NE + NB];             // extensions [0, NE), stays [NE, NE + beam), one zero pad
     __shared__ __attribute__((aligned(16))) lm_prefix_state st[2];
     __shared__ __attribute__((aligned(16))) float clmv[COCR_LM_NE], recs[2][COCR_LM_REC], spb[NB], spnb[NB], mval[NB];
-    __shared__ int mpos[NB], sbp[NB], s_cnt;
+    __shared__ int mpos[NB], sbp[NB], s_cnt, s_next;
     extern __shared__ __attribute__((aligned(16))) unsigned char lm_dyn[];
     const int n = blockIdx.x, tid = threadIdx.x;
     const int len = min(max(lens[n], 0), T);
@@ -269,13 +269,14 @@ __global__ __launch_bounds__(256) void ctc_lm_walk_kernel(const float *__restric
                 e = v >> 16;
             }
             s_cnt = cnt;
+            s_next = cnt > max_per_line ? stk[2 * (cnt - 1 - max_per_line) + 1] : len;      // the start of the first label a truncated row leaves out
             counts[n] = cnt;
         }
         __syncthreads();
         const int cnt = s_cnt;
         for (int k2 = tid; k2 < min(cnt, max_per_line); k2 += 256) { olab[k2] = stk[2 * (cnt - 1 - k2)]; ost[k2] = stk[2 * (cnt - 1 - k2) + 1]; }
     } else if (tid == 0) {
-        int cnt = 0, e = 0;
+        int cnt = 0, e = 0, nx = len;
         for (int t = len - 1; t >= 0; --t) {
             const int v = bpg[(size_t)t * NB + e];
             if (v & 0xffff) ++cnt;
@@ -286,16 +287,17 @@ __global__ __launch_bounds__(256) void ctc_lm_walk_kernel(const float *__restric
         e = 0;
         for (int t = len - 1; t >= 0; --t) {
             const int v = bpg[(size_t)t * NB + e];
-            if (v & 0xffff) { --k2; if (k2 < max_per_line) { olab[k2] = v & 0xffff; ost[k2] = t; } }
+            if (v & 0xffff) { --k2; if (k2 < max_per_line) { olab[k2] = v & 0xffff; ost[k2] = t; } else if (k2 == max_per_line) nx = t; }
             e = v >> 16;
         }
+        s_next = nx;
         counts[n] = cnt;
     }
     __threadfence_block();
     __syncthreads();
     const int cnt = min(s_cnt, max_per_line);
     for (int k2 = tid; k2 < cnt; k2 += 256) {
-        const int c = olab[k2], s0 = ost[k2], limit = k2 + 1 < cnt ? ost[k2 + 1] : len;
+        const int c = olab[k2], s0 = ost[k2], limit = k2 + 1 < cnt ? ost[k2 + 1] : s_next;
         int e = s0;
         while (e + 1 < limit && lg[(size_t)(e + 1) * C + c] > lg[(size_t)(e + 1) * C]) ++e;
         float mxp = -INFINITY;

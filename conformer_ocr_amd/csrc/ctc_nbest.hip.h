@@ -139,10 +139,10 @@ __global__ __launch_bounds__(256) void ctc_nbest_kernel(const float *__restrict_
     for (int i = tid; i < total; i += 256) {
         int j = 0;
         while (off_s[j + 1] <= i) ++j;
-        const int k = i - off_s[j], kept = off_s[j + 1] - off_s[j], cnt = cnt_s[j];
+        const int k = i - off_s[j], cnt = cnt_s[j];
         const unsigned *my = stk + (size_t)j * sstride;
         const unsigned ent = my[cnt - 1 - k];
-        const int c = (int)(ent >> 16), s0 = (int)(ent & 0xffffu), limit = k + 1 < kept ? (int)(my[cnt - 2 - k] & 0xffffu) : len;
+        const int c = (int)(ent >> 16), s0 = (int)(ent & 0xffffu), limit = k + 1 < cnt ? (int)(my[cnt - 2 - k] & 0xffffu) : len;      // (the next label's start, kept in the row or not)
         int e = s0;
         while (e + 1 < limit && lg[(size_t)(e + 1) * C + c] > lg[(size_t)(e + 1) * C]) ++e;
         float mxp = -INFINITY;

@@ -305,6 +305,21 @@ def _lse(a: np.float32, b: np.float32) -> np.float32:
     return np.float32(m + np.log1p(np.exp(d, dtype=np.float32), dtype=np.float32))
 
 
+def records_host(lp: np.ndarray, labels: Sequence[int], starts: Sequence[int]) -> List[Tuple[int, int, int, float]]:
+    """The post-pass of every beam decoder on (C, T) log-softmax scores: label k appended at frame starts[k] -> (label, start, end,
+    conf); end = start extended while the next frame (before the next label's start, or the line's end) scores the label above
+    blank; conf = max softmax(label) over [start, end]."""
+    T = lp.shape[1]
+    res = []
+    for i, (c, s) in enumerate(zip(labels, starts)):
+        limit = starts[i + 1] if i + 1 < len(starts) else T
+        e = s
+        while e + 1 < limit and lp[c, e + 1] > lp[0, e + 1]:
+            e += 1
+        res.append((int(c), int(s), int(e), float(np.exp(lp[c, s:e + 1].max()))))
+    return res
+
+
 def beam_decode_host(outputs: np.ndarray, lm: NGramLM, beam_size: int = 16, classes: int = 8, alpha: float = 0.5, beta: float = 0.0,
                      return_scores: bool = False, return_gap: bool = False):
     """THE DEFINITION of the LM beam search on one line's (C, T) logits: the CTC prefix beam search this build fixes
@@ -352,14 +367,7 @@ def beam_decode_host(outputs: np.ndarray, lm: NGramLM, beam_size: int = 16, clas
     if len(final) > 1:
         gap = min(gap, float(final[0]) - float(final[1]))
     labels, p_b, p_nb, starts, lmv = beam[0]
-    res = []
-    for i, (c, s) in enumerate(zip(labels, starts)):
-        limit = starts[i + 1] if i + 1 < len(starts) else T
-        e = s
-        while e + 1 < limit and lp[c, e + 1] > lp[0, e + 1]:
-            e += 1
-        res.append((int(c), int(s), int(e), float(np.exp(lp[c, s:e + 1].max()))))
-    out = (res,)
+    out = (records_host(lp, labels, starts),)
     if return_scores:
         out += ((float(_lse(p_b, p_nb)), float(lmv)),)
     if return_gap:

@@ -10,7 +10,7 @@ from typing import Dict, List, Optional, Sequence, Tuple
 
 import numpy as np
 
-from .lm import _log_softmax, _lse
+from .lm import _log_softmax, _lse, records_host
 
 MAX_LABELS = 255                    # csrc/ctc_lattice.hip.h COCR_LATTICE_MAX_LABELS
 
@@ -113,13 +113,7 @@ def nbest_host(outputs: np.ndarray, beam_size: int, nbest: int, lm=None, classes
     take = min(nbest, len(beam))
     hyps = []
     for labels, _, _, starts, _ in beam[:take]:
-        res: Records = []
-        for i, (c, s) in enumerate(zip(labels, starts)):
-            limit = starts[i + 1] if i + 1 < len(starts) else T
-            e = s
-            while e + 1 < limit and lp[c, e + 1] > lp[0, e + 1]:
-                e += 1
-            res.append((int(c), int(s), int(e), float(np.exp(lp[c, s:e + 1].max()))))
+        res: Records = records_host(lp, labels, starts)
         logp = ctc_logp(outputs, labels) if len(labels) <= MAX_LABELS else math.nan
         hyps.append((res, logp, lm_sum(lm, labels) if lm is not None else 0.0))
     if not return_gap:

@@ -45,25 +45,25 @@ def greedy_decoder(outputs: np.ndarray) -> List[Tuple[int, int, int, float]]:
     return res
 
 
-def log_softmax(outputs: np.ndarray) -> np.ndarray:
-    """Column-wise (over classes) log-softmax of a (C, T) logit matrix, float32 arithmetic."""
-    x = np.asarray(outputs, dtype=np.float32)
+def log_softmax(outputs: np.ndarray, dtype=np.float32) -> np.ndarray:
+    """Column-wise (over classes) log-softmax of a (C, T) logit matrix, float32 arithmetic (or `dtype`'s)."""
+    x = np.asarray(outputs, dtype=dtype)
     m = x.max(axis=0, keepdims=True)
-    return (x - m) - np.log(np.exp(x - m).sum(axis=0, keepdims=True, dtype=np.float32))
+    return (x - m) - np.log(np.exp(x - m).sum(axis=0, keepdims=True, dtype=dtype))
 
 
-def _lse(a: np.float32, b: np.float32) -> np.float32:
-    """logaddexp in float32 with the fixed form max + log1p(exp(-|a-b|)) (the GPU kernel uses the same form)."""
+def _lse(a, b, f=np.float32):
+    """logaddexp in float32 (or in `f`) with the fixed form max + log1p(exp(-|a-b|)) (the GPU kernel uses the same form)."""
     if a == -np.inf:
-        return np.float32(b)
+        return f(b)
     if b == -np.inf:
-        return np.float32(a)
+        return f(a)
     m = a if a > b else b
-    d = np.float32(-abs(np.float32(a - b)))
-    return np.float32(m + np.log1p(np.exp(d, dtype=np.float32), dtype=np.float32))
+    d = f(-abs(f(a - b)))
+    return f(m + np.log1p(np.exp(d, dtype=f), dtype=f))
 
 
-def beam_decoder(outputs: np.ndarray, beam_size: int = 16) -> List[Tuple[int, int, int, float]]:
+def beam_decoder(outputs: np.ndarray, beam_size: int = 16, return_gap: bool = False, dtype=np.float32):
     """CTC prefix beam search (the algorithm of kraken.lib.ctc_decoder.beam_decoder) with
     the semantics this build fixes, because the reference never calls it and kraken's version expects
     probabilities while the reference hands over raw logits:
@@ -77,27 +77,40 @@ def beam_decoder(outputs: np.ndarray, beam_size: int = 16) -> List[Tuple[int, in
       keep creation order (parents in beam order; per parent: itself, then labels ascending);
     * output for the best prefix: (label, start, end, conf); start = frame at which the label was
       appended on the chain of first creators; end = start extended while the next frame (before the
-      next label's start) scores the label above blank; conf = max softmax(label) over [start, end]."""
-    lp = log_softmax(outputs)
+      next label's start) scores the label above blank; conf = max softmax(label) over [start, end].
+
+    dtype: the arithmetic of every score (np.float32: the kernels'; np.float64: the same search with
+    rounding out of the way).  return_gap: also (the smallest difference, over the frames, between the
+    scores of the beam_size-th and the (beam_size + 1)-th candidate; the difference between the two
+    best final scores), inf where there is no such pair: a decision closer than the arithmetic's error
+    may fall the other way in another arithmetic."""
+    f = np.dtype(dtype).type
+    lp = log_softmax(outputs, f)
     C, T = lp.shape
-    NEG = np.float32(-np.inf)
-    beam = [((), np.float32(0.0), NEG, ())]               # (labels, p_b, p_nb, start frames)
+    NEG = f(-np.inf)
+    beam = [((), f(0.0), NEG, ())]                        # (labels, p_b, p_nb, start frames)
+    frame_gap = final_gap = float('inf')
     for t in range(T):
         cand = {}                                          # insertion-ordered: creation order
         for key, p_b, p_nb, starts in beam:
-            tot = _lse(p_b, p_nb)
+            tot = _lse(p_b, p_nb, f)
             last = key[-1] if key else None
             c = cand.setdefault(key, [NEG, NEG, starts])
-            c[0] = _lse(c[0], np.float32(tot + lp[0, t]))
+            c[0] = _lse(c[0], f(tot + lp[0, t]), f)
             if last is not None:
-                c[1] = _lse(c[1], np.float32(p_nb + lp[last, t]))
+                c[1] = _lse(c[1], f(p_nb + lp[last, t]), f)
             for s in range(1, C):
-                add = np.float32((p_b if s == last else tot) + lp[s, t])
+                add = f((p_b if s == last else tot) + lp[s, t])
                 if add == NEG:
                     continue
                 c = cand.setdefault(key + (s,), [NEG, NEG, starts + (t,)])
-                c[1] = _lse(c[1], add)
-        ranked = sorted(enumerate(cand.items()), key=lambda x: (-float(_lse(x[1][1][0], x[1][1][1])), x[0]))
+                c[1] = _lse(c[1], add, f)
+        ranked = sorted(enumerate(cand.items()), key=lambda x: (-float(_lse(x[1][1][0], x[1][1][1], f)), x[0]))
+        if return_gap:
+            score = [float(_lse(v[0], v[1], f)) for _, (_, v) in ranked[:beam_size + 1]]
+            if len(score) > beam_size:
+                frame_gap = min(frame_gap, score[beam_size - 1] - score[beam_size])
+            final_gap = score[0] - score[1] if len(score) > 1 else float('inf')
         beam = [(k, v[0], v[1], v[2]) for _, (k, v) in ranked[:beam_size]]
     labels, _, _, starts = beam[0]
     res = []
@@ -107,4 +120,4 @@ def beam_decoder(outputs: np.ndarray, beam_size: int = 16) -> List[Tuple[int, in
         while e + 1 < limit and lp[c, e + 1] > lp[0, e + 1]:
             e += 1
         res.append((int(c), int(s), int(e), float(np.exp(lp[c, s:e + 1].max()))))
-    return res
+    return (res, (frame_gap, final_gap)) if return_gap else res

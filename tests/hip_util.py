@@ -12,6 +12,15 @@ def make_engine(hp, state, dtype):
     return eng
 
 
+def fresh_decoder_engine():
+    """A new engine of the smallest model, for the decoders alone (they take any logits).  The environment switches, COCR_BEAM_REF among
+    them, are read when an engine is made: a test that sets one needs an engine of its own, not the cached scratch engine."""
+    from conformer_ocr_amd.spec import HParams
+    hp = HParams(num_classes=2, height=16, encoder_dim=16, num_encoder_layers=1, num_attention_heads=1, conv_kernel_size=3,
+                 subsampling_conv_channels=8)
+    return HipRecognizer(hp, torch.device('cuda', 0), 'fp32')
+
+
 def run_hip(hp, state, image, lens, dtype, debug=False, as_u8=False):
     eng = make_engine(hp, state, dtype)
     eng.set_debug(debug)

@@ -52,3 +52,20 @@ def test_beam_sums_paths_where_greedy_does_not():
     # "" : 0.16 ; "1": 0.35*0.4*2 + 0.35^2 = 0.4025 ; "2": 0.2625 ...
     assert [x[0] for x in beam_decoder(m, 16)] == [1]
     np.testing.assert_allclose(np.exp(log_softmax(m)), p, rtol=1e-5)
+
+
+def test_beam_gaps_and_float64_known_answer():
+    # the same two frames.  beam 16 never fills: no frame gap; final scores "1" 0.4025 | "2" 0.2625.  beam 2: frame 0 ranks
+    # "" 0.4 | "1" 0.35 | "2" 0.25, frame 1 ranks "1" 0.4025 | "" 0.16 | "2" 0.1 | "12" 0.0875: the closest cut is frame 0's.
+    # (The record starts at frame 1: the empty prefix ranks first after frame 0, so it is the first creator of "1" in frame 1.)
+    m = np.log(np.array([[0.4, 0.4], [0.35, 0.35], [0.25, 0.25]]))
+    for dtype, tol in ((np.float32, 1e-6), (np.float64, 1e-12)):
+        res, (frame_gap, final_gap) = beam_decoder(m, 16, return_gap=True, dtype=dtype)
+        assert [x[:3] for x in res] == [(1, 1, 1)] and frame_gap == np.inf
+        assert abs(final_gap - np.log(0.4025 / 0.2625)) <= tol
+        assert abs(res[0][3] - 0.35) <= tol
+        res, (frame_gap, final_gap) = beam_decoder(m, 2, return_gap=True, dtype=dtype)
+        assert [x[:3] for x in res] == [(1, 1, 1)]
+        assert abs(frame_gap - np.log(0.35 / 0.25)) <= tol and abs(final_gap - np.log(0.4025 / 0.16)) <= tol
+    assert beam_decoder(m, 16) == beam_decoder(m, 16, return_gap=True)[0] == beam_decoder(m.astype(np.float32), 16, dtype=np.float32)
+    assert beam_decoder(np.zeros((3, 0), np.float32), 4, return_gap=True) == ([], (np.inf, np.inf))

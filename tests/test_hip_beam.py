@@ -1,11 +1,15 @@
 """GPU: CTC prefix beam search (cocr_ctc_beam) against oracle/ctc_ref.py::beam_decoder.  The label sequences and start
 frames must be identical; scores are float32 logaddexp chains whose device / numpy libm may differ in the last ulps, so
-random cases allow a mismatch only where the oracle's own top-2 final scores are closer than 1e-4 (none observed)."""
+random cases allow a mismatch only where the oracle's own top-2 final scores are closer than 1e-4 (none observed).  Every kernel form
+(walk kernels, fold groups, class counts, back-pointer placements, the exhaustive kernel, masked classes) is compared on the cases of
+tests/beam_cases.py, whose decision gaps tests/test_beam_cases_host.py asserts on the CPU."""
 import numpy as np
 import pytest
 import torch
 
 from oracle.ctc_ref import beam_decoder as ref_beam, greedy_decoder as ref_greedy
+from tests import beam_cases as bc
+from tests.hip_util import fresh_decoder_engine
 
 pytestmark = pytest.mark.gpu
 
@@ -77,10 +81,6 @@ def test_beam_pruned_equals_exhaustive(C, T, beam, scale, monkeypatch):
     the kernel that ranks all beam x C of them.  (7, 500, 32): back-pointers in more than 64 KB of LDS; (40, 1500, 16): in global memory;
     256 and 2 classes: the ends of the fast path's range.  Every output field must agree exactly (same arithmetic, same tie rules), on peaked and on
     nearly flat logits (many near-ties), full-length and ragged lines."""
-    from conformer_ocr_amd.engine import HipRecognizer
-    from conformer_ocr_amd.spec import HParams
-    hp = HParams(num_classes=2, height=16, encoder_dim=16, num_encoder_layers=1, num_attention_heads=1, conv_kernel_size=3,
-                 subsampling_conv_channels=8)
     g = np.random.default_rng(C * 7919 + T)
     N = 6
     logits = (g.normal(size=(N, T, C)) * scale).astype(np.float32)
@@ -88,9 +88,9 @@ def test_beam_pruned_equals_exhaustive(C, T, beam, scale, monkeypatch):
     logits[1, :, 1:] = np.round(logits[1, :, 1:] * 2) / 2          # exact ties between classes
     lens = [T, T - 1, T // 2, 1, T, 7]
     x = torch.from_numpy(logits).cuda()
-    fast = HipRecognizer(hp, torch.device('cuda', 0), 'fp32').ctc_beam(x, lens, beam)
+    fast = fresh_decoder_engine().ctc_beam(x, lens, beam)
     monkeypatch.setenv('COCR_BEAM_REF', '1')
-    ref = HipRecognizer(hp, torch.device('cuda', 0), 'fp32').ctc_beam(x, lens, beam)
+    ref = fresh_decoder_engine().ctc_beam(x, lens, beam)
     assert fast == ref
 
 
@@ -115,3 +115,33 @@ def test_metric_model_forward_then_beam16_against_the_oracle(text_case):
             assert [r[:3] for r in got[k]] == [r[:3] for r in want], (dtype, k)
             np.testing.assert_allclose([r[3] for r in got[k]], [r[3] for r in want], rtol=1e-4)
             assert [r[0] for r in got[k]] == tc.ref_strings[idx[k]], (dtype, k)
+
+
+# ---- every kernel form against the oracle (tests/beam_cases.py; tests/test_beam_cases_host.py asserts that each line is decided by
+# ---- at least 1e-4 and that float32 and float64 evaluation of the oracle agree: no line is left out here)
+def _against_the_oracle(eng, spec, beam):
+    x, lens = bc.inputs(spec)
+    got = eng.ctc_beam(torch.from_numpy(x).cuda(), lens, beam)
+    worst = 0.0
+    for n, (want, _) in enumerate(bc.plain_host(spec, beam)):
+        assert [r[:3] for r in got[n]] == [r[:3] for r in want], (spec, beam, n)
+        g, w = np.asarray([r[3] for r in got[n]]), np.asarray([r[3] for r in want])
+        if len(w):
+            worst = max(worst, float(np.max(np.abs(g - w) / w)))
+        np.testing.assert_allclose(g, w, rtol=1e-4)
+    print(f'{spec}, beam {beam}: {sum(len(w) for w, _ in bc.plain_host(spec, beam))} records, worst relative conf difference {worst:.3g}')
+
+
+@pytest.mark.parametrize('name,beam', [(name, beam) for name, (_, beams) in bc.PLAIN.items() for beam in beams])
+def test_every_form_matches_the_oracle(name, beam):
+    """Labels, starts and ends exact, conf to 1e-4, on every line.  Which case selects which form: tests/beam_cases.py PLAIN."""
+    _against_the_oracle(_engine(), bc.PLAIN[name][0], beam)
+
+
+@pytest.mark.parametrize('name', list(bc.PLAIN_EXHAUSTIVE))
+def test_exhaustive_kernel_matches_the_oracle(name, monkeypatch):
+    """ctc_beam_kernel, selected by COCR_BEAM_REF=1 where production runs the fast path -- it is otherwise only the other side of
+    test_beam_pruned_equals_exhaustive, and shares lse2, the hash, the fold rule and the post-pass with the fast path."""
+    monkeypatch.setenv('COCR_BEAM_REF', '1')
+    spec, (beam,) = bc.PLAIN_EXHAUSTIVE[name]
+    _against_the_oracle(fresh_decoder_engine(), spec, beam)

@@ -12,6 +12,7 @@ from conformer_ocr_amd.codec import ascii_codec
 from conformer_ocr_amd.ctc_decoder import LMDecoder
 from conformer_ocr_amd.lm import NGramLM, beam_decode_host, build_lm
 from conformer_ocr_amd.pred import PytorchRecognitionModel
+from tests import beam_cases as bc
 
 pytestmark = pytest.mark.gpu
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -95,6 +96,23 @@ def test_edges(name, C, order, beam, classes, empty):
     lm = build_lm([], order, C) if empty else _chain_lm(C, order, seed=C + order)
     T = 24
     assert _against_host(_engine(), _logits(C, T, 2), [T, T - 5], lm, beam, classes, 0.7, 0.5) == 0, name
+
+
+@pytest.mark.parametrize('name', list(bc.LM))
+def test_every_form_with_the_model_on(name):
+    """tests/beam_cases.py LM: beam 32 x 64 classes (all 2048 candidates of the key array), beams 17 and 31, the planted long lines
+    (back-pointers in 68 KB of LDS at T = 500, in global memory for beam 32 at T = 730 and for beam 16 at T = 1386), masked classes.  Every line: integer fields
+    exact, conf and both scores to 1e-4 (tests/test_beam_cases_host.py asserts the definition's gap of every line: none is left out)."""
+    spec, beam, classes, _, _ = bc.LM[name]
+    lm, rows = bc.lm_host(name)
+    x, lens = bc.inputs(spec)
+    got, score = _engine().ctc_beam_lm(torch.from_numpy(x).cuda(), lens, lm, beam, classes, bc.LM_ALPHA, bc.LM_BETA, return_scores=True)
+    for n, (want, (ctc, lmv), gap) in enumerate(rows):
+        assert gap >= GAP
+        assert [r[:3] for r in got[n]] == [r[:3] for r in want], (name, n, gap)
+        np.testing.assert_allclose([r[3] for r in got[n]], [r[3] for r in want], rtol=1e-4)
+        print(f'{name} line {n}: scores {score[n].tolist()} definition {[ctc, lmv]}')
+        np.testing.assert_allclose(score[n], [ctc, lmv], rtol=1e-4, atol=1e-6)
 
 
 def test_arguments_are_checked():

@@ -10,7 +10,10 @@ import pytest
 import torch
 
 from conformer_ocr_amd import _lib
-from conformer_ocr_amd.nbest import ctc_logp, nbest_host
+from conformer_ocr_amd.lm import _log_softmax, records_host
+from conformer_ocr_amd.nbest import ctc_logp, lm_sum, nbest_host
+from tests import beam_cases as bc
+from tests.hip_util import fresh_decoder_engine
 from tests.test_nbest_host import CASES, FEWER, case_inputs, chain_lm, host_case
 
 pytestmark = pytest.mark.gpu
@@ -19,14 +22,6 @@ pytestmark = pytest.mark.gpu
 def _engine():
     from conformer_ocr_amd.ctc_decoder import _scratch_engine
     return _scratch_engine(torch.device('cuda', 0))
-
-
-def _fresh_engine():
-    from conformer_ocr_amd.engine import HipRecognizer
-    from conformer_ocr_amd.spec import HParams
-    hp = HParams(num_classes=2, height=16, encoder_dim=16, num_encoder_layers=1, num_attention_heads=1, conv_kernel_size=3,
-                 subsampling_conv_channels=8)
-    return HipRecognizer(hp, torch.device('cuda', 0), 'fp32')
 
 
 def _raw(eng, x, lens, beam, nbest, lm=None, classes=8, alpha=0.5, beta=0.0, mpl=None, null=None):
@@ -78,7 +73,7 @@ def test_first_hypothesis_is_the_beam_and_fast_equals_exhaustive(Cn, T, beam, sc
     exhaustive path (COCR_BEAM_REF=1).  300 classes: the exhaustive path alone."""
     logits, lens = _beam_shape(Cn, T, scale)
     x = torch.from_numpy(logits).cuda()
-    eng = _fresh_engine()
+    eng = fresh_decoder_engine()
     want = eng.ctc_beam(x, lens, beam)
     full = None
     for nbest in (1, beam):
@@ -88,7 +83,7 @@ def test_first_hypothesis_is_the_beam_and_fast_equals_exhaustive(Cn, T, beam, sc
         assert all(1 <= len(h) <= nbest for h in full)
     assert full[6] == [([], 0.0, 0.0)]                               # the line of length 0
     monkeypatch.setenv('COCR_BEAM_REF', '1')
-    _same(full, _fresh_engine().ctc_beam_nbest(x, lens, beam, beam))
+    _same(full, fresh_decoder_engine().ctc_beam_nbest(x, lens, beam, beam))
 
 
 @pytest.mark.parametrize('Cn,T,beam', [(17, 90, 16), (128, 60, 16)])
@@ -110,10 +105,13 @@ def test_first_hypothesis_is_the_lm_beam(Cn, T, beam):
 
 
 def _loss_of(eng, x, lens, hyps):
-    """-cocr_ctc_loss of every hypothesis of every line (one call per hypothesis rank)."""
+    """-cocr_ctc_loss of every hypothesis of every line (one call per hypothesis rank); None for one the criterion does not take (more
+    than 255 labels)."""
     out = [[None] * len(h) for h in hyps]
     for j in range(max(len(h) for h in hyps)):
-        rows = [n for n, h in enumerate(hyps) if j < len(h)]
+        rows = [n for n, h in enumerate(hyps) if j < len(h) and len(h[j][0]) <= 255]
+        if not rows:
+            continue
         labs = [[r[0] for r in hyps[n][j][0]] for n in rows]
         nll, _ = eng.ctc_loss(x[rows].contiguous(), [lens[n] for n in rows], np.asarray([c for l in labs for c in l], dtype=np.int32),
                               [len(l) for l in labs], with_grad=False)
@@ -158,6 +156,111 @@ def test_against_the_definition_with_a_language_model(Cn, T, beam, nbest):
             assert lmv == wlmv
 
 
+# ---- the scorer's widths, seams and stack placements: every hypothesis against independent references on ITS OWN labels and starts
+# ---- (no decision of the search is involved: tests/beam_cases.py NBEST_L)
+def _planted_batch(Ls, Cn=bc.NBEST_C, gain=bc.NBEST_GAIN, wide=0):
+    """The planted lines of Ls in one zero-padded batch; `wide`: that many classes in all, the added ones noise two below the rest."""
+    lines = [bc.planted_line(L, Cn, gain, 0)[0] for L in Ls]
+    if wide:
+        g = np.random.default_rng(wide)
+        lines = [np.concatenate([l, g.standard_normal((l.shape[0], wide - Cn)).astype(np.float32) - np.float32(2.0)], axis=1) for l in lines]
+    x = np.zeros((len(lines), max(l.shape[0] for l in lines), lines[0].shape[1]), dtype=np.float32)
+    for n, l in enumerate(lines):
+        x[n, :l.shape[0]] = l
+    return x, [l.shape[0] for l in lines]
+
+
+def _check_on_own_labels(eng, x, lens, got, lm=None):
+    """logp against float64 `ctc_logp` and against -cocr_ctc_loss (rtol 2e-6, atol 1e-3), NaN exactly beyond 255 labels; ends exact and
+    conf to 1e-4 against the post-pass restated on the host (lm.records_host) from the hypothesis's labels and starts; with `lm`,
+    lmv = nbest.lm_sum bit for bit.  Returns the label counts seen."""
+    loss = _loss_of(eng, torch.from_numpy(x).cuda(), lens, got)
+    seen, worst = [], 0.0
+    for n, L in enumerate(lens):
+        line = x[n, :L].T
+        lp = _log_softmax(line)
+        for j, (recs, logp, lmv) in enumerate(got[n]):
+            labels = [r[0] for r in recs]
+            seen.append(len(labels))
+            want = records_host(lp, labels, [r[1] for r in recs])
+            assert [r[:3] for r in recs] == [r[:3] for r in want], (n, j)
+            np.testing.assert_allclose([r[3] for r in recs], [r[3] for r in want], rtol=1e-4)
+            assert math.isnan(logp) == (len(labels) > 255), (n, j, len(labels), logp)
+            if len(labels) <= 255:
+                ref = ctc_logp(line, labels)
+                worst = max(worst, abs(logp - ref))
+                np.testing.assert_allclose(logp, ref, rtol=2e-6, atol=1e-3, err_msg=f'line {n} hypothesis {j}: {len(labels)} labels')
+                np.testing.assert_allclose(logp, loss[n][j], rtol=2e-6, atol=1e-3, err_msg=f'line {n} hypothesis {j}: {len(labels)} labels')
+            assert lmv == (lm_sum(lm, labels) if lm is not None else 0.0), (n, j)
+    print(f'{len(seen)} hypotheses of {sorted(set(seen))} labels: worst |logp - float64 definition| {worst:.3g}')
+    return seen
+
+
+_SEAM = {31: 31, 32: 31, 63: 63, 127: 127, 128: 127, 254: 255, 255: 255}      # labels: at most this many on one side, more on the other
+
+
+@pytest.mark.parametrize('Ls', [(L,) for L in bc.NBEST_L] + [bc.NBEST_L], ids=lambda Ls: '-'.join(map(str, Ls)))
+def test_scores_and_records_across_the_scorer_seams(Ls):
+    """nbest_forward<1|2|4|8>: 2 labels + 1 states, 64 per register; the seams are at 31 | 32, 63 | 64 and 127 | 128 labels, the limit
+    at 255 | 256.  Each planted line alone (the narrowest instantiation that holds its longest hypothesis) and all in one call (narrow
+    hypotheses in the widest instantiation).  The order of the hypotheses is the definition's (its gaps on these lines:
+    tests/test_beam_cases_host.py)."""
+    x, lens = _planted_batch(Ls)
+    eng = _engine()
+    got = eng.ctc_beam_nbest(torch.from_numpy(x).cuda(), lens, bc.NBEST_BEAM, bc.NBEST_BEAM)
+    seen = _check_on_own_labels(eng, x, lens, got)
+    for n, L in enumerate(Ls):
+        want = nbest_host(x[n, :lens[n]].T, bc.NBEST_BEAM, bc.NBEST_BEAM)
+        assert [[r[:2] for r in h[0]] for h in got[n]] == [[r[:2] for r in h[0]] for h in want], L
+        counts = [len(h[0]) for h in got[n]]
+        assert min(counts) <= _SEAM[L] < max(counts), (L, counts)                    # both sides of the seam within one line
+    if len(Ls) > 1:
+        for lo, hi in ((0, 31), (32, 63), (64, 127), (128, 255), (256, 10 ** 6)):     # S <= 64, <= 128, <= 256, <= 511, and no score
+            assert any(lo <= c <= hi for c in seen), (lo, hi)
+
+
+def test_workspace_stacks_equal_lds_stacks():
+    """beam = nbest = 32 on a line of 570 frames: 4 + (32 + 32) * 4 = 260 bytes of LDS per frame pass 144 KB from 568 frames on, so the
+    chains' stacks (and the back-pointer rows) are read from the workspace (IN_LDS = false) in the width-8 instantiation; nbest = 4 on
+    the same lines (148 bytes per frame, 84 KB) stays in LDS.
+    Hypotheses 0..3 must be equal in every byte.  The 282 labels of the long line have no score; the second line (200 labels, 401
+    states) is scored in that form, and checked against the references."""
+    x, lens = _planted_batch((282, 200), gain=6.0)
+    assert lens == [570, 406]
+    eng = _engine()
+    xd = torch.from_numpy(x).cuda()
+    rc, big = _raw(eng, xd, lens, 32, 32)
+    rc2, small = _raw(eng, xd, lens, 32, 4)
+    assert rc == rc2 == 0 and (small['nhyp'] == 4).all() and (big['nhyp'] >= 4).all()
+    for k in ('labels', 'starts', 'ends', 'conf', 'counts', 'scores'):
+        assert big[k][:, :4].tobytes() == small[k].tobytes(), k
+    assert (small['counts'][0] > 255).all() and np.isnan(small['scores'][0, :, 0]).all()
+    assert (small['counts'][1] > 127).all() and (small['counts'][1] <= 255).all()
+    seen = _check_on_own_labels(eng, x, lens, eng.ctc_beam_nbest(xd, lens, 32, 32))
+    assert len(seen) == 64
+
+
+def test_ngram_sum_across_the_chunk_border():
+    """Hypotheses of 111..114 labels: the n-gram sum runs in two chunks of 64 lookups, the contexts of labels 64..66 reach back across
+    the border.  lmv = the host's float32 sum bit for bit, for every hypothesis; logp and records as above."""
+    x, lens = _planted_batch((127,))
+    lm = chain_lm(bc.NBEST_C, 3, seed=5)
+    eng = _engine()
+    got = eng.ctc_beam_nbest(torch.from_numpy(x).cuda(), lens, bc.NBEST_BEAM, bc.NBEST_BEAM, lm, 5, 0.7, 0.5)
+    seen = _check_on_own_labels(eng, x, lens, got, lm)
+    assert len(seen) == bc.NBEST_BEAM and min(seen) > 64 + 8
+    assert len({h[2] for h in got[0]}) > 1                                         # (not one sum for all)
+
+
+def test_exhaustive_trail_on_long_hypotheses():
+    """300 classes: ctc_beam_kernel leaves the trail (log Z at stride 1).  The L = 63 line with 294 noise classes added."""
+    x, lens = _planted_batch((63,), wide=300)
+    eng = _engine()
+    got = eng.ctc_beam_nbest(torch.from_numpy(x).cuda(), lens, bc.NBEST_BEAM, bc.NBEST_BEAM)
+    seen = _check_on_own_labels(eng, x, lens, got)
+    assert len(seen) == bc.NBEST_BEAM and min(seen) > 31
+
+
 def _peaked(path, Cn=4, hi=12.0, lo=-6.0):
     m = np.full((len(path), Cn), lo, dtype=np.float32)
     m[np.arange(len(path)), path] = hi
@@ -189,7 +292,7 @@ def test_edges():
         for recs, logp, _ in got[n]:
             np.testing.assert_allclose(logp, ctc_logp(line, [r[0] for r in recs]), rtol=2e-6, atol=1e-3)
     assert [r[0] for r in got[1][0][0]] == [2, 2, 3, 1]
-    # max_per_line smaller than a hypothesis: the full count, truncated rows, as the 1-best writes them
+    # max_per_line smaller than a hypothesis: the full count and the head of the full rows, as the 1-best writes them
     logits, lens = case_inputs(11, 40)
     x = torch.from_numpy(logits).cuda()
     rc, full = _raw(eng, x, lens, 16, 8)
@@ -208,7 +311,9 @@ def test_edges():
     for n in range(4):
         for j in range(int(full['nhyp'][n])):
             keep = min(3, int(full['counts'][n, j]))
-            assert (cut['labels'][n, j, :keep] == full['labels'][n, j, :keep]).all() and (cut['starts'][n, j, :keep] == full['starts'][n, j, :keep]).all()
+            for k in ('labels', 'starts', 'ends'):                    # every field of the full row: the last kept record is bounded by the next label's start
+                assert (cut[k][n, j, :keep] == full[k][n, j, :keep]).all(), (k, n, j)
+            assert cut['conf'][n, j, :keep].tobytes() == full['conf'][n, j, :keep].tobytes(), (n, j)
             assert (cut['labels'][n, j, keep:] == -7).all()
     assert np.array_equal(cut['scores'], full['scores'], equal_nan=True)
     # slots past nhyp: counts 0 and both scores -inf
