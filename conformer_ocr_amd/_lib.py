@@ -59,6 +59,7 @@ SYMBOLS = {
     'cocr_ctc_loss': (_I, [_P, _P, _I, _I, _I, _I32P, _I32P, _I32P, _P, _P, _P]),
     'cocr_distill_loss': (_I, [_P, _P, _P, _I, _I, _I, _I32P, C.c_float, _P, _P, C.c_float, C.c_float, _I, _P]),
     'cocr_ctc_align': (_I, [_P, _P, _I, _I, _I, _I32P, _I32P, _I32P, _P, _P, _P, _P, _P, _P]),
+    'cocr_ctc_align_page': (_I, [_P, _P, _I, _I, _I, _I32P, _I, _I32P, _I32P, _I32P, _I32P, C.POINTER(C.c_uint8), _P, _P, _P, _P, _P, _P, _P, _P]),
     'cocr_ctc_spot': (_I, [_P, _P, _I, _I, _I, _I32P, _I32P, _I32P, _I, _I, C.c_float, _P, _P, _P, _P, _P]),
     'cocr_ctc_spot_pattern': (_I, [_P, _P, _I, _I, _I, _I32P, _I32P, _I32P, _I32P, _I32P, _I32P, _I, _I, C.c_float, _P, _P, _P, _P, _P, _P]),
     'cocr_posterior_pack': (_I, [_P, _P, _I, _I, _I, _I32P, _I, C.c_float, _P, _P, _P]),

@@ -1,5 +1,5 @@
 // What follows the forward behind the C ABI (units of the host layer: model.hip.h): the CTC decoders (greedy, beam, beam with an
-// n-gram model, n-best output of both), the n-gram model itself, the CTC criterion, the distillation term, forced alignment, keyword and pattern spotting and the search index's pack / unpack.
+// n-gram model, n-best output of both), the n-gram model itself, the CTC criterion, the distillation term, forced alignment, text-to-page alignment, keyword and pattern spotting and the search index's pack / unpack.
 #include "model.hip.h"
 #include "ctc.hip.h"
 #include "ctc_lm.hip.h"
@@ -7,6 +7,7 @@
 #include "ctc_loss.hip.h"
 #include "distill.hip.h"
 #include "ctc_align.hip.h"
+#include "ctc_align_page.hip.h"
 #include "ctc_spot.hip.h"
 #include "ctc_spot_graph.hip.h"
 #include "ctc_index.hip.h"
@@ -399,6 +400,96 @@ extern "C" int cocr_ctc_align(cocr_model *m, const float *logits, int N, int T, 
     if ((rc = place_lattice_table(row, row + words * 4, m->dec.align_ws, (size_t)N * words, tab))) return rc;
     HIP_TRY(launch_ctc_align((hipStream_t)stream, t.sj, tab.in_lds, tab.lds, logits, N, T, ncls, t.lens, t.label_lens, t.label_off, t.labels, starts, ends, conf, score,
                              counts, tab.ws, tab.in_lds ? 0 : words));
+    LAUNCH_CHECK();
+    return COCR_OK;
+}
+
+// ------------------------------------------------------------------------------------ text-to-page alignment (ctc_align_page.hip.h)
+extern "C" int cocr_ctc_align_page(cocr_model *m, const float *logits, int N, int T, int ncls, const int32_t *out_lens, int P, const int32_t *page_line_off,
+                                   const int32_t *page_lines, const int32_t *targets, const int32_t *label_lens, const uint8_t *optional, int32_t *line,
+                                   int32_t *starts, int32_t *ends, float *conf, float *score, int32_t *counts, float *line_score, void *stream) {
+    if (!m || !logits || !out_lens || !page_line_off || !label_lens || !score || !counts) return fail(COCR_EINVAL, "null argument");
+    if (N < 1 || T < 1 || ncls < 2) return fail(COCR_EINVAL, "empty problem");
+    if (P < 1) return fail(COCR_EINVAL, "no page");
+    if (ncls > COCR_PAGE_MAX_CLASSES) return fail(COCR_EUNSUPPORTED, "more than %d classes", COCR_PAGE_MAX_CLASSES);
+    int rc = check_out_lens(out_lens, N, T);
+    if (rc) return rc;
+    if (page_line_off[0] != 0) return fail(COCR_EINVAL, "the page line offsets do not begin at 0");
+    for (int p = 0; p < P; ++p)
+        if (page_line_off[p + 1] < page_line_off[p]) return fail(COCR_EINVAL, "page line offsets descend at page %d", p);
+    const size_t lines = (size_t)page_line_off[P];
+    if (lines && (!page_lines || !line_score)) return fail(COCR_EINVAL, "null argument");
+    std::vector<bool> used((size_t)N, false);
+    for (size_t i = 0; i < lines; ++i) {
+        const int32_t r = page_lines[i];
+        if (r < 0 || r >= N) return fail(COCR_EINVAL, "page line %zu names row %d outside [0, %d)", i, r, N);
+        if (used[(size_t)r]) return fail(COCR_EINVAL, "row %d is named by two page lines", r);
+        used[(size_t)r] = true;
+    }
+    size_t total = 0;
+    int max_l = 0;
+    for (int p = 0; p < P; ++p) {
+        if (label_lens[p] < 0) return fail(COCR_EINVAL, "negative label length (page %d)", p);
+        max_l = std::max(max_l, (int)label_lens[p]);
+        total += (size_t)label_lens[p];
+    }
+    if (total && (!targets || !optional || !line || !starts || !ends || !conf)) return fail(COCR_EINVAL, "null argument");
+    if ((rc = check_labels("target", targets, total, ncls))) return rc;
+    for (size_t at = 0, p = 0; p < (size_t)P; at += (size_t)label_lens[p], ++p) {
+        const int L = label_lens[p];
+        const uint8_t *o = optional + at;
+        if (L && (o[0] || o[L - 1])) return fail(COCR_EINVAL, "page %zu: the first and the last label cannot be optional", p);
+        for (int k = 1; k < L; ++k)
+            if (o[k] && o[k - 1]) return fail(COCR_EINVAL, "page %zu: labels %d and %d are both optional", p, k - 1, k);
+    }
+    if (max_l > COCR_PAGE_MAX_LABELS) return fail(COCR_EUNSUPPORTED, "a page of %d labels; the kernel holds %d", max_l, COCR_PAGE_MAX_LABELS);
+    int max_frames = 0;
+    for (int p = 0; p < P; ++p) {
+        const int K = page_line_off[p + 1] - page_line_off[p];
+        if (K > COCR_PAGE_MAX_LINES) return fail(COCR_EUNSUPPORTED, "page %d has %d lines; the kernel holds %d", p, K, COCR_PAGE_MAX_LINES);
+        size_t frames = 0;
+        for (int k = 0; k < K; ++k) frames += (size_t)out_lens[page_lines[page_line_off[p] + k]];
+        if (frames > COCR_PAGE_MAX_FRAMES) return fail(COCR_EUNSUPPORTED, "page %d has %zu frames; the kernel holds %d", p, frames, COCR_PAGE_MAX_FRAMES);
+        max_frames = std::max(max_frames, (int)frames);
+    }
+    // the kernel form by the call's largest S; one workspace region per page: back-pointers, lz, the path's states, the labels' runs
+    const int sj = page_sj_for_states(2 * max_l + 1), waves = page_waves_for_states(2 * max_l + 1, sj);
+    size_t words = 0;
+    std::vector<uint32_t> region((size_t)P);
+    for (int p = 0; p < P; ++p) {
+        size_t frames = 0;
+        for (int k = page_line_off[p]; k < page_line_off[p + 1]; ++k) frames += (size_t)out_lens[page_lines[k]];
+        if (words * 4 > ((size_t)1 << 31)) break;
+        region[(size_t)p] = (uint32_t)words;
+        words += (page_region_words((int)frames, label_lens[p], 64 * sj * waves) + 3) / 4 * 4;
+    }
+    if (words * 4 > ((size_t)1 << 31)) return fail(COCR_EUNSUPPORTED, "the call's tables exceed 2 GiB; align fewer pages per call");
+    HIP_TRY(hipSetDevice(m->device));
+    hipStream_t s = (hipStream_t)stream;
+    // [page line offsets P + 1 | rows | first frames (K + 1 per page) | label offsets P + 1 | labels (+ optional bit) | region offsets P]
+    const size_t ints = 3 * (size_t)P + 2 + 2 * lines + (size_t)P + total;
+    int32_t *h, *d;
+    HIP_TRY(m->dec.page_ring.stage(ints * 4, h, d));
+    int32_t *h_off = h, *h_rows = h + P + 1, *h_first = h_rows + lines, *h_loff = h_first + lines + P, *h_lab = h_loff + P + 1, *h_reg = h_lab + total;
+    memcpy(h_off, page_line_off, (size_t)(P + 1) * 4);
+    if (lines) memcpy(h_rows, page_lines, lines * 4);
+    int32_t lo = 0;
+    for (int p = 0; p < P; ++p) {
+        int32_t *f = h_first + page_line_off[p] + p;
+        int32_t g = 0;
+        for (int k = page_line_off[p]; k < page_line_off[p + 1]; ++k) { *f++ = g; g += out_lens[page_lines[k]]; }
+        *f = g;
+        h_loff[p] = lo;
+        for (int k = 0; k < label_lens[p]; ++k) h_lab[lo + k] = targets[lo + k] | (optional[lo + k] ? COCR_PAGE_OPTIONAL : 0);
+        lo += label_lens[p];
+        h_reg[p] = (int32_t)region[(size_t)p];
+    }
+    h_loff[P] = lo;
+    HIP_TRY(m->dec.page_ring.commit(ints * 4, s));
+    HIP_TRY(m->dec.page_ws.grow(std::max(words, (size_t)4)));
+    const size_t lds = max_frames <= COCR_PAGE_LZ_LDS_FRAMES ? lattice_row_bytes(max_frames) : 0;
+    HIP_TRY(launch_ctc_align_page(s, sj, waves, lds, logits, P, T, ncls, d, d + (h_rows - h), d + (h_first - h), d + (h_loff - h), d + (h_lab - h),
+                                  reinterpret_cast<const uint32_t *>(d + (h_reg - h)), m->dec.page_ws.p, line, starts, ends, conf, score, counts, line_score));
     LAUNCH_CHECK();
     return COCR_OK;
 }

@@ -178,6 +178,8 @@ struct COCR_INTERNAL DecodeScratch {
     DevBuf<float> loss_ws;                  // log-softmax + alpha / beta tables
     DevBuf<float> distill_ws;               // cocr_distill_loss: the per-frame KL values
     DevBuf<unsigned> align_ws;              // back-pointer tables of the lines too long for the LDS
+    UploadRing page_ring;                   // cocr_ctc_align_page: [page line offsets | rows | first frames | label offsets | labels | region offsets]
+    DevBuf<unsigned> page_ws;               // cocr_ctc_align_page: per page the back-pointers, lz, the path's states and the labels' runs
     UploadRing spot_ring;                   // cocr_ctc_spot: [lens | query lens | query offsets | queries]
     DevBuf<unsigned> spot_ws;               // cocr_ctc_spot: per (line, query) the candidate scores and starts of lines too long for the LDS
     UploadRing pattern_ring;                // cocr_ctc_spot_pattern: [lens | state counts | state offsets | edge offsets | classes | flags | predecessor offsets | predecessors]

@@ -441,6 +441,88 @@ class HipRecognizer:
     def ctc_align(self, logits: torch.Tensor, out_lens, targets, label_lens):
         return self.collect_align(self.ctc_align_async(logits, out_lens, targets, label_lens))
 
+    # ---- text-to-page alignment (include/cocr.h: cocr_ctc_align_page) ----------
+    def ctc_align_page_async(self, logits: torch.Tensor, out_lens, pages, targets, optional=None):
+        """Enqueues the alignment of every page's label sequence to the frames of its lines on the current stream, its outputs in
+        pinned host memory; returns a handle for `collect_align_page`.  logits (N,T,ncls) float32 on this device; out_lens (N) valid
+        frames; pages: per page the rows of `logits` that are its lines in reading order (a row in at most one page); targets: per
+        page its labels (at most 4095); optional: per page one bool per label (None: none may be skipped).  Does not touch the
+        forward's per-frame argmax."""
+        if logits.device != self.device or logits.dtype != torch.float32 or logits.dim() != 3:
+            raise RuntimeError('logits must be a float32 (N,T,num_classes) tensor on the model device')
+        cont = logits.contiguous()
+        N, T, ncls = cont.shape
+        P = len(pages)
+        if len(targets) != P or (optional is not None and len(optional) != P):
+            raise ValueError('targets and optional need one entry per page')
+        lens = np.ascontiguousarray(np.asarray(out_lens, dtype=np.int32).reshape(-1))
+        if lens.shape[0] != N:
+            raise ValueError('out_lens needs one entry per line')
+        rows = [np.asarray(pg, dtype=np.int32).reshape(-1) for pg in pages]
+        labs = [np.asarray(t, dtype=np.int32).reshape(-1) for t in targets]
+        opts = [np.zeros(l.shape[0], dtype=np.uint8) if optional is None or optional[p] is None else
+                np.asarray(optional[p]).astype(bool).astype(np.uint8).reshape(-1) for p, l in enumerate(labs)]
+        if any(o.shape[0] != l.shape[0] for o, l in zip(opts, labs)):
+            raise ValueError('optional needs one entry per label')
+        i32 = np.int32
+        line_off = np.ascontiguousarray(np.concatenate([[0], np.cumsum([r.shape[0] for r in rows])]).astype(i32))
+        tl = np.ascontiguousarray(np.array([l.shape[0] for l in labs], dtype=i32))
+        page_lines = np.ascontiguousarray(np.concatenate(rows + [np.zeros(0, i32)]).astype(i32))
+        tg = np.ascontiguousarray(np.concatenate(labs + [np.zeros(0, i32)]).astype(i32))
+        op = np.ascontiguousarray(np.concatenate(opts + [np.zeros(0, np.uint8)]).astype(np.uint8))
+        total, lines = int(tg.shape[0]), int(page_lines.shape[0])
+
+        def cap(n):
+            return 1 << max(int(n) - 1, 0).bit_length()
+        i32p = C.POINTER(C.c_int32)
+        with torch.cuda.device(self.device):
+            key = ('align_page', cap(total), cap(P), cap(lines))
+            pool = self._pinned.setdefault(key, [])
+            host = pool.pop() if pool else (torch.empty((3, key[1]), dtype=torch.int32).pin_memory(),
+                                            torch.empty((key[1],), dtype=torch.float32).pin_memory(),
+                                            torch.empty((key[2],), dtype=torch.float32).pin_memory(),
+                                            torch.empty((key[2],), dtype=torch.int32).pin_memory(),
+                                            torch.empty((key[3],), dtype=torch.float32).pin_memory())
+            ints, conf, score, counts, line_score = host
+            try:
+                _lib.check(self.lib.cocr_ctc_align_page(
+                    self._h, C.c_void_p(cont.data_ptr()), N, T, ncls, lens.ctypes.data_as(i32p), P, line_off.ctypes.data_as(i32p),
+                    page_lines.ctypes.data_as(i32p), tg.ctypes.data_as(i32p), tl.ctypes.data_as(i32p), op.ctypes.data_as(C.POINTER(C.c_uint8)),
+                    C.c_void_p(ints[0].data_ptr()), C.c_void_p(ints[1].data_ptr()), C.c_void_p(ints[2].data_ptr()), C.c_void_p(conf.data_ptr()),
+                    C.c_void_p(score.data_ptr()), C.c_void_p(counts.data_ptr()), C.c_void_p(line_score.data_ptr()), _stream_ptr(self.device)))
+            except Exception:
+                pool.append(host)                                   # nothing was launched: the buffers go back
+                raise
+            ev = torch.cuda.Event()
+            ev.record(torch.cuda.current_stream(self.device))
+        return (key, host, ev, (cont, tg, tl, line_off))
+
+    def collect_align_page(self, handle):
+        """Waits for a `ctc_align_page_async` handle; per page ([(label, line, start, end, conf)] -- one record per label, a skipped
+        optional label with line = start = end = -1 and conf 0 --, the page's score, the per-line scores as a float32 array), or
+        (None, -inf, None) where the text does not fit: the returns of `align.viterbi_align_page`."""
+        key, host, ev, (_, tg, tl, line_off) = handle
+        ev.synchronize()
+        total = int(tg.shape[0])
+        ln, st, en = host[0].numpy()[:, :total].tolist()
+        cf = host[1].numpy()[:total].tolist()
+        sc, cnt = host[2].numpy().tolist(), host[3].numpy().tolist()
+        ls = host[4].numpy()
+        lab = tg.tolist()
+        out, at = [], 0
+        for p, l in enumerate(tl.tolist()):
+            if cnt[p] >= 0:
+                out.append((list(zip(lab[at:at + l], ln[at:at + l], st[at:at + l], en[at:at + l], cf[at:at + l])), sc[p],
+                            ls[line_off[p]:line_off[p + 1]].copy()))
+            else:
+                out.append((None, sc[p], None))
+            at += l
+        self._pinned[key].append(host)
+        return out
+
+    def ctc_align_page(self, logits: torch.Tensor, out_lens, pages, targets, optional=None):
+        return self.collect_align_page(self.ctc_align_page_async(logits, out_lens, pages, targets, optional))
+
     # ---- keyword spotting (include/cocr.h: cocr_ctc_spot; DESIGN.md section 7i) ----------
     def ctc_spot_async(self, logits: torch.Tensor, out_lens, queries, hits: int = 1, min_score: float = -np.inf):
         """Enqueues the search for every query in every line on the current stream, its outputs in pinned host memory; returns a

@@ -224,6 +224,27 @@ int cocr_distill_loss(cocr_model *m, const float *student, const float *teacher,
 int cocr_ctc_align(cocr_model *m, const float *logits, int N, int T, int ncls, const int32_t *out_lens, const int32_t *targets,
                    const int32_t *label_lens, int32_t *starts, int32_t *ends, float *conf, float *score, int32_t *counts, void *stream);
 
+/* Text-to-page alignment (the definition is conformer_ocr_amd/align.py viterbi_align_page): the best path of each
+ * page's running text through the frames of its lines in reading order -- forced alignment over the concatenated frames, where a label
+ * never spans a line break, equal neighbours on the two sides of a break need no blank, and an optional label (a space of the text) may
+ * be absent.  Ties keep the earlier of (stay, from s-1, s-2, s-3, s-4).
+ * logits DEVICE float32 (N,T,ncls).  HOST, checked before any launch: out_lens (N); P pages; page_line_off (P+1) into page_lines, the rows
+ * of logits that are each page's lines in reading order, every row in at most one page; targets (concatenated) and label_lens (P);
+ * optional, one byte per label.  COCR_EINVAL: a label outside [1, ncls), out_lens[n] outside [0, T], a row outside [0, N) or named
+ * twice, two adjacent optional labels or an optional first / last label, descending offsets, P < 1.  COCR_EUNSUPPORTED: a page of more
+ * than 4095 labels (8191 states: 16 waves x 8 registers per lane; the form of 16 registers does not fit the register file without
+ * scratch and is not offered -- longer texts go through the host definition), 65535 frames or 4096 lines; a call whose tables exceed
+ * 2 GiB (then align fewer pages per call); more than 2^22 classes (a state's class travels as a byte offset beside its flags).
+ * Outputs DEVICE or device-visible pinned host memory.  Per label, packed in target order: line int32 (index within the page's lines),
+ * starts / ends int32 (frames within that line), conf float32; a skipped optional label has -1, -1, -1 and 0.  Per page: score float32,
+ * counts int32 = label_lens[p], or -1 where the text does not fit (score -inf; the page's line / starts / ends are -1, conf 0, its line
+ * scores -inf).  Per page line, packed as page_lines: line_score float32, the sum of the path's log-probabilities over the line's frames.
+ * Deterministic (no atomics).  Stream-ordered, does not synchronise (ring or workspace growth does).  Leaves the greedy decoder's
+ * per-frame argmax alone. */
+int cocr_ctc_align_page(cocr_model *m, const float *logits, int N, int T, int ncls, const int32_t *out_lens, int P, const int32_t *page_line_off,
+                        const int32_t *page_lines, const int32_t *targets, const int32_t *label_lens, const uint8_t *optional, int32_t *line,
+                        int32_t *starts, int32_t *ends, float *conf, float *score, int32_t *counts, float *line_score, void *stream);
+
 /* Keyword spotting (the definition is conformer_ocr_amd/search.py spot_host): where each of Q label sequences
  * occurs in each of N lines.  With r_t(c) = logits[t, c] - max_c' logits[t, c'], a candidate ending at frame t is the best path that
  * spells the query over some window [start, t] -- first frame on the first label, last frame on the last label, blanks between labels

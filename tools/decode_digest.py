@@ -116,6 +116,18 @@ def run_leg(leg):
         lm = TL._chain_lm(C, order, seed=C * 31 + order)
         got, score = eng.ctc_beam_lm(dev(TL._logits(C, T, 4)), [T, T - 3, max(1, T // 2), 1], lm, beam, classes, 0.7, 0.5, return_scores=True)
         out[f'beam_lm/model/{(C, T, beam, classes, order)}'] = {'records': sha(got), 'score': sha(score)}
+    # text-to-page alignment: the planted pages of its test (one, two and eight registers per lane), every output of the call
+    from tests import test_hip_align_page as TG
+    for P, K, T, C, L, seed in _params(TG.test_planted_pages):
+        rng = np.random.default_rng(seed)
+        pages = [TG._planted_page(K, T, C, L + p, rng) for p in range(P)]
+        h = eng.ctc_align_page_async(dev(np.concatenate([pg[0] for pg in pages])), [T] * (P * K), [list(range(p * K, (p + 1) * K)) for p in range(P)],
+                                     [pg[2] for pg in pages], [pg[3] for pg in pages])
+        records = eng.collect_align_page(h)
+        total = sum(len(pg[2]) for pg in pages)
+        ints, conf, score, counts, line_score = h[1]
+        raw = [ints.numpy()[:, :total], conf.numpy()[:total], score.numpy()[:P], counts.numpy()[:P], line_score.numpy()[:P * K]]
+        out[f'align_page/{(P, K, T, C, L)}'] = {'records': sha([(r, s, None if l is None else l.tolist()) for r, s, l in records]), 'raw': sha(raw)}
     return out
 
 
@@ -134,7 +146,9 @@ def main():
             print(f'leg {leg} ended with status {r.returncode}', file=sys.stderr)
             return r.returncode or 1
         out.update(json.loads(r.stdout.strip().splitlines()[-1]))
-    text = json.dumps(out, indent=1, sort_keys=True)
+    # the digests older runs have, sorted as they always were, then those of text-to-page alignment: the head of the output compares
+    new = {k: out.pop(k) for k in sorted(out) if k.startswith('align_page/')}
+    text = json.dumps(out, indent=1, sort_keys=True)[:-2] + ',\n' + json.dumps(new, indent=1, sort_keys=True)[2:]
     if args.out:
         with open(args.out, 'w') as fp:
             fp.write(text + '\n')
