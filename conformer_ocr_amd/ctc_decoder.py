@@ -8,7 +8,6 @@ GPU as well.  Any other callable put into `ctc_decoder` is honoured through the 
 per-line host loop."""
 from __future__ import annotations
 
-import ctypes as C
 from typing import List, Tuple
 
 import numpy as np
@@ -18,26 +17,22 @@ from . import _lib
 
 
 class _DeviceDecoder:
-    kind = 'greedy'
+    """A decoder the engine runs: `decode_async(eng, logits, out_lens)` enqueues the whole batch on `eng`'s device and returns a handle
+    for `eng.collect` / `eng.collect_labels`."""
     beam_size = 0
 
+    def decode(self, eng, logits, out_lens):
+        return eng.collect(self.decode_async(eng, logits, out_lens))
+
     def _run(self, outputs: np.ndarray, device=None):
-        lib = _lib.load()
+        _lib.load()
         dev = torch.device('cuda', torch.cuda.current_device()) if device is None else torch.device(device)
         m = np.ascontiguousarray(np.asarray(outputs, dtype=np.float32).T)           # (T, C)
-        T, ncls = m.shape
+        T = m.shape[0]
         if T == 0:
             return []
-        from .engine import HipRecognizer
-        from .spec import HParams
         # a decoder call needs only a device context: borrow a minimal model handle for scratch space
-        eng = _scratch_engine(dev)
-        lg = torch.from_numpy(m).to(dev).unsqueeze(0)
-        if self.kind == 'greedy':
-            return eng.ctc_greedy(lg, [T])[0]
-        if self.kind == 'lm':
-            return self.decode(eng, lg, [T])[0]
-        return eng.ctc_beam(lg, [T], self.beam_size)[0]
+        return self.decode(_scratch_engine(dev), torch.from_numpy(m).to(dev).unsqueeze(0), [T])[0]
 
     def __call__(self, outputs: np.ndarray) -> List[Tuple[int, int, int, float]]:
         return self._run(outputs)
@@ -45,7 +40,9 @@ class _DeviceDecoder:
 
 class GreedyDecoder(_DeviceDecoder):
     """kraken.lib.ctc_decoder.greedy_decoder: argmax, merge runs, drop blank 0."""
-    kind = 'greedy'
+
+    def decode_async(self, eng, logits, out_lens):
+        return eng.ctc_greedy_async(logits, out_lens)
 
     def __repr__(self):
         return 'greedy_decoder<hip>'
@@ -53,10 +50,12 @@ class GreedyDecoder(_DeviceDecoder):
 
 class BeamDecoder(_DeviceDecoder):
     """CTC prefix beam search over log-softmax(logits); semantics in include/cocr.h (cocr_ctc_beam)."""
-    kind = 'beam'
 
     def __init__(self, beam_size: int = 16):
         self.beam_size = int(beam_size)
+
+    def decode_async(self, eng, logits, out_lens):
+        return eng.ctc_beam_async(logits, out_lens, self.beam_size)
 
     def __repr__(self):
         return f'beam_decoder<hip,{self.beam_size}>'
@@ -67,7 +66,6 @@ class LMDecoder(_DeviceDecoder):
     cocr_ctc_beam_lm).  `lm`: an `lm.NGramLM` or the path of its file.  alpha weighs the model's log-probabilities, beta is a
     bonus per label, `classes` the candidate classes per frame.  The defaults 0.5 / 0 / 8 are placeholders, not tuned on real
     material: `python -m conformer_ocr_amd.lm tune` finds the values for yours."""
-    kind = 'lm'
 
     def __init__(self, lm, beam_size: int = 16, alpha: float = 0.5, beta: float = 0.0, classes: int = 8):
         if isinstance(lm, (str, bytes)) or hasattr(lm, '__fspath__'):
@@ -79,9 +77,6 @@ class LMDecoder(_DeviceDecoder):
     def decode_async(self, eng, logits, out_lens):
         """The whole batch in one launch pair on `eng`'s device; a handle for `eng.collect` / `eng.collect_labels`."""
         return eng.ctc_beam_lm_async(logits, out_lens, self.lm, self.beam_size, self.classes, self.alpha, self.beta)
-
-    def decode(self, eng, logits, out_lens):
-        return eng.collect(self.decode_async(eng, logits, out_lens))
 
     def __repr__(self):
         return f'lm_beam_decoder<hip,{self.beam_size},order {self.lm.order},alpha {self.alpha:g},beta {self.beta:g},classes {self.classes}>'

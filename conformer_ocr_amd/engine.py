@@ -13,22 +13,61 @@ from . import _lib
 from .spec import HParams
 
 DTYPES = {'bf16': _lib.BF16, 'bfloat16': _lib.BF16, 'fp32': _lib.F32, 'f32': _lib.F32, 'float32': _lib.F32}
+_OPTIMIZER_NAMES = {v: k for k, v in _lib.OPTIMIZERS.items()}
 
 
 def _stream_ptr(device: torch.device) -> C.c_void_p:
     return C.c_void_p(torch.cuda.current_stream(device).cuda_stream)
 
 
-def _target_arrays(N: int, out_lens, targets, label_lens):
-    """The contiguous int32 host vectors (lens, label lens, labels) `cocr_ctc_loss` and `cocr_ctc_align` take for N lines."""
-    lens = np.ascontiguousarray(np.asarray(out_lens, dtype=np.int32).reshape(-1))
-    tl = np.ascontiguousarray(np.asarray(label_lens, dtype=np.int32).reshape(-1))
-    tg = np.ascontiguousarray(np.asarray(targets, dtype=np.int32).reshape(-1))
+def _dp(t: Optional[torch.Tensor]) -> Optional[int]:
+    """Device (or pinned host) address of a tensor for a `void *` argument, None -> NULL; the declared argtypes convert the int."""
+    return None if t is None else t.data_ptr()
+
+
+_I32P, _I64P = C.POINTER(C.c_int32), C.POINTER(C.c_int64)
+_I32, _F32 = torch.int32, torch.float32
+
+
+def _hp(a: Optional[np.ndarray], ptr=_I32P):
+    """Pointer to a contiguous host array's elements (int32 unless `ptr` names another pointer type), None -> NULL."""
+    return None if a is None else a.ctypes.data_as(ptr)
+
+
+def _i32(values) -> np.ndarray:
+    return np.ascontiguousarray(np.asarray(values, dtype=np.int32).reshape(-1))
+
+
+def _target_arrays(N: int, lens: np.ndarray, targets, label_lens, what: str = 'out_lens'):
+    """Beside `HipRecognizer._lattice_args`, for the calls that take a transcription: the contiguous int32 host vectors (label lens,
+    labels) of N lines whose `lens` that helper (or `train_step`) has made."""
+    tl, tg = _i32(label_lens), _i32(targets)
     if lens.shape[0] != N or tl.shape[0] != N:
-        raise ValueError('out_lens and label_lens need one entry per line')
+        raise ValueError(f'{what} and label_lens need one entry per line')
     if int(tl.sum()) != tg.shape[0]:
         raise ValueError('targets must hold sum(label_lens) labels')
-    return lens, tl, tg
+    return tl, tg
+
+
+def _mem_view(owner, ptr: int, n: int, typestr: str, device: torch.device) -> torch.Tensor:
+    """`n` elements of library-owned device memory as a torch view; the view keeps `owner` (the model) alive."""
+    class _Mem:
+        __cuda_array_interface__ = {'shape': (n,), 'typestr': typestr, 'data': (ptr, False), 'version': 2}
+        keep = owner
+    return torch.as_tensor(_Mem(), device=device)
+
+
+class _Handle:
+    """An enqueued call whose outputs land in pinned host memory: the pool `key` its buffers `host` go back to, the event `ev` recorded
+    behind the call, what must stay alive until then (`keep`), and the values its `collect_*` reads (`meta`).  Indexable in that
+    order, for callers that look at the raw buffers."""
+    __slots__ = ('key', 'host', 'ev', 'keep', 'meta')
+
+    def __init__(self, key, host, ev, keep, meta):
+        self.key, self.host, self.ev, self.keep, self.meta = key, host, ev, keep, meta
+
+    def __getitem__(self, i):
+        return getattr(self, self.__slots__[i])
 
 
 _LAST_WRITER: Dict[int, int] = {}         # logits buffer address -> sequence number of the last `forward` (of any engine) that wrote it
@@ -79,7 +118,7 @@ class HipRecognizer:
             arr = val.detach().cpu().float().numpy() if isinstance(val, torch.Tensor) else np.asarray(val, dtype=np.float32)
             arr = np.ascontiguousarray(arr, dtype=np.float32)
             shape = (C.c_int64 * max(arr.ndim, 1))(*arr.shape)
-            _lib.check(self.lib.cocr_set_tensor(self._h, name.encode(), arr.ctypes.data_as(C.c_void_p), _lib.F32, arr.ndim, shape))
+            _lib.check(self.lib.cocr_set_tensor(self._h, name.encode(), _hp(arr, C.c_void_p), _lib.F32, arr.ndim, shape))
         if strict:
             buf = C.create_string_buffer(1 << 16)
             n = self.lib.cocr_missing_tensors(self._h, buf, len(buf))
@@ -102,33 +141,29 @@ class HipRecognizer:
 
     def weight_blob(self) -> torch.Tensor:
         """The packed device blob as a uint8 torch view (for an RCCL broadcast through torch.distributed)."""
+        return _mem_view(self, *self._blob(), '|u1', self.device)
+
+    def _blob(self) -> Tuple[int, int]:
         p, n = C.c_void_p(), C.c_size_t()
         _lib.check(self.lib.cocr_weight_blob(self._h, C.byref(p), C.byref(n)))
-
-        class _Mem:   # __cuda_array_interface__ view of library-owned memory; `owner` keeps the model alive
-            def __init__(s, owner):
-                s.owner = owner
-                s.__cuda_array_interface__ = {'shape': (n.value,), 'typestr': '|u1', 'data': (p.value, False), 'version': 2}
-        return torch.as_tensor(_Mem(self), device=self.device)
+        return p.value, int(n.value)
 
     def blob_nbytes(self) -> int:
-        p, n = C.c_void_p(), C.c_size_t()
-        _lib.check(self.lib.cocr_weight_blob(self._h, C.byref(p), C.byref(n)))
-        return int(n.value)
+        return self._blob()[1]
 
     def export_blob(self, out: Optional[torch.Tensor] = None) -> torch.Tensor:
         """Packed weights copied into a torch-owned uint8 tensor (the buffer a collective runs on)."""
         n = self.blob_nbytes()
         buf = out if out is not None else torch.empty(n, dtype=torch.uint8, device=self.device)
         with torch.cuda.device(self.device):
-            _lib.check(self.lib.cocr_blob_export(self._h, C.c_void_p(buf.data_ptr()), n, _stream_ptr(self.device)))
+            _lib.check(self.lib.cocr_blob_export(self._h, _dp(buf), n, _stream_ptr(self.device)))
         return buf
 
     def import_blob(self, buf: torch.Tensor) -> None:
         if buf.dtype != torch.uint8 or buf.device != self.device or not buf.is_contiguous():
             raise ValueError('blob buffer must be a contiguous uint8 tensor on the model device')
         with torch.cuda.device(self.device):
-            _lib.check(self.lib.cocr_blob_import(self._h, C.c_void_p(buf.data_ptr()), buf.numel(), _stream_ptr(self.device)))
+            _lib.check(self.lib.cocr_blob_import(self._h, _dp(buf), buf.numel(), _stream_ptr(self.device)))
 
     # ---- compute -------------------------------------------------------------------------------
     def out_len(self, w: int) -> int:
@@ -167,7 +202,7 @@ class HipRecognizer:
             ldt = _lib.F32
         lines = lines.contiguous()
         N, H, W = lines.shape
-        in_lens = np.ascontiguousarray(np.asarray(lens, dtype=np.int32).reshape(-1))
+        in_lens = _i32(lens)
         if in_lens.shape[0] != N:
             raise ValueError('lens must have one entry per line')
         out_lens = np.zeros(N, dtype=np.int32)
@@ -176,9 +211,7 @@ class HipRecognizer:
         if logits.shape != (N, T, self.hp.num_classes) or logits.dtype != torch.float32 or not logits.is_contiguous():
             raise ValueError('out must be a contiguous float32 (N,T,num_classes) tensor')
         with torch.cuda.device(self.device):
-            _lib.check(self.lib.cocr_forward(self._h, C.c_void_p(lines.data_ptr()), ldt, N, H, W,
-                                             in_lens.ctypes.data_as(C.POINTER(C.c_int32)), C.c_void_p(logits.data_ptr()),
-                                             out_lens.ctypes.data_as(C.POINTER(C.c_int32)), _stream_ptr(self.device)))
+            _lib.check(self.lib.cocr_forward(self._h, _dp(lines), ldt, N, H, W, _hp(in_lens), _dp(logits), _hp(out_lens), _stream_ptr(self.device)))
         # The decoder epilogue's per-frame argmax belongs to THESE values: to this tensor object (not to its address: the caching
         # allocator hands a freed address to the next same-sized tensor), at this version, and only while no other engine's forward
         # has written the same buffer since (writes through the C ABI do not bump `_version`: `_LAST_WRITER` records them).
@@ -193,84 +226,97 @@ class HipRecognizer:
         ref, ver, seq = getattr(self, '_fresh_logits', None) or (None, -1, -1)
         return ref is not None and ref() is logits and logits._version == ver and _LAST_WRITER.get(logits.data_ptr()) == seq
 
-    def _decode_async(self, fn, logits: torch.Tensor, out_lens, extra=()):
-        """Enqueues the decode kernel on the current stream, its outputs in pinned host memory; returns a handle for `collect`
-        (the pinned buffers + an event)."""
-        if logits.device != self.device or logits.dtype != torch.float32:
-            raise RuntimeError('logits must be float32 on the model device')
-        fresh = self._argmax_is_fresh(logits)
+    # ---- calls on a lattice: one argument check, one path for outputs in pinned host memory ----------
+    def _lattice_args(self, logits: torch.Tensor, out_lens=None, name: str = 'logits'):
+        """The argument check of every call that takes (N,T,ncls) values and their valid lengths: (contiguous logits, N, T, ncls, int32
+        host vector of the lengths -- None without `out_lens`).  RuntimeError for device, dtype or rank, ValueError for the count."""
+        if logits.device != self.device or logits.dtype != torch.float32 or logits.dim() != 3:
+            raise RuntimeError(f'{name} must be a float32 (N,T,num_classes) tensor on the model device')
         logits = logits.contiguous()
         N, T, ncls = logits.shape
-        lens = np.ascontiguousarray(np.asarray(out_lens, dtype=np.int32).reshape(-1))
-        if not fresh:
-            _lib.check(self.lib.cocr_forget_argmax(self._h))          # other logits, or edited in place since the forward: decode from the values
+        lens = None if out_lens is None else _i32(out_lens)
+        if lens is not None and lens.shape[0] != N:
+            raise ValueError('out_lens needs one entry per line')
+        return logits, N, T, ncls, lens
+
+    def _enqueue(self, fn, lat, key, shapes, tail, head=(), keep=(), meta=None) -> _Handle:
+        """Enqueues `fn(model, *head, logits, N, T, ncls, lens, *tail(*buffers), stream)` on the current stream, `lat` the checked
+        arguments of `_lattice_args`, the buffers taken from the pool `key` or allocated as `shapes` says ((shape, dtype) each).  The
+        kernels write their outputs STRAIGHT into that pinned host memory (device-visible): no device->host copy is enqueued.  A third
+        hipMemcpyAsync D2H in flight (three batches on three streams, each queued behind its forward) blocked the host for a whole
+        forward, 5.5 ms at every start of a run.  Returns the handle `_wait` and `_release` take; `meta` is for its `collect_*`."""
+        pool = self._pinned.setdefault(key, [])
         with torch.cuda.device(self.device):
-            # The decode kernels write their (sparse) label records STRAIGHT into pinned host memory (device-visible): no
-            # device->host copy is enqueued.  A third hipMemcpyAsync D2H in flight (three batches on three streams, each queued
-            # behind its forward) blocked the host for a whole forward, 5.5 ms at every start of a run.
-            key = (N, T)
-            pool = self._pinned.setdefault(key, [])
-            host = pool.pop() if pool else (torch.empty((3, N, T), dtype=torch.int32).pin_memory(),
-                                            torch.empty((N, T), dtype=torch.float32).pin_memory(),
-                                            torch.empty((N,), dtype=torch.int32).pin_memory())
-            ints, conf, counts = host
-            _lib.check(fn(self._h, C.c_void_p(logits.data_ptr()), N, T, ncls, lens.ctypes.data_as(C.POINTER(C.c_int32)),
-                          C.c_void_p(ints[0].data_ptr()), C.c_void_p(ints[1].data_ptr()), C.c_void_p(ints[2].data_ptr()),
-                          C.c_void_p(conf.data_ptr()), C.c_void_p(counts.data_ptr()), T, *extra, _stream_ptr(self.device)))
+            host = pool.pop() if pool else tuple(torch.empty(s, dtype=d).pin_memory() for s, d in shapes)
+            try:
+                _lib.check(fn(self._h, *head, _dp(lat[0]), *lat[1:4], _hp(lat[4]), *tail(*host), _stream_ptr(self.device)))
+            except Exception:
+                pool.append(host)                                   # nothing was launched: the buffers go back
+                raise
             ev = torch.cuda.Event()
             ev.record(torch.cuda.current_stream(self.device))
-        return (key, host, ev, (logits,))
+        return _Handle(key, host, ev, (lat[0],) + keep, meta)
+
+    def _wait(self, handle: _Handle):
+        handle.ev.synchronize()
+        return handle.host
+
+    def _release(self, handle: _Handle) -> None:
+        self._pinned[handle.key].append(handle.host)
+
+    def _decode_async(self, fn, logits: torch.Tensor, out_lens, extra=(), head=(), keep=()) -> _Handle:
+        """Enqueues a decode kernel (greedy or a beam) on the current stream; returns a handle for `collect` / `collect_labels`."""
+        fresh = self._argmax_is_fresh(logits)                        # of the caller's tensor: `.contiguous()` may make another
+        lat = self._lattice_args(logits, out_lens)
+        if not fresh:
+            _lib.check(self.lib.cocr_forget_argmax(self._h))          # other logits, or edited in place since the forward: decode from the values
+        N, T = lat[1], lat[2]
+        return self._enqueue(fn, lat, (N, T), (((3, N, T), _I32), ((N, T), _F32), ((N,), _I32)),
+                             lambda ints, conf, counts: (_dp(ints[0]), _dp(ints[1]), _dp(ints[2]), _dp(conf), _dp(counts), T, *extra), head, keep)
 
     def collect(self, handle) -> List[List[Tuple[int, int, int, float]]]:
-        """Waits for a `_decode_async` handle and builds the per-line (label, start, end, conf) lists."""
-        key, host, ev, _keep = handle
-        ev.synchronize()
+        """Waits for a decode handle and builds the per-line (label, start, end, conf) lists."""
+        host = self._wait(handle)
         ints_h, conf_h, cnt = host[0].numpy(), host[1].numpy(), host[2].numpy()
         # one conversion per array for the whole batch (per-line slices + tolist: 110 us for 32 lines, after the GPU has finished)
-        cl = cnt[:key[0]].tolist()
+        cl = cnt.tolist()
         mx = max(cl) if cl else 0
         lab, st, en = ints_h[:, :, :mx].tolist()
         cf = conf_h[:, :mx].tolist()
         out = [list(zip(lab[n][:c], st[n][:c], en[n][:c], cf[n][:c])) for n, c in enumerate(cl)]
-        self._pinned[key].append(host)
+        self._release(handle)
         return out
 
     def collect_labels(self, handle) -> List[np.ndarray]:
-        """Waits for a `_decode_async` handle; per line the int32 label array only (copies: the pinned buffers go back to the pool) --
+        """Waits for a decode handle; per line the int32 label array only (copies: the pinned buffers go back to the pool) --
         what `predict_string` needs, without building four Python lists per line."""
-        key, host, ev, _keep = handle
-        ev.synchronize()
-        lab, cnt = host[0].numpy()[0], host[2].numpy()
-        cl = cnt[:key[0]].tolist()
+        host = self._wait(handle)
+        cl = host[2].numpy().tolist()
         mx = max(cl) if cl else 0
-        block = lab[:, :mx].copy()
-        self._pinned[key].append(host)
+        block = host[0].numpy()[0, :, :mx].copy()
+        self._release(handle)
         return [block[n, :c] for n, c in enumerate(cl)]
 
-    def _decode(self, fn, logits: torch.Tensor, out_lens, extra=()) -> List[List[Tuple[int, int, int, float]]]:
-        return self.collect(self._decode_async(fn, logits, out_lens, extra))
-
-    def ctc_greedy_async(self, logits: torch.Tensor, out_lens):
+    def ctc_greedy_async(self, logits: torch.Tensor, out_lens) -> _Handle:
         return self._decode_async(self.lib.cocr_ctc_greedy, logits, out_lens)
 
     def ctc_greedy(self, logits: torch.Tensor, out_lens) -> List[List[Tuple[int, int, int, float]]]:
-        return self._decode(self.lib.cocr_ctc_greedy, logits, out_lens)
+        return self.collect(self.ctc_greedy_async(logits, out_lens))
+
+    def ctc_beam_async(self, logits: torch.Tensor, out_lens, beam: int = 16) -> _Handle:
+        return self._decode_async(self.lib.cocr_ctc_beam, logits, out_lens, (int(beam),))
 
     def ctc_beam(self, logits: torch.Tensor, out_lens, beam: int = 16) -> List[List[Tuple[int, int, int, float]]]:
-        return self._decode(self.lib.cocr_ctc_beam, logits, out_lens, extra=(int(beam),))
+        return self.collect(self.ctc_beam_async(logits, out_lens, beam))
 
     def ctc_beam_lm_async(self, logits: torch.Tensor, out_lens, lm, beam: int = 16, classes: int = 8, alpha: float = 0.5, beta: float = 0.0,
-                          score: Optional[torch.Tensor] = None):
+                          score: Optional[torch.Tensor] = None) -> _Handle:
         """`cocr_ctc_beam_lm` (include/cocr.h) enqueued on the current stream: the beam search with the n-gram
         model `lm` (an `lm.NGramLM`; its tables are copied to this device once) in the ranking.  Returns a handle for `collect` /
         `collect_labels`.  `score`: an optional pinned or device float32 (N,2) tensor for (CTC log-probability, lmv) per line."""
         dlm = lm.to_device(self)
-        sp = C.c_void_p(score.data_ptr()) if score is not None else None
-
-        def fn(h, *args):
-            return self.lib.cocr_ctc_beam_lm(h, dlm.handle, *args)
-        key, host, ev, keep = self._decode_async(fn, logits, out_lens, extra=(int(beam), int(classes), C.c_float(alpha), C.c_float(beta), sp))
-        return (key, host, ev, keep + (dlm, score))
+        return self._decode_async(self.lib.cocr_ctc_beam_lm, logits, out_lens, (int(beam), int(classes), float(alpha), float(beta), _dp(score)),
+                                  head=(dlm.handle,), keep=(dlm, score))
 
     def ctc_beam_lm(self, logits: torch.Tensor, out_lens, lm, beam: int = 16, classes: int = 8, alpha: float = 0.5, beta: float = 0.0,
                     return_scores: bool = False):
@@ -281,46 +327,24 @@ class HipRecognizer:
         return (recs, score.numpy().copy()) if return_scores else recs
 
     def ctc_beam_nbest_async(self, logits: torch.Tensor, out_lens, beam: int = 16, nbest: int = 4, lm=None, classes: int = 8, alpha: float = 0.5,
-                             beta: float = 0.0):
+                             beta: float = 0.0) -> _Handle:
         """`cocr_ctc_beam_nbest` (include/cocr.h) enqueued on the current stream: the first `nbest` prefixes of the
         final beam of `ctc_beam` (or, with `lm`, of `ctc_beam_lm`), each with its exact CTC log-probability and its raw n-gram sum.
-        The records and scores land in pinned host memory, like `_decode_async`'s.  Returns a handle for `collect_nbest`."""
-        if logits.device != self.device or logits.dtype != torch.float32 or logits.dim() != 3:
-            raise RuntimeError('logits must be a float32 (N,T,num_classes) tensor on the model device')
-        logits = logits.contiguous()
-        N, T, ncls = logits.shape
-        nbest = int(nbest)
-        lens = np.ascontiguousarray(np.asarray(out_lens, dtype=np.int32).reshape(-1))
-        if lens.shape[0] != N:
-            raise ValueError('one output length per line')
+        The records and scores land in pinned host memory, like the decoders'.  Returns a handle for `collect_nbest`."""
+        lat = self._lattice_args(logits, out_lens)
+        N, T, nbest = lat[1], lat[2], int(nbest)
+        B = max(nbest, 1)
         dlm = lm.to_device(self) if lm is not None else None
-        with torch.cuda.device(self.device):
-            key = ('nbest', N, T, max(nbest, 1))
-            pool = self._pinned.setdefault(key, [])
-            host = pool.pop() if pool else (torch.empty((3, N, key[3], T), dtype=torch.int32).pin_memory(),
-                                            torch.empty((N, key[3], T), dtype=torch.float32).pin_memory(),
-                                            torch.empty((N, key[3]), dtype=torch.int32).pin_memory(),
-                                            torch.empty((N,), dtype=torch.int32).pin_memory(),
-                                            torch.empty((N, key[3], 2), dtype=torch.float32).pin_memory())
-            ints, conf, counts, nhyp, scores = host
-            vp = lambda t: C.c_void_p(t.data_ptr())
-            try:
-                _lib.check(self.lib.cocr_ctc_beam_nbest(self._h, dlm.handle if dlm is not None else None, vp(logits), N, T, ncls,
-                                                        lens.ctypes.data_as(C.POINTER(C.c_int32)), int(beam), nbest, int(classes), C.c_float(alpha),
-                                                        C.c_float(beta), vp(ints[0]), vp(ints[1]), vp(ints[2]), vp(conf), vp(counts), vp(nhyp), vp(scores),
-                                                        T, _stream_ptr(self.device)))
-            except Exception:
-                pool.append(host)
-                raise
-            ev = torch.cuda.Event()
-            ev.record(torch.cuda.current_stream(self.device))
-        return (key, host, ev, (logits, dlm))
+        return self._enqueue(
+            self.lib.cocr_ctc_beam_nbest, lat, ('nbest', N, T, B),
+            (((3, N, B, T), _I32), ((N, B, T), _F32), ((N, B), _I32), ((N,), _I32), ((N, B, 2), _F32)),
+            lambda ints, conf, counts, nhyp, scores: (int(beam), nbest, int(classes), float(alpha), float(beta), _dp(ints[0]), _dp(ints[1]),
+                                                      _dp(ints[2]), _dp(conf), _dp(counts), _dp(nhyp), _dp(scores), T),
+            head=(dlm.handle if dlm is not None else None,), keep=(dlm,))
 
     def collect_nbest(self, handle) -> List[List[Tuple[List[Tuple[int, int, int, float]], float, float]]]:
         """Waits for a `ctc_beam_nbest_async` handle; per line its hypotheses in beam order, each (records, logp, lm_logp)."""
-        key, host, ev, _keep = handle
-        ev.synchronize()
-        ints, conf, counts, nhyp, scores = (h.numpy() for h in host)
+        ints, conf, counts, nhyp, scores = (h.numpy() for h in self._wait(handle))
         out = []
         for n, nh in enumerate(nhyp.tolist()):
             hyps = []
@@ -329,7 +353,7 @@ class HipRecognizer:
                 lab, st, en = ints[:, n, j, :c].tolist()
                 hyps.append((list(zip(lab, st, en, conf[n, j, :c].tolist())), float(scores[n, j, 0]), float(scores[n, j, 1])))
             out.append(hyps)
-        self._pinned[key].append(host)
+        self._release(handle)
         return out
 
     def ctc_beam_nbest(self, logits: torch.Tensor, out_lens, beam: int = 16, nbest: int = 4, lm=None, classes: int = 8, alpha: float = 0.5,
@@ -343,19 +367,13 @@ class HipRecognizer:
         probits (N,T,ncls) float32 on this device; out_lens (N) valid frames; targets: the batch's concatenated 1-D label vector,
         label_lens (N) its per-line lengths (host sequences).  Returns (per-line nll (N) float32 device tensor -- 0 where no
         alignment exists --, d sum(nll) / d probits (N,T,ncls) or None); the reference's loss is `nll.sum()`.  Stream-ordered."""
-        if probits.device != self.device or probits.dtype != torch.float32 or probits.dim() != 3:
-            raise RuntimeError('probits must be a float32 (N,T,num_classes) tensor on the model device')
-        probits = probits.contiguous()
-        N, T, ncls = probits.shape
-        lens, tl, tg = _target_arrays(N, out_lens, targets, label_lens)
+        probits, N, T, ncls, lens = self._lattice_args(probits, out_lens, 'probits')
+        tl, tg = _target_arrays(N, lens, targets, label_lens)
         nll = torch.empty((N,), dtype=torch.float32, device=self.device)
         grad = torch.empty_like(probits) if with_grad else None
-        i32 = C.POINTER(C.c_int32)
         with torch.cuda.device(self.device):
-            _lib.check(self.lib.cocr_ctc_loss(self._h, C.c_void_p(probits.data_ptr()), N, T, ncls, lens.ctypes.data_as(i32),
-                                              tg.ctypes.data_as(i32) if tg.shape[0] else None, tl.ctypes.data_as(i32),
-                                              C.c_void_p(nll.data_ptr()), C.c_void_p(grad.data_ptr()) if with_grad else None,
-                                              _stream_ptr(self.device)))
+            _lib.check(self.lib.cocr_ctc_loss(self._h, _dp(probits), N, T, ncls, _hp(lens), _hp(tg if tg.shape[0] else None), _hp(tl),
+                                              _dp(nll), _dp(grad), _stream_ptr(self.device)))
         return nll, grad
 
     def distill_loss(self, student: torch.Tensor, teacher: torch.Tensor, out_lens, tau: float, grad: Optional[torch.Tensor] = None,
@@ -372,7 +390,7 @@ class HipRecognizer:
             raise ValueError(f'student logits are {tuple(student.shape)}, teacher logits {tuple(teacher.shape)}')
         student, teacher = student.contiguous(), teacher.contiguous()
         N, T, ncls = student.shape
-        lens = np.ascontiguousarray(np.asarray(out_lens, dtype=np.int32).reshape(-1))
+        lens = _i32(out_lens)
         if lens.shape[0] != N:
             raise ValueError('out_lens needs one entry per line')
         accumulate = grad is not None
@@ -382,50 +400,28 @@ class HipRecognizer:
             grad = torch.empty_like(student)
         kd = torch.empty((N,), dtype=torch.float32, device=self.device)
         with torch.cuda.device(self.device):
-            _lib.check(self.lib.cocr_distill_loss(self._h, C.c_void_p(student.data_ptr()), C.c_void_p(teacher.data_ptr()), N, T, ncls,
-                                                  lens.ctypes.data_as(C.POINTER(C.c_int32)), float(tau), C.c_void_p(kd.data_ptr()),
-                                                  C.c_void_p(grad.data_ptr()) if grad is not None else None, float(ctc_weight), float(kd_weight),
-                                                  int(accumulate), _stream_ptr(self.device)))
+            _lib.check(self.lib.cocr_distill_loss(self._h, _dp(student), _dp(teacher), N, T, ncls, _hp(lens), float(tau), _dp(kd), _dp(grad),
+                                                  float(ctc_weight), float(kd_weight), int(accumulate), _stream_ptr(self.device)))
         return kd, grad
 
     # ---- forced alignment (include/cocr.h: cocr_ctc_align) ----------
-    def ctc_align_async(self, logits: torch.Tensor, out_lens, targets, label_lens):
+    def ctc_align_async(self, logits: torch.Tensor, out_lens, targets, label_lens) -> _Handle:
         """Enqueues the forced alignment of every line's label sequence on the current stream, its outputs in pinned host memory;
         returns a handle for `collect_align`.  logits (N,T,ncls) float32 on this device; out_lens (N) valid frames; targets: the
         batch's concatenated 1-D label vector, label_lens (N) its per-line lengths (host sequences; at most 255 labels per line).
         Does not touch the forward's per-frame argmax: a `ctc_greedy` on the same logits afterwards still takes its shortcut."""
-        if logits.device != self.device or logits.dtype != torch.float32 or logits.dim() != 3:
-            raise RuntimeError('logits must be a float32 (N,T,num_classes) tensor on the model device')
-        cont = logits.contiguous()
-        N, T, ncls = cont.shape
-        lens, tl, tg = _target_arrays(N, out_lens, targets, label_lens)
-        i32 = C.POINTER(C.c_int32)
-        with torch.cuda.device(self.device):
-            key = ('align', N)
-            pool = self._pinned.setdefault(key, [])
-            cap = max(N, 1) * 255                                   # the kernel's bound on a line's labels
-            host = pool.pop() if pool else (torch.empty((2, cap), dtype=torch.int32).pin_memory(),
-                                            torch.empty((cap,), dtype=torch.float32).pin_memory(),
-                                            torch.empty((N,), dtype=torch.float32).pin_memory(),
-                                            torch.empty((N,), dtype=torch.int32).pin_memory())
-            ints, conf, score, counts = host
-            try:
-                _lib.check(self.lib.cocr_ctc_align(self._h, C.c_void_p(cont.data_ptr()), N, T, ncls, lens.ctypes.data_as(i32),
-                                                   tg.ctypes.data_as(i32) if tg.shape[0] else None, tl.ctypes.data_as(i32),
-                                                   C.c_void_p(ints[0].data_ptr()), C.c_void_p(ints[1].data_ptr()), C.c_void_p(conf.data_ptr()),
-                                                   C.c_void_p(score.data_ptr()), C.c_void_p(counts.data_ptr()), _stream_ptr(self.device)))
-            except Exception:
-                pool.append(host)                                   # nothing was launched: the buffers go back
-                raise
-            ev = torch.cuda.Event()
-            ev.record(torch.cuda.current_stream(self.device))
-        return (key, host, ev, (cont, tg, tl))
+        lat = self._lattice_args(logits, out_lens)
+        N = lat[1]
+        tl, tg = _target_arrays(N, lat[4], targets, label_lens)
+        cap = max(N, 1) * 255                                       # the kernel's bound on a line's labels
+        return self._enqueue(self.lib.cocr_ctc_align, lat, ('align', N), (((2, cap), _I32), ((cap,), _F32), ((N,), _F32), ((N,), _I32)),
+                             lambda ints, conf, score, counts: (_hp(tg if tg.shape[0] else None), _hp(tl), _dp(ints[0]), _dp(ints[1]), _dp(conf),
+                                                                _dp(score), _dp(counts)), meta=(tg, tl))
 
     def collect_align(self, handle) -> List[Tuple[Optional[List[Tuple[int, int, int, float]]], float]]:
         """Waits for a `ctc_align_async` handle; per line ([(label, start, end, conf)] -- one record per label, in order -- or None
         where no alignment fits, the path's log-probability)."""
-        key, host, ev, (_, tg, tl) = handle
-        ev.synchronize()
+        host, (tg, tl) = self._wait(handle), handle.meta
         total = int(tg.shape[0])
         st, en = host[0].numpy()[:, :total].tolist()
         cf = host[1].numpy()[:total].tolist()
@@ -435,29 +431,23 @@ class HipRecognizer:
         for n, l in enumerate(tl.tolist()):
             out.append((list(zip(lab[at:at + l], st[at:at + l], en[at:at + l], cf[at:at + l])) if cnt[n] >= 0 else None, sc[n]))
             at += l
-        self._pinned[key].append(host)
+        self._release(handle)
         return out
 
     def ctc_align(self, logits: torch.Tensor, out_lens, targets, label_lens):
         return self.collect_align(self.ctc_align_async(logits, out_lens, targets, label_lens))
 
     # ---- text-to-page alignment (include/cocr.h: cocr_ctc_align_page) ----------
-    def ctc_align_page_async(self, logits: torch.Tensor, out_lens, pages, targets, optional=None):
+    def ctc_align_page_async(self, logits: torch.Tensor, out_lens, pages, targets, optional=None) -> _Handle:
         """Enqueues the alignment of every page's label sequence to the frames of its lines on the current stream, its outputs in
         pinned host memory; returns a handle for `collect_align_page`.  logits (N,T,ncls) float32 on this device; out_lens (N) valid
         frames; pages: per page the rows of `logits` that are its lines in reading order (a row in at most one page); targets: per
         page its labels (at most 4095); optional: per page one bool per label (None: none may be skipped).  Does not touch the
         forward's per-frame argmax."""
-        if logits.device != self.device or logits.dtype != torch.float32 or logits.dim() != 3:
-            raise RuntimeError('logits must be a float32 (N,T,num_classes) tensor on the model device')
-        cont = logits.contiguous()
-        N, T, ncls = cont.shape
+        lat = self._lattice_args(logits, out_lens)
         P = len(pages)
         if len(targets) != P or (optional is not None and len(optional) != P):
             raise ValueError('targets and optional need one entry per page')
-        lens = np.ascontiguousarray(np.asarray(out_lens, dtype=np.int32).reshape(-1))
-        if lens.shape[0] != N:
-            raise ValueError('out_lens needs one entry per line')
         rows = [np.asarray(pg, dtype=np.int32).reshape(-1) for pg in pages]
         labs = [np.asarray(t, dtype=np.int32).reshape(-1) for t in targets]
         opts = [np.zeros(l.shape[0], dtype=np.uint8) if optional is None or optional[p] is None else
@@ -470,39 +460,21 @@ class HipRecognizer:
         page_lines = np.ascontiguousarray(np.concatenate(rows + [np.zeros(0, i32)]).astype(i32))
         tg = np.ascontiguousarray(np.concatenate(labs + [np.zeros(0, i32)]).astype(i32))
         op = np.ascontiguousarray(np.concatenate(opts + [np.zeros(0, np.uint8)]).astype(np.uint8))
-        total, lines = int(tg.shape[0]), int(page_lines.shape[0])
 
         def cap(n):
             return 1 << max(int(n) - 1, 0).bit_length()
-        i32p = C.POINTER(C.c_int32)
-        with torch.cuda.device(self.device):
-            key = ('align_page', cap(total), cap(P), cap(lines))
-            pool = self._pinned.setdefault(key, [])
-            host = pool.pop() if pool else (torch.empty((3, key[1]), dtype=torch.int32).pin_memory(),
-                                            torch.empty((key[1],), dtype=torch.float32).pin_memory(),
-                                            torch.empty((key[2],), dtype=torch.float32).pin_memory(),
-                                            torch.empty((key[2],), dtype=torch.int32).pin_memory(),
-                                            torch.empty((key[3],), dtype=torch.float32).pin_memory())
-            ints, conf, score, counts, line_score = host
-            try:
-                _lib.check(self.lib.cocr_ctc_align_page(
-                    self._h, C.c_void_p(cont.data_ptr()), N, T, ncls, lens.ctypes.data_as(i32p), P, line_off.ctypes.data_as(i32p),
-                    page_lines.ctypes.data_as(i32p), tg.ctypes.data_as(i32p), tl.ctypes.data_as(i32p), op.ctypes.data_as(C.POINTER(C.c_uint8)),
-                    C.c_void_p(ints[0].data_ptr()), C.c_void_p(ints[1].data_ptr()), C.c_void_p(ints[2].data_ptr()), C.c_void_p(conf.data_ptr()),
-                    C.c_void_p(score.data_ptr()), C.c_void_p(counts.data_ptr()), C.c_void_p(line_score.data_ptr()), _stream_ptr(self.device)))
-            except Exception:
-                pool.append(host)                                   # nothing was launched: the buffers go back
-                raise
-            ev = torch.cuda.Event()
-            ev.record(torch.cuda.current_stream(self.device))
-        return (key, host, ev, (cont, tg, tl, line_off))
+        ct, cp, cl = cap(tg.shape[0]), cap(P), cap(page_lines.shape[0])
+        return self._enqueue(
+            self.lib.cocr_ctc_align_page, lat, ('align_page', ct, cp, cl), (((3, ct), _I32), ((ct,), _F32), ((cp,), _F32), ((cp,), _I32), ((cl,), _F32)),
+            lambda ints, conf, score, counts, line_score: (P, _hp(line_off), _hp(page_lines), _hp(tg), _hp(tl), _hp(op, C.POINTER(C.c_uint8)),
+                                                           _dp(ints[0]), _dp(ints[1]), _dp(ints[2]), _dp(conf), _dp(score), _dp(counts), _dp(line_score)),
+            meta=(tg, tl, line_off))
 
     def collect_align_page(self, handle):
         """Waits for a `ctc_align_page_async` handle; per page ([(label, line, start, end, conf)] -- one record per label, a skipped
         optional label with line = start = end = -1 and conf 0 --, the page's score, the per-line scores as a float32 array), or
         (None, -inf, None) where the text does not fit: the returns of `align.viterbi_align_page`."""
-        key, host, ev, (_, tg, tl, line_off) = handle
-        ev.synchronize()
+        host, (tg, tl, line_off) = self._wait(handle), handle.meta
         total = int(tg.shape[0])
         ln, st, en = host[0].numpy()[:, :total].tolist()
         cf = host[1].numpy()[:total].tolist()
@@ -517,113 +489,68 @@ class HipRecognizer:
             else:
                 out.append((None, sc[p], None))
             at += l
-        self._pinned[key].append(host)
+        self._release(handle)
         return out
 
     def ctc_align_page(self, logits: torch.Tensor, out_lens, pages, targets, optional=None):
         return self.collect_align_page(self.ctc_align_page_async(logits, out_lens, pages, targets, optional))
 
     # ---- keyword spotting (include/cocr.h: cocr_ctc_spot) ----------
-    def ctc_spot_async(self, logits: torch.Tensor, out_lens, queries, hits: int = 1, min_score: float = -np.inf):
+    def ctc_spot_async(self, logits: torch.Tensor, out_lens, queries, hits: int = 1, min_score: float = -np.inf) -> _Handle:
         """Enqueues the search for every query in every line on the current stream, its outputs in pinned host memory; returns a
         handle for `collect_spot`.  logits (N,T,ncls) float32 on this device; out_lens (N) valid frames; queries: Q label sequences
         (1..255 labels each); hits: 1..8 per (line, query); min_score: the selection stops below it.  Does not touch the forward's
         per-frame argmax: a `ctc_greedy` on the same logits afterwards still takes its shortcut."""
-        if logits.device != self.device or logits.dtype != torch.float32 or logits.dim() != 3:
-            raise RuntimeError('logits must be a float32 (N,T,num_classes) tensor on the model device')
-        cont = logits.contiguous()
-        N, T, ncls = cont.shape
-        lens = np.ascontiguousarray(np.asarray(out_lens, dtype=np.int32).reshape(-1))
-        if lens.shape[0] != N:
-            raise ValueError('out_lens needs one entry per line')
+        lat = self._lattice_args(logits, out_lens)
         qs = [np.asarray(q, dtype=np.int32).reshape(-1) for q in queries]
-        Q, K = len(qs), int(hits)
-        ql = np.ascontiguousarray(np.asarray([q.shape[0] for q in qs], dtype=np.int32))
+        N, Q, K = lat[1], len(qs), int(hits)
+        ql = _i32([q.shape[0] for q in qs])
         qv = np.ascontiguousarray(np.concatenate(qs + [np.zeros(0, dtype=np.int32)]), dtype=np.int32)
-        i32 = C.POINTER(C.c_int32)
-        with torch.cuda.device(self.device):
-            cap = max(N * Q, 1) * min(max(K, 1), 8)
-            key = ('spot', cap, max(N * Q, 1))
-            pool = self._pinned.setdefault(key, [])
-            host = pool.pop() if pool else (torch.empty((2, cap), dtype=torch.int32).pin_memory(),
-                                            torch.empty((cap,), dtype=torch.float32).pin_memory(),
-                                            torch.empty((key[2],), dtype=torch.int32).pin_memory())
-            ints, score, counts = host
-            try:
-                _lib.check(self.lib.cocr_ctc_spot(self._h, C.c_void_p(cont.data_ptr()), N, T, ncls, lens.ctypes.data_as(i32),
-                                                  qv.ctypes.data_as(i32), ql.ctypes.data_as(i32), Q, K, C.c_float(min_score),
-                                                  C.c_void_p(ints[0].data_ptr()), C.c_void_p(ints[1].data_ptr()), C.c_void_p(score.data_ptr()),
-                                                  C.c_void_p(counts.data_ptr()), _stream_ptr(self.device)))
-            except Exception:
-                pool.append(host)                                   # nothing was launched: the buffers go back
-                raise
-            ev = torch.cuda.Event()
-            ev.record(torch.cuda.current_stream(self.device))
-        return (key, host, ev, (cont, N, Q, K))
+        cells = max(N * Q, 1)
+        cap = cells * min(max(K, 1), 8)
+        return self._enqueue(self.lib.cocr_ctc_spot, lat, ('spot', cap, cells), (((2, cap), _I32), ((cap,), _F32), ((cells,), _I32)),
+                             lambda ints, score, counts: (_hp(qv), _hp(ql), Q, K, float(min_score), _dp(ints[0]), _dp(ints[1]), _dp(score), _dp(counts)),
+                             meta=(N, Q, K))
 
     def collect_spot(self, handle) -> List[List[List[Tuple[int, int, float]]]]:
         """Waits for a `ctc_spot_async` handle; per line, per query [(start, end, score)], best first."""
-        key, host, ev, (_, N, Q, K) = handle
-        ev.synchronize()
+        host, (N, Q, K) = self._wait(handle), handle.meta
         st, en = host[0].numpy()[:, :N * Q * K].reshape(2, N, Q, K).tolist()
         sc = host[1].numpy()[:N * Q * K].reshape(N, Q, K).tolist()
         cnt = host[2].numpy()[:N * Q].reshape(N, Q).tolist()
         out = [[list(zip(st[n][q][:cnt[n][q]], en[n][q][:cnt[n][q]], sc[n][q][:cnt[n][q]])) for q in range(Q)] for n in range(N)]
-        self._pinned[key].append(host)
+        self._release(handle)
         return out
 
     def ctc_spot(self, logits: torch.Tensor, out_lens, queries, hits: int = 1, min_score: float = -np.inf):
         return self.collect_spot(self.ctc_spot_async(logits, out_lens, queries, hits, min_score))
 
     # ---- pattern spotting (include/cocr.h: cocr_ctc_spot_pattern; DESIGN.md section 7m) ----------
-    def ctc_spot_pattern_async(self, logits: torch.Tensor, out_lens, graphs, hits: int = 1, min_score: float = -np.inf):
+    def ctc_spot_pattern_async(self, logits: torch.Tensor, out_lens, graphs, hits: int = 1, min_score: float = -np.inf) -> _Handle:
         """Enqueues the search for every pattern in every line on the current stream, its outputs in pinned host memory; returns a
         handle for `collect_spot_pattern`.  logits (N,T,ncls) float32 on this device; out_lens (N) valid frames; graphs: Q
         `pattern.PatternGraph`s (1..256 label states, at most 4096 edges each; a chain is run as a graph like any other); hits: 1..8
         per (line, pattern); min_score: the selection stops below it.  Does not touch the forward's per-frame argmax."""
-        if logits.device != self.device or logits.dtype != torch.float32 or logits.dim() != 3:
-            raise RuntimeError('logits must be a float32 (N,T,num_classes) tensor on the model device')
-        cont = logits.contiguous()
-        N, T, ncls = cont.shape
-        lens = np.ascontiguousarray(np.asarray(out_lens, dtype=np.int32).reshape(-1))
-        if lens.shape[0] != N:
-            raise ValueError('out_lens needs one entry per line')
+        lat = self._lattice_args(logits, out_lens)
         tabs = [g.tables() for g in graphs]
-        Q, K = len(tabs), int(hits)
-        empty = [np.zeros(0, dtype=np.int32)]
-        counts_in = np.ascontiguousarray(np.asarray([t[0].shape[0] for t in tabs], dtype=np.int32))
-        cls, flags, off, preds = (np.ascontiguousarray(np.concatenate([t[i] for t in tabs] + empty), dtype=np.int32) for i in range(4))
-        i32 = C.POINTER(C.c_int32)
-        with torch.cuda.device(self.device):
-            cap = max(N * Q, 1) * min(max(K, 1), 8)
-            key = ('spot_pattern', cap, max(N * Q, 1))
-            pool = self._pinned.setdefault(key, [])
-            host = pool.pop() if pool else (torch.empty((3, cap), dtype=torch.int32).pin_memory(),
-                                            torch.empty((cap,), dtype=torch.float32).pin_memory(),
-                                            torch.empty((key[2],), dtype=torch.int32).pin_memory())
-            ints, score, counts = host
-            try:
-                _lib.check(self.lib.cocr_ctc_spot_pattern(self._h, C.c_void_p(cont.data_ptr()), N, T, ncls, lens.ctypes.data_as(i32),
-                                                          counts_in.ctypes.data_as(i32), cls.ctypes.data_as(i32), flags.ctypes.data_as(i32),
-                                                          off.ctypes.data_as(i32), preds.ctypes.data_as(i32), Q, K, C.c_float(min_score),
-                                                          C.c_void_p(ints[0].data_ptr()), C.c_void_p(ints[1].data_ptr()), C.c_void_p(score.data_ptr()),
-                                                          C.c_void_p(ints[2].data_ptr()), C.c_void_p(counts.data_ptr()), _stream_ptr(self.device)))
-            except Exception:
-                pool.append(host)                                   # nothing was launched: the buffers go back
-                raise
-            ev = torch.cuda.Event()
-            ev.record(torch.cuda.current_stream(self.device))
-        return (key, host, ev, (cont, N, Q, K))
+        N, Q, K = lat[1], len(tabs), int(hits)
+        states = _i32([t[0].shape[0] for t in tabs])
+        cls, flags, off, preds = (np.ascontiguousarray(np.concatenate([t[i] for t in tabs] + [np.zeros(0, dtype=np.int32)]), dtype=np.int32)
+                                  for i in range(4))
+        cells = max(N * Q, 1)
+        cap = cells * min(max(K, 1), 8)
+        return self._enqueue(self.lib.cocr_ctc_spot_pattern, lat, ('spot_pattern', cap, cells), (((3, cap), _I32), ((cap,), _F32), ((cells,), _I32)),
+                             lambda ints, score, counts: (_hp(states), _hp(cls), _hp(flags), _hp(off), _hp(preds), Q, K, float(min_score),
+                                                          _dp(ints[0]), _dp(ints[1]), _dp(score), _dp(ints[2]), _dp(counts)), meta=(N, Q, K))
 
     def collect_spot_pattern(self, handle, raw: bool = False):
         """Waits for a `ctc_spot_pattern_async` handle; per line, per pattern [(start, end, score, final state)], best first.  `raw`:
         the output arrays themselves, copies of (starts, ends, scores, finals (N,Q,hits), counts (N,Q))."""
-        key, host, ev, (_, N, Q, K) = handle
-        ev.synchronize()
+        host, (N, Q, K) = self._wait(handle), handle.meta
         ints = host[0].numpy()[:, :N * Q * K].reshape(3, N, Q, K).copy()
         score = host[1].numpy()[:N * Q * K].reshape(N, Q, K).copy()
         counts = host[2].numpy()[:N * Q].reshape(N, Q).copy()
-        self._pinned[key].append(host)
+        self._release(handle)
         if raw:
             return ints[0], ints[1], score, ints[2], counts
         st, en, fi = ints.tolist()
@@ -639,20 +566,13 @@ class HipRecognizer:
         frames at or beyond out_lens[n] hold class 0 / code 255.  logits (N,T,ncls) float32 on this device.  Does not touch the
         forward's per-frame argmax."""
         from .index import inv_step
-        if logits.device != self.device or logits.dtype != torch.float32 or logits.dim() != 3:
-            raise RuntimeError('logits must be a float32 (N,T,num_classes) tensor on the model device')
-        cont = logits.contiguous()
-        N, T, ncls = cont.shape
-        lens = np.ascontiguousarray(np.asarray(out_lens, dtype=np.int32).reshape(-1))
-        if lens.shape[0] != N:
-            raise ValueError('out_lens needs one entry per line')
-        inv = inv_step(step)
+        cont, N, T, ncls, lens = self._lattice_args(logits, out_lens)
+        inv = float(inv_step(step))
         K = max(int(keep), 0)
         classes = torch.empty((N, T, K), dtype=torch.uint16, device=self.device)
         codes = torch.empty((N, T, K), dtype=torch.uint8, device=self.device)
         with torch.cuda.device(self.device):
-            _lib.check(self.lib.cocr_posterior_pack(self._h, C.c_void_p(cont.data_ptr()), N, T, ncls, lens.ctypes.data_as(C.POINTER(C.c_int32)),
-                                                    int(keep), C.c_float(inv), C.c_void_p(classes.data_ptr()), C.c_void_p(codes.data_ptr()),
+            _lib.check(self.lib.cocr_posterior_pack(self._h, _dp(cont), N, T, ncls, _hp(lens), int(keep), inv, _dp(classes), _dp(codes),
                                                     _stream_ptr(self.device)))
         return classes, codes
 
@@ -668,18 +588,14 @@ class HipRecognizer:
         step32 = float(np.float32(step))
         out = torch.empty((N, T, max(int(ncls), 0)), dtype=torch.float32, device=self.device)
         with torch.cuda.device(self.device):
-            _lib.check(self.lib.cocr_posterior_unpack(self._h, C.c_void_p(classes.data_ptr()), C.c_void_p(codes.data_ptr()), N, T, K, int(ncls),
-                                                      C.c_float(step32), C.c_void_p(out.data_ptr()), _stream_ptr(self.device)))
+            _lib.check(self.lib.cocr_posterior_unpack(self._h, _dp(classes), _dp(codes), N, T, K, int(ncls), step32, _dp(out), _stream_ptr(self.device)))
         return out
 
     # ---- output-layer training step (include/cocr.h: cocr_decoder_backward / cocr_decoder_adamw) ----------
     def decoder_backward(self, grad_probits: torch.Tensor, with_input_grad: bool = False):
         """Gradients of the decoder `nn.Linear` for the LAST forward on this engine: (grad_weight (ncls, D), grad_bias (ncls),
         grad_output (N, T, D) or None), float32 device tensors."""
-        if grad_probits.device != self.device or grad_probits.dtype != torch.float32 or grad_probits.dim() != 3:
-            raise RuntimeError('grad_probits must be a float32 (N,T,num_classes) tensor on the model device')
-        grad_probits = grad_probits.contiguous()
-        N, T, ncls = grad_probits.shape
+        grad_probits, N, T, ncls, _ = self._lattice_args(grad_probits, name='grad_probits')
         if ncls != self.hp.num_classes:
             raise ValueError('grad_probits has the wrong number of classes')
         D = self.hp.encoder_dim
@@ -687,9 +603,7 @@ class HipRecognizer:
         gb = torch.empty((ncls,), dtype=torch.float32, device=self.device)
         gy = torch.empty((N, T, D), dtype=torch.float32, device=self.device) if with_input_grad else None
         with torch.cuda.device(self.device):
-            _lib.check(self.lib.cocr_decoder_backward(self._h, C.c_void_p(grad_probits.data_ptr()), N, T, C.c_void_p(gw.data_ptr()),
-                                                      C.c_void_p(gb.data_ptr()), C.c_void_p(gy.data_ptr()) if with_input_grad else None,
-                                                      _stream_ptr(self.device)))
+            _lib.check(self.lib.cocr_decoder_backward(self._h, _dp(grad_probits), N, T, _dp(gw), _dp(gb), _dp(gy), _stream_ptr(self.device)))
         return gw, gb, gy
 
     def decoder_adamw(self, grad_weight: torch.Tensor, grad_bias: torch.Tensor, lr: float, betas=(0.9, 0.999), eps: float = 1e-8,
@@ -697,8 +611,8 @@ class HipRecognizer:
         """One torch.optim.AdamW step on the decoder (state kept inside the engine); defaults are torch's."""
         self._check_decoder_grads(grad_weight, grad_bias)
         with torch.cuda.device(self.device):
-            _lib.check(self.lib.cocr_decoder_adamw(self._h, C.c_void_p(grad_weight.data_ptr()), C.c_void_p(grad_bias.data_ptr()), float(lr),
-                                                   float(betas[0]), float(betas[1]), float(eps), float(weight_decay), _stream_ptr(self.device)))
+            _lib.check(self.lib.cocr_decoder_adamw(self._h, _dp(grad_weight), _dp(grad_bias), float(lr), float(betas[0]), float(betas[1]), float(eps),
+                                                   float(weight_decay), _stream_ptr(self.device)))
 
     def _check_decoder_grads(self, grad_weight: torch.Tensor, grad_bias: torch.Tensor) -> None:
         for g in (grad_weight, grad_bias):
@@ -720,16 +634,14 @@ class HipRecognizer:
         self._check_decoder_grads(grad_weight, grad_bias)
         o = self._optim(kind, lr, weight_decay, betas, eps, momentum, alpha)
         with torch.cuda.device(self.device):
-            _lib.check(self.lib.cocr_decoder_optim_step(self._h, C.c_void_p(grad_weight.data_ptr()), C.c_void_p(grad_bias.data_ptr()), C.byref(o),
-                                                        _stream_ptr(self.device)))
+            _lib.check(self.lib.cocr_decoder_optim_step(self._h, _dp(grad_weight), _dp(grad_bias), C.byref(o), _stream_ptr(self.device)))
 
     def decoder_optim_state(self) -> Dict:
         """The output layer's optimizer state: {'kind': name or None, 'step', 'state': float32 torch view of the library's
         [master copy | slot 0 | slot 1] vector, or None before the first step}."""
         kind, step, p, n = C.c_int(), C.c_int64(), C.c_void_p(), C.c_size_t()
         _lib.check(self.lib.cocr_decoder_optim_state(self._h, C.byref(kind), C.byref(step), C.byref(p), C.byref(n)))
-        names = {v: k for k, v in _lib.OPTIMIZERS.items()}
-        return {'kind': names.get(kind.value), 'step': int(step.value), 'state': self._device_view(p.value, n.value) if p.value else None}
+        return {'kind': _OPTIMIZER_NAMES.get(kind.value), 'step': int(step.value), 'state': self._device_view(p.value, n.value) if p.value else None}
 
     def decoder_optim_restore(self, kind: Optional[str], step: int, state: torch.Tensor) -> None:
         """Puts a `decoder_optim_state` back: the vector (float32, this device), the kind and the step count; the serving copy of
@@ -737,8 +649,8 @@ class HipRecognizer:
         if state.device != self.device or state.dtype != torch.float32 or not state.is_contiguous() or state.dim() != 1:
             raise RuntimeError('the state must be a contiguous float32 vector on the model device')
         with torch.cuda.device(self.device):
-            _lib.check(self.lib.cocr_decoder_optim_restore(self._h, -1 if kind is None else _lib.OPTIMIZERS[kind], int(step), C.c_void_p(state.data_ptr()),
-                                                           state.numel(), _stream_ptr(self.device)))
+            _lib.check(self.lib.cocr_decoder_optim_restore(self._h, -1 if kind is None else _lib.OPTIMIZERS[kind], int(step), _dp(state), state.numel(),
+                                                           _stream_ptr(self.device)))
 
     def decoder_state(self) -> Dict[str, np.ndarray]:
         """{'decoder.weight', 'decoder.bias'}: float32 host copies of the (trained) output layer."""
@@ -746,7 +658,7 @@ class HipRecognizer:
         for name, shape in (('decoder.weight', (self.hp.num_classes, self.hp.encoder_dim)), ('decoder.bias', (self.hp.num_classes,))):
             a = np.empty(shape, dtype=np.float32)
             with torch.cuda.device(self.device):
-                _lib.check(self.lib.cocr_get_tensor(self._h, name.encode(), a.ctypes.data_as(C.c_void_p), a.size, _stream_ptr(self.device)))
+                _lib.check(self.lib.cocr_get_tensor(self._h, name.encode(), _hp(a, C.c_void_p), a.size, _stream_ptr(self.device)))
             out[name] = a
         return out
 
@@ -773,12 +685,9 @@ class HipRecognizer:
         ldt = _lib.U8 if lines.dtype == torch.uint8 else _lib.F32
         lines = (lines if ldt == _lib.U8 else lines.float()).contiguous()
         N, H, W = lines.shape
-        i32 = C.POINTER(C.c_int32)
-        il = np.ascontiguousarray(np.asarray(lens, dtype=np.int32).reshape(-1))
-        tg = np.ascontiguousarray(np.asarray(targets, dtype=np.int32).reshape(-1))
-        tl = np.ascontiguousarray(np.asarray(label_lens, dtype=np.int32).reshape(-1))
-        if il.shape[0] != N or tl.shape[0] != N or int(tl.sum()) != tg.shape[0]:
-            raise ValueError('lens / label_lens need one entry per line and targets sum(label_lens) labels')
+        il = _i32(lens)
+        tl, tg = _target_arrays(N, il, targets, label_lens, 'lens')
+        labels = (_hp(tg if tg.shape[0] else None), _hp(tl))
         dp = (C.c_float * 4)(*[float(x) for x in dropout])
         if teacher_logits is not None:
             tz = teacher_logits
@@ -787,16 +696,13 @@ class HipRecognizer:
             tz = tz.contiguous()
             both = (C.c_float * 2)()
             with torch.cuda.device(self.device):
-                _lib.check(self.lib.cocr_train_step_distill(self._h, C.c_void_p(lines.data_ptr()), ldt, N, H, W, il.ctypes.data_as(i32),
-                                                            tg.ctypes.data_as(i32) if tg.shape[0] else None, tl.ctypes.data_as(i32), dp,
-                                                            C.c_uint64(int(seed)), C.c_void_p(tz.data_ptr()), float(tau), float(distill_weight), both,
-                                                            _stream_ptr(self.device)))
+                _lib.check(self.lib.cocr_train_step_distill(self._h, _dp(lines), ldt, N, H, W, _hp(il), *labels, dp, C.c_uint64(int(seed)), _dp(tz),
+                                                            float(tau), float(distill_weight), both, _stream_ptr(self.device)))
             return float(both[0]), float(both[1])
         loss = C.c_float()
         with torch.cuda.device(self.device):
-            _lib.check(self.lib.cocr_train_step(self._h, C.c_void_p(lines.data_ptr()), ldt, N, H, W, il.ctypes.data_as(i32),
-                                                tg.ctypes.data_as(i32) if tg.shape[0] else None, tl.ctypes.data_as(i32), dp, C.c_uint64(int(seed)),
-                                                C.byref(loss), _stream_ptr(self.device)))
+            _lib.check(self.lib.cocr_train_step(self._h, _dp(lines), ldt, N, H, W, _hp(il), *labels, dp, C.c_uint64(int(seed)), C.byref(loss),
+                                                _stream_ptr(self.device)))
         return float(loss.value)
 
     def _train_get(self, name: str, kind: int) -> np.ndarray:
@@ -804,7 +710,7 @@ class HipRecognizer:
         shape = model_state_spec(self.hp)[name][0]
         a = np.empty(shape, dtype=np.float32)
         with torch.cuda.device(self.device):
-            _lib.check(self.lib.cocr_train_get(self._h, name.encode(), kind, a.ctypes.data_as(C.c_void_p), a.size, _stream_ptr(self.device)))
+            _lib.check(self.lib.cocr_train_get(self._h, name.encode(), kind, _hp(a, C.c_void_p), a.size, _stream_ptr(self.device)))
         return a
 
     def train_grad(self, name: str) -> np.ndarray:
@@ -829,11 +735,7 @@ class HipRecognizer:
 
     def _device_view(self, ptr: int, n: int) -> torch.Tensor:
         """`n` floats of library-owned device memory as a float32 torch view."""
-        class _Mem:
-            def __init__(s, owner):
-                s.owner = owner
-                s.__cuda_array_interface__ = {'shape': (n,), 'typestr': '<f4', 'data': (ptr, False), 'version': 2}
-        return torch.as_tensor(_Mem(self), device=self.device)
+        return _mem_view(self, ptr, n, '<f4', self.device)
 
     def train_grad_buffer(self) -> torch.Tensor:
         """The flat gradient vector of all parameters as a float32 torch view of library-owned memory (for an all-reduce)."""
@@ -864,8 +766,7 @@ class HipRecognizer:
             if grad.numel() != self.train_grad_buffer().numel():
                 raise ValueError(f'grad has {grad.numel()} floats, the gradient vector {self.train_grad_buffer().numel()}')
         with torch.cuda.device(self.device):
-            _lib.check(self.lib.cocr_train_optim_step_ex(self._h, C.byref(o), C.c_void_p(grad.data_ptr()) if grad is not None else None,
-                                                         float(grad_scale), _stream_ptr(self.device)))
+            _lib.check(self.lib.cocr_train_optim_step_ex(self._h, C.byref(o), _dp(grad), float(grad_scale), _stream_ptr(self.device)))
 
     # ---- the gradient window on flat vectors (include/cocr.h: cocr_grad_accumulate / cocr_grad_norm) ------
     def _check_flat(self, t: torch.Tensor) -> None:
@@ -880,15 +781,15 @@ class HipRecognizer:
         if dst.numel() != src.numel():
             raise ValueError(f'dst has {dst.numel()} floats, src {src.numel()}')
         with torch.cuda.device(self.device):
-            _lib.check(self.lib.cocr_grad_accumulate(C.c_void_p(dst.data_ptr()), C.c_void_p(src.data_ptr()), dst.numel(), float(scale), int(bool(overwrite)),
-                                                     self.device.index or 0, _stream_ptr(self.device)))
+            _lib.check(self.lib.cocr_grad_accumulate(_dp(dst), _dp(src), dst.numel(), float(scale), int(bool(overwrite)), self.device.index or 0,
+                                                     _stream_ptr(self.device)))
 
     def grad_norm(self, t: torch.Tensor) -> float:
         """The L2 norm of a float32 vector on this device, squares and sums in double, the same bits on every call; waits for the stream."""
         self._check_flat(t)
         out = C.c_double()
         with torch.cuda.device(self.device):
-            _lib.check(self.lib.cocr_grad_norm(C.c_void_p(t.data_ptr()), t.numel(), self.device.index or 0, C.byref(out), _stream_ptr(self.device)))
+            _lib.check(self.lib.cocr_grad_norm(_dp(t), t.numel(), self.device.index or 0, C.byref(out), _stream_ptr(self.device)))
         return float(out.value)
 
     def train_optim_state(self) -> Dict:
@@ -897,8 +798,7 @@ class HipRecognizer:
         include/cocr.h)."""
         kind, step, dec, p0, p1, n = C.c_int(), C.c_int64(), C.c_int64(), C.c_void_p(), C.c_void_p(), C.c_size_t()
         _lib.check(self.lib.cocr_train_optim_state(self._h, C.byref(kind), C.byref(step), C.byref(dec), C.byref(p0), C.byref(p1), C.byref(n)))
-        names = {v: k for k, v in _lib.OPTIMIZERS.items()}
-        return {'kind': names.get(kind.value), 'step': int(step.value), 'dec_steps': int(dec.value),
+        return {'kind': _OPTIMIZER_NAMES.get(kind.value), 'step': int(step.value), 'dec_steps': int(dec.value),
                 'slot0': self._device_view(p0.value, n.value), 'slot1': self._device_view(p1.value, n.value)}
 
     def train_optim_restore(self, kind: Optional[str], step: int, dec_steps: int = 0) -> None:
@@ -916,9 +816,7 @@ class HipRecognizer:
         batch `forward` ingests, and the lines' widths after scaling and padding (the batch's `seq_lens`).  Grayscale, Pillow
         LANCZOS scaling to `height` (default: the model's), `pad` zero columns left and right, right-zero-filled to Wb = `width`,
         or the widest line rounded up to a multiple of `bucket_edge`, or the widest line."""
-        height = int(height or self.hp.height)
-        n = len(lines)
-        if n < 1:
+        if len(lines) < 1:
             raise ValueError('empty batch')
         hs = np.array([x.shape[0] for x in lines], dtype=np.int32)
         ws = np.array([x.shape[1] for x in lines], dtype=np.int32)
@@ -929,20 +827,8 @@ class HipRecognizer:
         sizes = hs.astype(np.int64) * ws * ch
         offs = np.concatenate([[0], np.cumsum(sizes)[:-1]]).astype(np.int64)
         flat = np.concatenate([np.ascontiguousarray(x).reshape(-1) for x in lines])
-        wl = [int(self.lib.cocr_preproc_width(int(h), int(w), height, int(pad))) for h, w in zip(hs, ws)]
-        wb = int(width) if width else max(wl)
-        if not width and bucket_edge:
-            wb = -(-wb // int(bucket_edge)) * int(bucket_edge)
-        px = torch.from_numpy(flat).to(self.device)
-        out = torch.empty((n, height, wb), dtype=torch.uint8, device=self.device)
-        lens = np.zeros(n, dtype=np.int32)
-        _lib.check(self.lib.cocr_preproc_lines(self._h, C.c_void_p(px.data_ptr()), offs.ctypes.data_as(C.POINTER(C.c_int64)),
-                                               hs.ctypes.data_as(C.POINTER(C.c_int32)), ws.ctypes.data_as(C.POINTER(C.c_int32)),
-                                               ch.ctypes.data_as(C.POINTER(C.c_int32)), n, height, int(pad), wb,
-                                               C.c_void_p(out.data_ptr()), lens.ctypes.data_as(C.POINTER(C.c_int32)),
-                                               _stream_ptr(self.device)))
-        self._keep = px            # the kernels read it asynchronously on the current stream
-        return out, lens
+        self._keep = px = torch.from_numpy(flat).to(self.device)            # the kernels read it asynchronously on the current stream
+        return self.preprocess_device(px, offs, hs, ws, ch, height, pad, width, bucket_edge)
 
     def preprocess_device(self, pixels: torch.Tensor, offsets, heights, widths, channels=None, height: Optional[int] = None,
                           pad: int = 16, width: int = 0, bucket_edge: int = 0) -> Tuple[torch.Tensor, np.ndarray]:
@@ -952,10 +838,9 @@ class HipRecognizer:
         if pixels.device != self.device or pixels.dtype != torch.uint8 or not pixels.is_contiguous():
             raise ValueError('pixels must be a contiguous uint8 buffer on the model device')
         offs = np.ascontiguousarray(np.asarray(offsets, dtype=np.int64).reshape(-1))
-        hs = np.ascontiguousarray(np.asarray(heights, dtype=np.int32).reshape(-1))
-        ws = np.ascontiguousarray(np.asarray(widths, dtype=np.int32).reshape(-1))
+        hs, ws = _i32(heights), _i32(widths)
         n = offs.shape[0]
-        ch = np.ones(n, dtype=np.int32) if channels is None else np.ascontiguousarray(np.asarray(channels, dtype=np.int32).reshape(-1))
+        ch = np.ones(n, dtype=np.int32) if channels is None else _i32(channels)
         if n < 1:
             raise ValueError('empty batch')
         if hs.shape[0] != n or ws.shape[0] != n or ch.shape[0] != n:
@@ -969,11 +854,8 @@ class HipRecognizer:
             wb = -(-wb // int(bucket_edge)) * int(bucket_edge)
         out = torch.empty((n, height, wb), dtype=torch.uint8, device=self.device)
         lens = np.zeros(n, dtype=np.int32)
-        _lib.check(self.lib.cocr_preproc_lines(self._h, C.c_void_p(pixels.data_ptr()), offs.ctypes.data_as(C.POINTER(C.c_int64)),
-                                               hs.ctypes.data_as(C.POINTER(C.c_int32)), ws.ctypes.data_as(C.POINTER(C.c_int32)),
-                                               ch.ctypes.data_as(C.POINTER(C.c_int32)), n, height, int(pad), wb,
-                                               C.c_void_p(out.data_ptr()), lens.ctypes.data_as(C.POINTER(C.c_int32)),
-                                               _stream_ptr(self.device)))
+        _lib.check(self.lib.cocr_preproc_lines(self._h, _dp(pixels), _hp(offs, _I64P), _hp(hs), _hp(ws), _hp(ch), n, height, int(pad), wb, _dp(out),
+                                               _hp(lens), _stream_ptr(self.device)))
         return out, lens
 
     # ---- training augmentation (include/cocr.h: cocr_augment_lines) -----------------------------------------------------------
@@ -986,7 +868,7 @@ class HipRecognizer:
         if lines.device != self.device or lines.dtype != torch.uint8 or lines.dim() != 3 or not lines.is_contiguous():
             raise ValueError('expected a contiguous (N, H, W) uint8 batch on the model device')
         N, H, W = lines.shape
-        sl = np.ascontiguousarray(np.asarray(seq_lens, dtype=np.int32).reshape(-1))
+        sl = _i32(seq_lens)
         if sl.shape[0] != N:
             raise ValueError('one seq_len per line')
         if H > _aug.MAX_H or W > _aug.MAX_W or sl.min() < 0 or sl.max() > W:
@@ -1002,9 +884,8 @@ class HipRecognizer:
         d_params = torch.from_numpy(np.ascontiguousarray(params)).pin_memory().to(self.device, non_blocking=True)
         d_grid = torch.from_numpy(np.ascontiguousarray(grid)).pin_memory().to(self.device, non_blocking=True)
         with torch.cuda.device(self.device):
-            _lib.check(self.lib.cocr_augment_lines(self._h, C.c_void_p(lines.data_ptr()), C.c_void_p(out.data_ptr()), N, H, W,
-                                                   sl.ctypes.data_as(C.POINTER(C.c_int32)), C.c_void_p(d_params.data_ptr()),
-                                                   C.c_void_p(d_grid.data_ptr()), int(grid.shape[1]), _stream_ptr(self.device)))
+            _lib.check(self.lib.cocr_augment_lines(self._h, _dp(lines), _dp(out), N, H, W, _hp(sl), _dp(d_params), _dp(d_grid), int(grid.shape[1]),
+                                                   _stream_ptr(self.device)))
         return out
 
     # ---- scoring (include/cocr.h: cocr_edit_align) ---------------------------------------------------------------------------
@@ -1032,8 +913,8 @@ class HipRecognizer:
         if ao.shape[0] < 1 or ao.shape != bo.shape or ao[0] != 0 or bo[0] != 0:
             raise ValueError('a_offs and b_offs hold P + 1 offsets each, starting at 0')
         P = ao.shape[0] - 1
-        a = np.ascontiguousarray(np.asarray(a, dtype=np.int32).reshape(-1))
-        b = np.ascontiguousarray(np.asarray(b, dtype=np.int32).reshape(-1))
+        a = _i32(a)
+        b = _i32(b)
         if a.shape[0] != ao[-1] or b.shape[0] != bo[-1]:
             raise ValueError('the last offsets must equal the lengths of a and b')
         if P == 0:
@@ -1041,7 +922,6 @@ class HipRecognizer:
                 (np.zeros(0, dtype=np.int32) if want_ops else None)
         na, nb = a.shape[0], b.shape[0]
         nops = (na + nb) if want_ops else 0
-        i64p = C.POINTER(C.c_int64)
         with torch.cuda.device(self.device):
             stream = torch.cuda.current_stream(self.device)
             h_in = self._score_pinned('score_in', (na + nb) * 4 + 16)
@@ -1053,10 +933,8 @@ class HipRecognizer:
             out_bytes = 20 * P + nops
             d_out = torch.empty(out_bytes + 16, dtype=torch.uint8, device=self.device)
             base = d_out.data_ptr()
-            _lib.check(self.lib.cocr_edit_align(self._h, C.c_void_p(d_in.data_ptr()), ao.ctypes.data_as(i64p),
-                                                C.c_void_p(d_in.data_ptr() + 4 * na), bo.ctypes.data_as(i64p), P, C.c_void_p(base),
-                                                C.c_void_p(base + 20 * P) if want_ops else None,
-                                                C.c_void_p(base + 16 * P) if want_ops else None, C.c_void_p(stream.cuda_stream)))
+            _lib.check(self.lib.cocr_edit_align(self._h, _dp(d_in), _hp(ao, _I64P), _dp(d_in) + 4 * na, _hp(bo, _I64P), P, base,
+                                                base + 20 * P if want_ops else None, base + 16 * P if want_ops else None, _stream_ptr(self.device)))
             h_out = self._score_pinned('score_out', out_bytes)
             h_out[:out_bytes].copy_(d_out[:out_bytes], non_blocking=True)
             ev = torch.cuda.Event()
@@ -1096,11 +974,8 @@ class HipRecognizer:
         offs = np.concatenate([[0], np.cumsum(sizes)[:-1]]).astype(np.int64)
         out = torch.empty((int(sizes.sum()),), dtype=torch.uint8, device=self.device)
         with torch.cuda.device(self.device):
-            _lib.check(self.lib.cocr_extract_lines(self._h, page_ptrs, page_dims.ctypes.data_as(C.POINTER(C.c_int32)), P,
-                                                   lp.ctypes.data_as(C.POINTER(C.c_int32)), dims.ctypes.data_as(C.POINTER(C.c_int32)),
-                                                   cols.ctypes.data_as(C.POINTER(C.c_int64)), verts.ctypes.data_as(C.POINTER(C.c_int32)),
-                                                   nv.ctypes.data_as(C.POINTER(C.c_int32)), len(gs), int(fill), C.c_void_p(out.data_ptr()),
-                                                   offs.ctypes.data_as(C.POINTER(C.c_int64)), _stream_ptr(self.device)))
+            _lib.check(self.lib.cocr_extract_lines(self._h, page_ptrs, _hp(page_dims), P, _hp(lp), _hp(dims), _hp(cols, _I64P), _hp(verts), _hp(nv),
+                                                   len(gs), int(fill), _dp(out), _hp(offs, _I64P), _stream_ptr(self.device)))
         self._keep_pages = dp          # the sampler reads them asynchronously on the current stream
         return out, offs, hs, ws
 
@@ -1112,7 +987,7 @@ class HipRecognizer:
         n = C.c_int64()
         _lib.check(self.lib.cocr_debug_tap(self._h, name.encode(), None, 0, C.byref(n)))
         out = np.empty(n.value, dtype=np.float32)
-        _lib.check(self.lib.cocr_debug_tap(self._h, name.encode(), out.ctypes.data_as(C.c_void_p), n.value, C.byref(n)))
+        _lib.check(self.lib.cocr_debug_tap(self._h, name.encode(), _hp(out, C.c_void_p), n.value, C.byref(n)))
         return out
 
     def profile(self, on: bool) -> None:

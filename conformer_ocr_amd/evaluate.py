@@ -292,11 +292,10 @@ def recognize(net, lines: Sequence[np.ndarray], batch_size: int = 32, edge: int 
     batches = make_batches([l.shape[1] for l in lines], batch_size, edge)
     out: Dict[int, str] = {}
     dev = torch.device(device)
-    from .ctc_decoder import BeamDecoder, GreedyDecoder, LMDecoder
-    if pipelined and streams > 1 and isinstance(net.ctc_decoder, (GreedyDecoder, BeamDecoder, LMDecoder)):
+    from .ctc_decoder import _DeviceDecoder
+    if pipelined and streams > 1 and isinstance(net.ctc_decoder, _DeviceDecoder):
         engines = net.engine_pool(streams, dev)
         cuda_streams = net.pool_streams(streams, dev)
-        beam = net.ctc_decoder.beam_size if isinstance(net.ctc_decoder, BeamDecoder) else 0
         inflight: List[tuple] = []
 
         lut = net._codec_lut()
@@ -320,10 +319,7 @@ def recognize(net, lines: Sequence[np.ndarray], batch_size: int = 32, edge: int 
                     copied.record()
                     stager.release(key, staged, copied)
                     lg, ol = eng.forward(d_im.squeeze(1), lens.numpy())
-                    if isinstance(net.ctc_decoder, LMDecoder):
-                        handle = net.ctc_decoder.decode_async(eng, lg, ol)
-                    else:
-                        handle = (eng._decode_async(eng.lib.cocr_ctc_beam, lg, ol, extra=(int(beam),)) if beam else eng.ctc_greedy_async(lg, ol))
+                    handle = net.ctc_decoder.decode_async(eng, lg, ol)
                 inflight.append((idx, k, handle, (d_im, lg)))
                 if len(inflight) >= streams:
                     finish(inflight.pop(0))

@@ -22,7 +22,7 @@ import torch
 from torch import nn
 
 from .codec import PytorchCodec
-from .ctc_decoder import BeamDecoder, GreedyDecoder, LMDecoder, greedy_decoder
+from .ctc_decoder import BeamDecoder, LMDecoder, _DeviceDecoder, greedy_decoder
 from .engine import HipRecognizer
 from .spec import HParams, encoder_state_spec
 
@@ -269,16 +269,8 @@ class PytorchRecognitionModel(nn.Module):
         return batch.unsqueeze(1), torch.from_numpy(lens)
 
     def _label_records(self, line: torch.Tensor, lens: torch.Tensor) -> List[List[Tuple[int, int, int, float]]]:
-        o, olens = self.forward(line, lens)
-        if isinstance(self.ctc_decoder, GreedyDecoder):
-            return self._engine.ctc_greedy(o, olens.numpy())
-        if isinstance(self.ctc_decoder, BeamDecoder):
-            return self._engine.ctc_beam(o, olens.numpy(), self.ctc_decoder.beam_size)
-        if isinstance(self.ctc_decoder, LMDecoder):
-            return self.ctc_decoder.decode(self._engine, o, olens.numpy())
-        # a user-supplied decoder: the reference's own host loop (pred.py:158-162)
-        o = o.transpose(1, 2).cpu().float().numpy()
-        return [self.ctc_decoder(seq[:, :int(seq_len)]) for seq, seq_len in zip(o, olens)]
+        kind, h, eng = self.predict_string_async(line, lens)
+        return eng.collect(h) if kind == 'device' else h
 
     def predict(self, line: torch.Tensor, lens: Optional[torch.Tensor] = None) -> List[List[Tuple[str, int, int, float]]]:
         """
@@ -293,21 +285,7 @@ class PytorchRecognitionModel(nn.Module):
         Forward pass on a (N, C, H, W) batch; returns one string per line, batch order
         preserved (pred.py:148-164).
         """
-        lut = self._codec_lut()
-        if lut is not None and isinstance(self.ctc_decoder, (GreedyDecoder, BeamDecoder, LMDecoder)):
-            # device decode + a 1:1 codec: label arrays -> characters by one table lookup per line (the record lists of `predict_labels`
-            # and the codec's tuple walk cost 0.26 ms per 32 lines on the host, after the GPU had finished: a fifth of the call)
-            o, olens = self.forward(line, lens)
-            eng = self._engine
-            if isinstance(self.ctc_decoder, GreedyDecoder):
-                h = eng.ctc_greedy_async(o, olens.numpy())
-            elif isinstance(self.ctc_decoder, LMDecoder):
-                h = self.ctc_decoder.decode_async(eng, o, olens.numpy())
-            else:
-                h = eng._decode_async(eng.lib.cocr_ctc_beam, o, olens.numpy(), extra=(int(self.ctc_decoder.beam_size),))
-            size = lut.shape[0]
-            return [''.join(lut[np.minimum(lab, size - 1)].tolist()) for lab in eng.collect_labels(h)]
-        return [''.join(x[0] for x in self.codec.decode(locs)) for locs in self._label_records(line, lens)]
+        return self.collect_strings(self.predict_string_async(line, lens))
 
     def predict_nbest(self, line: torch.Tensor, seq_lens: torch.Tensor, nbest: int) -> List[List[Tuple[str, float, float, List[Tuple[int, int, int, float]]]]]:
         """Forward pass + n-best decoding: per line the first `nbest` hypotheses of the beam of `ctc_decoder` (a
@@ -349,19 +327,17 @@ class PytorchRecognitionModel(nn.Module):
         that batch only -- the next batch's upload and forward can be in flight meanwhile."""
         o, olens = self.forward(line, lens)
         eng = self._engine             # the handle carries the engine that owns its pinned records (a re-pack may replace `self._engine` before the collect)
-        if isinstance(self.ctc_decoder, GreedyDecoder):
-            return ('device', eng.ctc_greedy_async(o, olens.numpy()), eng)
-        if isinstance(self.ctc_decoder, BeamDecoder):
-            return ('device', eng._decode_async(eng.lib.cocr_ctc_beam, o, olens.numpy(), extra=(int(self.ctc_decoder.beam_size),)), eng)
-        if isinstance(self.ctc_decoder, LMDecoder):
+        if isinstance(self.ctc_decoder, _DeviceDecoder):
             return ('device', self.ctc_decoder.decode_async(eng, o, olens.numpy()), eng)
-        o = o.transpose(1, 2).cpu().float().numpy()           # a user-supplied decoder: the reference's own host loop
+        o = o.transpose(1, 2).cpu().float().numpy()           # a user-supplied decoder: the reference's own host loop (pred.py:158-162)
         return ('host', [self.ctc_decoder(seq[:, :int(seq_len)]) for seq, seq_len in zip(o, olens)], None)
 
     def collect_strings(self, handle) -> List[str]:
         kind, h, eng = handle
         lut = self._codec_lut() if kind == 'device' else None
         if lut is not None:
+            # device decode + a 1:1 codec: label arrays -> characters by one table lookup per line (the record lists of `predict_labels`
+            # and the codec's tuple walk cost 0.26 ms per 32 lines on the host, after the GPU had finished: a fifth of the call)
             size = lut.shape[0]
             return [''.join(lut[np.minimum(lab, size - 1)].tolist()) for lab in eng.collect_labels(h)]
         records = eng.collect(h) if kind == 'device' else h

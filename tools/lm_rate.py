@@ -74,7 +74,7 @@ if not args.build_only:
         e1.synchronize()
         eng.collect(h)
         return e0.elapsed_time(e1)                                       # ms
-    legs = {'ctc_beam': lambda: eng._decode_async(eng.lib.cocr_ctc_beam, logits, lens, extra=(16,)),
+    legs = {'ctc_beam': lambda: eng.ctc_beam_async(logits, lens, 16),
             'ctc_beam_lm_order3': lambda: eng.ctc_beam_lm_async(logits, lens, lms[3], 16, 8, 0.5, 0.0),
             'ctc_beam_lm_order5': lambda: eng.ctc_beam_lm_async(logits, lens, lms[5], 16, 8, 0.5, 0.0),
             'ctc_beam_lm_order5_alpha0': lambda: eng.ctc_beam_lm_async(logits, lens, lms[5], 16, 8, 0.0, 0.0)}

@@ -63,7 +63,7 @@ def timed(fn, collect):
 
 legs = {}
 for kind, logits in kinds.items():
-    legs[f'{kind}_ctc_beam'] = (lambda logits=logits: eng._decode_async(eng.lib.cocr_ctc_beam, logits, lens, extra=(BEAM,)), eng.collect)
+    legs[f'{kind}_ctc_beam'] = (lambda logits=logits: eng.ctc_beam_async(logits, lens, BEAM), eng.collect)
     legs[f'{kind}_ctc_beam_lm'] = (lambda logits=logits: eng.ctc_beam_lm_async(logits, lens, lm, BEAM, 8, 0.5, 0.0), eng.collect)
     for k in (1, 4, 16):
         legs[f'{kind}_nbest{k}'] = (lambda k=k, logits=logits: eng.ctc_beam_nbest_async(logits, lens, BEAM, k), eng.collect_nbest)
