@@ -95,6 +95,79 @@ __device__ __forceinline__ float lse2(float a, float b) {
     return m + 0.6931471805599453f * __builtin_amdgcn_logf(1.f + __builtin_amdgcn_exp2f(d * 1.4426950408889634f));
 }
 
+// ---- the beam searches' post-pass, one copy of each piece (DESIGN.md "The beam kernels' shared post-pass"; the host's copy is
+// lm.records_host).  A back-pointer is (parent rank << 16) | appended label, label 0 = the prefix stayed.
+// prefix identity: h_0 = seed, h_k = h_{k-1} * prime + (label_k + 1) (FNV's 64-bit constants; ctc_lm.hip.h's n-gram keys run the same chain)
+#define COCR_HASH_SEED 1469598103934665603ull
+#define COCR_HASH_PRIME 1099511628211ull
+
+// back-pointer of prefix i's stay candidate: its first creator -- the extension at position mp that was folded into it, if that came first
+__device__ __forceinline__ int beam_stay_bp(int i, int mp, int C) { return mp < i * C ? (((mp / C) << 16) | (mp % C)) : (i << 16); }
+
+// One label's run: label c of the line's logits lg [.][C], appended at frame s, holds while it beats the blank and the next label has
+// not started (limit); conf = exp(max over the run of logit - log Z).  logz(t): log Z of frame t, read where the kernel keeps it.
+struct BeamRun { int end; float lmax; __device__ __forceinline__ float conf() const { return expf(lmax); } };      // lmax: the max before exp
+template <class LZ>
+__device__ __forceinline__ BeamRun beam_run(const float *lg, int C, int c, int s, int limit, LZ logz) {
+    int e = s;
+    while (e + 1 < limit && lg[(size_t)(e + 1) * C + c] > lg[(size_t)(e + 1) * C]) ++e;
+    float mxp = -INFINITY;
+    for (int t = s; t <= e; ++t) mxp = fmaxf(mxp, lg[(size_t)t * C + c] - logz(t));
+    return {e, mxp};
+}
+
+// ends / confidences of a line's cnt kept labels (olab, ost: its labels and starts; its row of ends and conf begins at `row`), NT threads;
+// next: the start of the first label a truncated row leaves out (else len).  By reference: it is read from LDS where the last label needs it.
+template <int NT, class LZ>
+__device__ __forceinline__ void beam_records(const float *lg, int C, const int32_t *olab, const int32_t *ost, int cnt, const int &next, int tid,
+                                             int32_t *ends, float *conf, size_t row, LZ logz) {
+    for (int k = tid; k < cnt; k += NT) {
+        const BeamRun r = beam_run(lg, C, olab[k], ost[k], k + 1 < cnt ? ost[k + 1] : next, logz);
+        ends[row + k] = r.end;
+        conf[row + k] = r.conf();
+    }
+}
+
+// The best prefix from back-pointer rows [len][COCR_BEAM_MAX] in global memory, one thread: count its labels, then place the first
+// max_per_line of them and their start frames.  cnt: the full count; next: as above.
+struct BeamWalk { int cnt, next; };
+__device__ __forceinline__ BeamWalk beam_walk_rows(const int32_t *bp, int len, int max_per_line, int32_t *olab, int32_t *ost) {
+    int cnt = 0, e = 0, nx = len;
+    for (int t = len - 1; t >= 0; --t) {
+        const int v = bp[(size_t)t * COCR_BEAM_MAX + e];
+        if (v & 0xffff) ++cnt;
+        e = v >> 16;
+    }
+    int k = cnt;
+    e = 0;
+    for (int t = len - 1; t >= 0; --t) {
+        const int v = bp[(size_t)t * COCR_BEAM_MAX + e];
+        if (v & 0xffff) { --k; if (k < max_per_line) { olab[k] = v & 0xffff; ost[k] = t; } else if (k == max_per_line) nx = t; }
+        e = v >> 16;
+    }
+    return {cnt, nx};
+}
+
+// The same from rows [len][beam] in LDS, walked ONCE (the serial chain is not made twice as long): thread 0 pushes (label, frame) on
+// stk [len][2], last label first; then the workgroup's 256 threads copy the kept rows out.
+__device__ __forceinline__ void beam_walk_lds(const int32_t *bpl, int beam, int32_t *stk, int len, int max_per_line, int tid, int32_t *olab, int32_t *ost,
+                                              int &cnt_out, int &next, int32_t &count) {
+    if (tid == 0) {
+        int cnt = 0, e = 0;
+        for (int t = len - 1; t >= 0; --t) {
+            const int v = bpl[t * beam + e];
+            if (v & 0xffff) { stk[2 * cnt] = v & 0xffff; stk[2 * cnt + 1] = t; ++cnt; }
+            e = v >> 16;
+        }
+        cnt_out = cnt;
+        next = cnt > max_per_line ? stk[2 * (cnt - 1 - max_per_line) + 1] : len;
+        count = cnt;
+    }
+    __syncthreads();
+    const int cnt = cnt_out;
+    for (int k = tid; k < min(cnt, max_per_line); k += 256) { olab[k] = stk[2 * (cnt - 1 - k)]; ost[k] = stk[2 * (cnt - 1 - k) + 1]; }
+}
+
 __global__ __launch_bounds__(64) void ctc_beam_kernel(const float *__restrict__ logits, int T, int C, const int32_t *__restrict__ lens, int beam,
                                                       int32_t *__restrict__ labels, int32_t *__restrict__ starts, int32_t *__restrict__ ends,
                                                       float *__restrict__ conf, int32_t *__restrict__ counts, int max_per_line,
@@ -117,7 +190,7 @@ __global__ __launch_bounds__(64) void ctc_beam_kernel(const float *__restrict__ 
     const float *lg = logits + (size_t)n * T * C;
     int32_t *bp = bp_all + (size_t)n * T * COCR_BEAM_MAX;            // (parent << 16) | label, per frame and rank
     float *logz = logz_all + (size_t)n * T;
-    if (lane == 0) { pb[0] = 0.f; pnb[0] = -INFINITY; last[0] = 0; hash[0] = 1469598103934665603ull; }
+    if (lane == 0) { pb[0] = 0.f; pnb[0] = -INFINITY; last[0] = 0; hash[0] = COCR_HASH_SEED; }
     int nb = 1;
     for (int t = 0; t < len; ++t) {
         // 1. log-softmax of the frame
@@ -139,7 +212,7 @@ __global__ __launch_bounds__(64) void ctc_beam_kernel(const float *__restrict__ 
                 } else {
                     e = (c == li ? p_b : tot) + lp[c];
                     if (e > -INFINITY) {
-                        const unsigned long long hc = hi * 1099511628211ull + (unsigned long long)(c + 1);
+                        const unsigned long long hc = hi * COCR_HASH_PRIME + (unsigned long long)(c + 1);
                         for (int q = 0; q < nb; ++q)
                             if (q != i && hash[q] == hc) { mval[q] = e; mpos[q] = i * C + c; e = -INFINITY; break; }
                     }
@@ -182,10 +255,10 @@ __global__ __launch_bounds__(64) void ctc_beam_kernel(const float *__restrict__ 
             if (c == 0) {
                 npb[lane] = spb[i]; npnb[lane] = spnb[i]; nlast[lane] = last[i]; nhash[lane] = hash[i];
                 const int mp = mpos[i];
-                bp[(size_t)t * COCR_BEAM_MAX + lane] = mp < i * C ? (((mp / C) << 16) | (mp % C)) : (i << 16);   // first creator
+                bp[(size_t)t * COCR_BEAM_MAX + lane] = beam_stay_bp(i, mp, C);
             } else {
                 npb[lane] = -INFINITY; npnb[lane] = (c == last[i] ? pb[i] : lse2(pb[i], pnb[i])) + lp[c]; nlast[lane] = c;
-                nhash[lane] = hash[i] * 1099511628211ull + (unsigned long long)(c + 1);
+                nhash[lane] = hash[i] * COCR_HASH_PRIME + (unsigned long long)(c + 1);
                 bp[(size_t)t * COCR_BEAM_MAX + lane] = (i << 16) | c;
             }
         }
@@ -195,38 +268,13 @@ __global__ __launch_bounds__(64) void ctc_beam_kernel(const float *__restrict__ 
         __syncthreads();
     }
     // ---- best prefix: walk the back-pointers (one lane), then ends / confidences in parallel over the labels
-    __shared__ int s_cnt, s_next;                                    // s_next: the start of the first label a truncated row leaves out (else len)
+    __shared__ int s_cnt, s_next;
     int32_t *olab = labels + (size_t)n * max_per_line, *ost = starts + (size_t)n * max_per_line;
-    if (lane == 0) {
-        int cnt = 0, e = 0, nx = len;
-        for (int t = len - 1; t >= 0; --t) {
-            const int v = bp[(size_t)t * COCR_BEAM_MAX + e];
-            if (v & 0xffff) ++cnt;
-            e = v >> 16;
-        }
-        s_cnt = cnt;
-        int k = cnt;
-        e = 0;
-        for (int t = len - 1; t >= 0; --t) {
-            const int v = bp[(size_t)t * COCR_BEAM_MAX + e];
-            if (v & 0xffff) { --k; if (k < max_per_line) { olab[k] = v & 0xffff; ost[k] = t; } else if (k == max_per_line) nx = t; }
-            e = v >> 16;
-        }
-        s_next = nx;
-        counts[n] = cnt;
-    }
+    if (lane == 0) { const BeamWalk w = beam_walk_rows(bp, len, max_per_line, olab, ost); s_cnt = w.cnt; s_next = w.next; counts[n] = w.cnt; }
     __syncthreads();
     __threadfence_block();
-    const int cnt = min(s_cnt, max_per_line);
-    for (int k = lane; k < cnt; k += 64) {
-        const int c = olab[k], s = ost[k], limit = k + 1 < cnt ? ost[k + 1] : s_next;
-        int e = s;
-        while (e + 1 < limit && lg[(size_t)(e + 1) * C + c] > lg[(size_t)(e + 1) * C]) ++e;
-        float mxp = -INFINITY;
-        for (int t = s; t <= e; ++t) mxp = fmaxf(mxp, lg[(size_t)t * C + c] - logz[t]);
-        ends[(size_t)n * max_per_line + k] = e;
-        conf[(size_t)n * max_per_line + k] = expf(mxp);
-    }
+    beam_records<64>(lg, C, olab, ost, min(s_cnt, max_per_line), s_next, lane, ends, conf, (size_t)n * max_per_line,
+                     [=](int t) { return logz[t]; });
 }
 
 
@@ -353,7 +401,6 @@ __global__ __launch_bounds__(256) void ctc_beam_walk_kernel(const float *__restr
                                                             const unsigned char *__restrict__ rec_all, int32_t *__restrict__ bp_gbl, int bp_in_lds,
                                                             unsigned long long *dbg) {
     constexpr int NB = COCR_BEAM_MAX, KM = COCR_BEAM_KMAX, RING = 4, STAY0 = 192;
-    constexpr unsigned long long PRIME = 1099511628211ull;
     __shared__ __attribute__((aligned(16))) unsigned char ring[RING][COCR_BEAM_REC];
     __shared__ __attribute__((aligned(16))) unsigned long long ckey[STAY0 + NB];                 // extensions [0, nep), stays [nep, nep + beam), zeros between
     __shared__ __attribute__((aligned(16))) unsigned long long hash[NB], phash[NB], hx[NB];
@@ -385,7 +432,7 @@ __global__ __launch_bounds__(256) void ctc_beam_walk_kernel(const float *__restr
     if (tid < NB) {
         const bool root = tid == 0;
         pb[tid] = root ? 0.f : -INFINITY; tot[tid] = root ? 0.f : -INFINITY; spb[tid] = -INFINITY; spnb[tid] = -INFINITY; lpl[tid] = 0.f;
-        last[tid] = 0; hash[tid] = root ? 1469598103934665603ull : 0ull; phash[tid] = 0ull; hx[tid] = root ? 1469598103934665603ull * PRIME : 0ull;
+        last[tid] = 0; hash[tid] = root ? COCR_HASH_SEED : 0ull; phash[tid] = 0ull; hx[tid] = root ? COCR_HASH_SEED * COCR_HASH_PRIME : 0ull;
         pair_s[tid] = -1;
     }
     if (tid < 4) live_s[tid] = 0;
@@ -523,7 +570,7 @@ __global__ __launch_bounds__(256) void ctc_beam_walk_kernel(const float *__restr
         if (key != 0ull && rank < beam) {
             const int R = rank, nl = n_last;
             const float l2 = lpn[nl], lp0n = lpn[0];
-            pb[R] = n_pb; tot[R] = n_tot; last[R] = nl; hash[R] = n_hash; phash[R] = n_ph; hx[R] = n_hash * PRIME;
+            pb[R] = n_pb; tot[R] = n_tot; last[R] = nl; hash[R] = n_hash; phash[R] = n_ph; hx[R] = n_hash * COCR_HASH_PRIME;
             spb[R] = n_tot + lp0n; spnb[R] = nl > 0 ? n_pnb + l2 : -INFINITY; lpl[R] = nl > 0 ? l2 : 0.f;
             if (bp_in_lds) bpl[t * beam + R] = n_bp; else bpg[(size_t)t * NB + R] = n_bp;
         }
@@ -538,6 +585,9 @@ __global__ __launch_bounds__(256) void ctc_beam_walk_kernel(const float *__restr
     __syncthreads();
     // ---- best prefix: walk the back-pointers (one lane), then ends / confidences in parallel over the labels
     int32_t *olab = labels + (size_t)n * max_per_line, *ost = starts + (size_t)n * max_per_line;
+    // beam_walk_lds and beam_records' loop stand written out here: a change to either goes into both places.  As calls they move this kernel's
+    // frame loop (other registers, neighbouring instructions swapped) and cocr_ctc_beam measured 0.2 % slower, outside the parent's spread
+    // (DESIGN.md "The beam kernels' shared post-pass").
     if (bp_in_lds) {
         int32_t *stk = bpl + (size_t)T * beam;                                 // [T][2] (label, frame), last label first
         if (tid == 0) {
@@ -554,35 +604,15 @@ __global__ __launch_bounds__(256) void ctc_beam_walk_kernel(const float *__restr
         __syncthreads();
         const int cnt = s_cnt;
         for (int k2 = tid; k2 < min(cnt, max_per_line); k2 += 256) { olab[k2] = stk[2 * (cnt - 1 - k2)]; ost[k2] = stk[2 * (cnt - 1 - k2) + 1]; }
-    } else if (tid == 0) {
-        int cnt = 0, e = 0, nx = len;
-        for (int t = len - 1; t >= 0; --t) {
-            const int v = bpg[(size_t)t * NB + e];
-            if (v & 0xffff) ++cnt;
-            e = v >> 16;
-        }
-        s_cnt = cnt;
-        int k2 = cnt;
-        e = 0;
-        for (int t = len - 1; t >= 0; --t) {
-            const int v = bpg[(size_t)t * NB + e];
-            if (v & 0xffff) { --k2; if (k2 < max_per_line) { olab[k2] = v & 0xffff; ost[k2] = t; } else if (k2 == max_per_line) nx = t; }
-            e = v >> 16;
-        }
-        s_next = nx;
-        counts[n] = cnt;
-    }
+    } else if (tid == 0) { const BeamWalk w = beam_walk_rows(bpg, len, max_per_line, olab, ost); s_cnt = w.cnt; s_next = w.next; counts[n] = w.cnt; }
     __threadfence_block();
     __syncthreads();
     const int cnt = min(s_cnt, max_per_line);
-    for (int k2 = tid; k2 < cnt; k2 += 256) {
-        const int c = olab[k2], s0 = ost[k2], limit = k2 + 1 < cnt ? ost[k2 + 1] : s_next;
-        int e = s0;
-        while (e + 1 < limit && lg[(size_t)(e + 1) * C + c] > lg[(size_t)(e + 1) * C]) ++e;
-        float mxp = -INFINITY;
-        for (int t = s0; t <= e; ++t) mxp = fmaxf(mxp, lg[(size_t)t * C + c] - *reinterpret_cast<const float *>(rec + (size_t)t * COCR_BEAM_REC + COCR_BEAM_REC_LZ));
-        ends[(size_t)n * max_per_line + k2] = e;
-        conf[(size_t)n * max_per_line + k2] = expf(mxp);
+    for (int k = tid; k < cnt; k += 256) {
+        const BeamRun r = beam_run(lg, C, olab[k], ost[k], k + 1 < cnt ? ost[k + 1] : s_next,
+                                   [=](int t) { return *reinterpret_cast<const float *>(rec + (size_t)t * COCR_BEAM_REC + COCR_BEAM_REC_LZ); });
+        ends[(size_t)n * max_per_line + k] = r.end;
+        conf[(size_t)n * max_per_line + k] = r.conf();
     }
 #ifdef COCR_CHAIN_STAMPS_BUILD
     BSTAMP(4)

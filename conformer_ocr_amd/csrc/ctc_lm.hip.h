@@ -62,13 +62,13 @@ __device__ __forceinline__ float lm_lookup(const cocr_lm_tables &L, const unsign
     for (int k = 0; k < COCR_LM_CTX; ++k) kmax += (k < L.order - 1 && ctx[k] != 0) ? 1 : 0;      // (labels fill ctx from the front)
     unsigned long long kn[COCR_LM_CTX], kc[COCR_LM_CTX], gn[COCR_LM_CTX], gc[COCR_LM_CTX];
     float vn[COCR_LM_CTX], vc[COCR_LM_CTX];
-    unsigned long long h = 1469598103934665603ull;
+    unsigned long long h = COCR_HASH_SEED;
     const float uni = L.unigram[c];
 #pragma unroll
     for (int k = 0; k < COCR_LM_CTX; ++k) {
         kn[k] = kc[k] = gn[k] = gc[k] = 0ull; vn[k] = vc[k] = 0.f;
         if (k < kmax) {
-            h = h * 1099511628211ull + (unsigned long long)(ctx[k] + 1);
+            h = h * COCR_HASH_PRIME + (unsigned long long)(ctx[k] + 1);
             kn[k] = lm_key(h, (unsigned)c, (unsigned)(k + 1));
             kc[k] = lm_key(h, 0u, (unsigned)(k + 1));
             const unsigned sn = (unsigned)kn[k] & L.nmask, sc = (unsigned)kc[k] & L.cmask;
@@ -143,7 +143,6 @@ __global__ __launch_bounds__(256) void ctc_lm_walk_kernel(const float *__restric
                                                           float *__restrict__ conf, int32_t *__restrict__ counts, float *__restrict__ score, int max_per_line,
                                                           const float *__restrict__ rec_all, int32_t *__restrict__ bp_gbl, int bp_in_lds) {
     constexpr int NB = COCR_BEAM_MAX, STAY0 = 256 - NB;
-    constexpr unsigned long long PRIME = 1099511628211ull;
     __shared__ __attribute__((aligned(16))) unsigned long long ckey[COCR_LM_NE + NB];             // extensions [0, NE), stays [NE, NE + beam), one zero pad
     __shared__ __attribute__((aligned(16))) lm_prefix_state st[2];
     __shared__ __attribute__((aligned(16))) float clmv[COCR_LM_NE], recs[2][COCR_LM_REC], spb[NB], spnb[NB], mval[NB];
@@ -160,7 +159,7 @@ __global__ __launch_bounds__(256) void ctc_lm_walk_kernel(const float *__restric
     if (tid < NB) {
         const bool root = tid == 0;
         lm_prefix_state &s = st[0];
-        s.hash[tid] = root ? 1469598103934665603ull : 0ull; s.ctx[tid] = make_uint4(0u, 0u, 0u, 0u);
+        s.hash[tid] = root ? COCR_HASH_SEED : 0ull; s.ctx[tid] = make_uint4(0u, 0u, 0u, 0u);
         s.pb[tid] = root ? 0.f : -INFINITY; s.pnb[tid] = -INFINITY; s.tot[tid] = root ? 0.f : -INFINITY; s.lmv[tid] = 0.f; s.last[tid] = 0;
         mval[tid] = -INFINITY; mpos[tid] = 0x7fffffff;
     }
@@ -188,7 +187,7 @@ __global__ __launch_bounds__(256) void ctc_lm_walk_kernel(const float *__restric
             unsigned long long key = 0ull;
             const float e = c > 0 ? (c == li ? cur.pb[i] : cur.tot[i]) + tlc[r] : -INFINITY;
             if (e > -INFINITY) {
-                const unsigned long long hc = cur.hash[i] * PRIME + (unsigned long long)(c + 1);
+                const unsigned long long hc = cur.hash[i] * COCR_HASH_PRIME + (unsigned long long)(c + 1);
                 bool folded = false;                                           // it equals live prefix q: it adds to q's stay candidate
                 for (int q = 0; q < beam; ++q)
                     if (q != i && cur.hash[q] == hc && cur.tot[q] > -INFINITY) { mval[q] = e; mpos[q] = i * C + c; folded = true; break; }
@@ -217,7 +216,7 @@ __global__ __launch_bounds__(256) void ctc_lm_walk_kernel(const float *__restric
             const float total = lse2(s_b, s_nb);
             const int mp = mpos[i];
             spb[i] = s_b; spnb[i] = s_nb;
-            sbp[i] = mp < i * C ? (((mp / C) << 16) | (mp % C)) : (i << 16);   // first creator
+            sbp[i] = beam_stay_bp(i, mp, C);
             ckey[NE + i] = beam_key(__fadd_rn(total, cur.lmv[i]), (unsigned)min(i * C, mp));
         }
         __syncthreads();                                                       // (B) all keys are in LDS
@@ -245,7 +244,7 @@ __global__ __launch_bounds__(256) void ctc_lm_walk_kernel(const float *__restric
                 const float e = (c == cur.last[i] ? cur.pb[i] : cur.tot[i]) + tlc[r];
                 const uint4 cw = cur.ctx[i];
                 nxt.pb[R] = -INFINITY; nxt.pnb[R] = e; nxt.tot[R] = e; nxt.lmv[R] = clmv[j];
-                nxt.last[R] = c; nxt.hash[R] = cur.hash[i] * PRIME + (unsigned long long)(c + 1);
+                nxt.last[R] = c; nxt.hash[R] = cur.hash[i] * COCR_HASH_PRIME + (unsigned long long)(c + 1);
                 nxt.ctx[R] = make_uint4((cw.x << 16) | (unsigned)c, (cw.y << 16) | (cw.x >> 16), (cw.z << 16) | (cw.y >> 16), (cw.w << 16) | (cw.z >> 16));
                 bpv = (i << 16) | c;
             }
@@ -259,50 +258,10 @@ __global__ __launch_bounds__(256) void ctc_lm_walk_kernel(const float *__restric
     if (tid == 0 && score) { score[2 * n] = fin.tot[0]; score[2 * n + 1] = fin.lmv[0]; }
     // ---- best prefix: walk the back-pointers (one lane), then ends / confidences in parallel over the labels
     int32_t *olab = labels + (size_t)n * max_per_line, *ost = starts + (size_t)n * max_per_line;
-    if (bp_in_lds) {
-        int32_t *stk = bpl + (size_t)T * beam;                                 // [T][2] (label, frame), last label first
-        if (tid == 0) {
-            int cnt = 0, e = 0;
-            for (int t = len - 1; t >= 0; --t) {
-                const int v = bpl[t * beam + e];
-                if (v & 0xffff) { stk[2 * cnt] = v & 0xffff; stk[2 * cnt + 1] = t; ++cnt; }
-                e = v >> 16;
-            }
-            s_cnt = cnt;
-            s_next = cnt > max_per_line ? stk[2 * (cnt - 1 - max_per_line) + 1] : len;      // the start of the first label a truncated row leaves out
-            counts[n] = cnt;
-        }
-        __syncthreads();
-        const int cnt = s_cnt;
-        for (int k2 = tid; k2 < min(cnt, max_per_line); k2 += 256) { olab[k2] = stk[2 * (cnt - 1 - k2)]; ost[k2] = stk[2 * (cnt - 1 - k2) + 1]; }
-    } else if (tid == 0) {
-        int cnt = 0, e = 0, nx = len;
-        for (int t = len - 1; t >= 0; --t) {
-            const int v = bpg[(size_t)t * NB + e];
-            if (v & 0xffff) ++cnt;
-            e = v >> 16;
-        }
-        s_cnt = cnt;
-        int k2 = cnt;
-        e = 0;
-        for (int t = len - 1; t >= 0; --t) {
-            const int v = bpg[(size_t)t * NB + e];
-            if (v & 0xffff) { --k2; if (k2 < max_per_line) { olab[k2] = v & 0xffff; ost[k2] = t; } else if (k2 == max_per_line) nx = t; }
-            e = v >> 16;
-        }
-        s_next = nx;
-        counts[n] = cnt;
-    }
+    if (bp_in_lds) beam_walk_lds(bpl, beam, bpl + (size_t)T * beam, len, max_per_line, tid, olab, ost, s_cnt, s_next, counts[n]);
+    else if (tid == 0) { const BeamWalk w = beam_walk_rows(bpg, len, max_per_line, olab, ost); s_cnt = w.cnt; s_next = w.next; counts[n] = w.cnt; }
     __threadfence_block();
     __syncthreads();
-    const int cnt = min(s_cnt, max_per_line);
-    for (int k2 = tid; k2 < cnt; k2 += 256) {
-        const int c = olab[k2], s0 = ost[k2], limit = k2 + 1 < cnt ? ost[k2 + 1] : s_next;
-        int e = s0;
-        while (e + 1 < limit && lg[(size_t)(e + 1) * C + c] > lg[(size_t)(e + 1) * C]) ++e;
-        float mxp = -INFINITY;
-        for (int t = s0; t <= e; ++t) mxp = fmaxf(mxp, lg[(size_t)t * C + c] - rec[(size_t)t * COCR_LM_REC + 1]);
-        ends[(size_t)n * max_per_line + k2] = e;
-        conf[(size_t)n * max_per_line + k2] = expf(mxp);
-    }
+    beam_records<256>(lg, C, olab, ost, min(s_cnt, max_per_line), s_next, tid, ends, conf, (size_t)n * max_per_line,
+                      [=](int t) { return rec[(size_t)t * COCR_LM_REC + 1]; });
 }

@@ -9,8 +9,8 @@
 //   trace   lane j < nbest of wave 0 walks chain j from (len - 1, j): up to 32 independent chains advance in one wave.  A sentinel at
 //           the first step: hypothesis j does not exist.  Every appended label is pushed on the chain's stack as (label << 16) |
 //           frame, last label first (LDS with IN_LDS, else a workspace region);
-//   records ends / confidences by the 1-best kernels' post-pass, parallel over (hypothesis, label), the same float operations in the
-//           same order: hypothesis 0 is bit for bit what the walk kernel writes;
+//   records ends / confidences by the 1-best kernels' beam_run (ctc.hip.h), parallel over (hypothesis, label): hypothesis 0 is bit for
+//           bit what the walk kernel writes;
 //   score   one wave per hypothesis, the four waves round robin: the forward recursion of the criterion (ctc_loss.hip.h) on the
 //           blank-extended labels with the shared pieces of ctc_lattice.hip.h -- nothing goes through memory inside the T-step chain
 //           -- in the narrowest form (1, 2, 4 or 8 states per lane) that holds the hypothesis; more than COCR_LATTICE_MAX_LABELS
@@ -143,12 +143,9 @@ __global__ __launch_bounds__(256) void ctc_nbest_kernel(const float *__restrict_
         const unsigned *my = stk + (size_t)j * sstride;
         const unsigned ent = my[cnt - 1 - k];
         const int c = (int)(ent >> 16), s0 = (int)(ent & 0xffffu), limit = k + 1 < cnt ? (int)(my[cnt - 2 - k] & 0xffffu) : len;      // (the next label's start, kept in the row or not)
-        int e = s0;
-        while (e + 1 < limit && lg[(size_t)(e + 1) * C + c] > lg[(size_t)(e + 1) * C]) ++e;
-        float mxp = -INFINITY;
-        for (int t = s0; t <= e; ++t) mxp = fmaxf(mxp, lg[(size_t)t * C + c] - lz[t]);
+        const BeamRun r = beam_run(lg, C, c, s0, limit, [=](int t) { return lz[t]; });
         const size_t o = ((size_t)n * nbest + j) * max_per_line + k;
-        labels[o] = c; starts[o] = s0; ends[o] = e; conf[o] = expf(mxp);
+        labels[o] = c; starts[o] = s0; ends[o] = r.end; conf[o] = r.conf();
     }
 
     // ---- scores: hypothesis j0 + wave

@@ -39,6 +39,21 @@ static int check_labels(const char *noun, const int32_t *labels, size_t total, i
     return COCR_OK;
 }
 
+// The shape checks the entry points repeat: a batch of N lines of T frames and ncls >= min_cls classes (rows: max_per_line, where the
+// call has one); frame_limit: the call's kernels hold a line's frames in LDS.
+static int check_frames(int T) { return T > 8000 ? fail(COCR_EUNSUPPORTED, "more than 8000 frames per line") : COCR_OK; }
+static int check_shape(int N, int T, int ncls, int min_cls, bool frame_limit, int rows = 1) {
+    if (N < 1 || T < 1 || ncls < min_cls || rows < 1) return fail(COCR_EINVAL, "empty problem");
+    return frame_limit ? check_frames(T) : COCR_OK;
+}
+
+// Behind a call's checks: its device, its stream, and the per-line lengths on their way to the device.
+static int begin_call(cocr_model *m, const int32_t *lens, int N, void *stream, hipStream_t &s, const int32_t *&d_lens) {
+    HIP_TRY(hipSetDevice(m->device));
+    s = (hipStream_t)stream;
+    return upload_lens(m, lens, N, s, d_lens);
+}
+
 // Where the per-line (per-pair) table of a lattice kernel lives: in dynamic LDS behind the frame statistics when all of it
 // (`lds_all` bytes) fits -- the kernels have ~5 KB of static LDS of their own -- else in `ws`, grown to `ws_words`, the statistics
 // (`lds_stats` bytes) alone in LDS.  `lds`: the dynamic LDS to launch with; `ws`: null for the LDS form.
@@ -65,13 +80,11 @@ int ensure_ctc_scratch(cocr_model *m, size_t rows) {
 extern "C" int cocr_ctc_greedy(cocr_model *m, const float *logits, int N, int T, int ncls, const int32_t *out_lens, int32_t *labels,
                                int32_t *starts, int32_t *ends, float *conf, int32_t *counts, int max_per_line, void *stream) {
     if (!m || !logits || !out_lens || !labels || !starts || !ends || !conf || !counts) return fail(COCR_EINVAL, "null argument");
-    if (N < 1 || T < 1 || ncls < 1 || max_per_line < 1) return fail(COCR_EINVAL, "empty problem");
-    if (T > 8000) return fail(COCR_EUNSUPPORTED, "more than 8000 frames per line");
-    HIP_TRY(hipSetDevice(m->device));
-    hipStream_t s = (hipStream_t)stream;
-    const int32_t *d_lens;
-    int rc = upload_lens(m, out_lens, N, s, d_lens);
+    int rc = check_shape(N, T, ncls, 1, true, max_per_line);
     if (rc) return rc;
+    hipStream_t s;
+    const int32_t *d_lens;
+    if ((rc = begin_call(m, out_lens, N, stream, s, d_lens))) return rc;
     const bool have_argmax = logits == m->dec.amax_logits && N * T == m->dec.amax_rows && ncls == m->ncls;      // the decoder's epilogue computed it for these logits
     if (!have_argmax && (rc = ensure_ctc_scratch(m, (size_t)N * T))) return rc;
     ProfScope ps(m, s, FAM_GREEDY);
@@ -90,58 +103,67 @@ extern "C" int cocr_ctc_greedy(cocr_model *m, const float *logits, int N, int T,
 // frame (n, t) at lz[(n T + t) lz_stride], and `extra` bytes of the caller's behind both (16-byte aligned).
 struct BeamTrail { const int32_t *bp; const float *lz; int lz_stride; unsigned char *extra; };
 
-// The walk kernel's own 1-best outputs of an n-best call, one record per line (max_per_line 1: it is asked for no more), at the head of
-// `extra`.
+// The outputs of a 1-best call.  The walk kernel's own of an n-best call, one record per line (max_per_line 1: it is asked for no more),
+// sit at the head of `extra`.
+struct BeamOut { int32_t *labels, *starts, *ends; float *conf; int32_t *counts; };
 static size_t walk_out_bytes(int N) { return ((size_t)N * 5 * 4 + 15) / 16 * 16; }
-static void walk_out_at(unsigned char *p, int N, int32_t *&labels, int32_t *&starts, int32_t *&ends, float *&conf, int32_t *&counts) {
+static BeamOut walk_out_at(unsigned char *p, int N) {
     int32_t *q = reinterpret_cast<int32_t *>(p);
-    labels = q; starts = q + N; ends = q + 2 * N; conf = reinterpret_cast<float *>(q + 3 * N); counts = q + 4 * N;
+    return {q, q + N, q + 2 * N, reinterpret_cast<float *>(q + 3 * N), q + 4 * N};
 }
 
-// The launches of cocr_ctc_beam behind its checks.  `trail`: null for the 1-best call; else the back-pointers go to global memory over
-// a region filled with 0xFF bytes (-1: the rank was not alive in that frame), `extra` >= walk_out_bytes(N) bytes are kept behind the
-// scratch, and the kernel's 1-best outputs go to their head (the caller passes max_per_line 1 and no output pointers).
-static int beam_launch(cocr_model *m, const float *logits, int N, int T, int ncls, const int32_t *d_lens, int32_t *labels, int32_t *starts, int32_t *ends,
-                       float *conf, int32_t *counts, int max_per_line, int beam, hipStream_t s, size_t extra, BeamTrail *trail) {
+// A beam search's scratch in `buf`: the back-pointers [N][T][COCR_BEAM_MAX] i32, then what the search keeps per frame (rec: so many bytes,
+// log Z at byte lz_off of the first and every lz_stride floats).  `trail`: null for the 1-best call; else the back-pointers go to global
+// memory over a region filled with 0xFF bytes (-1: the rank was not alive in that frame), `extra` >= walk_out_bytes(N) bytes are kept behind
+// the scratch (16-byte aligned), and the kernel's 1-best outputs go to their head (the caller passes max_per_line 1 and no outputs).
+// dyn: the walk kernels' dynamic LDS -- a line's back-pointers and the label stack of the final walk -- which they get when it fits.
+struct BeamRec { size_t bytes, lz_off; int lz_stride; };
+struct BeamScratch { int32_t *bp; unsigned char *rec; size_t dyn; int bp_in_lds; };
+static int plan_beam_scratch(DevBuf<unsigned char> &buf, int N, int T, BeamRec r, int beam, hipStream_t s, size_t extra, BeamTrail *trail, BeamOut &out,
+                             BeamScratch &b) {
+    const size_t bp_bytes = (size_t)N * T * COCR_BEAM_MAX * 4, need = bp_bytes + (size_t)N * T * r.bytes, kept = (need + 15) / 16 * 16;
+    HIP_TRY(buf.grow(trail ? kept + extra : need));
+    b = {reinterpret_cast<int32_t *>(buf.p), buf.p + bp_bytes, (size_t)T * ((size_t)beam * 4 + 8), 0};
+    b.bp_in_lds = !trail && b.dyn <= 96 * 1024;
+    if (trail) {
+        HIP_TRY(hipMemsetAsync(b.bp, 0xFF, bp_bytes, s));
+        *trail = {b.bp, reinterpret_cast<const float *>(b.rec + r.lz_off), r.lz_stride, buf.p + kept};
+        out = walk_out_at(trail->extra, N);
+    }
+    return COCR_OK;
+}
+
+// The launches of cocr_ctc_beam behind its checks; `extra` and `trail` as in plan_beam_scratch.
+static int beam_launch(cocr_model *m, const float *logits, int N, int T, int ncls, const int32_t *d_lens, BeamOut out, int max_per_line, int beam,
+                       hipStream_t s, size_t extra, BeamTrail *trail) {
     const bool fast = ncls <= 256 && !m->sw.beam_ref;            // ctc_beam_rank_kernel + ctc_beam_walk_kernel: frames ranked in parallel, a static pruned candidate set per frame
     const int K = std::min(beam + 1, ncls - 1);
-    // scratch: back-pointers [N][T][COCR_BEAM_MAX] i32, then log Z [N][T] (exhaustive kernel) or the frame records (fast)
-    const size_t bp_bytes = (size_t)N * T * COCR_BEAM_MAX * 4;
-    const size_t need = (size_t)N * T * ((size_t)COCR_BEAM_MAX * 4 + (fast ? (size_t)COCR_BEAM_REC : 4));
-    HIP_TRY(m->dec.beam_bp.grow(trail ? (need + 15) / 16 * 16 + extra : need));
-    int32_t *bp = reinterpret_cast<int32_t *>(m->dec.beam_bp.p);
-    if (trail) {
-        HIP_TRY(hipMemsetAsync(bp, 0xFF, bp_bytes, s));
-        *trail = {bp, nullptr, 1, m->dec.beam_bp.p + (need + 15) / 16 * 16};
-        walk_out_at(trail->extra, N, labels, starts, ends, conf, counts);
-    }
+    BeamScratch b;                                               // behind the back-pointers: the frame records (fast) or log Z [N][T] (exhaustive kernel)
+    const int rc = plan_beam_scratch(m->dec.beam_bp, N, T, fast ? BeamRec{COCR_BEAM_REC, COCR_BEAM_REC_LZ, COCR_BEAM_REC / 4} : BeamRec{4, 0, 1}, beam, s, extra,
+                                     trail, out, b);
+    if (rc) return rc;
     if (fast) {
-        unsigned char *rec = reinterpret_cast<unsigned char *>(bp + (size_t)N * T * COCR_BEAM_MAX);
-        const size_t dyn = (size_t)T * ((size_t)beam * 4 + 8);                 // back-pointers + the label stack of the final walk, in LDS when they fit
-        const int bp_in_lds = !trail && dyn <= 96 * 1024;
-        hipLaunchKernelGGL(ctc_beam_rank_kernel, dim3(N * T), dim3(256), 0, s, logits, T, ncls, d_lens, K, rec);
+        hipLaunchKernelGGL(ctc_beam_rank_kernel, dim3(N * T), dim3(256), 0, s, logits, T, ncls, d_lens, K, b.rec);
         auto walk = ctc_beam_walk_kernel<3>;                          // candidates per lane of a wave: <= 88 for beam <= 16, <= 184 for beam 32
         if (beam <= 16) walk = ctc_beam_walk_kernel<2>;
         // (the kernel also has ~12 KB of static LDS: the limit raised for the dynamic part stays below 160 KB - static)
-        if (bp_in_lds) HIP_TRY(raise_lds_limit((const void *)walk, dyn, 48 * 1024, 96 * 1024));
-        hipLaunchKernelGGL(walk, dim3(N), dim3(256), bp_in_lds ? dyn : 0, s, logits, T, ncls, d_lens, beam, K, labels, starts,
-                           ends, conf, counts, max_per_line, rec, bp, bp_in_lds, m->stamps ? m->stamps + 240 : nullptr);
-        if (trail) { trail->lz = reinterpret_cast<const float *>(rec + COCR_BEAM_REC_LZ); trail->lz_stride = COCR_BEAM_REC / 4; }
+        if (b.bp_in_lds) HIP_TRY(raise_lds_limit((const void *)walk, b.dyn, 48 * 1024, 96 * 1024));
+        hipLaunchKernelGGL(walk, dim3(N), dim3(256), b.bp_in_lds ? b.dyn : 0, s, logits, T, ncls, d_lens, beam, K, out.labels, out.starts,
+                           out.ends, out.conf, out.counts, max_per_line, b.rec, b.bp, b.bp_in_lds, m->stamps ? m->stamps + 240 : nullptr);
     } else {
-        float *logz = reinterpret_cast<float *>(bp + (size_t)N * T * COCR_BEAM_MAX);
         const size_t lds = ((size_t)ncls + (size_t)beam * ncls) * 4 + COCR_BEAM_MAX * (11 * 4 + 2 * 8) + 64;
         if (lds > 150 * 1024) return fail(COCR_EUNSUPPORTED, "beam x classes too large for the LDS candidate table");
         HIP_TRY(raise_lds_limit((const void *)ctc_beam_kernel, lds));
-        hipLaunchKernelGGL(ctc_beam_kernel, dim3(N), dim3(64), lds, s, logits, T, ncls, d_lens, beam, labels, starts, ends, conf, counts,
-                           max_per_line, bp, logz);
-        if (trail) trail->lz = logz;
+        hipLaunchKernelGGL(ctc_beam_kernel, dim3(N), dim3(64), lds, s, logits, T, ncls, d_lens, beam, out.labels, out.starts, out.ends, out.conf, out.counts,
+                           max_per_line, b.bp, reinterpret_cast<float *>(b.rec));
     }
     LAUNCH_CHECK();
     return COCR_OK;
 }
 
 static int beam_check(int N, int T, int ncls, int max_per_line, int beam) {
-    if (N < 1 || T < 1 || ncls < 2 || max_per_line < 1) return fail(COCR_EINVAL, "empty problem");
+    const int rc = check_shape(N, T, ncls, 2, false, max_per_line);
+    if (rc) return rc;
     if (beam < 1 || beam > COCR_BEAM_MAX) return fail(COCR_EINVAL, "beam must be in 1..%d", COCR_BEAM_MAX);
     if (ncls > 65535) return fail(COCR_EUNSUPPORTED, "more than 65535 classes");
     return COCR_OK;
@@ -152,12 +174,11 @@ extern "C" int cocr_ctc_beam(cocr_model *m, const float *logits, int N, int T, i
     if (!m || !logits || !out_lens || !labels || !starts || !ends || !conf || !counts) return fail(COCR_EINVAL, "null argument");
     int rc = beam_check(N, T, ncls, max_per_line, beam);
     if (rc) return rc;
-    HIP_TRY(hipSetDevice(m->device));
-    hipStream_t s = (hipStream_t)stream;
+    hipStream_t s;
     const int32_t *d_lens;
-    if ((rc = upload_lens(m, out_lens, N, s, d_lens))) return rc;
+    if ((rc = begin_call(m, out_lens, N, stream, s, d_lens))) return rc;
     ProfScope ps(m, s, FAM_BEAM);
-    return beam_launch(m, logits, N, T, ncls, d_lens, labels, starts, ends, conf, counts, max_per_line, beam, s, 0, nullptr);
+    return beam_launch(m, logits, N, T, ncls, d_lens, {labels, starts, ends, conf, counts}, max_per_line, beam, s, 0, nullptr);
 }
 
 // ------------------------------------------------------------------------------------ beam search with an n-gram model (ctc_lm.hip.h)
@@ -209,8 +230,8 @@ extern "C" void cocr_lm_destroy(cocr_lm *lm) {
 }
 
 static int beam_lm_check(cocr_model *m, cocr_lm *lm, int N, int T, int ncls, int max_per_line, int beam, int classes, float alpha, float beta) {
-    if (N < 1 || T < 1 || ncls < 2 || max_per_line < 1) return fail(COCR_EINVAL, "empty problem");
-    if (T > 8000) return fail(COCR_EUNSUPPORTED, "more than 8000 frames per line");
+    const int rc = check_shape(N, T, ncls, 2, true, max_per_line);
+    if (rc) return rc;
     if (beam < 1 || beam > COCR_BEAM_MAX) return fail(COCR_EINVAL, "beam must be in 1..%d", COCR_BEAM_MAX);
     if (classes < 1 || classes > COCR_LM_KMAX) return fail(COCR_EINVAL, "classes must be in 1..%d", COCR_LM_KMAX);
     if (ncls != lm->ncls) return fail(COCR_EINVAL, "the logits have %d classes, the language model %d", ncls, lm->ncls);
@@ -227,29 +248,19 @@ static cocr_lm_tables lm_tables(const cocr_lm *lm) {
 }
 
 // The launches of cocr_ctc_beam_lm behind its checks; `extra` and `trail` as in beam_launch.
-static int beam_lm_launch(cocr_model *m, cocr_lm *lm, const float *logits, int N, int T, int ncls, const int32_t *d_lens, int32_t *labels, int32_t *starts,
-                          int32_t *ends, float *conf, int32_t *counts, int max_per_line, int beam, int classes, float alpha, float beta, float *score,
-                          hipStream_t s, size_t extra, BeamTrail *trail) {
+static int beam_lm_launch(cocr_model *m, cocr_lm *lm, const float *logits, int N, int T, int ncls, const int32_t *d_lens, BeamOut out, int max_per_line,
+                          int beam, int classes, float alpha, float beta, float *score, hipStream_t s, size_t extra, BeamTrail *trail) {
     const int K = std::min(classes, ncls - 1);
-    // scratch: back-pointers [N][T][COCR_BEAM_MAX] i32, then the frame records [N][T][COCR_LM_REC] f32
-    const size_t bp_bytes = (size_t)N * T * COCR_BEAM_MAX * 4;
-    const size_t need = bp_bytes + (size_t)N * T * COCR_LM_REC * 4;
-    HIP_TRY(m->dec.lm_scratch.grow(trail ? (need + 15) / 16 * 16 + extra : need));
-    int32_t *bp = reinterpret_cast<int32_t *>(m->dec.lm_scratch.p);
-    float *rec = reinterpret_cast<float *>(m->dec.lm_scratch.p + bp_bytes);
-    if (trail) {
-        HIP_TRY(hipMemsetAsync(bp, 0xFF, bp_bytes, s));
-        *trail = {bp, rec + 1, COCR_LM_REC, m->dec.lm_scratch.p + (need + 15) / 16 * 16};
-        walk_out_at(trail->extra, N, labels, starts, ends, conf, counts);
-    }
-    const size_t dyn = (size_t)T * ((size_t)beam * 4 + 8);                     // back-pointers + the label stack of the final walk, in LDS when they fit
-    const int bp_in_lds = !trail && dyn <= 96 * 1024;
-    if (bp_in_lds) HIP_TRY(raise_lds_limit((const void *)ctc_lm_walk_kernel, dyn, 16 * 1024, 96 * 1024));      // (the kernel has ~30 KB of static LDS)
+    BeamScratch b;                                               // behind the back-pointers: the frame records [N][T][COCR_LM_REC] f32
+    const int rc = plan_beam_scratch(m->dec.lm_scratch, N, T, BeamRec{COCR_LM_REC * 4, 4, COCR_LM_REC}, beam, s, extra, trail, out, b);
+    if (rc) return rc;
+    float *rec = reinterpret_cast<float *>(b.rec);
+    if (b.bp_in_lds) HIP_TRY(raise_lds_limit((const void *)ctc_lm_walk_kernel, b.dyn, 16 * 1024, 96 * 1024));      // (the kernel has ~30 KB of static LDS)
     const cocr_lm_tables L = lm_tables(lm);
     hipLaunchKernelGGL(ctc_lm_topk_kernel, dim3(ceil_div(N * T, 4)), dim3(256), 0, s, logits, T, ncls, N * T, d_lens, K, rec);
     LAUNCH_CHECK();
-    hipLaunchKernelGGL(ctc_lm_walk_kernel, dim3(N), dim3(256), bp_in_lds ? dyn : 0, s, logits, T, ncls, d_lens, beam, K, L, alpha, beta, labels, starts,
-                       ends, conf, counts, score, max_per_line, rec, bp, bp_in_lds);
+    hipLaunchKernelGGL(ctc_lm_walk_kernel, dim3(N), dim3(256), b.bp_in_lds ? b.dyn : 0, s, logits, T, ncls, d_lens, beam, K, L, alpha, beta, out.labels,
+                       out.starts, out.ends, out.conf, out.counts, score, max_per_line, rec, b.bp, b.bp_in_lds);
     LAUNCH_CHECK();
     return COCR_OK;
 }
@@ -260,12 +271,11 @@ extern "C" int cocr_ctc_beam_lm(cocr_model *m, cocr_lm *lm, const float *logits,
     if (!m || !lm || !logits || !out_lens || !labels || !starts || !ends || !conf || !counts) return fail(COCR_EINVAL, "null argument");
     int rc = beam_lm_check(m, lm, N, T, ncls, max_per_line, beam, classes, alpha, beta);
     if (rc) return rc;
-    HIP_TRY(hipSetDevice(m->device));
-    hipStream_t s = (hipStream_t)stream;
+    hipStream_t s;
     const int32_t *d_lens;
-    if ((rc = upload_lens(m, out_lens, N, s, d_lens))) return rc;
+    if ((rc = begin_call(m, out_lens, N, stream, s, d_lens))) return rc;
     ProfScope ps(m, s, FAM_BEAM);
-    return beam_lm_launch(m, lm, logits, N, T, ncls, d_lens, labels, starts, ends, conf, counts, max_per_line, beam, classes, alpha, beta, score, s, 0, nullptr);
+    return beam_lm_launch(m, lm, logits, N, T, ncls, d_lens, {labels, starts, ends, conf, counts}, max_per_line, beam, classes, alpha, beta, score, s, 0, nullptr);
 }
 
 // ------------------------------------------------------------------------------------ n-best output (ctc_nbest.hip.h)
@@ -276,21 +286,20 @@ extern "C" int cocr_ctc_beam_nbest(cocr_model *m, cocr_lm *lm, const float *logi
     int rc = lm ? beam_lm_check(m, lm, N, T, ncls, max_per_line, beam, classes, alpha, beta) : beam_check(N, T, ncls, max_per_line, beam);
     if (rc) return rc;
     if (nbest < 1 || nbest > beam) return fail(COCR_EINVAL, "nbest must be in 1..beam (%d)", beam);
-    if (T > 8000) return fail(COCR_EUNSUPPORTED, "more than 8000 frames per line");
+    if ((rc = check_frames(T))) return rc;
     if ((rc = check_out_lens(out_lens, N, T))) return rc;
     const int cap = std::max(1, (int)*std::max_element(out_lens, out_lens + N));        // frames of the longest line
-    HIP_TRY(hipSetDevice(m->device));
-    hipStream_t s = (hipStream_t)stream;
+    hipStream_t s;
     const int32_t *d_lens;
-    if ((rc = upload_lens(m, out_lens, N, s, d_lens))) return rc;
+    if ((rc = begin_call(m, out_lens, N, stream, s, d_lens))) return rc;
     // behind the search's scratch: the walk kernel's own 1-best outputs, then the chains' label stacks [N][nbest][T] of a call whose
     // lines do not fit the LDS
     const bool in_lds = nbest_lds_bytes(cap, beam, nbest, true) <= 144 * 1024;
     const size_t walk_out = walk_out_bytes(N), extra = walk_out + (in_lds ? 0 : (size_t)N * nbest * T * 4);
     ProfScope ps(m, s, FAM_BEAM);
     BeamTrail tr;
-    if (lm) rc = beam_lm_launch(m, lm, logits, N, T, ncls, d_lens, nullptr, nullptr, nullptr, nullptr, nullptr, 1, beam, classes, alpha, beta, nullptr, s, extra, &tr);
-    else rc = beam_launch(m, logits, N, T, ncls, d_lens, nullptr, nullptr, nullptr, nullptr, nullptr, 1, beam, s, extra, &tr);
+    if (lm) rc = beam_lm_launch(m, lm, logits, N, T, ncls, d_lens, {}, 1, beam, classes, alpha, beta, nullptr, s, extra, &tr);
+    else rc = beam_launch(m, logits, N, T, ncls, d_lens, {}, 1, beam, s, extra, &tr);
     if (rc) return rc;
     unsigned *stk_ws = in_lds ? nullptr : reinterpret_cast<unsigned *>(tr.extra + walk_out);
     const cocr_lm_tables L = lm ? lm_tables(lm) : cocr_lm_tables{};
@@ -338,10 +347,11 @@ static int upload_targets(cocr_model *m, int N, int T, int ncls, const int32_t *
 extern "C" int cocr_ctc_loss(cocr_model *m, const float *probits, int N, int T, int ncls, const int32_t *out_lens, const int32_t *targets,
                              const int32_t *label_lens, float *nll, float *grad, void *stream) {
     if (!m || !probits || !out_lens || !label_lens || !nll) return fail(COCR_EINVAL, "null argument");
-    if (N < 1 || T < 1 || ncls < 2) return fail(COCR_EINVAL, "empty problem");
+    int rc = check_shape(N, T, ncls, 2, false);
+    if (rc) return rc;
     if (ncls > 16384) return fail(COCR_EUNSUPPORTED, "more than 16384 classes");
     CtcTargets t;
-    const int rc = upload_targets(m, N, T, ncls, out_lens, targets, label_lens, true, COCR_EUNSUPPORTED, stream, t);
+    rc = upload_targets(m, N, T, ncls, out_lens, targets, label_lens, true, COCR_EUNSUPPORTED, stream, t);
     if (rc) return rc;
     hipStream_t s = (hipStream_t)stream;
     const int sj = t.sj;
@@ -358,14 +368,14 @@ extern "C" int cocr_ctc_loss(cocr_model *m, const float *probits, int N, int T, 
 int distill_loss_on(cocr_model *m, const float *student, const float *teacher, int N, int T, int ncls, const int32_t *out_lens, float tau, float *kd, float *grad,
                     float ctc_weight, float kd_weight, int accumulate, float *frame_ws, hipStream_t s) {
     if (!m || !student || !teacher || !out_lens || !kd) return fail(COCR_EINVAL, "null argument");
-    if (N < 1 || T < 1 || ncls < 2) return fail(COCR_EINVAL, "empty problem");
+    int rc = check_shape(N, T, ncls, 2, false);
+    if (rc) return rc;
     if ((size_t)N * T > (size_t)1 << 30) return fail(COCR_EUNSUPPORTED, "more than 2^30 frames in one call");
     if (!std::isfinite(tau) || !(tau > 0.f)) return fail(COCR_EINVAL, "the temperature must be finite and positive, not %g", (double)tau);
     if (!std::isfinite(ctc_weight) || ctc_weight < 0.f || !std::isfinite(kd_weight) || kd_weight < 0.f)
         return fail(COCR_EINVAL, "the weights must be finite and not negative (%g, %g)", (double)ctc_weight, (double)kd_weight);
     if (accumulate != 0 && accumulate != 1) return fail(COCR_EINVAL, "accumulate must be 0 or 1");
-    int rc = check_out_lens(out_lens, N, T);
-    if (rc) return rc;
+    if ((rc = check_out_lens(out_lens, N, T))) return rc;
     if (ncls > 16384) return fail(COCR_EUNSUPPORTED, "more than 16384 classes");
     HIP_TRY(hipSetDevice(m->device));
     if (!frame_ws) {
@@ -389,10 +399,10 @@ extern "C" int cocr_distill_loss(cocr_model *m, const float *student, const floa
 extern "C" int cocr_ctc_align(cocr_model *m, const float *logits, int N, int T, int ncls, const int32_t *out_lens, const int32_t *targets,
                               const int32_t *label_lens, int32_t *starts, int32_t *ends, float *conf, float *score, int32_t *counts, void *stream) {
     if (!m || !logits || !out_lens || !label_lens || !score || !counts) return fail(COCR_EINVAL, "null argument");
-    if (N < 1 || T < 1 || ncls < 2) return fail(COCR_EINVAL, "empty problem");
-    if (T > 8000) return fail(COCR_EUNSUPPORTED, "more than 8000 frames per line");
+    int rc = check_shape(N, T, ncls, 2, true);
+    if (rc) return rc;
     CtcTargets t;
-    int rc = upload_targets(m, N, T, ncls, out_lens, targets, label_lens, starts && ends && conf, COCR_EINVAL, stream, t);
+    rc = upload_targets(m, N, T, ncls, out_lens, targets, label_lens, starts && ends && conf, COCR_EINVAL, stream, t);
     if (rc) return rc;
     // the back-pointer table: beside lz, or one region per line of the workspace
     const size_t words = ctca_bp_words(T, t.sj), row = lattice_row_bytes(T);
@@ -409,11 +419,11 @@ extern "C" int cocr_ctc_align_page(cocr_model *m, const float *logits, int N, in
                                    const int32_t *page_lines, const int32_t *targets, const int32_t *label_lens, const uint8_t *optional, int32_t *line,
                                    int32_t *starts, int32_t *ends, float *conf, float *score, int32_t *counts, float *line_score, void *stream) {
     if (!m || !logits || !out_lens || !page_line_off || !label_lens || !score || !counts) return fail(COCR_EINVAL, "null argument");
-    if (N < 1 || T < 1 || ncls < 2) return fail(COCR_EINVAL, "empty problem");
+    int rc = check_shape(N, T, ncls, 2, false);
+    if (rc) return rc;
     if (P < 1) return fail(COCR_EINVAL, "no page");
     if (ncls > COCR_PAGE_MAX_CLASSES) return fail(COCR_EUNSUPPORTED, "more than %d classes", COCR_PAGE_MAX_CLASSES);
-    int rc = check_out_lens(out_lens, N, T);
-    if (rc) return rc;
+    if ((rc = check_out_lens(out_lens, N, T))) return rc;
     if (page_line_off[0] != 0) return fail(COCR_EINVAL, "the page line offsets do not begin at 0");
     for (int p = 0; p < P; ++p)
         if (page_line_off[p + 1] < page_line_off[p]) return fail(COCR_EINVAL, "page line offsets descend at page %d", p);
@@ -444,24 +454,23 @@ extern "C" int cocr_ctc_align_page(cocr_model *m, const float *logits, int N, in
     }
     if (max_l > COCR_PAGE_MAX_LABELS) return fail(COCR_EUNSUPPORTED, "a page of %d labels; the kernel holds %d", max_l, COCR_PAGE_MAX_LABELS);
     int max_frames = 0;
+    std::vector<int> page_frames((size_t)P);
     for (int p = 0; p < P; ++p) {
         const int K = page_line_off[p + 1] - page_line_off[p];
         if (K > COCR_PAGE_MAX_LINES) return fail(COCR_EUNSUPPORTED, "page %d has %d lines; the kernel holds %d", p, K, COCR_PAGE_MAX_LINES);
         size_t frames = 0;
         for (int k = 0; k < K; ++k) frames += (size_t)out_lens[page_lines[page_line_off[p] + k]];
         if (frames > COCR_PAGE_MAX_FRAMES) return fail(COCR_EUNSUPPORTED, "page %d has %zu frames; the kernel holds %d", p, frames, COCR_PAGE_MAX_FRAMES);
-        max_frames = std::max(max_frames, (int)frames);
+        max_frames = std::max(max_frames, page_frames[(size_t)p] = (int)frames);
     }
     // the kernel form by the call's largest S; one workspace region per page: back-pointers, lz, the path's states, the labels' runs
     const int sj = page_sj_for_states(2 * max_l + 1), waves = page_waves_for_states(2 * max_l + 1, sj);
     size_t words = 0;
     std::vector<uint32_t> region((size_t)P);
     for (int p = 0; p < P; ++p) {
-        size_t frames = 0;
-        for (int k = page_line_off[p]; k < page_line_off[p + 1]; ++k) frames += (size_t)out_lens[page_lines[k]];
         if (words * 4 > ((size_t)1 << 31)) break;
         region[(size_t)p] = (uint32_t)words;
-        words += (page_region_words((int)frames, label_lens[p], 64 * sj * waves) + 3) / 4 * 4;
+        words += (page_region_words(page_frames[(size_t)p], label_lens[p], 64 * sj * waves) + 3) / 4 * 4;
     }
     if (words * 4 > ((size_t)1 << 31)) return fail(COCR_EUNSUPPORTED, "the call's tables exceed 2 GiB; align fewer pages per call");
     HIP_TRY(hipSetDevice(m->device));
@@ -499,14 +508,14 @@ extern "C" int cocr_ctc_spot(cocr_model *m, const float *logits, int N, int T, i
                              const int32_t *query_lens, int Q, int hits, float min_score, int32_t *starts, int32_t *ends, float *score,
                              int32_t *counts, void *stream) {
     if (!m || !logits || !out_lens || !queries || !query_lens || !starts || !ends || !score || !counts) return fail(COCR_EINVAL, "null argument");
-    if (N < 1 || T < 1 || ncls < 2) return fail(COCR_EINVAL, "empty problem");
+    int rc = check_shape(N, T, ncls, 2, false);
+    if (rc) return rc;
     if (Q < 1) return fail(COCR_EINVAL, "no query");
     if (hits < 1 || hits > COCR_SPOT_MAX_HITS) return fail(COCR_EINVAL, "hits must be in 1..%d", COCR_SPOT_MAX_HITS);
     if (std::isnan(min_score)) return fail(COCR_EINVAL, "min_score is NaN");
-    if (T > 8000) return fail(COCR_EUNSUPPORTED, "more than 8000 frames per line");
+    if ((rc = check_frames(T))) return rc;
     if (N > 65535) return fail(COCR_EUNSUPPORTED, "more than 65535 lines in one call");
-    int rc = check_out_lens(out_lens, N, T);
-    if (rc) return rc;
+    if ((rc = check_out_lens(out_lens, N, T))) return rc;
     size_t total = 0;
     int max_l = 0;
     for (int q = 0; q < Q; ++q) {
@@ -542,14 +551,14 @@ extern "C" int cocr_ctc_spot_pattern(cocr_model *m, const float *logits, int N, 
                                      float min_score, int32_t *starts, int32_t *ends, float *score, int32_t *finals, int32_t *counts, void *stream) {
     if (!m || !logits || !out_lens || !state_counts || !classes || !flags || !pred_off || !starts || !ends || !score || !finals || !counts)
         return fail(COCR_EINVAL, "null argument");
-    if (N < 1 || T < 1 || ncls < 2) return fail(COCR_EINVAL, "empty problem");
+    int rc = check_shape(N, T, ncls, 2, false);
+    if (rc) return rc;
     if (Q < 1) return fail(COCR_EINVAL, "no pattern");
     if (hits < 1 || hits > COCR_GRAPH_MAX_HITS) return fail(COCR_EINVAL, "hits must be in 1..%d", COCR_GRAPH_MAX_HITS);
     if (std::isnan(min_score)) return fail(COCR_EINVAL, "min_score is NaN");
-    if (T > 8000) return fail(COCR_EUNSUPPORTED, "more than 8000 frames per line");
+    if ((rc = check_frames(T))) return rc;
     if (N > 65535) return fail(COCR_EUNSUPPORTED, "more than 65535 lines in one call");
-    int rc = check_out_lens(out_lens, N, T);
-    if (rc) return rc;
+    if ((rc = check_out_lens(out_lens, N, T))) return rc;
     size_t states = 0, edges = 0;
     int max_p = 0;
     for (int q = 0; q < Q; ++q) {
@@ -612,18 +621,17 @@ extern "C" int cocr_ctc_spot_pattern(cocr_model *m, const float *logits, int N, 
 extern "C" int cocr_posterior_pack(cocr_model *m, const float *logits, int N, int T, int ncls, const int32_t *out_lens, int keep, float inv_step,
                                    uint16_t *classes, uint8_t *codes, void *stream) {
     if (!m || !logits || !out_lens || !classes || !codes) return fail(COCR_EINVAL, "null argument");
-    if (N < 1 || T < 1 || ncls < 1) return fail(COCR_EINVAL, "empty problem");
+    int rc = check_shape(N, T, ncls, 1, false);
+    if (rc) return rc;
     if (ncls > 65535) return fail(COCR_EUNSUPPORTED, "more than 65535 classes");
     if (N > 65535) return fail(COCR_EUNSUPPORTED, "more than 65535 lines in one call");
     if ((size_t)N * T > (size_t)INT_MAX) return fail(COCR_EUNSUPPORTED, "more than 2^31 - 1 frames in one call");
     if (keep < 1 || keep > std::min(ncls, COCR_INDEX_MAX_KEEP)) return fail(COCR_EINVAL, "keep must be in 1..%d", std::min(ncls, COCR_INDEX_MAX_KEEP));
     if (!std::isfinite(inv_step) || !(inv_step > 0.f)) return fail(COCR_EINVAL, "inv_step must be finite and positive, not %g", (double)inv_step);
-    int rc = check_out_lens(out_lens, N, T);
-    if (rc) return rc;
-    HIP_TRY(hipSetDevice(m->device));
-    hipStream_t s = (hipStream_t)stream;
+    if ((rc = check_out_lens(out_lens, N, T))) return rc;
+    hipStream_t s;
     const int32_t *d_lens;
-    if ((rc = upload_lens(m, out_lens, N, s, d_lens))) return rc;
+    if ((rc = begin_call(m, out_lens, N, stream, s, d_lens))) return rc;
     HIP_TRY(launch_posterior_pack(s, logits, N, T, ncls, d_lens, keep, inv_step, classes, codes));
     return COCR_OK;
 }
@@ -631,7 +639,8 @@ extern "C" int cocr_posterior_pack(cocr_model *m, const float *logits, int N, in
 extern "C" int cocr_posterior_unpack(cocr_model *m, const uint16_t *classes, const uint8_t *codes, int N, int T, int keep, int ncls, float step,
                                      float *logits_out, void *stream) {
     if (!m || !classes || !codes || !logits_out) return fail(COCR_EINVAL, "null argument");
-    if (N < 1 || T < 1 || ncls < 1) return fail(COCR_EINVAL, "empty problem");
+    const int rc = check_shape(N, T, ncls, 1, false);
+    if (rc) return rc;
     if (ncls > 65535) return fail(COCR_EUNSUPPORTED, "more than 65535 classes");
     if ((size_t)N * T > (size_t)INT_MAX) return fail(COCR_EUNSUPPORTED, "more than 2^31 - 1 frames in one call");
     if (keep < 1 || keep > std::min(ncls, COCR_INDEX_MAX_KEEP)) return fail(COCR_EINVAL, "keep must be in 1..%d", std::min(ncls, COCR_INDEX_MAX_KEEP));

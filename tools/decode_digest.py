@@ -15,6 +15,11 @@ instantiation of the kernels:
   beam_lm       the seven shapes of tests/test_hip_lm.py `test_without_the_model_every_field_equals_the_plain_beam` with alpha = beta
                 = 0, and the six of `test_equals_the_definition_with_a_real_model` with their models
   greedy        the logits of the beam shapes
+  post/         the beam searches' post-passes: plain and LM beam on the planted 500-, 730- and 1386-frame lines of tests/beam_cases.py
+                (back-pointers in the raised LDS limit and in global memory); the raw buffers of the truncated calls of
+                tests/test_hip_truncation.py (every decoder, every back-pointer placement); n-best on the definition cases of
+                tests/test_hip_nbest.py with and without a model, its workspace-stack case, a planted line on each side of a scorer seam,
+                and the exhaustive kernel's trail
 A value is the sha256 of the outputs' bit patterns.  Each environment leg runs in a process of its own (the switch is read when the
 engine is made); this process only starts them and does not open the GPU."""
 import argparse
@@ -60,6 +65,60 @@ def _params(test):
     return [tuple(p) for m in test.pytestmark if m.name == 'parametrize' for p in m.args[1]]
 
 
+def post_pass_legs(leg, eng, dev):
+    """The `post/` keys: what the beam searches' post-passes write (the back-pointer walks, the ends / confidences pass, n-best's
+    records), on the inputs of tests/beam_cases.py, tests/test_hip_truncation.py and tests/test_hip_nbest.py."""
+    import ctypes as C
+    from tests import beam_cases as bc, test_hip_nbest as TN, test_hip_truncation as TT
+    from tests.test_nbest_host import CASES, case_inputs, chain_lm
+    assert leg in ('default', 'beam_ref')                             # (the keys below carry no leg name: a further leg needs one)
+    out = {}
+    raw = lambda d: sha([d[k] for k in sorted(d)])
+
+    def cut(fn, spec, extra=()):                                       # a 1-best call truncated at max_per_line 3: the raw output buffers
+        x, lens = TT._inputs(spec)
+        return raw(TT._call(eng, fn, dev(x), lens, TT.CUT, extra))
+
+    def nbest(x, lens, beam, n, **kw):
+        rc, got = TN._raw(eng, dev(x), lens, beam, n, **kw)
+        assert rc == 0
+        return raw(got)
+    nbest_lm = dict(lm=chain_lm(11, 3, seed=5), classes=5, alpha=bc.LM_ALPHA, beta=bc.LM_BETA)
+    if leg == 'beam_ref':                                              # ctc_beam_kernel where production runs the fast path
+        out['post/beam_ref/cut/beam'] = cut(eng.lib.cocr_ctc_beam, TT.SHORT, (16,))
+        out['post/beam_ref/nbest/trail'] = nbest(*bc.inputs(TT.SHORT), 16, 8)
+        out['post/beam_ref/nbest/cut'] = nbest(*bc.inputs(TT.SHORT), 16, 8, mpl=TT.CUT)
+        return out
+    # back-pointers in 68 KB of LDS (the raised limit), and in global memory for beam 32 and for beam 16
+    for name in ('planted 500', 'planted 730', 'planted 1386'):
+        spec, beams = bc.PLAIN[name]
+        x, lens = bc.inputs(spec)
+        out[f'post/beam/{name}'] = sha(eng.ctc_beam(dev(x), lens, beams[0]))
+        spec, beam, classes, order, seed = bc.LM[name]
+        x, lens = bc.inputs(spec)
+        got, score = eng.ctc_beam_lm(dev(x), lens, chain_lm(x.shape[2], order, seed), beam, classes, bc.LM_ALPHA, bc.LM_BETA, return_scores=True)
+        out[f'post/beam_lm/{name}'] = {'records': sha(got), 'score': sha(score)}
+    out['post/cut/greedy'] = cut(eng.lib.cocr_ctc_greedy, TT.SHORT)
+    out['post/cut/beam/lds'] = cut(eng.lib.cocr_ctc_beam, TT.SHORT, (16,))
+    out['post/cut/beam/global'] = cut(eng.lib.cocr_ctc_beam, TT.LONG, (32,))
+    for form, spec, beam in (('lds', TT.SHORT, 16), ('global', TT.LONG, 32)):
+        dlm = chain_lm(TT._inputs(spec)[0].shape[2], 3, seed=5).to_device(eng)
+        out[f'post/cut/beam_lm/{form}'] = cut(lambda h, *a: eng.lib.cocr_ctc_beam_lm(h, dlm.handle, *a), spec,
+                                              (beam, 5, C.c_float(bc.LM_ALPHA), C.c_float(bc.LM_BETA), None))
+    out['post/cut/nbest/plain'] = nbest(*bc.inputs(TT.SHORT), 16, 8, mpl=TT.CUT)
+    out['post/cut/nbest/lm'] = nbest(*bc.inputs(TT.SHORT), 16, 8, mpl=TT.CUT, **nbest_lm)
+    for Cn, T, beam, n in CASES:                                       # the definition cases
+        out[f'post/nbest/plain/{(Cn, T, beam, n)}'] = nbest(*case_inputs(Cn, T), beam, n)
+    for Cn, T, beam, n in _params(TN.test_against_the_definition_with_a_language_model):
+        out[f'post/nbest/lm/{(Cn, T, beam, n)}'] = nbest(*case_inputs(Cn, T), beam, n, lm=chain_lm(Cn, 3, seed=Cn), classes=6, alpha=0.7, beta=0.3)
+    x, lens = TN._planted_batch((282, 200), gain=6.0)                  # the chains' stacks in the workspace, and in LDS
+    out['post/nbest/workspace stacks'] = {'nbest 32': nbest(x, lens, 32, 32), 'nbest 4': nbest(x, lens, 32, 4)}
+    for L in (31, 32, 127, 128):                                       # one planted line on each side of a scorer seam
+        out[f'post/nbest/seam/{L}'] = nbest(*TN._planted_batch((L,)), bc.NBEST_BEAM, bc.NBEST_BEAM)
+    out['post/nbest/exhaustive trail, 300 classes'] = nbest(*TN._planted_batch((63,), wide=300), bc.NBEST_BEAM, bc.NBEST_BEAM)
+    return out
+
+
 def run_leg(leg):
     sys.path.insert(0, ROOT)
     import numpy as np
@@ -79,6 +138,7 @@ def run_leg(leg):
         beam_cases.append(((C, T, beam, scale), dev(logits), [T, T - 1, T // 2, 1, T, 7], beam))
     for key, x, lens, beam in beam_cases:
         out[f'{leg}/beam/{key}'] = sha(eng.ctc_beam(x, lens, beam))
+    out.update(post_pass_legs(leg, eng, dev))
     if leg != 'default':
         return out
     for key, x, lens, beam in beam_cases:
@@ -146,9 +206,14 @@ def main():
             print(f'leg {leg} ended with status {r.returncode}', file=sys.stderr)
             return r.returncode or 1
         out.update(json.loads(r.stdout.strip().splitlines()[-1]))
-    # the digests older runs have, sorted as they always were, then those of text-to-page alignment: the head of the output compares
-    new = {k: out.pop(k) for k in sorted(out) if k.startswith('align_page/')}
-    text = json.dumps(out, indent=1, sort_keys=True)[:-2] + ',\n' + json.dumps(new, indent=1, sort_keys=True)[2:]
+    # the digests older runs have, sorted as they always were, then those of text-to-page alignment, then those of the beam searches'
+    # post-passes: the head of the output compares
+    text = ''
+    for prefix in ('post/', 'align_page/'):
+        new = {k: out.pop(k) for k in sorted(out) if k.startswith(prefix)}
+        if new:
+            text = ',\n' + json.dumps(new, indent=1, sort_keys=True)[2:-2] + text
+    text = json.dumps(out, indent=1, sort_keys=True)[:-2] + text + '\n}'
     if args.out:
         with open(args.out, 'w') as fp:
             fp.write(text + '\n')

@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Rate of the beam search with an n-gram model.
 
-    python tools/lm_rate.py [--iters 100] [--build-only] [--skip-build]
+    python tools/lm_rate.py [--iters 100] [--beam 16] [--build-only] [--skip-build]
 
 (a) ms per call on cfg2-shaped logits (32 x 300 x 128, random normal x 2.5, blank + 1.5), beam 16: `cocr_ctc_beam` next to
     `cocr_ctc_beam_lm` with 8 classes at orders 3 and 5 (models of 2000 lines of a random first-order chain) -- HIP-event medians,
@@ -24,6 +24,7 @@ from conformer_ocr_amd.lm import build_lm, tune_grid  # noqa: E402
 
 ap = argparse.ArgumentParser()
 ap.add_argument('--iters', type=int, default=100)
+ap.add_argument('--beam', type=int, default=16, help='beam of leg (a): above 16 the plain search runs ctc_beam_walk_kernel<3>')
 ap.add_argument('--build-only', action='store_true', help='leg (c) only: no GPU needed')
 ap.add_argument('--skip-build', action='store_true')
 args = ap.parse_args()
@@ -74,10 +75,10 @@ if not args.build_only:
         e1.synchronize()
         eng.collect(h)
         return e0.elapsed_time(e1)                                       # ms
-    legs = {'ctc_beam': lambda: eng.ctc_beam_async(logits, lens, 16),
-            'ctc_beam_lm_order3': lambda: eng.ctc_beam_lm_async(logits, lens, lms[3], 16, 8, 0.5, 0.0),
-            'ctc_beam_lm_order5': lambda: eng.ctc_beam_lm_async(logits, lens, lms[5], 16, 8, 0.5, 0.0),
-            'ctc_beam_lm_order5_alpha0': lambda: eng.ctc_beam_lm_async(logits, lens, lms[5], 16, 8, 0.0, 0.0)}
+    legs = {'ctc_beam': lambda: eng.ctc_beam_async(logits, lens, args.beam),
+            'ctc_beam_lm_order3': lambda: eng.ctc_beam_lm_async(logits, lens, lms[3], args.beam, 8, 0.5, 0.0),
+            'ctc_beam_lm_order5': lambda: eng.ctc_beam_lm_async(logits, lens, lms[5], args.beam, 8, 0.5, 0.0),
+            'ctc_beam_lm_order5_alpha0': lambda: eng.ctc_beam_lm_async(logits, lens, lms[5], args.beam, 8, 0.0, 0.0)}
     for fn in legs.values():
         for _ in range(3):
             timed(fn)
@@ -88,7 +89,7 @@ if not args.build_only:
     a = {k + '_ms_median': round(float(np.median(v)), 4) for k, v in ts.items()}
     a.update({k + '_ms_p10_p90': [round(float(np.percentile(v, q)), 4) for q in (10, 90)] for k, v in ts.items()})
     a['lm_order5_over_plain'] = round(float(np.median(ts['ctc_beam_lm_order5']) / np.median(ts['ctc_beam'])), 2)
-    out['a'] = dict(a, shape=[N, T, C], beam=16, classes=8, iters=args.iters)
+    out['a'] = dict(a, shape=[N, T, C], beam=args.beam, classes=8, iters=args.iters)
     # (b) the grid
     batches = [(batch(), lens) for _ in range(4)]
     truths = [''.join(chr(33 + int(l)) for l in row) for row in chain_corpus(4 * N, 60, C, 9)]
