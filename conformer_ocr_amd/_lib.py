@@ -100,6 +100,7 @@ SYMBOLS = {
     'cocr_get_chain_rows': (_I, [_P, _I, _I, C.POINTER(C.c_int)]),
     'cocr_set_debug': (_I, [_P, _I]),
     'cocr_debug_tap': (_I, [_P, C.c_char_p, _P, C.c_int64, C.POINTER(C.c_int64)]),
+    'cocr_debug_attention': (_I, [_P, _I, _I, _I, _P, _P, _P, C.c_int64, _P, C.c_int64, _I32P, _P]),
     'cocr_profile': (_I, [_P, _I]),
     'cocr_profile_read': (_I, [_P, C.c_char_p, C.c_size_t, C.POINTER(C.c_double), C.POINTER(C.c_int64), _I]),
 }

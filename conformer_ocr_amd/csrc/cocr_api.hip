@@ -689,6 +689,31 @@ extern "C" int cocr_debug_tap(cocr_model *m, const char *name, float *host_out, 
     return COCR_OK;
 }
 
+extern "C" int cocr_debug_attention(cocr_model *m, int layer, int N, int T, const void *q, const void *k, const void *v, int64_t qkv_elems, void *ctx,
+                                    int64_t ctx_elems, int32_t *dims, void *stream) {
+    if (!m) return fail(COCR_EINVAL, "null argument");
+    if (!m->w->blob) return fail(COCR_ESTATE, "model not finalized");
+    { const int rc = adopt_layout(m); if (rc) return rc; }
+    if (layer < 0 || layer >= m->L) return fail(COCR_EINVAL, "block %d of a model with %d blocks", layer, m->L);
+    if (N < 1 || T < 1) return fail(COCR_EINVAL, "empty batch");
+    const int Tp = round_up(T, 64);
+    if (Tp > 65536) return fail(COCR_EUNSUPPORTED, "more than 65536 output frames");
+    if ((int64_t)N * m->heads > 65535) return fail(COCR_EUNSUPPORTED, "more than 65535 (line, head) pairs");
+    if (dims) { dims[0] = m->heads; dims[1] = m->dh; dims[2] = m->dhp; dims[3] = Tp; }
+    if (!q && !k && !v && !ctx) return dims ? COCR_OK : fail(COCR_EINVAL, "null argument");      // the layout alone
+    if (!q || !k || !v || !ctx) return fail(COCR_EINVAL, "null argument");
+    const int64_t want_qkv = (int64_t)N * m->heads * Tp * m->dhp, want_ctx = (int64_t)N * T * m->heads * m->dh;
+    if (qkv_elems != want_qkv) return fail(COCR_EINVAL, "q, k, v hold [%d][%d][%d][%d] = %lld elements each, not %lld", N, m->heads, Tp, m->dhp, (long long)want_qkv, (long long)qkv_elems);
+    if (ctx_elems != want_ctx) return fail(COCR_EINVAL, "ctx holds [%d][%d][%d] = %lld elements, not %lld", N, T, m->heads * m->dh, (long long)want_ctx, (long long)ctx_elems);
+    for (const void *p : {q, k, v, (const void *)ctx})
+        if ((uintptr_t)p % 16) return fail(COCR_EINVAL, "q, k, v and ctx must be 16-byte aligned");
+    HIP_TRY(hipSetDevice(m->device));
+    hipStream_t s = (hipStream_t)stream;
+    int rc;
+    if ((rc = m->w->cover_positions(Tp)) || (rc = m->w->ensure_ptab(s))) return rc;
+    return attention_core_on(m, layer, N, T, q, k, v, ctx, s);
+}
+
 extern "C" int cocr_profile(cocr_model *m, int on) {
     if (!m) return fail(COCR_EINVAL, "null argument");
     m->sw.profile = on != 0;

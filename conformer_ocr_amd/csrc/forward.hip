@@ -148,6 +148,9 @@ static Form forward_form(const cocr_model *m, int N, int W) {
 }
 
 // ------------------------------------------------------------------------------------ forward
+// the attention scores' 1/sqrt(d_head): of the model's own d_head (a padded model's engine d_head is its 64-wide slot)
+static float attention_scale(const cocr_model *m) { return 1.0f / sqrtf((float)m->rdh); }
+
 // What every stage of one forward reads: the model, its form, the stream, the plan, the dimensions and the workspace
 template <typename T> struct Fwd {
     cocr_model *m;
@@ -155,14 +158,14 @@ template <typename T> struct Fwd {
     hipStream_t s;
     const BlobPlan &P;
     const int N, W, D, T1, T2, F1, F2, Tn, M, Tp;        // T1 / F1, T2 / F2: frames / height after the first, second stride-2 stage
-    const float ffr, scale;     // feed-forward residual factor; 1/sqrt(d_head) of the model (a padded model's engine d_head is its 64-wide slot)
+    const float ffr;            // feed-forward residual factor
     T *const za, *const zb;     // frontend: each stage's output in zb, its intermediate in za
     float *const x;             // the fp32 residual stream
     T *const xn, *const hid, *const q, *const k, *const v, *const ctx, *const glu, *const dwo;
     Fwd(cocr_model *m_, const Form &f_, int N_, int W_, hipStream_t s_)
         : m(m_), f(f_), s(s_), P(m_->w->plan), N(N_), W(W_), D(m_->D), T1(out_len1(W_)), T2(m_->snum == 1 ? T1 : out_len1(T1)), F1(m_->feats[0]),
           F2(m_->feats[m_->snum == 1 ? 0 : 1]), Tn(cocr_out_len(W_, m_->hp.subsampling_factor)), M(N_ * Tn), Tp(round_up(Tn, 64)),
-          ffr(m_->hp.half_step_residual ? 0.5f : 1.0f), scale(1.0f / sqrtf((float)m_->rdh)), za((T *)m_->ws.z_a), zb((T *)m_->ws.z_b), x(m_->ws.x),
+          ffr(m_->hp.half_step_residual ? 0.5f : 1.0f), za((T *)m_->ws.z_a), zb((T *)m_->ws.z_b), x(m_->ws.x),
           xn((T *)m_->ws.xn), hid((T *)m_->ws.hid), q((T *)m_->ws.q), k((T *)m_->ws.k), v((T *)m_->ws.vt), ctx((T *)m_->ws.ctx), glu((T *)m_->ws.glu), dwo((T *)m_->ws.dwo) {}
     const float *F32(size_t off) const { return (const float *)(m->w->blob + off); }
     const T *WT(size_t off) const { return (const T *)(m->w->blob + off); }
@@ -322,20 +325,33 @@ template <typename T> static int ffn(const Fwd<T> &c, const FfnW &fw, size_t g1,
     return rc ? rc : gemm_to_stream(c, FAM_FFN_DOWN, c.hid, c.m->ff, fw.w2, fw.b2, c.ffr, true, g1, b1, g2, b2);
 }
 
-template <typename T, int DHP> static hipError_t attention_dhp(const Fwd<T> &c, int l, unsigned long long *stamps) {
-    const cocr_model *m = c.m;
-    const LayerW &w = c.P.layers[l];
-    return launch_attention<T, DHP>(c.s, c.N, c.q, c.k, c.v, (const T *)(m->w->ptab + (size_t)l * m->w->ptab_stride), c.F32(w.ub), c.F32(w.vb), c.ctx, c.Tn,
-                                    c.Tp, m->heads, m->dh, c.scale, m->w->pos_maxlen - 1, stamps, m->sw.att_tiled, m->sw.att_resident_min, m->sw.att_resident_long);
+// block l's attention core on the given operands: the launch of a forward and of cocr_debug_attention (launch_attention chooses the kernel
+// from the head geometry, the batch shape and the switches)
+template <typename T, int DHP> static hipError_t attention_dhp(const cocr_model *m, hipStream_t s, int l, int N, const T *q, const T *k, const T *v, T *ctx, int Tn,
+                                                               int Tp, unsigned long long *stamps) {
+    const LayerW &w = m->w->plan.layers[l];
+    return launch_attention<T, DHP>(s, N, q, k, v, (const T *)(m->w->ptab + (size_t)l * m->w->ptab_stride), (const float *)(m->w->blob + w.ub),
+                                    (const float *)(m->w->blob + w.vb), ctx, Tn, Tp, m->heads, m->dh, attention_scale(m), m->w->pos_maxlen - 1, stamps,
+                                    m->sw.att_tiled, m->sw.att_resident_min, m->sw.att_resident_long);
 }
-// block l's attention core: ctx <- attention(q, k, v) (launch_attention chooses the kernel)
+template <typename T> static hipError_t attention_on(const cocr_model *m, hipStream_t s, int l, int N, const T *q, const T *k, const T *v, T *ctx, int Tn, int Tp,
+                                                     unsigned long long *stamps) {
+    const int dhp = m->dhp;
+    return dhp == 32   ? attention_dhp<T, 32>(m, s, l, N, q, k, v, ctx, Tn, Tp, stamps)
+           : dhp == 64 ? attention_dhp<T, 64>(m, s, l, N, q, k, v, ctx, Tn, Tp, stamps)
+           : dhp == 96 ? attention_dhp<T, 96>(m, s, l, N, q, k, v, ctx, Tn, Tp, stamps)
+                       : attention_dhp<T, 128>(m, s, l, N, q, k, v, ctx, Tn, Tp, stamps);
+}
 template <typename T> static int attention(const Fwd<T> &c, int l, unsigned long long *stamps) {
     ProfScope ps(c.m, c.s, FAM_ATTN);
-    const int dhp = c.m->dhp;
-    GEMM_TRY((dhp == 32   ? attention_dhp<T, 32>(c, l, stamps)
-              : dhp == 64 ? attention_dhp<T, 64>(c, l, stamps)
-              : dhp == 96 ? attention_dhp<T, 96>(c, l, stamps)
-                          : attention_dhp<T, 128>(c, l, stamps)));
+    GEMM_TRY(attention_on<T>(c.m, c.s, l, c.N, c.q, c.k, c.v, c.ctx, c.Tn, c.Tp, stamps));
+    return COCR_OK;
+}
+// cocr_debug_attention (cocr_api.hip): that launch alone, on the caller's device tensors in the model's compute type
+int attention_core_on(cocr_model *m, int l, int N, int Tn, const void *q, const void *k, const void *v, void *ctx, hipStream_t s) {
+    const int Tp = round_up(Tn, 64);
+    if (m->dtype == COCR_BF16) GEMM_TRY(attention_on<bf16_t>(m, s, l, N, (const bf16_t *)q, (const bf16_t *)k, (const bf16_t *)v, (bf16_t *)ctx, Tn, Tp, nullptr));
+    else GEMM_TRY(attention_on<float>(m, s, l, N, (const float *)q, (const float *)k, (const float *)v, (float *)ctx, Tn, Tp, nullptr));
     return COCR_OK;
 }
 

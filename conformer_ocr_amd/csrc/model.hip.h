@@ -266,6 +266,8 @@ struct ProfScope {
 COCR_INTERNAL int adopt_layout(cocr_model *m);
 template <typename T> COCR_INTERNAL int tap(cocr_model *m, hipStream_t s, const std::string &name, const T *src, size_t n);      // T: float, bf16_t
 COCR_INTERNAL void blob_to_f32(const cocr_model *m, size_t off, float *dst, size_t n, hipStream_t s);      // owns to_f32_kernel with the taps
+// forward.hip
+COCR_INTERNAL int attention_core_on(cocr_model *m, int l, int N, int Tn, const void *q, const void *k, const void *v, void *ctx, hipStream_t s);      // block l's attention launch alone
 // decode.hip
 COCR_INTERNAL int ensure_ctc_scratch(cocr_model *m, size_t rows);
 COCR_INTERNAL int distill_loss_on(cocr_model *m, const float *student, const float *teacher, int N, int T, int ncls, const int32_t *out_lens, float tau, float *kd,

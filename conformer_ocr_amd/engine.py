@@ -990,6 +990,28 @@ class HipRecognizer:
         _lib.check(self.lib.cocr_debug_tap(self._h, name.encode(), _hp(out, C.c_void_p), n.value, C.byref(n)))
         return out
 
+    def attention_layout(self, n: int, T: int) -> Tuple[int, int, int, int]:
+        """(heads, dh, dhp, Tp) of `attention_core`'s tensors for n lines of T frames: the engine's d_head (a zero-padded narrow model:
+        its slot), that rounded up to 32, T rounded up to 64."""
+        dims = np.zeros(4, dtype=np.int32)
+        _lib.check(self.lib.cocr_debug_attention(self._h, 0, int(n), int(T), None, None, None, 0, None, 0, _hp(dims), None))
+        return tuple(int(d) for d in dims)
+
+    def attention_core(self, q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, layer: int, T: int) -> torch.Tensor:
+        """Block `layer`'s attention core alone (include/cocr.h: cocr_debug_attention) on q, k, v of shape (N, heads, Tp, dhp) in the compute
+        dtype on this device, zero beyond T and beyond d_head.  Returns ctx (N, T, heads * dh) in the compute dtype."""
+        want = torch.bfloat16 if DTYPES[self.compute_dtype] == _lib.BF16 else torch.float32
+        for t in (q, k, v):
+            if t.device != self.device or t.dtype != want or t.dim() != 4 or t.shape != q.shape or not t.is_contiguous():
+                raise ValueError(f'q, k, v must be contiguous (N, heads, Tp, dhp) {want} tensors of one shape on {self.device}')
+        N = int(q.shape[0])
+        heads, dh, _, _ = self.attention_layout(N, T)
+        ctx = torch.empty((N, int(T), heads * dh), dtype=want, device=self.device)
+        with torch.cuda.device(self.device):
+            _lib.check(self.lib.cocr_debug_attention(self._h, int(layer), N, int(T), _dp(q), _dp(k), _dp(v), q.numel(), _dp(ctx), ctx.numel(), None,
+                                                     _stream_ptr(self.device)))
+        return ctx
+
     def profile(self, on: bool) -> None:
         _lib.check(self.lib.cocr_profile(self._h, int(on)))
 

@@ -413,6 +413,16 @@ int cocr_get_chain_rows(cocr_model *m, int N, int W, int *rows);
 int cocr_set_debug(cocr_model *m, int on);
 int cocr_debug_tap(cocr_model *m, const char *name, float *host_out, int64_t max_elems, int64_t *n_elems);
 
+/* Test entry: block `layer`'s attention core alone -- the one launch cocr_forward makes between the q / k / v projection and the
+ * out-projection -- on the caller's DEVICE tensors in the model's compute type.  q, k, v: [N][heads][Tp][dhp] (Tp = T rounded up to 64,
+ * dhp = the engine's d_head rounded up to 32), ZERO in the rows beyond T and the columns beyond d_head: the kernels read whole tiles.
+ * ctx: [N][T][heads * dh], dh the engine's d_head (a zero-padded narrow model: its slot, the model's own columns first).  The
+ * positional table, u / v biases, scale and the kernel form (COCR_ATT_TILED, COCR_ATT_RESIDENT_MIN, COCR_ATT_RESIDENT_LONG) are
+ * those of a forward of N lines of T frames.  qkv_elems / ctx_elems: the element counts of the buffers, checked against the layout.
+ * dims (may be null) receives {heads, dh, dhp, Tp}; with q, k, v and ctx all null nothing is launched (the layout alone). */
+int cocr_debug_attention(cocr_model *m, int layer, int N, int T, const void *q, const void *k, const void *v, int64_t qkv_elems, void *ctx,
+                         int64_t ctx_elems, int32_t *dims, void *stream);
+
 /* Kernel timing hook for bench.py's roofline leg: average device time (ms) per launch of each
  * kernel family over the forwards run since cocr_profile(m,1), measured with HIP events on the
  * forward's own stream.  Names are '\n'-separated in `names`; ms[i], launches[i] per family. */

@@ -130,6 +130,65 @@ def test_chain_kernel_stages_in_isolation_against_bf16_oracle(n, w, ksz):
     assert worst['chained logits vs bf16 oracle'] <= 0.05 and worst['chained logits vs fp32 oracle'] <= 0.15
 
 
+@pytest.mark.parametrize('n,w', [(2, 520), (17, 1200)])
+def test_attention_stages_in_isolation_where_the_online_softmax_rescales(n, w, monkeypatch):
+    """The stage-in-isolation check of ctx and of the attention module's output on a model whose attention is peaked: the model of the
+    test above with the query path of both blocks x 16 (tests/attention_cases.py: gain16_model; scores of +-120 log2 units).  With the
+    plain synthetic weights no key tile's maximum ever exceeds the first tile's by 8, so the kernels' running reference never moves and
+    their rescale branch does not run; here it runs in most 16-query walks (tests/test_attention_cases_host.py: 61 and 66 events in the 72
+    walks of (2, 520) with the 64-key rule).  (2, 520): 130 frames, the tiled kernel; (17, 1200): 300 frames, the LDS-resident one.
+
+    fp32 against the fp32 oracle: q, k, v, ctx and the module's output within 2e-4 (measured: q 6.5e-5 on values of +-88, ctx 4.1e-5).
+
+    bf16 against the bf16-operand oracle.  _ulp_ok's 5e-3 term does not hold here, for the oracle's own reasons: the oracle recomputes q
+    from the stage's input, a flipped bf16 rounding of the LayerNorm output moves a projection by 1 - 3e-3 (_ulp_ok) and this q by 16 x
+    that (measured: q off by one or two bf16 steps, 0.125 - 0.25 on values of +-88), which moves a score by ~0.1 log2 units and a
+    probability by several per cent.  As the bar, 1.5 x the deviation of the bf16-operand oracle from the float64 oracle on the same
+    input, computed here: what the operand roundings themselves cost at these magnitudes.  Measured on the CPU, block 0 / 1:
+        (2, 520)     ctx 0.125 / 0.189    module output 0.021 / 0.030    (the kernels: ctx 0.016 / 0.016, output 0.0014 / 0.0018)
+        (17, 1200)   ctx 0.234 / 0.276    module output 0.046 / 0.047    (the kernels: ctx 0.023 / 0.051, output 0.0053 / 0.011)
+    k and v, which the gain does not touch, stay at _ulp_ok."""
+    from oracle.conformer_ref import Oracle
+    from tests import attention_cases as ac
+    hp, state = ac.gain16_model()
+    image, lens = synth.make_lines(n, hp.height, w, seed=77, widths=[max(40, w - 37 * i) for i in range(n)])
+    if n == 17:
+        monkeypatch.setenv('COCR_ATT_RESIDENT_MIN', '1')       # 2 x 17 x 4 = 136 workgroups: fewer than the 192 from which the library picks it
+    worst, bad = {}, {}
+    o64 = Oracle(hp, state, torch.float64)
+    for dtype in ('bf16', 'fp32'):
+        eng, logits, _ = run_hip(hp, state, image, lens, dtype, debug=True)
+        N, T = n, logits.shape[1]
+        o = Oracle(hp, state, bf16_operands=dtype == 'bf16')
+        tap = lambda nm: torch.from_numpy(np.ascontiguousarray(hip_tap(eng, nm, hp, N, T))).reshape(N, T, -1)
+        with torch.no_grad():
+            for l in range(hp.num_encoder_layers):
+                y, t, t64 = tap(f'l{l}.ffn1'), {}, {}
+                t[f'l{l}.mhsa'] = o.mhsa(y, l, t)
+                bar = {}
+                if dtype == 'bf16':
+                    t64[f'l{l}.mhsa'] = o64.mhsa(y.double(), l, t64)
+                    bar = {nm: 1.5 * float((t[f'l{l}.{nm}'].double() - t64[f'l{l}.{nm}']).abs().max()) for nm in ('ctx', 'mhsa')}
+                for nm in ('q', 'k', 'v', 'ctx', 'mhsa'):
+                    if dtype == 'bf16' and nm == 'q':
+                        continue
+                    got, want = tap(f'l{l}.{nm}'), t[f'l{l}.{nm}'].reshape(N, T, -1)
+                    dev = (got - want).abs()
+                    key = f'{dtype} l{l}.{nm}'
+                    worst[key] = float(dev.max())
+                    print(f'{key}: max dev {worst[key]:.3g}, max |ref| {float(want.abs().max()):.3g}' + (f', bar {bar[nm]:.3g}' if nm in bar else ''))
+                    if dtype == 'fp32':
+                        ok = bool((dev <= 2e-4).all())
+                    elif nm in bar:
+                        ok = worst[key] <= bar[nm]
+                    else:
+                        ok = bool(_ulp_ok(got.numpy(), want.numpy()).all())
+                    if not ok:
+                        bad[key] = worst[key]
+    _log(f'gain16_attention_stages_n{n}_w{w}', worst)
+    assert not bad, bad
+
+
 def test_rows_per_workgroup_forms_are_bit_identical():
     """cocr_set_chain_rows: 32-, 48- and 96-row workgroups of the row-chain kernels compute every row with the same arithmetic in the same
     order (explicit fused multiply-adds in the LayerNorm statistics: no instantiation-dependent contraction) -- bit-identical logits."""
