@@ -24,12 +24,6 @@
 #pragma once
 #include "common.hip.h"
 
-// hardware workgroup id -> logical id such that each XCD (id % 8) owns a contiguous range of logical ids
-__device__ __forceinline__ int xcd_remap_i(int bid, int nwg) {
-    const int q = nwg >> 3, r = nwg & 7, xcd = bid & 7;
-    return (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + (bid >> 3);
-}
-
 // max of three without the NaN-quieting v_max x, x the compiler puts in front of every fmaxf operand (scores are never NaN: finite
 // products, or -inf from the tail mask)
 __device__ __forceinline__ float max3_f(float a, float b, float c) {
@@ -48,15 +42,6 @@ __device__ __forceinline__ void mfma_results_fence(f32x4 (&a)[4]) { asm volatile
 __device__ __forceinline__ void mfma_results_fence(f32x4 (&a)[4], f32x4 (&b)[4]) {
     asm volatile(COCR_MFMA_WAIT : "+v"(a[0]), "+v"(a[1]), "+v"(a[2]), "+v"(a[3]), "+v"(b[0]), "+v"(b[1]), "+v"(b[2]), "+v"(b[3]));
 }
-__device__ __forceinline__ void mfma_results_fence(f32x4 (&a)[4], f32x4 (&b)[4], f32x4 (&c)[4]) {
-    asm volatile(COCR_MFMA_WAIT : "+v"(a[0]), "+v"(a[1]), "+v"(a[2]), "+v"(a[3]), "+v"(b[0]), "+v"(b[1]), "+v"(b[2]), "+v"(b[3]), "+v"(c[0]), "+v"(c[1]), "+v"(c[2]),
-                 "+v"(c[3]));
-}
-
-#ifndef COCR_ATT_EXP
-#define COCR_ATT_EXP 0          // dev: timing experiments (wrong results): 1 no shift through LDS, 2 no positional products, 4 no exponentials,
-                               // 8 no P.V products, 16 tiles staged once, 32 no content products, 64 no barriers
-#endif
 
 // V^T fragment of one k-chunk (32 keys) for head-dim row tile d: element e of quad g <-> key 16 (e>>2) + 4g + (e&3)
 // (the same permutation the exponentiated scores have in their accumulator registers).
@@ -83,6 +68,126 @@ __device__ __forceinline__ f32x8 load_vt_frag(const unsigned char *vtile, int st
     return r;
 }
 
+// ---------------------------------------------------------------------------------------------------------------------------------
+// The pieces the kernels below share.  Scores are TRANSPOSED accumulator tiles: lane (il = lane & 15, g = lane >> 4) holds, in register
+// r of score tile tt, the score of query il and key (first key of the step) + 16 tt + 4 g + r.
+
+constexpr int ATT_SK = 20;            // row stride (floats) of a wave's shift tile: conflict-free write and skewed read
+constexpr int ATT_SROWS = 48;         // its rows in the tiled kernel: the 48 band rows of a (wave, 32-key sub-tile)
+
+// Lazy rescaling: a walk's running reference m_run is only raised when some query of the wave exceeds it by more than ATT_LAZY (softmax is
+// invariant to the reference; exp2(score - m_run) <= 2^ATT_LAZY stays well inside fp32 / bf16 range), so the accumulators are not touched
+// by the VALU in the common case.  The line's first key step sets the reference (key 0 is valid: finite).
+constexpr float ATT_LAZY = 8.0f;
+
+// max of a lane's 16 scores of a 64-key step.  Inline assembly (max3_f): the caller fences the products first (mfma_results_fence).
+__device__ __forceinline__ float max16(const f32x4 (&sc)[4]) {
+    float m = max3_f(sc[0][0], sc[0][1], sc[0][2]);
+    m = max3_f(m, sc[0][3], sc[1][0]);
+    m = max3_f(m, sc[1][1], sc[1][2]);
+    m = max3_f(m, sc[1][3], sc[2][0]);
+    m = max3_f(m, sc[2][1], sc[2][2]);
+    m = max3_f(m, sc[2][3], sc[3][0]);
+    m = max3_f(m, sc[3][1], sc[3][2]);
+    return max3_f(m, sc[3][3], sc[3][3]);
+}
+// ... and over the four quads that hold a query's keys: every lane of query il ends with the query's maximum
+__device__ __forceinline__ float quad_max(float m) {
+    { const float x = __shfl_xor(m, 16, 64); m = max3_f(m, x, x); }
+    { const float x = __shfl_xor(m, 32, 64); m = max3_f(m, x, x); }
+    return m;
+}
+
+// Keys beyond the line (only a line's last key step has any): their scores become -inf; returns the lane's new maximum.  The callers
+// take a REAL, uniform branch around it, held by an asm statement -- the compiler would otherwise turn it into selects per score in
+// EVERY step.
+__device__ __forceinline__ float mask_tail16(f32x4 (&sc)[4], int first_key, int g, int Tn) {
+    float m = -INFINITY;
+#pragma unroll
+    for (int tt = 0; tt < 4; ++tt)
+#pragma unroll
+        for (int r = 0; r < 4; ++r) {
+            if (first_key + 16 * tt + 4 * g + r >= Tn) sc[tt][r] = -INFINITY;
+            m = fmaxf(m, sc[tt][r]);
+        }
+    return m;
+}
+
+// One 64-key softmax step of NT walks (16-query tiles; state of walk t: m_run[t], osum[t], o[t][]) whose scores sc[t] = score - m_run[t]
+// have the maxima tmax[t] (max16 / mask_tail16 / quad_max): where a reference moves (ATT_LAZY), by delta, the walk's denominator and output
+// are scaled by alpha = 2^-delta and delta leaves its scores.  Returns whether any reference moved.  Every step runs over all walks before
+// the next and there is ONE uniform branch for all of them: a branch per walk would cut the walks' chains into basic blocks that cannot
+// interleave.  A walk whose reference stays while another's moves gets delta = 0, alpha = 2^-0 = 1: the same bits.  The tiled kernel's
+// merged form is the case NT = 1.
+template <int NT, int DT>
+__device__ __forceinline__ bool softmax_step64(bool first_tile, const float *tmax, float *m_run, f32x4 *osum, f32x4 (*o)[DT], f32x4 (*sc)[4]) {
+    bool need[NT], any = first_tile;
+#pragma unroll
+    for (int t = 0; t < NT; ++t) { need[t] = first_tile || __builtin_amdgcn_ballot_w64(tmax[t] > ATT_LAZY) != 0; any = any || need[t]; }
+    if (any) {
+#pragma unroll
+        for (int t = 0; t < NT; ++t) {
+            const float delta = first_tile ? tmax[t] : (need[t] ? fmaxf(tmax[t], 0.f) : 0.f);
+            const float alpha = first_tile ? 1.0f : __builtin_amdgcn_exp2f(-delta);
+            m_run[t] = first_tile ? tmax[t] : m_run[t] + delta;
+#pragma unroll
+            for (int r = 0; r < 4; ++r) osum[t][r] *= alpha;
+#pragma unroll
+            for (int d = 0; d < DT; ++d)
+#pragma unroll
+                for (int r = 0; r < 4; ++r) o[t][d][r] *= alpha;
+#pragma unroll
+            for (int tt = 0; tt < 4; ++tt)
+#pragma unroll
+                for (int r = 0; r < 4; ++r) sc[t][tt][r] -= delta;
+        }
+    }
+    return any;
+}
+
+// A operand whose row 0 is all ones
+template <typename T> __device__ __forceinline__ typename FragOf<T>::type ones_row_frag(int il) {
+    typename FragOf<T>::type ones;
+#pragma unroll
+    for (int j = 0; j < 8; ++j) ones[j] = il == 0 ? (T)1.0f : (T)0.0f;
+    return ones;
+}
+// The probabilities of a 64-key step as the B operands pb of the P.V product, and the softmax denominators on the matrix cores as well:
+// one more row tile whose row 0 is all ones (2 MFMAs per step instead of 16 VALU adds; the sum is over the SAME rounded probabilities
+// the numerator uses).  Row 0 of osum (register 0 of lanes 0..15) = the denominator of query `lane`.
+template <typename T>
+__device__ __forceinline__ void probs_and_denominator(const f32x4 (&sc)[4], const typename FragOf<T>::type &ones, typename FragOf<T>::type (&pb)[2], f32x4 &osum) {
+#pragma unroll
+    for (int tt = 0; tt < 4; ++tt)
+#pragma unroll
+        for (int r = 0; r < 4; ++r) pb[tt >> 1][4 * (tt & 1) + r] = from_f32<T>(__builtin_amdgcn_exp2f(sc[tt][r]));
+    osum = mma16(ones, pb[0], osum);
+    osum = mma16(ones, pb[1], osum);
+}
+
+// One 16-query tile (bf16, d_head 64; lane holds head dims 16 d + 4g + r of query il), normalised by inv, to rows i_tile .. i_tile + 15
+// of `ctxh` (the (line, head)'s first row; rows beyond Tn are not stored): the wave's 16 x 128 bytes go through its shift tile (128-byte
+// rows, 16-byte chunks XOR-ed with row & 7) and leave as two instructions of eight whole 128-byte rows each.  Straight from the
+// accumulators an instruction stores 16 rows x 32 bytes: four instructions that each touch all sixteen cache lines.
+// (LDS operations of one wave execute in order: the reads see the writes, and whatever the wave writes there next follows the reads.)
+__device__ __forceinline__ void store_rows_via_shift_tile(float *sk, const f32x4 (&o)[4], float inv, bf16_t *ctxh, int ctx_stride, int i_tile, int Tn, int lane) {
+    const int il = lane & 15, g = lane >> 4;
+    unsigned char *stg = reinterpret_cast<unsigned char *>(sk);
+#pragma unroll
+    for (int d = 0; d < 4; ++d) {
+        const f32x4 r4 = o[d] * inv;
+        const bf16x4 w = {(bf16_t)r4[0], (bf16_t)r4[1], (bf16_t)r4[2], (bf16_t)r4[3]};
+        *reinterpret_cast<bf16x4 *>(stg + il * 128 + (((2 * d + (g >> 1)) ^ (il & 7)) << 4) + 8 * (g & 1)) = w;
+    }
+#pragma unroll
+    for (int j = 0; j < 2; ++j) {
+        const int row = 8 * j + (lane >> 3), ch = lane & 7;
+        const bf16x8 v8 = *reinterpret_cast<const bf16x8 *>(stg + row * 128 + ((ch ^ (row & 7)) << 4));
+        const int i = i_tile + row;
+        if (i < Tn) *reinterpret_cast<bf16x8 *>(ctxh + (size_t)i * ctx_stride + 8 * ch) = v8;
+    }
+}
+
 template <typename T, int DHP>   // DHP = padded head dim, multiple of 32
 __global__ __launch_bounds__(256) void relpos_attention_kernel(const T *__restrict__ q, const T *__restrict__ k, const T *__restrict__ v,
                                                                const T *__restrict__ ptab, const float *__restrict__ ub,
@@ -91,7 +196,7 @@ __global__ __launch_bounds__(256) void relpos_attention_kernel(const T *__restri
     constexpr int KC = DHP / 32;                      // k-chunks over the head dim
     constexpr bool MERGE = sizeof(T) == 2 && DHP <= 64;   // one softmax step per 64 keys (bf16: the registers allow it at 3 waves per SIMD)
     constexpr int DT = DHP / 16;                      // 16-row tiles of O^T
-    constexpr int SK = 20;                            // row stride (floats) of the shift tile: conflict-free write and skewed read
+    constexpr int SK = ATT_SK;
     constexpr int RB = DHP * (int)sizeof(T);          // bytes per operand row
     // LDS rows: 128-byte rows (bf16, d_head 64: the measured configuration) are stored unpadded with the 16-byte chunk index
     // XOR-ed with (row & 7): ds_read_b128 fragment reads, the ds_read_b64_tr_b16 reads of V and the staging ds_write_b128 are all
@@ -114,7 +219,7 @@ __global__ __launch_bounds__(256) void relpos_attention_kernel(const T *__restri
     // XCD-aware order: the query tiles of one (line, head) re-read the same K / V / P rows; consecutive LOGICAL workgroups share
     // an XCD (hardware id % 8 picks the XCD), so those rows are fetched into one L2 instead of up to five
     // (PMC: 61 MB of HBM traffic per launch against 21 MB algorithmic with the plain (x, y) order).
-    const int nqt = gridDim.x, logical = xcd_remap_i(blockIdx.x + nqt * blockIdx.y, nqt * gridDim.y);
+    const int nqt = gridDim.x, logical = xcd_remap(blockIdx.x + nqt * blockIdx.y, nqt * gridDim.y);
     const int qtile = logical % nqt;
     const int bh = logical / nqt, b = bh / heads, hh = bh - b * heads;
     const int i0b = qtile * 64, i0 = i0b + wave * 16;
@@ -158,7 +263,7 @@ __global__ __launch_bounds__(256) void relpos_attention_kernel(const T *__restri
     for (int it = 0; it < P_IT; ++it) { const int id = it * 256 + tid, row = id / CPR, ch = id - row * CPR; poff[it] = (unsigned)row * (unsigned)prow * (unsigned)sizeof(T) + ch * 16; }
     // The band of consecutive key tiles overlaps by half (it moves by 64 rows per tile): the 128 band rows in LDS are a ring, local band row
     // lr of tile t sits in slot (lr + 64 (t & 1)) & 127, and every tile after the first stages only its 64 new rows (24 KB instead of 32 KB
-    // per tile through the memory pipeline: staging is a quarter of this kernel's time, timing experiment COCR_ATT_EXP=16).
+    // per tile through the memory pipeline: staging is a quarter of this kernel's time, DESIGN.md "The attention core by subtraction").
     auto load_tile = [&](int j0, bool first) {
         const unsigned char *kt = reinterpret_cast<const unsigned char *>(kbase) + (size_t)j0 * RB;
         const unsigned char *vt = reinterpret_cast<const unsigned char *>(vbase) + (size_t)j0 * RB;
@@ -190,6 +295,8 @@ __global__ __launch_bounds__(256) void relpos_attention_kernel(const T *__restri
 
     // B operands: (q + u) and (q + v) of this lane's query, per k-chunk; padded dims stay zero.  All loads (q fragments
     // and the 8 consecutive bias values of each) are issued before the first use: one round trip, not one per element.
+    // (Three copies of one build: the two branches here and relpos_attention_full_kernel's, which is the dh == DHP branch at DHP = 64.
+    // A shared function changed the compiled code of instantiations no test runs, DESIGN.md: a fix goes into all three.)
     frag_t qu[KC], qv[KC];
     if (dh == DHP) {
         // common case (d_head a multiple of 32): no padded dims -- 16-byte loads only, no per-element selects
@@ -253,20 +360,18 @@ __global__ __launch_bounds__(256) void relpos_attention_kernel(const T *__restri
     float m_run = -INFINITY, l_run = 0.f;
     f32x4 negm4 = {0.f, 0.f, 0.f, 0.f};               // -m_run in the accumulator layout (64-key form); zero until the first tile has set it
     f32x4 osum = {0.f, 0.f, 0.f, 0.f};                // 64-key form: row 0 (register 0 of lanes 0..15) = softmax denominator of query `lane`
-    frag_t ones;                                      // A operand whose row 0 is all ones
-#pragma unroll
-    for (int j = 0; j < 8; ++j) ones[j] = il == 0 ? (T)1.0f : (T)0.0f;
-    float *sk = skew + wave * 48 * SK;
+    const frag_t ones = ones_row_frag<T>(il);
+    float *sk = skew + wave * ATT_SROWS * SK;
 
     stamp();
     for (int j0 = 0; j0 < Tn; j0 += 64) {
-        if constexpr (!(COCR_ATT_EXP & 64)) __syncthreads();                       // every wave is done with the previous tile
+        __syncthreads();                       // every wave is done with the previous tile
         stamp();
         const int bslot = 64 * ((j0 >> 6) & 1);    // ring offset of this tile's band rows
-        if (!(COCR_ATT_EXP & 16) || j0 == 0) store_tile(j0 >> 6);
-        if constexpr (!(COCR_ATT_EXP & 64)) __syncthreads();
+        store_tile(j0 >> 6);
+        __syncthreads();
         stamp();
-        if (!(COCR_ATT_EXP & 16)) load_tile(j0 + 64 < Tn ? j0 + 64 : j0, false);   // in flight during the compute below (unconditional: the staging registers stay registers)
+        load_tile(j0 + 64 < Tn ? j0 + 64 : j0, false);   // in flight during the compute below (unconditional: the staging registers stay registers)
         if constexpr (MERGE) {
             // ---- one softmax step per 64-key tile: the two 32-key halves still take the shift tile in turn (it holds 48 band rows),
             // but the cross-lane maximum (two dependent ds_bpermute round trips), the rescale test, the exponentials and the P.V
@@ -287,88 +392,40 @@ __global__ __launch_bounds__(256) void relpos_attention_kernel(const T *__restri
                     else {
                         rr = negm4;
                         const unsigned char *pr = ps + ((lb0 + 16 * (2 * half + ml) + il + bslot) & 127) * RS;
-                        if constexpr (!(COCR_ATT_EXP & 2)) {
 #pragma unroll
-                            for (int c = 0; c < KC; ++c) rr = mma16(load_frag(reinterpret_cast<const T *>(pr + frag_off(c))), qv[c], rr); }
+                        for (int c = 0; c < KC; ++c) rr = mma16(load_frag(reinterpret_cast<const T *>(pr + frag_off(c))), qv[c], rr);
                     }
                     if (half == 0 && ml == 2) keep = rr;
-                    if constexpr (COCR_ATT_EXP & 1) { if (ml < 2) sc[2 * half + ml] = rr; }
-                    else {
 #pragma unroll
                     for (int r = 0; r < 4; ++r) sk[(16 * ml + 4 * g + r) * SK + il] = rr[r];
-                    }
                 }
                 asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");   // the shift tile is private to the wave; its LDS operations execute in order
-                if constexpr (!(COCR_ATT_EXP & 1)) {
 #pragma unroll
                 for (int tl = 0; tl < 2; ++tl)
 #pragma unroll
                     for (int r = 0; r < 4; ++r) sc[2 * half + tl][r] = sk[(15 - il + 16 * tl + 4 * g + r) * SK + il];
-                }
                 asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");   // reads done before the tile is overwritten
 #pragma unroll
                 for (int tl = 0; tl < 2; ++tl) {
                     const int tt = 2 * half + tl;
                     const unsigned char *kr = ks + (16 * tt + il) * RS;
-                    if constexpr (!(COCR_ATT_EXP & 32)) {
 #pragma unroll
-                        for (int c = 0; c < KC; ++c) sc[tt] = mma16(load_frag(reinterpret_cast<const T *>(kr + frag_off(c))), qu[c], sc[tt]); }
+                    for (int c = 0; c < KC; ++c) sc[tt] = mma16(load_frag(reinterpret_cast<const T *>(kr + frag_off(c))), qu[c], sc[tt]);
                 }
             }
             // sc = score - m_run (log2 units).  The maxima are inline assembly (max3_f): fence first
             mfma_results_fence(sc);
-            float tmax = max3_f(sc[0][0], sc[0][1], sc[0][2]);
-            tmax = max3_f(tmax, sc[0][3], sc[1][0]);
-            tmax = max3_f(tmax, sc[1][1], sc[1][2]);
-            tmax = max3_f(tmax, sc[1][3], sc[2][0]);
-            tmax = max3_f(tmax, sc[2][1], sc[2][2]);
-            tmax = max3_f(tmax, sc[2][3], sc[3][0]);
-            tmax = max3_f(tmax, sc[3][1], sc[3][2]);
-            tmax = max3_f(tmax, sc[3][3], sc[3][3]);
-            if (j0 + 64 > Tn) {                                      // uniform: only the last tile has keys beyond T (a real branch, see below)
+            float tmax = max16(sc);
+            if (j0 + 64 > Tn) {                                      // uniform: only the last tile has keys beyond T (a real branch: mask_tail16)
                 asm volatile("; keys beyond the line" ::: "memory");
-                tmax = -INFINITY;
-#pragma unroll
-                for (int tt = 0; tt < 4; ++tt)
-#pragma unroll
-                    for (int r = 0; r < 4; ++r) {
-                        if (j0 + 16 * tt + 4 * g + r >= Tn) sc[tt][r] = -INFINITY;
-                        tmax = fmaxf(tmax, sc[tt][r]);
-                    }
+                tmax = mask_tail16(sc, j0, g, Tn);
             }
-            { const float x = __shfl_xor(tmax, 16, 64); tmax = max3_f(tmax, x, x); }
-            { const float x = __shfl_xor(tmax, 32, 64); tmax = max3_f(tmax, x, x); }
-            // Lazy rescaling (see the 32-key form below): the reference moves only when some query of the wave exceeds it by > LAZY;
-            // the first tile sets it (key 0 is valid: finite).
-            constexpr float LAZY = 8.0f;
-            if (j0 == 0 || __builtin_amdgcn_ballot_w64(tmax > LAZY) != 0) {
-                const float delta = j0 == 0 ? tmax : fmaxf(tmax, 0.f);
-                const float alpha = j0 == 0 ? 1.0f : __builtin_amdgcn_exp2f(-delta);
-                m_run = j0 == 0 ? tmax : m_run + delta;
-                negm4 = (f32x4){-m_run, -m_run, -m_run, -m_run};
-#pragma unroll
-                for (int r = 0; r < 4; ++r) osum[r] *= alpha;
-#pragma unroll
-                for (int d = 0; d < DT; ++d)
-#pragma unroll
-                    for (int r = 0; r < 4; ++r) o[d][r] *= alpha;
-#pragma unroll
-                for (int tt = 0; tt < 4; ++tt)
-#pragma unroll
-                    for (int r = 0; r < 4; ++r) sc[tt][r] -= delta;
-            }
+            tmax = quad_max(tmax);
+            if (softmax_step64<1, DT>(j0 == 0, &tmax, &m_run, &osum, &o, &sc)) negm4 = (f32x4){-m_run, -m_run, -m_run, -m_run};
             frag_t pb[2];
-#pragma unroll
-            for (int tt = 0; tt < 4; ++tt)
-#pragma unroll
-                for (int r = 0; r < 4; ++r) pb[tt >> 1][4 * (tt & 1) + r] = from_f32<T>((COCR_ATT_EXP & 4) ? sc[tt][r] : __builtin_amdgcn_exp2f(sc[tt][r]));
-            // the softmax denominators on the matrix cores as well: one more row tile whose row 0 is all ones (2 MFMAs per key tile
-            // instead of 16 VALU adds; the sum is over the SAME bf16-rounded probabilities the numerator uses)
-            osum = mma16(ones, pb[0], osum);
-            osum = mma16(ones, pb[1], osum);
+            probs_and_denominator<T>(sc, ones, pb, osum);
 #pragma unroll
             for (int d = 0; d < DT; ++d) {
-                if constexpr (COCR_ATT_EXP & 8) { asm volatile("" : "+v"(o[d]) : "v"(pb[0]), "v"(pb[1])); continue; }
                 o[d] = mma16(load_vt_frag<SWZ>(vs, RS, 0, d, il, g, T()), pb[0], o[d]);
                 o[d] = mma16(load_vt_frag<SWZ>(vs, RS, 32, d, il, g, T()), pb[1], o[d]);
             }
@@ -413,7 +470,8 @@ __global__ __launch_bounds__(256) void relpos_attention_kernel(const T *__restri
                 }
             asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");   // reads done before the next sub-tile overwrites the shift tile
             if (tail) {
-                // a real branch (the asm statement keeps the compiler from turning it into 4 selects per score in EVERY sub-tile)
+                // mask_tail16 on two score tiles, written out: through the function every 32-key instantiation compiles to other code, and no
+                // test runs four of them
                 asm volatile("; keys beyond the line" ::: "memory");
                 tmax = -INFINITY;
 #pragma unroll
@@ -426,13 +484,10 @@ __global__ __launch_bounds__(256) void relpos_attention_kernel(const T *__restri
             }
             tmax = fmaxf(tmax, __shfl_xor(tmax, 16, 64));
             tmax = fmaxf(tmax, __shfl_xor(tmax, 32, 64));
-            // Lazy rescaling: the running reference m_run is only raised when some query of the wave exceeds it by more than
-            // LAZY (softmax is invariant to the reference; exp(score - m_run) <= e^LAZY stays well inside fp32 / bf16 range), so
-            // the accumulators are not touched by the VALU in the common case.  The first sub-tile sets the reference.
-            constexpr float LAZY = 8.0f;
+            // lazy rescaling (ATT_LAZY) on scores that still carry their reference; the first sub-tile sets it
             if (j0 == 0 && s2 == 0) {
                 m_run = tmax;                                     // finite: key 0 is valid
-            } else if (__builtin_amdgcn_ballot_w64(tmax > m_run + LAZY) != 0) {
+            } else if (__builtin_amdgcn_ballot_w64(tmax > m_run + ATT_LAZY) != 0) {
                 const float m_new = fmaxf(m_run, tmax);
                 const float alpha = __builtin_amdgcn_exp2f(m_run - m_new);
                 m_run = m_new;
@@ -474,23 +529,8 @@ __global__ __launch_bounds__(256) void relpos_attention_kernel(const T *__restri
     const float inv = 1.0f / l_run;
     if constexpr (sizeof(T) == 2 && DHP == 64) {
         if (dh == DHP) {
-            // the measured case (bf16, d_head 64): the wave's 16 x 128 bytes go through its shift tile (free by now; 128-byte rows, 16-byte
-            // chunks XOR-ed with row & 7) and leave as two instructions of eight whole 128-byte rows each.  Straight from the accumulators
-            // an instruction stores 16 rows x 32 bytes: four instructions that each touch all sixteen cache lines.
-            unsigned char *stg = reinterpret_cast<unsigned char *>(sk);
-#pragma unroll
-            for (int d = 0; d < DT; ++d) {
-                const f32x4 r4 = o[d] * inv;
-                const bf16x4 w = {(T)r4[0], (T)r4[1], (T)r4[2], (T)r4[3]};
-                *reinterpret_cast<bf16x4 *>(stg + il * 128 + (((2 * d + (g >> 1)) ^ (il & 7)) << 4) + 8 * (g & 1)) = w;
-            }
-            // (LDS operations of one wave execute in order: the reads below see the writes above)
-#pragma unroll
-            for (int j = 0; j < 2; ++j) {
-                const int row = 8 * j + (lane >> 3), ch = lane & 7;
-                const bf16x8 v8 = *reinterpret_cast<const bf16x8 *>(stg + row * 128 + ((ch ^ (row & 7)) << 4));
-                if (i0 + row < Tn) *reinterpret_cast<bf16x8 *>(ctx + ((size_t)b * Tn + i0 + row) * (heads * DHP) + hh * DHP + 8 * ch) = v8;
-            }
+            // the measured case (bf16, d_head 64): whole 128-byte rows through the wave's shift tile (free by now)
+            store_rows_via_shift_tile(sk, o, inv, ctx + (size_t)b * Tn * (heads * DHP) + hh * DHP, heads * DHP, i0, Tn, lane);
             return;
         }
     }
@@ -539,13 +579,12 @@ __global__ __launch_bounds__(256) void relpos_attention_kernel(const T *__restri
 // i.e. the tiled kernel's shift R^T[15 - il + jl][il] on the 48 band rows from lb.
 constexpr int AF_QT = 10;                          // query tiles (16 queries) per workgroup at most
 constexpr int AF_TK = 320;                         // keys resident at most
-constexpr int AF_SK = 20;                          // row stride (floats) of a wave's shift tile
-#ifndef COCR_AF_TWOPART
-#define COCR_AF_TWOPART 1       // dev: 0 = the first pass staged in one part
-#endif
 constexpr int AF_WAVES = 8;                        // waves per workgroup: two per SIMD (round 4; the first form had one per SIMD with up to three query tiles)
 constexpr int AF_SROWS = 32;                       // rows of a wave's shift tile (the 48 band rows of a step go through it in two overlapping rounds)
-constexpr size_t AF_LDS = (size_t)(2 * AF_TK + 16 * AF_QT + AF_TK) * 128 + AF_WAVES * AF_SROWS * AF_SK * sizeof(float);
+static_assert(16 * 128 <= AF_SROWS * ATT_SK * sizeof(float), "store_rows_via_shift_tile: a 16-query tile of bf16 rows fits in the shift tile");
+// K and V rows of a pass of Tk keys, the 16 ntw + Tk band rows the workgroup's ntw query tiles touch in it, the waves' shift tiles
+constexpr size_t attention_full_lds_bytes(int Tk, int ntw) { return (size_t)(2 * Tk + 16 * ntw + Tk) * 128 + AF_WAVES * AF_SROWS * ATT_SK * sizeof(float); }
+constexpr size_t AF_LDS = attention_full_lds_bytes(AF_TK, AF_QT);
 static_assert(AF_LDS <= 160 * 1024, "LDS of the resident attention kernel");
 
 // A wave's state across the key passes: the query operands of its (at most two) tiles, their output accumulators, denominators and running
@@ -562,6 +601,7 @@ template <int NT>
 __device__ __forceinline__ void attn_full_tiles(const unsigned char *ks, const unsigned char *vs, const unsigned char *ps, float *sk,
                                                 AttnFullState &st, int lb_first, int Tn, int Tk, int kg0, int lane, bool sync_after_first = false) {
     typedef bf16_t T;
+    static_assert(NT <= 2, "a wave walks at most two query tiles (AF_QT <= 2 AF_WAVES)");
     constexpr int KC = 2, DT = 4, RS = 128;
     const int il = lane & 15, g = lane >> 4;
     const int fo0 = ((g ^ (il & 7)) << 4), fo1 = (((4 + g) ^ (il & 7)) << 4);        // byte offset of this lane's 16 bytes of k-chunk 0 / 1 in a row = il mod 8
@@ -570,9 +610,7 @@ __device__ __forceinline__ void attn_full_tiles(const unsigned char *ks, const u
     auto &o = st.o;
     auto &osum = st.osum;
     auto &m_run = st.m_run;
-    bf16x8 ones;
-#pragma unroll
-    for (int j = 0; j < 8; ++j) ones[j] = il == 0 ? (T)1.0f : (T)0.0f;
+    const bf16x8 ones = ones_row_frag<T>(il);
 
     for (int j0 = 0; j0 < Tk; j0 += 64) {
         const bool first_tile = kg0 + j0 == 0;                                // the line's first key tile sets the running references
@@ -610,10 +648,10 @@ __device__ __forceinline__ void attn_full_tiles(const unsigned char *ks, const u
                     // sees the writes before it and no write overtakes a read.  The first use of the shifted values, the content products, is
                     // where the wave waits.
 #pragma unroll
-                    for (int r = 0; r < 4; ++r) sk[((16 * ml + 4 * g + r) & (AF_SROWS - 1)) * AF_SK + il] = rr[r];
+                    for (int r = 0; r < 4; ++r) sk[((16 * ml + 4 * g + r) & (AF_SROWS - 1)) * ATT_SK + il] = rr[r];
                     if (ml >= 1) {
 #pragma unroll
-                        for (int r = 0; r < 4; ++r) sc[t][2 * half + ml - 1][r] = sk[((15 - il + 16 * (ml - 1) + 4 * g + r) & (AF_SROWS - 1)) * AF_SK + il];
+                        for (int r = 0; r < 4; ++r) sc[t][2 * half + ml - 1][r] = sk[((15 - il + 16 * (ml - 1) + 4 * g + r) & (AF_SROWS - 1)) * ATT_SK + il];
                     }
                 }
             }
@@ -632,78 +670,25 @@ __device__ __forceinline__ void attn_full_tiles(const unsigned char *ks, const u
 #pragma unroll
                     for (int c = 0; c < KC; ++c) sc[t][2 * half + tl] = mma16(kf[tl][c], qu[t][c], sc[t][2 * half + tl]);
         }
-        // ---- one softmax step per 64 keys and query tile (sc = score - m_run, log2 units), as in the tiled kernel
+        // ---- one softmax step per 64 keys (sc = score - m_run, log2 units).  Each piece runs over all query tiles before the next, and the
+        // two uniform branches -- keys beyond the line, reference moved -- are taken once for all tiles (softmax_step64 says why).
         bf16x8 pb[NT][2];
-        // The maxima below are inline assembly (max3_f): one fence for all query tiles' scores first
+        // The maxima are inline assembly (max3_f): one fence for all query tiles' scores first
         if constexpr (NT == 1) mfma_results_fence(sc[0]);
-        else if constexpr (NT == 2) mfma_results_fence(sc[0], sc[1]);
-        else mfma_results_fence(sc[0], sc[1], sc[2]);
-        // (the steps below run over all query tiles before the next step starts, and the two uniform branches -- keys beyond the line, reference
-        // moved -- are taken once for all tiles: a branch per tile would cut the tiles' chains into basic blocks that cannot interleave)
+        else mfma_results_fence(sc[0], sc[1]);
         float tmax[NT];
 #pragma unroll
-        for (int t = 0; t < NT; ++t) {
-            float m = max3_f(sc[t][0][0], sc[t][0][1], sc[t][0][2]);
-            m = max3_f(m, sc[t][0][3], sc[t][1][0]);
-            m = max3_f(m, sc[t][1][1], sc[t][1][2]);
-            m = max3_f(m, sc[t][1][3], sc[t][2][0]);
-            m = max3_f(m, sc[t][2][1], sc[t][2][2]);
-            m = max3_f(m, sc[t][2][3], sc[t][3][0]);
-            m = max3_f(m, sc[t][3][1], sc[t][3][2]);
-            tmax[t] = max3_f(m, sc[t][3][3], sc[t][3][3]);
-        }
+        for (int t = 0; t < NT; ++t) tmax[t] = max16(sc[t]);
         if (kg0 + j0 + 64 > Tn) {                                            // uniform: only the line's last tile has keys beyond T
             asm volatile("; keys beyond the line" ::: "memory");
 #pragma unroll
-            for (int t = 0; t < NT; ++t) {
-                float m = -INFINITY;
-#pragma unroll
-                for (int tt = 0; tt < 4; ++tt)
-#pragma unroll
-                    for (int r = 0; r < 4; ++r) {
-                        if (kg0 + j0 + 16 * tt + 4 * g + r >= Tn) sc[t][tt][r] = -INFINITY;
-                        m = fmaxf(m, sc[t][tt][r]);
-                    }
-                tmax[t] = m;
-            }
+            for (int t = 0; t < NT; ++t) tmax[t] = mask_tail16(sc[t], kg0 + j0, g, Tn);
         }
 #pragma unroll
-        for (int t = 0; t < NT; ++t) { const float x = __shfl_xor(tmax[t], 16, 64); tmax[t] = max3_f(tmax[t], x, x); }
+        for (int t = 0; t < NT; ++t) tmax[t] = quad_max(tmax[t]);
+        softmax_step64<NT, DT>(first_tile, tmax, m_run, osum, o, sc);
 #pragma unroll
-        for (int t = 0; t < NT; ++t) { const float x = __shfl_xor(tmax[t], 32, 64); tmax[t] = max3_f(tmax[t], x, x); }
-        // Lazy rescaling, per query tile exactly as in the tiled kernel (the reference of a tile moves only when one of ITS queries exceeds it
-        // by more than LAZY; the first key tile sets it) -- a tile whose reference stays gets delta = 0, alpha = 2^-0 = 1: the same bits
-        constexpr float LAZY = 8.0f;
-        bool need[NT], any = first_tile;
-#pragma unroll
-        for (int t = 0; t < NT; ++t) { need[t] = first_tile || __builtin_amdgcn_ballot_w64(tmax[t] > LAZY) != 0; any = any || need[t]; }
-        if (any) {
-#pragma unroll
-            for (int t = 0; t < NT; ++t) {
-                const float delta = first_tile ? tmax[t] : (need[t] ? fmaxf(tmax[t], 0.f) : 0.f);
-                const float alpha = first_tile ? 1.0f : __builtin_amdgcn_exp2f(-delta);
-                m_run[t] = first_tile ? tmax[t] : m_run[t] + delta;
-#pragma unroll
-                for (int r = 0; r < 4; ++r) osum[t][r] *= alpha;
-#pragma unroll
-                for (int d = 0; d < DT; ++d)
-#pragma unroll
-                    for (int r = 0; r < 4; ++r) o[t][d][r] *= alpha;
-#pragma unroll
-                for (int tt = 0; tt < 4; ++tt)
-#pragma unroll
-                    for (int r = 0; r < 4; ++r) sc[t][tt][r] -= delta;
-            }
-        }
-#pragma unroll
-        for (int t = 0; t < NT; ++t) {
-#pragma unroll
-            for (int tt = 0; tt < 4; ++tt)
-#pragma unroll
-                for (int r = 0; r < 4; ++r) pb[t][tt >> 1][4 * (tt & 1) + r] = (T)__builtin_amdgcn_exp2f(sc[t][tt][r]);
-            osum[t] = mma16(ones, pb[t][0], osum[t]);
-            osum[t] = mma16(ones, pb[t][1], osum[t]);
-        }
+        for (int t = 0; t < NT; ++t) probs_and_denominator<T>(sc[t], ones, pb[t], osum[t]);
         // ---- O^T += V^T P^T: a V^T fragment serves every query tile
 #pragma unroll
         for (int d = 0; d < DT; ++d) {
@@ -721,32 +706,13 @@ __device__ __forceinline__ void attn_full_tiles(const unsigned char *ks, const u
     }
 }
 
-// normalise and store: whole 128-byte rows through the wave's shift tile, as in the tiled kernel
+// normalise and store the wave's query tiles, one after the other through its shift tile
 template <int NT>
 __device__ __forceinline__ void attn_full_store(float *sk, const AttnFullState &st, bf16_t *ctxh, int ctx_stride, int i_first, int Tn, int lane) {
-    typedef bf16_t T;
-    constexpr int DT = 4;
-    const int il = lane & 15, g = lane >> 4;
-    auto &o = st.o;
-    auto &osum = st.osum;
-    unsigned char *stg = reinterpret_cast<unsigned char *>(sk);
 #pragma unroll
     for (int t = 0; t < NT; ++t) {
-        const float inv = 1.0f / __shfl(osum[t][0], il, 64);                  // the denominator of query il sits in lane il
-#pragma unroll
-        for (int d = 0; d < DT; ++d) {
-            const f32x4 r4 = o[t][d] * inv;
-            const bf16x4 w = {(T)r4[0], (T)r4[1], (T)r4[2], (T)r4[3]};
-            *reinterpret_cast<bf16x4 *>(stg + il * 128 + (((2 * d + (g >> 1)) ^ (il & 7)) << 4) + 8 * (g & 1)) = w;
-        }
-#pragma unroll
-        for (int j = 0; j < 2; ++j) {
-            const int row = 8 * j + (lane >> 3), ch = lane & 7;
-            const bf16x8 v8 = *reinterpret_cast<const bf16x8 *>(stg + row * 128 + ((ch ^ (row & 7)) << 4));
-            const int i = i_first + 16 * t + row;
-            if (i < Tn) *reinterpret_cast<bf16x8 *>(ctxh + (size_t)i * ctx_stride + 8 * ch) = v8;
-        }
-        // (the next tile's staging writes follow these reads in the wave's LDS order)
+        const float inv = 1.0f / __shfl(st.osum[t][0], lane & 15, 64);        // the denominator of query il sits in lane il
+        store_rows_via_shift_tile(sk, st.o[t], inv, ctxh, ctx_stride, i_first + 16 * t, Tn, lane);
     }
 }
 
@@ -770,7 +736,7 @@ __global__ __launch_bounds__(64 * AF_WAVES) void relpos_attention_full_kernel(co
     const int tid = threadIdx.x, lane = tid & 63;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     // XCD-aware order: the workgroups of one (line, head) read the same K / V rows
-    const int nqb = gridDim.x, logical = xcd_remap_i(blockIdx.x + nqb * blockIdx.y, nqb * gridDim.y);
+    const int nqb = gridDim.x, logical = xcd_remap(blockIdx.x + nqb * blockIdx.y, nqb * gridDim.y);
     const int qb = logical % nqb, bh = logical / nqb, b = bh / heads, hh = bh - b * heads;
     const int i0 = qb * 16 * ntw;                      // first query of this workgroup
     const int nt_here = min(ntw, (Tn - i0 + 15) >> 4); // its query tiles (the last workgroup of a line may hold fewer)
@@ -816,8 +782,9 @@ __global__ __launch_bounds__(64 * AF_WAVES) void relpos_attention_full_kernel(co
         for (int rg = (a ? (16 * ntw + a) / 8 : 0) + wave; rg < (16 * ntw + b2) / 8; rg += AF_WAVES)
             __builtin_amdgcn_global_load_lds((gbl_ptr_t)(pb + (size_t)(rg * 8 + r8) * prow + gch), (lds_ptr_t)(ps + rg * 1024), 16, 0, 0);
     };
-    stage(0, 0, (!LONG && COCR_AF_TWOPART) ? min(64, Kp) : Kp);
-    // ---- query operands: (q + u) scale and (q + v) scale of this lane's query in each tile; empty accumulators
+    stage(0, 0, !LONG ? min(64, Kp) : Kp);
+    // ---- query operands: (q + u) scale and (q + v) scale of this lane's query in each tile; empty accumulators.  A copy of
+    // relpos_attention_kernel's dh == DHP branch at DHP = 64 (its loads are the ones requested above): kept in step with it by hand
     AttnFullState st;
 #pragma unroll
     for (int t = 0; t < 2; ++t) {
@@ -835,13 +802,13 @@ __global__ __launch_bounds__(64 * AF_WAVES) void relpos_attention_full_kernel(co
         for (int d = 0; d < 4; ++d) st.o[t][d] = (f32x4){0.f, 0.f, 0.f, 0.f};
     }
     const int lb_first = 16 * ntw - 16 - 16 * first;   // band row of R^T row 0 for the first tile and the pass's key 0; tile t: 16 t lower; keys from js: + js
-    float *sk = skew + wave * AF_SROWS * AF_SK;
+    float *sk = skew + wave * AF_SROWS * ATT_SK;
     if constexpr (!LONG) {
         // one pass (lines of at most kpass frames; the measured shape).  Staged in two parts: the first key tile (K / V rows 0..63 and the
         // 16 ntw + 64 band rows its scores touch: 44 of 143 KB at the metric's shape) is waited for and published alone, the rest is
         // requested behind that barrier and lands while the tile is computed; a second barrier at the end of the first loop iteration
         // (attn_full_tiles: sync_after_first) publishes it.  Waves without a query tile take part in both barriers and leave.
-        const bool two = COCR_AF_TWOPART && Kp > 64;
+        const bool two = Kp > 64;
         asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
         __builtin_amdgcn_s_barrier();
         if (two) stage(0, 64, Kp);
@@ -872,5 +839,5 @@ __global__ __launch_bounds__(64 * AF_WAVES) void relpos_attention_full_kernel(co
 
 template <typename T, int DHP> static inline size_t attention_lds_bytes() {
     const size_t rb = DHP * sizeof(T);
-    return (size_t)(64 + 64 + 128) * ((rb == 128 && sizeof(T) == 2) ? rb : rb + 16) + 4 * 48 * 20 * sizeof(float);
+    return (size_t)(64 + 64 + 128) * ((rb == 128 && sizeof(T) == 2) ? rb : rb + 16) + 4 * ATT_SROWS * ATT_SK * sizeof(float);
 }

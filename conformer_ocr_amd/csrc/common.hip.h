@@ -90,6 +90,15 @@ __device__ __forceinline__ float wave_max(float v) {
     return __builtin_bit_cast(float, __builtin_amdgcn_readlane(__builtin_bit_cast(int, v), 63));
 }
 
+// XCD-aware workgroup remap (8 XCDs, private L2 each; workgroups are dealt round-robin, so hardware ids b and b+8 share an XCD).
+// Logical id L = chunk(b % 8) + b / 8 gives every XCD a CONTIGUOUS run of logical ids: the GEMMs' column tiles of a row block read that
+// block's A rows, the attention kernels' query tiles of a (line, head) its K / V / P rows, the row chains' neighbouring row blocks their
+// halo rows through ONE L2 instead of eight.  Bijective for any grid size (speed only, never correctness).
+__device__ __forceinline__ int xcd_remap(int bid, int nwg) {
+    const int q = nwg >> 3, r = nwg & 7, xcd = bid & 7;
+    return (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + (bid >> 3);
+}
+
 static inline int ceil_div(int a, int b) { return (a + b - 1) / b; }
 static inline int round_up(int a, int b) { return ceil_div(a, b) * b; }
 

@@ -26,7 +26,7 @@ static hipError_t launch_attention(hipStream_t s, int N, const T *q, const T *k,
             // (lines of more than AF_TK frames: their keys in passes of at most AF_TK, balanced -- 600 frames = 2 x 320, 700 = 3 x 256)
             const int Tk0 = round_up(Tn, 64), npass = ceil_div(Tk0, AF_TK), Tk = round_up(ceil_div(Tk0, npass), 64);
             const int ntw = ceil_div(ntiles, nqb);
-            const size_t lds = (size_t)(2 * Tk + 16 * ntw + Tk) * 128 + AF_WAVES * AF_SROWS * AF_SK * sizeof(float);
+            const size_t lds = attention_full_lds_bytes(Tk, ntw);
             auto kern = npass > 1 ? relpos_attention_full_kernel<true> : relpos_attention_full_kernel<false>;
             hipError_t e = raise_lds_limit((const void *)kern, lds);
             if (e != hipSuccess) return e;

@@ -26,15 +26,6 @@
 
 enum { ACT_NONE = 0, ACT_RELU = 1, ACT_SILU = 2 };
 
-// XCD-aware workgroup remap (8 XCDs, private L2 each; workgroups are dealt round-robin, so ids b and b+8
-// share an XCD).  Logical tile L = chunk(b % 8) + b / 8 gives every XCD a CONTIGUOUS run of logical tiles:
-// all column tiles of a row block then read that row block's A rows through ONE L2 instead of eight.
-// Bijective for any grid size (speed only, never correctness).
-__device__ __forceinline__ int xcd_remap(int bid, int nwg) {
-    const int q = nwg >> 3, r = nwg & 7, xcd = bid & 7;
-    return (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + (bid >> 3);
-}
-
 // ---- epilogues -------------------------------------------------------------------------------------------
 // stage_t            element type of the LDS-staged tile (compute dtype or float)
 // transform(n, v, r) 4 accumulator columns n..n+3 (n % 4 == 0) -> 4 staged values; GLU: (n, value, gate, r)

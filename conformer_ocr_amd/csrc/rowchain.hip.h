@@ -57,12 +57,6 @@ __device__ __forceinline__ float butterfly4(float a, float b, float c, float d) 
     return ab + cd;                        // rows: a, c, b, d
 }
 
-// hardware workgroup id -> row block such that XCD (id % 8) owns a contiguous range of row blocks (as attention.hip.h: xcd_remap_i)
-__device__ __forceinline__ int xcd_remap_rows(int bid, int nwg) {
-    const int q = nwg >> 3, r = nwg & 7, xcd = bid & 7;
-    return (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + (bid >> 3);
-}
-
 // slack behind the two hidden-chunk images (the q / k / v output tiles' padded rows reach into it)
 constexpr size_t ROWCHAIN_SLACK = 4096;
 // channels per pass of the depthwise prologue (window + taps of that many channels in LDS at a time)
@@ -144,7 +138,7 @@ __global__ __launch_bounds__(512, 2) void rowchain_kernel(ChainArgs p) {
     // XCD-aware order (p.xcd_order): hardware workgroup ids go round the 8 XCDs; the row block a workgroup owns is chosen so that each XCD
     // holds a contiguous range of row blocks, i.e. of lines -- the same lines whose (line, head) workgroups the attention kernels put on that
     // XCD: what one launch writes (context rows, GLU output, stream, q / k / v) the next one reads from the same L2
-    const int rblk = p.xcd_order ? xcd_remap_rows(blockIdx.x, gridDim.x) : (int)blockIdx.x;
+    const int rblk = p.xcd_order ? xcd_remap(blockIdx.x, gridDim.x) : (int)blockIdx.x;
     const int M = p.M, m0 = rblk * BMC, mend = min(M, m0 + BMC);
     const int lrow = lane >> 3, cpos = lane & 7;
 #ifdef COCR_CHAIN_STAMPS_BUILD
