@@ -118,3 +118,11 @@ static inline hipError_t raise_lds_limit(const void *kern, size_t lds, size_t ab
     if (e == hipSuccess) raised.insert(kern);
     return e;
 }
+// One launch with `lds` bytes of dynamic LDS: the limit raised where needed, the launch, its error
+template <typename... P, typename... A>
+static inline hipError_t launch_lds(void (*kern)(P...), dim3 grid, dim3 block, size_t lds, hipStream_t s, A... args) {
+    const hipError_t e = raise_lds_limit((const void *)kern, lds);
+    if (e != hipSuccess) return e;
+    hipLaunchKernelGGL(kern, grid, block, lds, s, args...);
+    return hipGetLastError();
+}

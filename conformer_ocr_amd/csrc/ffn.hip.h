@@ -142,16 +142,7 @@ __global__ __launch_bounds__(512) void ffn_fused_kernel(const bf16_t *__restrict
     __syncthreads();
     // ---- epilogue: alpha (acc + b2) staged as fp32 rows over the (now idle) weight buffers, then residual + LayerNorm per row
     constexpr int RS = D * 4 + 16;
-#pragma unroll
-    for (int i = 0; i < 3; ++i)
-#pragma unroll
-        for (int j = 0; j < 2; ++j) {
-            const int row = 16 * i + r16, n = 32 * wave + 16 * j + 4 * g;
-            const float v[4] = {acc2[i][j][0], acc2[i][j][1], acc2[i][j][2], acc2[i][j][3]};
-            float r[4];
-            epi.transform(n, v, r);
-            *reinterpret_cast<f32x4 *>(wreg + row * RS + n * 4) = (f32x4){r[0], r[1], r[2], r[3]};
-        }
+    stage_acc<3, 2, RS>(acc2, wreg, 0, 32 * wave, 0, epi);
     __syncthreads();
     epi.rows4(m0 + 4 * wave, mend, reinterpret_cast<const float *>(wreg + 4 * wave * RS), RS / 4, lane, xr[0]);
     if (wave < 4) epi.rows4(m0 + 4 * (wave + 8), mend, reinterpret_cast<const float *>(wreg + 4 * (wave + 8) * RS), RS / 4, lane, xr[1]);
@@ -164,9 +155,5 @@ static inline hipError_t launch_ffn_fused(hipStream_t s, const bf16_t *xn, const
                                           const Epi &epi) {
     constexpr int DD = 256;
     const size_t lds = (size_t)4 * 48 * 128 + 8 * 2 * 8192 + (size_t)FF * 4;     // hidden chunks + per-wave weight slices + b1
-    auto kern = ffn_fused_kernel<DD, Epi>;
-    hipError_t e = raise_lds_limit((const void *)kern, lds);
-    if (e != hipSuccess) return e;
-    hipLaunchKernelGGL(kern, dim3(ceil_div(M, 48)), dim3(512), lds, s, xn, W1, b1, W2, M, FF, epi);
-    return hipGetLastError();
+    return launch_lds(ffn_fused_kernel<DD, Epi>, dim3(ceil_div(M, 48)), dim3(512), lds, s, xn, W1, b1, W2, M, FF, epi);
 }

@@ -1,5 +1,5 @@
 // The forward behind the C ABI (units of the host layer: model.hip.h): its form (forward_form), its stages, the weights' packed copies,
-// the hipGraph replay, the entry point; the setters that change its launches; the GEMM micro-benchmark.
+// the hipGraph replay, the entry point; the setters that change its launches.
 #include "model.hip.h"
 #include "attention.hip.h"
 #include "conv.hip.h"
@@ -28,24 +28,17 @@ static hipError_t launch_attention(hipStream_t s, int N, const T *q, const T *k,
             const int ntw = ceil_div(ntiles, nqb);
             const size_t lds = attention_full_lds_bytes(Tk, ntw);
             auto kern = npass > 1 ? relpos_attention_full_kernel<true> : relpos_attention_full_kernel<false>;
-            hipError_t e = raise_lds_limit((const void *)kern, lds);
-            if (e != hipSuccess) return e;
-            hipLaunchKernelGGL(kern, dim3(nqb, N * heads), dim3(64 * AF_WAVES), lds, s, (const bf16_t *)q, (const bf16_t *)k, (const bf16_t *)v,
-                               (const bf16_t *)ptab, ub, vb, (bf16_t *)ctx, Tn, Tp, heads, scale * 1.44269504088896340736f, pos_center, ntw, Tk);
-            return hipGetLastError();
+            return launch_lds(kern, dim3(nqb, N * heads), dim3(64 * AF_WAVES), lds, s, (const bf16_t *)q, (const bf16_t *)k, (const bf16_t *)v,
+                              (const bf16_t *)ptab, ub, vb, (bf16_t *)ctx, Tn, Tp, heads, scale * 1.44269504088896340736f, pos_center, ntw, Tk);
         }
     }
     const size_t lds = attention_lds_bytes<T, DHP>();
-    auto kern = relpos_attention_kernel<T, DHP>;
-    hipError_t e = raise_lds_limit((const void *)kern, lds);
-    if (e != hipSuccess) return e;
     // log2(e) rides on the 1/sqrt(d_head) factor folded into the query operands: the kernel's scores are in log2 units and its
     // softmax uses v_exp_f32 (2^x) directly -- one multiply per score less.
     // (80-query tiles -- 5 waves, 512 workgroups = one round of 2 per CU at cfg2 instead of 1280 in two rounds -- measured SLOWER:
     // 19.4 us against 16.3 us per launch)
-    hipLaunchKernelGGL(kern, dim3(ceil_div(Tn, 64), N * heads), dim3(256), lds, s, q, k, v, ptab, ub, vb, ctx, Tn, Tp, heads, dh,
-                       scale * 1.44269504088896340736f, pos_center, stamps);
-    return hipGetLastError();
+    return launch_lds(relpos_attention_kernel<T, DHP>, dim3(ceil_div(Tn, 64), N * heads), dim3(256), lds, s, q, k, v, ptab, ub, vb, ctx, Tn, Tp, heads, dh,
+                      scale * 1.44269504088896340736f, pos_center, stamps);
 }
 
 // ------------------------------------------------------------------------------------ forward: its form
@@ -118,9 +111,7 @@ static int chain_rows_for(const cocr_model *m, int M) {
 }
 
 // split-K over 2 workgroup groups (2 measured best of 2, 4, 8: 63 vs 74 vs 91 us for product + reduction)
-#ifndef COCR_FO_SPLITS
-#define COCR_FO_SPLITS 2
-#endif
+constexpr int FRONT_OUT_SPLITS = 2;
 static Form forward_form(const cocr_model *m, int N, int W) {
     const bool bf16 = m->dtype == COCR_BF16, f2only = m->snum == 1;
     const int es = bf16 ? 2 : 4, D = m->D, C = m->C, H = m->H;
@@ -136,7 +127,7 @@ static Form forward_form(const cocr_model *m, int N, int W) {
     else if (bf16 && C == 32 && F2 <= 32 && lds32 <= 160 * 1024 && !f.taps && !m->sw.no_front32) f.front = FRONT_PW32;
     else f.front = bf16 && C % 64 == 0 ? FRONT_MFMA : FRONT_VALU;
     if (f.chain && Kf % 256 == 0 && !m->sw.no_front_chain) f.out = OUT_IN_CHAIN;
-    else if (f.rowln && Kf % (COCR_FO_SPLITS * (128 / es)) == 0 && D <= 256 && (size_t)COCR_FO_SPLITS * M * D * 4 <= (size_t)N * T2 * F2 * C * es)
+    else if (f.rowln && Kf % (FRONT_OUT_SPLITS * (128 / es)) == 0 && D <= 256 && (size_t)FRONT_OUT_SPLITS * M * D * 4 <= (size_t)N * T2 * F2 * C * es)
         f.out = OUT_SPLITK;     // (the parts fit the idle frontend buffer)
     else f.out = OUT_GEMM;
     f.ffn_fused = bf16 && f.rowln && ffn_fused_supported<int>(D, m->ff);
@@ -168,6 +159,7 @@ template <typename T> struct Fwd {
           ffr(m_->hp.half_step_residual ? 0.5f : 1.0f), za((T *)m_->ws.z_a), zb((T *)m_->ws.z_b), x(m_->ws.x),
           xn((T *)m_->ws.xn), hid((T *)m_->ws.hid), q((T *)m_->ws.q), k((T *)m_->ws.k), v((T *)m_->ws.vt), ctx((T *)m_->ws.ctx), glu((T *)m_->ws.glu), dwo((T *)m_->ws.dwo) {}
     const float *F32(size_t off) const { return (const float *)(m->w->blob + off); }
+    const float *F32_opt(long off) const { return off >= 0 ? F32((size_t)off) : nullptr; }      // (an optional second LayerNorm's parameters: -1 without)
     const T *WT(size_t off) const { return (const T *)(m->w->blob + off); }
     template <typename S> int tap(int l, const char *what, const S *src, size_t n) const {      // debug tap "what" (l < 0) or "l<l>.what"
         if (!f.taps) return COCR_OK;
@@ -211,11 +203,8 @@ template <typename T, typename TIn> static int frontend(const Fwd<T> &c, const T
     } else if (form == FRONT_PW32) {
         ProfScope ps(m, s, FAM_CONV12);
         const size_t lds = (size_t)(4 * 16 + 3) * ((H + 11) & ~3) * 4 + (size_t)16 * F2 * 80;      // line tile + Z2 rows of 16 frames
-        auto kern = frontend_conv12pw32_kernel<TIn>;
-        GEMM_TRY(raise_lds_limit((const void *)kern, lds));
-        hipLaunchKernelGGL(kern, dim3(ceil_div(T2, 16), N), dim3(256), lds, s, lines, H, W, T1, F1, T2, F2, c.F32(P.w0), c.F32(P.b0),
-                           c.F32(P.stages[0].dw_w), c.F32(P.stages[0].dw_b), (const bf16_t *)c.WT(P.stages[0].pw_w), c.F32(P.stages[0].pw_b), (bf16_t *)zb);
-        LAUNCH_CHECK();
+        GEMM_TRY(launch_lds(frontend_conv12pw32_kernel<TIn>, dim3(ceil_div(T2, 16), N), dim3(256), lds, s, lines, H, W, T1, F1, T2, F2, c.F32(P.w0), c.F32(P.b0),
+                            c.F32(P.stages[0].dw_w), c.F32(P.stages[0].dw_b), (const bf16_t *)c.WT(P.stages[0].pw_w), c.F32(P.stages[0].pw_b), (bf16_t *)zb));
     } else {
         {
             ProfScope ps(m, s, FAM_CONV12);
@@ -258,10 +247,15 @@ template <typename T, typename TIn> static int frontend(const Fwd<T> &c, const T
 // xn <- LN1(x); g2 >= 0: x <- LN1(x), xn <- LN2(x) (a block-final LayerNorm chained with the next block's first); write_f32: x <- LN1(x)
 template <typename T> static int layernorm(const Fwd<T> &c, size_t g1, size_t b1, bool write_f32, long g2, long b2) {
     ProfScope ps(c.m, c.s, FAM_LN);
-    launch_layernorm<T>(c.s, c.x, c.M, c.D, c.F32(g1), c.F32(b1), write_f32 ? c.x : nullptr, g2 >= 0 ? c.F32((size_t)g2) : nullptr,
-                        b2 >= 0 ? c.F32((size_t)b2) : nullptr, c.xn, c.m->rD);
+    launch_layernorm<T>(c.s, c.x, c.M, c.D, c.m->rD, c.F32(g1), c.F32(b1), write_f32 ? c.x : nullptr, c.F32_opt(g2), c.F32_opt(b2), c.xn);
     LAUNCH_CHECK();
     return COCR_OK;
+}
+
+// The row-complete epilogue of a product into the stream (Form::rowln): x <- [x +] alpha (acc + bias), then the LayerNorm(s) that follow in the
+// reference, over the model's own width (layernorm)
+template <typename T> static EpiResidualLN<T> stream_ln_epi(const Fwd<T> &c, size_t bias, float alpha, bool resid, size_t g1, size_t b1, long g2, long b2) {
+    return {c.x, c.D, c.F32(bias), alpha, c.D, resid ? 1 : 0, c.F32(g1), c.F32(b1), c.F32_opt(g2), c.F32_opt(b2), c.xn, c.m->rD};
 }
 
 // x <- [x +] alpha (A W^T + bias); then the LayerNorm(s) that follow in the reference (layernorm)
@@ -271,10 +265,7 @@ template <typename T> static int gemm_to_stream(const Fwd<T> &c, int fam, const 
     {
         ProfScope ps(c.m, c.s, fam);
         if (c.f.rowln) {
-            EpiResidualLN<T, 1> e{c.x, D, c.F32(bias), alpha, D, resid ? 1 : 0, c.F32(g1), c.F32(b1), g2 >= 0 ? c.F32((size_t)g2) : nullptr,
-                                  b2 >= 0 ? c.F32((size_t)b2) : nullptr, c.xn};
-            e.Dn = c.m->rD;
-            GEMM_TRY(launch_gemm_rowln<T>(c.s, A, K, c.WT(w), K, M, D, K, e));
+            GEMM_TRY(launch_gemm_rowln<T>(c.s, A, K, c.WT(w), K, M, D, K, stream_ln_epi(c, bias, alpha, resid, g1, b1, g2, b2)));
             return COCR_OK;
         }
         if (resid) { EpiResidual e{c.x, D, c.F32(bias), alpha, D}; GEMM_TRY(launch_gemm<T>(c.s, A, K, c.WT(w), K, M, D, K, e)); }
@@ -292,9 +283,9 @@ template <typename T> static int front_out(const Fwd<T> &c) {
     if (c.f.out == OUT_IN_CHAIN) return COCR_OK;                  // (encoder_chains; front.y is tapped there)
     if (c.f.out == OUT_SPLITK) {
         float *partial = reinterpret_cast<float *>(c.za);          // the other frontend buffer is free now
-        { ProfScope ps(m, c.s, FAM_FOUT); GEMM_TRY(launch_gemm_splitk<T>(c.s, c.zb, Kf, c.WT(P.wout), Kf, M, D, Kf, COCR_FO_SPLITS, partial)); }
+        { ProfScope ps(m, c.s, FAM_FOUT); GEMM_TRY(launch_gemm_splitk<T>(c.s, c.zb, Kf, c.WT(P.wout), Kf, M, D, Kf, FRONT_OUT_SPLITS, partial)); }
         ProfScope ps(m, c.s, FAM_LN);
-        hipLaunchKernelGGL((splitk_reduce_ln_kernel<T>), dim3(ceil_div(M, 16)), dim3(256), 0, c.s, partial, COCR_FO_SPLITS, (size_t)M * D, c.F32(P.bout), M, D,
+        hipLaunchKernelGGL((splitk_reduce_ln_kernel<T>), dim3(ceil_div(M, 16)), dim3(256), 0, c.s, partial, FRONT_OUT_SPLITS, (size_t)M * D, c.F32(P.bout), M, D,
                            m->rD, c.F32(f0.ln_g), c.F32(f0.ln_b), c.x, c.xn);
         LAUNCH_CHECK();
     } else {
@@ -315,9 +306,8 @@ template <typename T> static int ffn(const Fwd<T> &c, const FfnW &fw, size_t g1,
     if constexpr (sizeof(T) == 2) {
         if (c.f.ffn_fused) {
             ProfScope ps(c.m, c.s, FAM_FFN_FUSED);
-            EpiResidualLN<T, 1> e{c.x, c.D, c.F32(fw.b2), c.ffr, c.D, 1, c.F32(g1), c.F32(b1), g2 >= 0 ? c.F32((size_t)g2) : nullptr,
-                                  b2 >= 0 ? c.F32((size_t)b2) : nullptr, c.xn};
-            GEMM_TRY(launch_ffn_fused(c.s, (const bf16_t *)c.xn, (const bf16_t *)c.WT(fw.w1), c.F32(fw.b1), (const bf16_t *)c.WT(fw.w2), c.M, c.D, c.m->ff, e));
+            GEMM_TRY(launch_ffn_fused(c.s, (const bf16_t *)c.xn, (const bf16_t *)c.WT(fw.w1), c.F32(fw.b1), (const bf16_t *)c.WT(fw.w2), c.M, c.D, c.m->ff,
+                                      stream_ln_epi(c, fw.b2, c.ffr, true, g1, b1, g2, b2)));
             return COCR_OK;
         }
     }
@@ -431,7 +421,7 @@ template <typename T> static int encoder_chains(const Fwd<T> &c) {
     auto st_ffn = [&](const FfnW &fw, size_t g1, size_t b1, long g2, long b2) {
         ChainStage st{}; st.kind = ST_FFN; st.W = CW(fw.w1); st.W2 = CW(fw.w2); st.bias = c.F32(fw.b1); st.bias2 = c.F32(fw.b2);
         st.N = m->ff; st.alpha = c.ffr; st.g1 = c.F32(g1); st.b1 = c.F32(b1);      // (W2's fragment-major copy is pre-scaled by ffr: ensure_packed)
-        st.g2 = g2 >= 0 ? c.F32((size_t)g2) : nullptr; st.b2 = b2 >= 0 ? c.F32((size_t)b2) : nullptr; return st; };
+        st.g2 = c.F32_opt(g2); st.b2 = c.F32_opt(b2); return st; };
     auto st_qkv = [&](const LayerW &lw) {
         ChainStage st{}; st.kind = ST_QKV; st.W = CW(lw.wqkv); st.bias = c.F32(lw.bqkv); st.N = 3 * D;
         st.q = (bf16_t *)c.q; st.k = (bf16_t *)c.k; st.v = (bf16_t *)c.v; return st; };
@@ -669,83 +659,6 @@ extern "C" int cocr_forward(cocr_model *m, const void *lines, int line_dtype, in
 extern "C" int cocr_forget_argmax(cocr_model *m) {
     if (!m) return fail(COCR_EINVAL, "null argument");
     m->dec.amax_logits = nullptr;
-    return COCR_OK;
-}
-
-// ------------------------------------------------------------------------------------ kernel micro-benchmarks (development hook)
-__global__ void fill_kernel(unsigned short *p, size_t n, unsigned seed, int as_f32) {
-    for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (size_t)gridDim.x * blockDim.x) {
-        unsigned h = (unsigned)i * 2654435761u + seed;
-        h ^= h >> 15; h *= 2246822519u; h ^= h >> 13;
-        const float v = ((float)(h & 0xffff) / 65536.0f - 0.5f);
-        if (as_f32) ((float *)p)[i] = v; else ((bf16_t *)p)[i] = (bf16_t)v;
-    }
-}
-
-struct EpiNull {   // ablation: keeps the accumulators alive, stores (almost) nothing
-    typedef float stage_t;
-    static constexpr bool GLU = false;
-    static constexpr bool ROWWISE = false;
-    float *sink;
-    __device__ __forceinline__ void transform(int n, const float *v, float *r) const { for (int i = 0; i < 4; ++i) r[i] = v[i]; }
-    __device__ __forceinline__ void store(int m, int c, const float *src, int cnt) const { if (src[0] == 123.456f) sink[0] = 1.0f; }
-};
-
-// Times one GEMM variant on random operands: returns the average device time per launch in microseconds.
-extern "C" int cocr_dev_bench_gemm(int variant, int M, int N, int K, int iters, double *us_out) {
-    typedef bf16_t T;
-    void *A = nullptr, *W = nullptr, *O = nullptr;
-    float *X = nullptr, *bias = nullptr, *gam = nullptr;
-    HIP_TRY(hipMalloc(&A, (size_t)M * K * 2)); HIP_TRY(hipMalloc(&W, (size_t)N * K * 2)); HIP_TRY(hipMalloc(&O, (size_t)M * N * 4));
-    HIP_TRY(hipMalloc((void **)&X, (size_t)M * K * 4)); HIP_TRY(hipMalloc((void **)&bias, (size_t)N * 4)); HIP_TRY(hipMalloc((void **)&gam, (size_t)K * 4));
-    hipLaunchKernelGGL(fill_kernel, dim3(1024), dim3(256), 0, 0, (unsigned short *)A, (size_t)M * K, 1u, 0);
-    hipLaunchKernelGGL(fill_kernel, dim3(1024), dim3(256), 0, 0, (unsigned short *)W, (size_t)N * K, 2u, 0);
-    hipLaunchKernelGGL(fill_kernel, dim3(1024), dim3(256), 0, 0, (unsigned short *)X, (size_t)M * K, 3u, 1);
-    hipLaunchKernelGGL(fill_kernel, dim3(64), dim3(256), 0, 0, (unsigned short *)bias, (size_t)N, 4u, 1);
-    hipLaunchKernelGGL(fill_kernel, dim3(64), dim3(256), 0, 0, (unsigned short *)gam, (size_t)K, 5u, 1);
-    HIP_TRY(hipMemset(O, 0, (size_t)M * N * 4));
-    GemmArgs<T> a{(const T *)A, K, (const T *)W, K, M, N, K, 0};
-    EpiBiasAct<T, ACT_SILU> eh{(T *)O, N, bias, N};
-    EpiResidual er{(float *)O, N, bias, 0.5f, N};
-    EpiNull en{(float *)O};
-    const bool resid = N <= 256;
-    auto run = [&]() -> hipError_t {
-#define RING(BM, BN, NST) (resid ? launch_ring_cfg<T, BM, BN, NST>(0, a, er) : launch_ring_cfg<T, BM, BN, NST>(0, a, eh))
-        switch (variant) {
-            case 0: return resid ? launch_gemm<T>(0, a.A, K, a.W, K, M, N, K, er) : launch_gemm<T>(0, a.A, K, a.W, K, M, N, K, eh);
-            case 1: return RING(64, 64, 3);
-            case 2: return RING(64, 64, 4);
-            case 3: return RING(64, 128, 3);
-            case 4: return RING(128, 128, 2);
-            case 5: return RING(128, 128, 3);
-            case 6: return RING(128, 64, 3);
-            case 7: return RING(64, 128, 2);
-            case 8: return RING(64, 64, 2);
-            case 9: return resid ? launch_stream_cfg<T, 64, 64>(0, a, er) : launch_stream_cfg<T, 64, 64>(0, a, eh);
-            case 30: return launch_ring_cfg<T, 128, 128, 2>(0, a, en);
-            case 31: return launch_ring_cfg<T, 64, 64, 3>(0, a, en);
-            case 40: {   // fused FFN on (M, D=256, FF=N): A = xn [M][256], W = W1 [N][256], O reused as W2 [256][N]
-                EpiResidualLN<T, 1> e{X, 256, bias, 0.5f, 256, 1, gam, gam, nullptr, nullptr, (T *)A};
-                return launch_ffn_fused<EpiResidualLN<T, 1>>(0, (const T *)A, (const T *)W, bias, (const T *)O, M, 256, N, e);
-            }
-            case 20: launch_layernorm<T>(0, X, M, K, gam, gam, nullptr, nullptr, nullptr, (T *)A); return hipGetLastError();
-            case 21: launch_layernorm<T>(0, X, M, K, gam, gam, X, gam, gam, (T *)A); return hipGetLastError();
-            default: return hipErrorInvalidValue;
-        }
-#undef RING
-    };
-    for (int i = 0; i < 3; ++i) HIP_TRY(run());
-    hipEvent_t e0, e1;
-    HIP_TRY(hipEventCreate(&e0)); HIP_TRY(hipEventCreate(&e1));
-    HIP_TRY(hipEventRecord(e0, 0));
-    for (int i = 0; i < iters; ++i) HIP_TRY(run());
-    HIP_TRY(hipEventRecord(e1, 0));
-    HIP_TRY(hipEventSynchronize(e1));
-    float ms = 0.f;
-    HIP_TRY(hipEventElapsedTime(&ms, e0, e1));
-    *us_out = (double)ms * 1e3 / iters;
-    (void)hipEventDestroy(e0); (void)hipEventDestroy(e1);
-    (void)hipFree(A); (void)hipFree(W); (void)hipFree(O); (void)hipFree(X); (void)hipFree(bias); (void)hipFree(gam);
     return COCR_OK;
 }
 

@@ -5,7 +5,8 @@
 // the decoder (pred.py:90).  Both operands are k-contiguous, which is the MFMA fragment order
 // (common.hip.h), so activations (M,K) and nn.Linear weights (N,K) are used as stored.
 //
-// Two kernels share one epilogue:
+// Two kernels share one epilogue (the ring's pieces -- ring_wait, RingTile, ring_mma, stage_acc -- are shared with the row-complete
+// gemm_rowln48_kernel, the K-major gemm_tn_kernel and ffn.hip.h):
 //   gemm_ring_kernel   K % BK == 0.  Operand tiles go global -> LDS by LDS-DMA (global_load_lds, 16 B per
 //                      lane, no VGPR staging) into an NST-deep ring; the k-loop waits with a COUNTED vmcnt so
 //                      NST-1 tiles stay in flight across the raw barrier (one barrier per k-tile).  The LDS
@@ -23,6 +24,7 @@
 #include <type_traits>
 
 #include "common.hip.h"
+#include "norm.hip.h"
 
 enum { ACT_NONE = 0, ACT_RELU = 1, ACT_SILU = 2 };
 
@@ -215,175 +217,56 @@ template <typename T> struct EpiPosTable {
 //   single:  x <- x_new ;            xn <- LN1(x_new)                 (the next module's LayerNorm)
 //   chained: x <- LN1(x_new) ;       xn <- LN2(LN1(x_new))            (block-final LayerNorm encoder.py:99 + next FFN's)
 // so no standalone LayerNorm launch and no re-read of the stream is left in a block.
-template <typename T, int NV> struct EpiResidualLN {
+template <typename T> struct EpiResidualLN {
     typedef float stage_t;
     static constexpr bool GLU = false;
     static constexpr bool ROWWISE = true;
     float *x; int D; const float *bias; float alpha; int N; int has_resid;
     const float *g1, *b1, *g2, *b2;
     T *xn;
-    int Dn = 0;            // LayerNorm width when D is a zero-padded row width (0: D).  Columns [Dn, D) hold exact zeros: the sums need no mask, the
-                           // centred squares and the divisor do
+    int Dn;                // LayerNorm width: D, or less when D is a zero-padded row width.  Columns [Dn, D) hold exact zeros (ln_rows4)
     __device__ __forceinline__ void transform(int n, const float *v, float *r) const {
 #pragma unroll
         for (int i = 0; i < 4; ++i) r[i] = alpha * (v[i] + (n + i < N ? bias[n + i] : 0.f));
     }
     // The residual rows can be fetched long before the accumulators are ready (kernel prologue): the epilogue then has no
     // global-load latency left in it.  rows m0 .. m0+3; clamped addresses, rows >= M are discarded at the stores.
-    struct Rows4 { f32x4 v[4][NV]; };
+    struct Rows4 { f32x4 v[4][1]; };      // one chunk per lane: N <= 256 (gemm_rowln_supported)
     __device__ __forceinline__ Rows4 rows4_load(int m0, int M, int lane) const {
-        const int nchunk = D >> 2;
+        const int cc = min(lane, (D >> 2) - 1);
         Rows4 p;
 #pragma unroll
-        for (int r = 0; r < 4; ++r)
-#pragma unroll
-            for (int v = 0; v < NV; ++v) {
-                const int cc = min(lane + 64 * v, nchunk - 1);
-                p.v[r][v] = *reinterpret_cast<const f32x4 *>(x + (size_t)min(m0 + r, M - 1) * D + 4 * cc);
-            }
+        for (int r = 0; r < 4; ++r) p.v[r][0] = *reinterpret_cast<const f32x4 *>(x + (size_t)min(m0 + r, M - 1) * D + 4 * cc);
         return p;
     }
     __device__ __forceinline__ void rows4(int m0, int M, const float *staged, int rs_floats, int lane) const {
         rows4(m0, M, staged, rs_floats, lane, rows4_load(m0, M, lane));
     }
-    // Chain form (chain.hip.h): the residual rows come in through `xr` and the NEW stream rows go back out through it (the next
-    // stage of the chain adds to them without touching global memory); x / xn are written to global only when asked; the new
-    // normalised rows are also written as bf16 into the swizzled operand image `lds` (panels of [rows][128 B], tile row = row0 + r).
-    __device__ __forceinline__ void rows4_chain(int m0, int M, const float *staged, int rs_floats, int lane, Rows4 &xr, int store_x, int store_xn,
-                                                unsigned char *lds, int row0, int panel_bytes) const {
-        static_assert(NV == 1, "chain kernels are written for encoder_dim <= 256");
-        const int nchunk = D >> 2;
-        const float inv_d = 1.0f / (float)D;
-        const int c = lane, cc = min(c, nchunk - 1);
-        f32x4 xv[4];
+    // rows m0 .. m0+3 (row r valid if m0 + r < M); staged row r at `staged + r * rs_floats`; xr = rows4_load(m0, M, lane)
+    __device__ __forceinline__ void rows4(int m0, int M, const float *staged, int rs_floats, int lane, const Rows4 &xr) const {
+        const int nchunk = D >> 2, nnorm = Dn >> 2, cc = min(lane, nchunk - 1);
+        const float inv_d = 1.0f / (float)Dn;
+        f32x4 xv[4][1], ga[1], be[1];
         float s[4];
 #pragma unroll
         for (int r = 0; r < 4; ++r) {
             f32x4 t = *reinterpret_cast<const f32x4 *>(staged + r * rs_floats + 4 * cc);
             if (has_resid) t += xr.v[r][0];
-            if (c >= nchunk) t = (f32x4){0, 0, 0, 0};
-            xv[r] = t;
+            if (lane >= nchunk) t = (f32x4){0, 0, 0, 0};
+            xv[r][0] = t;
             s[r] = t[0] + t[1] + t[2] + t[3];
         }
-        auto normalise = [&](const float *gam, const float *bet) {
-            float mean[4], q[4], rstd[4];
-#pragma unroll
-            for (int r = 0; r < 4; ++r) mean[r] = wave_sum(s[r]) * inv_d;
-#pragma unroll
-            for (int r = 0; r < 4; ++r) {
-                q[r] = 0.f;
-#pragma unroll
-                for (int e = 0; e < 4; ++e) { const float d = c < nchunk ? xv[r][e] - mean[r] : 0.f; q[r] += d * d; }
-            }
-#pragma unroll
-            for (int r = 0; r < 4; ++r) rstd[r] = 1.0f / sqrtf(wave_sum(q[r]) * inv_d + 1e-5f);
-            const f32x4 ga = c < nchunk ? *reinterpret_cast<const f32x4 *>(gam + 4 * cc) : (f32x4){0, 0, 0, 0};
-            const f32x4 be = c < nchunk ? *reinterpret_cast<const f32x4 *>(bet + 4 * cc) : (f32x4){0, 0, 0, 0};
-#pragma unroll
-            for (int r = 0; r < 4; ++r) {
-#pragma unroll
-                for (int e = 0; e < 4; ++e) xv[r][e] = (xv[r][e] - mean[r]) * rstd[r] * ga[e] + be[e];
-                s[r] = xv[r][0] + xv[r][1] + xv[r][2] + xv[r][3];
-            }
-        };
-        auto keep_x = [&]() {
-#pragma unroll
-            for (int r = 0; r < 4; ++r) {
-                xr.v[r][0] = xv[r];
-                if (store_x && m0 + r < M && c < nchunk) *reinterpret_cast<f32x4 *>(x + (size_t)(m0 + r) * D + 4 * c) = xv[r];
-            }
-        };
-        if (!g2) keep_x();
-        normalise(g1, b1);
-        if (g2) { keep_x(); normalise(g2, b2); }
-#pragma unroll
-        for (int r = 0; r < 4; ++r) {
-            bf16x4 o = {(T)xv[r][0], (T)xv[r][1], (T)xv[r][2], (T)xv[r][3]};
-            if (c < nchunk) {
-                const int row = row0 + r, col = 4 * c;
-                *reinterpret_cast<bf16x4 *>(lds + (col >> 6) * panel_bytes + row * 128 + ((((col & 63) >> 3) ^ (row & 7)) << 4) + ((col & 7) >> 2) * 8) = o;
-                if (store_xn && m0 + r < M) *reinterpret_cast<bf16x4 *>(xn + (size_t)(m0 + r) * D + col) = o;
-            }
+        if (!g2) ln_rows4_store<float, 1>(x, m0, M, D, lane, xv);
+        ln_affine_load<1>(ga, g1, nchunk, lane);
+        ln_affine_load<1>(be, b1, nchunk, lane);
+        ln_rows4<1>(xv, s, ga, be, lane, nnorm, inv_d, 1e-5f);
+        if (g2) {
+            ln_rows4_store<float, 1>(x, m0, M, D, lane, xv);
+            ln_affine_load<1>(ga, g2, nchunk, lane);
+            ln_affine_load<1>(be, b2, nchunk, lane);
+            ln_rows4<1>(xv, s, ga, be, lane, nnorm, inv_d, 1e-5f);
         }
-    }
-    // rows m0 .. m0+3 (row r valid if m0 + r < M); staged row r at `staged + r * rs_floats`; xr = rows4_load(m0, M, lane)
-    __device__ __forceinline__ void rows4(int m0, int M, const float *staged, int rs_floats, int lane, const Rows4 &xr) const {
-        const int nchunk = D >> 2, nnorm = (Dn > 0 ? Dn : D) >> 2;
-        const float inv_d = 1.0f / (float)(Dn > 0 ? Dn : D);
-        f32x4 xv[4][NV];
-        float s[4];
-#pragma unroll
-        for (int r = 0; r < 4; ++r) {
-            s[r] = 0.f;
-#pragma unroll
-            for (int v = 0; v < NV; ++v) {
-                const int c = lane + 64 * v;
-                const int cc = min(c, nchunk - 1);
-                f32x4 t = *reinterpret_cast<const f32x4 *>(staged + r * rs_floats + 4 * cc);
-                if (has_resid) t += xr.v[r][v];
-                if (c >= nchunk) t = (f32x4){0, 0, 0, 0};
-                xv[r][v] = t;
-                s[r] += t[0] + t[1] + t[2] + t[3];
-            }
-        }
-        auto write_x = [&]() {
-#pragma unroll
-            for (int r = 0; r < 4; ++r)
-#pragma unroll
-                for (int v = 0; v < NV; ++v) {
-                    const int c = lane + 64 * v;
-                    if (m0 + r < M && c < nchunk) *reinterpret_cast<f32x4 *>(x + (size_t)(m0 + r) * D + 4 * c) = xv[r][v];
-                }
-        };
-        auto normalise = [&](const float *gam, const float *bet) {
-            float mean[4], q[4];
-#pragma unroll
-            for (int r = 0; r < 4; ++r) mean[r] = wave_sum(s[r]) * inv_d;
-#pragma unroll
-            for (int r = 0; r < 4; ++r) {
-                q[r] = 0.f;
-#pragma unroll
-                for (int v = 0; v < NV; ++v) {
-                    const bool ok = lane + 64 * v < nnorm;
-#pragma unroll
-                    for (int e = 0; e < 4; ++e) { const float d = ok ? xv[r][v][e] - mean[r] : 0.f; q[r] += d * d; }
-                }
-            }
-            float rstd[4];
-#pragma unroll
-            for (int r = 0; r < 4; ++r) rstd[r] = 1.0f / sqrtf(wave_sum(q[r]) * inv_d + 1e-5f);
-#pragma unroll
-            for (int v = 0; v < NV; ++v) {
-                const int c = lane + 64 * v;
-                const bool ok = c < nchunk;
-                const f32x4 ga = ok ? *reinterpret_cast<const f32x4 *>(gam + 4 * c) : (f32x4){0, 0, 0, 0};
-                const f32x4 be = ok ? *reinterpret_cast<const f32x4 *>(bet + 4 * c) : (f32x4){0, 0, 0, 0};
-#pragma unroll
-                for (int r = 0; r < 4; ++r)
-#pragma unroll
-                    for (int e = 0; e < 4; ++e) xv[r][v][e] = (xv[r][v][e] - mean[r]) * rstd[r] * ga[e] + be[e];
-            }
-#pragma unroll
-            for (int r = 0; r < 4; ++r) {
-                s[r] = 0.f;
-#pragma unroll
-                for (int v = 0; v < NV; ++v) s[r] += xv[r][v][0] + xv[r][v][1] + xv[r][v][2] + xv[r][v][3];
-            }
-        };
-        if (!g2) write_x();
-        normalise(g1, b1);
-        if (g2) { write_x(); normalise(g2, b2); }
-#pragma unroll
-        for (int r = 0; r < 4; ++r)
-#pragma unroll
-            for (int v = 0; v < NV; ++v) {
-                const int c = lane + 64 * v;
-                if (m0 + r < M && c < nchunk) {
-                    T *p = xn + (size_t)(m0 + r) * D + 4 * c;
-                    if constexpr (sizeof(T) == 2) { bf16x4 o = {(T)xv[r][v][0], (T)xv[r][v][1], (T)xv[r][v][2], (T)xv[r][v][3]}; *reinterpret_cast<bf16x4 *>(p) = o; }
-                    else { *reinterpret_cast<f32x4 *>(p) = xv[r][v]; }
-                }
-            }
+        ln_rows4_store<T, 1>(xn, m0, M, D, lane, xv);
     }
 };
 
@@ -392,6 +275,27 @@ template <> __device__ __forceinline__ void stage4<float>(float *dst, const floa
 template <> __device__ __forceinline__ void stage4<bf16_t>(bf16_t *dst, const float *r) {
     bf16x4 o = {(bf16_t)r[0], (bf16_t)r[1], (bf16_t)r[2], (bf16_t)r[3]};
     *reinterpret_cast<bf16x4 *>(dst) = o;
+}
+
+// A wave's MI x NI accumulator tiles (16 x 16 each; rows from `row0`, columns from `col0` of the workgroup's tile, whose first column is
+// column n0 of the product) through epi.transform into the staged tile: rows of RS bytes at smem.  For the 1 x 4 and 1 x 8 wave layouts of
+// gemm_rowln48_kernel and ffn_fused_kernel; gemm_epilogue keeps a copy of these loops (there is why)
+template <int MI, int NI, int RS, typename Epi>
+__device__ __forceinline__ void stage_acc(const f32x4 (&acc)[MI][NI], unsigned char *smem, int row0, int col0, int n0, const Epi &epi) {
+    typedef typename Epi::stage_t S;
+    const int r16 = threadIdx.x & 15, g = (threadIdx.x & 63) >> 4;
+#pragma unroll
+    for (int i = 0; i < MI; ++i) {
+        const int row = row0 + 16 * i + r16;
+#pragma unroll
+        for (int j = 0; j < NI; ++j) {
+            const int nl = col0 + 16 * j + 4 * g;
+            const float v[4] = {acc[i][j][0], acc[i][j][1], acc[i][j][2], acc[i][j][3]};
+            float r[4];
+            epi.transform(n0 + nl, v, r);
+            stage4<S>(reinterpret_cast<S *>(smem + row * RS) + nl, r);
+        }
+    }
 }
 
 // bytes of LDS the staged epilogue needs
@@ -423,7 +327,7 @@ __device__ __forceinline__ void gemm_epilogue(f32x4 (&acc)[MI][NI], unsigned cha
                 if (n0 + nl + 19 < N) epi.transform(n0 + nl, v, w, r);
                 stage4<S>(reinterpret_cast<S *>(smem + row * RS) + ((nl >> 5) << 4) + (nl & 15), r);
             }
-        } else {
+        } else {      // a copy of stage_acc's loops: through the function the fp32 64 x 64 stream kernels take 81 VGPRs for 80 and lose a wave per SIMD (6 -> 5)
 #pragma unroll
             for (int j = 0; j < NI; ++j) {
                 const int nl = wn * (BN / 2) + 16 * j + 4 * g;
@@ -463,6 +367,7 @@ template <typename T> struct GemmArgs {
     long long a_zb = 0, a_zh = 0, w_zb = 0, w_zh = 0, o_zb = 0, o_zh = 0;
 };
 
+// ---- pieces of the LDS-DMA ring -----------------------------------------------------------------------------------
 __device__ __forceinline__ bf16x8 lds_frag_swz(const unsigned char *row, int kc, int g, int swz, bf16_t) {
     return *reinterpret_cast<const bf16x8 *>(row + (((kc * 4 + g) ^ swz) << 4));
 }
@@ -473,6 +378,56 @@ __device__ __forceinline__ f32x8 lds_frag_swz(const unsigned char *row, int kc, 
 }
 template <int N> __device__ __forceinline__ void wait_vmcnt() { asm volatile("s_waitcnt vmcnt(%0)" ::"n"(N) : "memory"); }
 
+// The counted wait of an NST-deep ring whose k-tile is PER DMA wave-instructions per wave, before the barrier of k-tile kt of nk: tile kt
+// must have landed, only the tiles issued after it (at most NST - 2: the depth cuts the cases off at compile time) may still be in flight.
+template <int NST, int PER> __device__ __forceinline__ void ring_wait(int kt, int nk) {
+    static_assert(NST >= 2 && NST <= 4, "ring depth");
+    const int after = min(nk, kt + NST - 1) - (kt + 1);
+    if (NST > 3 && after >= 2) wait_vmcnt<2 * PER>(); else if (NST > 2 && after == 1) wait_vmcnt<PER>(); else wait_vmcnt<0>();
+}
+
+// One operand's tile of a ring stage: ROWS rows of 128 bytes (one k-tile), a wave's DMA instruction i = 8 rows = the 1 KiB piece wave + 4 i
+// of the image.  The per-lane byte offsets are loop-invariant (row clamp + swizzled chunk); a k-tile only moves the UNIFORM base by 128
+// bytes, so an issue costs no vector arithmetic (it was ~60 VALU instructions per k-tile beside 32 MFMAs).
+// 32-bit offsets: the launchers check (rows - 1) * ld * sizeof(T) + 128 < 4 GiB (ring_off32).  The tiles of gemm_rowln48_kernel;
+// gemm_ring_kernel keeps a copy of this in its own text (there is why).
+template <int ROWS> struct RingTile {
+    unsigned off[ROWS / 32];
+    // rows row0 .. row0 + ROWS - 1 of an operand of `nrows` rows, `ldb` bytes apart (rows beyond the last: clamped to it)
+    __device__ __forceinline__ void init(int row0, int nrows, unsigned ldb, int wave, int lane) {
+        const int lrow = lane >> 3, cpos = lane & 7;
+#pragma unroll
+        for (int i = 0; i < ROWS / 32; ++i) {
+            const int row = (wave + 4 * i) * 8 + lrow;
+            off[i] = (unsigned)min(row0 + row, nrows - 1) * ldb + ((cpos ^ (row & 7)) << 4);
+        }
+    }
+    // base: the operand's first row at this k-tile (uniform)
+    __device__ __forceinline__ void issue(const char *base, unsigned char *tile, int wave) const {
+#pragma unroll
+        for (int i = 0; i < ROWS / 32; ++i)
+            __builtin_amdgcn_global_load_lds((gbl_ptr_t)(base + off[i]), (lds_ptr_t)(tile + (wave + 4 * i) * 1024), 16, 0, 0);
+    }
+};
+
+// One k-tile of a wave's MI x NI output tiles from the swizzled images: sa / sw = the lane's row (r16) of the wave's first A / W tile
+template <typename T, int MI, int NI>
+__device__ __forceinline__ void ring_mma(f32x4 (&acc)[MI][NI], const unsigned char *sa, const unsigned char *sw, int g, int swz) {
+    constexpr int ROWB = 128, BK = ROWB / sizeof(T);
+#pragma unroll
+    for (int kc = 0; kc < BK / 32; ++kc) {
+        typename FragOf<T>::type a[MI], b[NI];
+#pragma unroll
+        for (int i = 0; i < MI; ++i) a[i] = lds_frag_swz(sa + i * 16 * ROWB, kc, g, swz, T());
+#pragma unroll
+        for (int j = 0; j < NI; ++j) b[j] = lds_frag_swz(sw + j * 16 * ROWB, kc, g, swz, T());
+#pragma unroll
+        for (int i = 0; i < MI; ++i)
+#pragma unroll
+            for (int j = 0; j < NI; ++j) acc[i][j] = mma16(b[j], a[i], acc[i][j]);   // swapped: rows = n, columns = m
+    }
+}
+
 // ---- LDS-DMA ring kernel (K % BK == 0) --------------------------------------------------------------------
 template <typename T, int BM, int BN, int NST, typename Epi>
 __global__ __launch_bounds__(256) void gemm_ring_kernel(GemmArgs<T> p, Epi epi) {
@@ -481,7 +436,7 @@ __global__ __launch_bounds__(256) void gemm_ring_kernel(GemmArgs<T> p, Epi epi) 
     constexpr int MI = BM / 32, NI = BN / 32;
     constexpr int PER = BM / 32 + BN / 32;                 // DMA wave-instructions per wave per k-tile
     constexpr int STAGE = (BM + BN) * ROWB;
-    static_assert(NST >= 2 && NST <= 4 && BM % 32 == 0 && BN % 64 == 0, "config");
+    static_assert(BM % 32 == 0 && BN % 64 == 0, "config");
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
     const int M = p.M, N = p.N, K = p.K;
     const int tid = threadIdx.x, lane = tid & 63;
@@ -500,10 +455,8 @@ __global__ __launch_bounds__(256) void gemm_ring_kernel(GemmArgs<T> p, Epi epi) 
         p.W += zb * p.w_zb + zh * p.w_zh;
         out_off = zb * p.o_zb + zh * p.o_zh;
     }
-
-    // Per-lane byte offsets of this thread's DMA pieces are loop-invariant (row clamp + swizzled chunk); a k-tile only moves the
-    // UNIFORM base by 128 bytes, so an issue costs no vector arithmetic (it was ~60 VALU instructions per k-tile beside 32 MFMAs).
-    // 32-bit offsets: the launchers check (rows - 1) * ld * sizeof(T) + 128 < 4 GiB.
+    // The A and W tiles as RingTile holds and issues them, in this kernel's own text: through the struct the prologue compiles to other
+    // code, and the 128 x 128 q/k/v product of the wide model measured 2 % slower
     unsigned offA[BM / 32], offW[BN / 32];
     {
         const int lrow = lane >> 3, cpos = lane & 7;
@@ -540,26 +493,11 @@ __global__ __launch_bounds__(256) void gemm_ring_kernel(GemmArgs<T> p, Epi epi) 
         for (int j = 0; j < NI; ++j) acc[i][j] = (f32x4){0.f, 0.f, 0.f, 0.f};
 
     for (int kt = 0; kt < nk; ++kt) {
-        // tile kt must have landed: only tiles issued after it may still be in flight
-        const int after = min(nk, kt + NST - 1) - (kt + 1);
-        if (after >= 2) wait_vmcnt<2 * PER>(); else if (after == 1) wait_vmcnt<PER>(); else wait_vmcnt<0>();
+        ring_wait<NST, PER>(kt, nk);
         __builtin_amdgcn_s_barrier();
         if (kt + NST - 1 < nk) issue(kt + NST - 1);       // refills the slot every wave finished reading before this barrier
         const unsigned char *st = smem + (kt % NST) * STAGE;
-        const unsigned char *sa = st + (wm * (BM / 2) + r16) * ROWB;
-        const unsigned char *sw = st + BM * ROWB + (wn * (BN / 2) + r16) * ROWB;
-#pragma unroll
-        for (int kc = 0; kc < BK / 32; ++kc) {
-            typename FragOf<T>::type a[MI], b[NI];
-#pragma unroll
-            for (int i = 0; i < MI; ++i) a[i] = lds_frag_swz(sa + i * 16 * ROWB, kc, g, swz, T());
-#pragma unroll
-            for (int j = 0; j < NI; ++j) b[j] = lds_frag_swz(sw + j * 16 * ROWB, kc, g, swz, T());
-#pragma unroll
-            for (int i = 0; i < MI; ++i)
-#pragma unroll
-                for (int j = 0; j < NI; ++j) acc[i][j] = mma16(b[j], a[i], acc[i][j]);   // swapped: rows = n, columns = m
-        }
+        ring_mma<T, MI, NI>(acc, st + (wm * (BM / 2) + r16) * ROWB, st + BM * ROWB + (wn * (BN / 2) + r16) * ROWB, g, swz);
     }
     __syncthreads();                                     // every wave is done reading the ring: reuse it for the staged tile
     if constexpr (std::is_same<Epi, EpiStoreF32>::value) {
@@ -571,7 +509,7 @@ __global__ __launch_bounds__(256) void gemm_ring_kernel(GemmArgs<T> p, Epi epi) 
     }
 }
 
-// ---- both operands K-MAJOR (round 4; the weight-gradient product of a training step: dW = dY^T X with dY (rows, N_out) and X (rows, K_in)
+// ---- both operands K-MAJOR (the weight-gradient product of a training step: dW = dY^T X with dY (rows, N_out) and X (rows, K_in)
 // as the forward left them) ---------------------------------------------------------------------------------------------------------------
 //     out (M, N) = sum_k A[k][m] B[k][n]        A: (K, M) row-major, lda;  B: (K, N) row-major, ldb;  bf16, fp32 accumulation
 // No transposed copies: a k-tile of 32 rows x 128 columns of each operand goes to LDS as it lies in memory (LDS-DMA, 256-byte rows, the
@@ -639,8 +577,7 @@ __global__ __launch_bounds__(256) void gemm_tn_kernel(GemmArgs<bf16_t> p, EpiSto
         return (bf16x8){lo[0], lo[1], lo[2], lo[3], hi[0], hi[1], hi[2], hi[3]};
     };
     for (int kt = 0; kt < nk; ++kt) {
-        const int after = min(nk, kt + NST - 1) - (kt + 1);
-        if (after >= 2) wait_vmcnt<2 * (PA + PB)>(); else if (after == 1) wait_vmcnt<PA + PB>(); else wait_vmcnt<0>();
+        ring_wait<NST, PA + PB>(kt, nk);
         __builtin_amdgcn_s_barrier();
         if (kt + NST - 1 < nk) issue(kt + NST - 1);
         const unsigned char *sa = smem + (kt % NST) * STAGE, *sb = sa + BK * AROW;
@@ -743,23 +680,21 @@ __global__ __launch_bounds__(256) void gemm_stream_kernel(GemmArgs<T> p, Epi epi
 }
 
 // ---- host side ---------------------------------------------------------------------------------------
+// The DMA kernels address an operand's rows with 32-bit byte offsets from a uniform base: `rows` rows of `ld` elements must stay below 4 GiB
+static inline bool ring_off32(size_t rows, size_t ld, size_t esize) { return rows * ld * esize < ((size_t)1 << 32) - 256; }
+template <typename T> static inline bool ring_off32(const GemmArgs<T> &a) { return ring_off32(a.M, a.lda, sizeof(T)) && ring_off32(a.N, a.ldw, sizeof(T)); }
+
+// gy: grid.y = splits (GemmArgs::k_zstride) or batches (GemmArgs::z_div)
 template <typename T, int BM, int BN, int NST, typename Epi>
-static inline hipError_t launch_ring_cfg(hipStream_t s, const GemmArgs<T> &a, const Epi &epi) {
+static inline hipError_t launch_ring_cfg(hipStream_t s, const GemmArgs<T> &a, const Epi &epi, int gy = 1) {
+    if (!ring_off32(a)) return hipErrorInvalidValue;
     const size_t lds = std::max((size_t)NST * (BM + BN) * 128, epi_lds_bytes<Epi, BM, BN>());
-    auto kern = gemm_ring_kernel<T, BM, BN, NST, Epi>;
-    hipError_t e = raise_lds_limit((const void *)kern, lds);
-    if (e != hipSuccess) return e;
-    hipLaunchKernelGGL(kern, dim3(ceil_div(a.N, BN) * ceil_div(a.M, BM)), dim3(256), lds, s, a, epi);
-    return hipGetLastError();
+    return launch_lds(gemm_ring_kernel<T, BM, BN, NST, Epi>, dim3(ceil_div(a.N, BN) * ceil_div(a.M, BM), gy), dim3(256), lds, s, a, epi);
 }
 template <typename T, int BM, int BN, typename Epi>
 static inline hipError_t launch_stream_cfg(hipStream_t s, const GemmArgs<T> &a, const Epi &epi) {
     const size_t lds = std::max((size_t)2 * (BM + BN) * 144, epi_lds_bytes<Epi, BM, BN>());
-    auto kern = gemm_stream_kernel<T, BM, BN, Epi>;
-    hipError_t e = raise_lds_limit((const void *)kern, lds);
-    if (e != hipSuccess) return e;
-    hipLaunchKernelGGL(kern, dim3(ceil_div(a.N, BN) * ceil_div(a.M, BM)), dim3(256), lds, s, a, epi);
-    return hipGetLastError();
+    return launch_lds(gemm_stream_kernel<T, BM, BN, Epi>, dim3(ceil_div(a.N, BN) * ceil_div(a.M, BM)), dim3(256), lds, s, a, epi);
 }
 
 // Requirements (checked at model build): K % (16/sizeof(T)) == 0, lda/ldw multiples of 16 bytes, 16-byte aligned bases.
@@ -768,9 +703,7 @@ static inline hipError_t launch_gemm(hipStream_t s, const T *A, int lda, const T
     GemmArgs<T> a{A, lda, W, ldw, M, N, K, 0};
     constexpr int BK = 128 / (int)sizeof(T);
     const long t128 = (long)ceil_div(M, 128) * ceil_div(N, 128);
-    // the ring kernel addresses its operand rows with 32-bit byte offsets from a uniform base
-    const bool off32 = (size_t)M * lda * sizeof(T) < ((size_t)1 << 32) - 256 && (size_t)N * ldw * sizeof(T) < ((size_t)1 << 32) - 256;
-    if (K % BK == 0 && off32) {
+    if (K % BK == 0 && ring_off32(a)) {
         if (t128 >= 1024) return launch_ring_cfg<T, 128, 128, 2, Epi>(s, a, epi);
         if (N >= 512) return launch_ring_cfg<T, 64, 128, 3, Epi>(s, a, epi);
         return launch_ring_cfg<T, 64, 64, 3, Epi>(s, a, epi);
@@ -784,11 +717,11 @@ static inline hipError_t launch_gemm(hipStream_t s, const T *A, int lda, const T
 // 37.5 rows per CU: 48-row workgroups give 200 workgroups = ONE wave of workgroups at one per CU (64-row ones leave 106
 // CUs idle, 32-row ones need two rounds).  4 waves side by side (1 x 4): each wave owns all 48 rows x 64 columns
 // (3 x 4 MFMA tiles: 12 MFMAs per 7 fragment reads).  The A tile is DMA'd as 64 rows (rows >= 48 are never read), the
-// ring is 3 deep (one workgroup per CU: the ring is the latency hiding).
+// ring is 3 deep (one workgroup per CU: the ring is the latency hiding).  Built from gemm_ring_kernel's pieces.
 template <typename T, typename Epi>
 __global__ __launch_bounds__(256) void gemm_rowln48_kernel(GemmArgs<T> p, Epi epi) {
     constexpr int BMC = 48, BMD = 64, BN = 256, NST = 3;
-    constexpr int ROWB = 128, BK = ROWB / sizeof(T), EPC = 16 / sizeof(T);
+    constexpr int ROWB = 128, BK = ROWB / sizeof(T);
     constexpr int MI = 3, NI = 4;
     constexpr int PER = BMD / 32 + BN / 32;
     constexpr int STAGE = (BMD + BN) * ROWB;
@@ -799,65 +732,37 @@ __global__ __launch_bounds__(256) void gemm_rowln48_kernel(GemmArgs<T> p, Epi ep
     const int r16 = lane & 15, g = lane >> 4, swz = r16 & 7;
     const int m0 = blockIdx.x * BMC;
     const int nk = K / BK;
+    RingTile<BMD> ta;
+    RingTile<BN> tw;
+    ta.init(m0, M, (unsigned)(p.lda * (int)sizeof(T)), wave, lane);
+    tw.init(0, N, (unsigned)(p.ldw * (int)sizeof(T)), wave, lane);
     auto issue = [&](int kt) {
         unsigned char *st = smem + (kt % NST) * STAGE;
-        const int k0 = kt * BK, lrow = lane >> 3, cpos = lane & 7;
-#pragma unroll
-        for (int i = 0; i < BMD / 32; ++i) {
-            const int rg = wave + 4 * i, row = rg * 8 + lrow;
-            const T *src = p.A + (size_t)min(m0 + row, M - 1) * p.lda + k0 + ((cpos ^ (row & 7)) * EPC);
-            __builtin_amdgcn_global_load_lds((gbl_ptr_t)src, (lds_ptr_t)(st + rg * 1024), 16, 0, 0);
-        }
-#pragma unroll
-        for (int i = 0; i < BN / 32; ++i) {
-            const int rg = wave + 4 * i, row = rg * 8 + lrow;
-            const T *src = p.W + (size_t)min(row, N - 1) * p.ldw + k0 + ((cpos ^ (row & 7)) * EPC);
-            __builtin_amdgcn_global_load_lds((gbl_ptr_t)src, (lds_ptr_t)(st + BMD * ROWB + rg * 1024), 16, 0, 0);
-        }
+        ta.issue(reinterpret_cast<const char *>(p.A) + (size_t)kt * ROWB, st, wave);
+        tw.issue(reinterpret_cast<const char *>(p.W) + (size_t)kt * ROWB, st + BMD * ROWB, wave);
     };
     // residual rows of this wave's share of the LayerNorm epilogue: requested first, consumed last
     typename Epi::Rows4 xr[BMC / 16];
 #pragma unroll
     for (int it = 0; it < BMC / 16; ++it) xr[it] = epi.rows4_load(m0 + wave * 4 + 16 * it, min(M, m0 + BMC), lane);
-    issue(0);
-    if (nk > 1) issue(1);
+#pragma unroll
+    for (int t = 0; t < NST - 1; ++t)
+        if (t < nk) issue(t);
     f32x4 acc[MI][NI];
 #pragma unroll
     for (int i = 0; i < MI; ++i)
 #pragma unroll
         for (int j = 0; j < NI; ++j) acc[i][j] = (f32x4){0.f, 0.f, 0.f, 0.f};
     for (int kt = 0; kt < nk; ++kt) {
-        if (kt + 1 < nk) wait_vmcnt<PER>(); else wait_vmcnt<0>();      // at this point tiles 0 .. kt+1 have been issued
+        ring_wait<NST, PER>(kt, nk);
         __builtin_amdgcn_s_barrier();
-        if (kt + 2 < nk) issue(kt + 2);
+        if (kt + NST - 1 < nk) issue(kt + NST - 1);
         const unsigned char *st = smem + (kt % NST) * STAGE;
-        const unsigned char *sa = st + r16 * ROWB;
-        const unsigned char *sw = st + BMD * ROWB + (wave * 64 + r16) * ROWB;
-#pragma unroll
-        for (int kc = 0; kc < BK / 32; ++kc) {
-            typename FragOf<T>::type a[MI], b[NI];
-#pragma unroll
-            for (int i = 0; i < MI; ++i) a[i] = lds_frag_swz(sa + i * 16 * ROWB, kc, g, swz, T());
-#pragma unroll
-            for (int j = 0; j < NI; ++j) b[j] = lds_frag_swz(sw + j * 16 * ROWB, kc, g, swz, T());
-#pragma unroll
-            for (int i = 0; i < MI; ++i)
-#pragma unroll
-                for (int j = 0; j < NI; ++j) acc[i][j] = mma16(b[j], a[i], acc[i][j]);
-        }
+        ring_mma<T, MI, NI>(acc, st + r16 * ROWB, st + BMD * ROWB + (wave * 64 + r16) * ROWB, g, swz);
     }
     __syncthreads();
     constexpr int RS = BN * 4 + 16;
-#pragma unroll
-    for (int i = 0; i < MI; ++i)
-#pragma unroll
-        for (int j = 0; j < NI; ++j) {
-            const int row = 16 * i + r16, n = wave * 64 + 16 * j + 4 * g;
-            const float v[4] = {acc[i][j][0], acc[i][j][1], acc[i][j][2], acc[i][j][3]};
-            float r[4];
-            epi.transform(n, v, r);
-            *reinterpret_cast<f32x4 *>(smem + row * RS + n * 4) = (f32x4){r[0], r[1], r[2], r[3]};
-        }
+    stage_acc<MI, NI, RS>(acc, smem, 0, wave * 64, 0, epi);
     __syncthreads();
 #pragma unroll
     for (int it = 0; it < BMC / 16; ++it) {
@@ -872,67 +777,41 @@ template <typename T, typename Epi>
 static inline hipError_t launch_gemm_rowln(hipStream_t s, const T *A, int lda, const T *W, int ldw, int M, int N, int K, const Epi &epi) {
     GemmArgs<T> a{A, lda, W, ldw, M, N, K, 0};
     constexpr int BK = 128 / (int)sizeof(T);
-    if (K % BK == 0) {
+    if (K % BK == 0 && ring_off32(a)) {
         const size_t lds = (size_t)3 * (64 + 256) * 128;          // >= the 48 x (256*4+16) staged tile
-        auto kern = gemm_rowln48_kernel<T, Epi>;
-        hipError_t e = raise_lds_limit((const void *)kern, lds);
-        if (e != hipSuccess) return e;
-        hipLaunchKernelGGL(kern, dim3(ceil_div(M, 48)), dim3(256), lds, s, a, epi);
-        return hipGetLastError();
+        return launch_lds(gemm_rowln48_kernel<T, Epi>, dim3(ceil_div(M, 48)), dim3(256), lds, s, a, epi);
     }
     return launch_stream_cfg<T, 32, 256, Epi>(s, a, epi);
 }
 
-// Split-K product for the frontend output linear (M x 256 x 6144): `splits` partial sums [z][M][N] fp32 (no bias), summed by
-// splitk_reduce_ln_kernel.  One launch, grid.y = splits; 128 x 128 tiles.
-#ifndef COCR_FO_BM
-#define COCR_FO_BM 128
-#define COCR_FO_BN 128
-#define COCR_FO_NST 2
-#endif
 // Batched exact-fp32 products (GemmArgs::z_div): out_z (M x N, row stride ldo) = A_z (M x K) W_z (N x K)^T, K % 32 == 0, 64 x 64 tiles.
 static inline hipError_t launch_gemm_batched_f32(hipStream_t s, GemmArgs<float> a, float *out, int ldo, int batches) {
-    constexpr int BM = 64, BN = 64, NST = 3;
     if (a.K % 32 || a.z_div < 1 || batches < 1) return hipErrorInvalidValue;
     EpiStoreF32 e{out, ldo, nullptr, a.N};
-    const size_t lds = std::max((size_t)NST * (BM + BN) * 128, epi_lds_bytes<EpiStoreF32, BM, BN>());
-    auto kern = gemm_ring_kernel<float, BM, BN, NST, EpiStoreF32>;
-    hipError_t err = raise_lds_limit((const void *)kern, lds);
-    if (err != hipSuccess) return err;
-    hipLaunchKernelGGL(kern, dim3(ceil_div(a.N, BN) * ceil_div(a.M, BM), batches), dim3(256), lds, s, a, e);
-    return hipGetLastError();
+    return launch_ring_cfg<float, 64, 64, 3, EpiStoreF32>(s, a, e, batches);
 }
 
+// Split-K product for the frontend output linear (M x 256 x 6144) and the training step's weight gradients: `splits` partial sums
+// [z][M][N] fp32 (no bias), summed by the caller (splitk_reduce_ln_kernel).  One launch, grid.y = splits; 128 x 128 tiles, a ring of 2.
+constexpr int SPLITK_BM = 128, SPLITK_BN = 128, SPLITK_NST = 2;
 template <typename T>
 static inline hipError_t launch_gemm_splitk(hipStream_t s, const T *A, int lda, const T *W, int ldw, int M, int N, int K, int splits, float *partial) {
     constexpr int BK = 128 / (int)sizeof(T);
-    constexpr int BM = COCR_FO_BM, BN = COCR_FO_BN, NST = COCR_FO_NST;
     if (K % (splits * BK)) return hipErrorInvalidValue;
-    if ((size_t)M * lda * sizeof(T) >= ((size_t)1 << 32) - 256 || (size_t)N * ldw * sizeof(T) >= ((size_t)1 << 32) - 256) return hipErrorInvalidValue;
     GemmArgs<T> a{A, lda, W, ldw, M, N, K / splits, K / splits};
     EpiStoreF32 e{partial, N, nullptr, N};
     e.zstride = (size_t)M * N;
-    const size_t lds = std::max((size_t)NST * (BM + BN) * 128, epi_lds_bytes<EpiStoreF32, BM, BN>());
-    auto kern = gemm_ring_kernel<T, BM, BN, NST, EpiStoreF32>;
-    hipError_t err = raise_lds_limit((const void *)kern, lds);
-    if (err != hipSuccess) return err;
-    hipLaunchKernelGGL(kern, dim3(ceil_div(N, BN) * ceil_div(M, BM), splits), dim3(256), lds, s, a, e);
-    return hipGetLastError();
+    return launch_ring_cfg<T, SPLITK_BM, SPLITK_BN, SPLITK_NST, EpiStoreF32>(s, a, e, splits);
 }
 
 // out (M, N) (or `splits` partial sums at partial + z M N, to be added by the caller) = A^T B for K-major A (K, M) and B (K, N)
 static inline hipError_t launch_gemm_tn(hipStream_t s, const bf16_t *A, int lda, const bf16_t *B, int ldb, int M, int N, int K, int splits, float *out) {
     constexpr int BM = 128, BN = 128, NST = 4;
     if (splits < 1 || K % (splits * 32) || M % 8 || N % 8 || lda % 8 || ldb % 8) return hipErrorInvalidValue;
-    if ((size_t)K * lda * 2 >= ((size_t)1 << 32) - 256 || (size_t)K * ldb * 2 >= ((size_t)1 << 32) - 256) return hipErrorInvalidValue;      // (32-bit row offsets inside a split)
+    if (!ring_off32(K, lda, 2) || !ring_off32(K, ldb, 2)) return hipErrorInvalidValue;      // (the k rows of a split, at most)
     GemmArgs<bf16_t> a{A, lda, B, ldb, M, N, K / splits, splits > 1 ? K / splits : 0};
     EpiStoreF32 e{out, N, nullptr, N};
     e.zstride = (size_t)M * N;
     const size_t lds = std::max((size_t)NST * 32 * (BM + BN) * 2, epi_lds_bytes<EpiStoreF32, BM, BN>());
-    auto kern = gemm_tn_kernel<BM, BN, NST>;
-    hipError_t err = raise_lds_limit((const void *)kern, lds);
-    if (err != hipSuccess) return err;
-    hipLaunchKernelGGL(kern, dim3(ceil_div(N, BN) * ceil_div(M, BM), splits), dim3(256), lds, s, a, e);
-    return hipGetLastError();
+    return launch_lds(gemm_tn_kernel<BM, BN, NST>, dim3(ceil_div(N, BN) * ceil_div(M, BM), splits), dim3(256), lds, s, a, e);
 }
-

@@ -11,6 +11,63 @@
 #pragma once
 #include "common.hip.h"
 
+// ---- the row pass every LayerNorm of the dense-product path shares (layernorm_kernel and splitk_reduce_ln_kernel below, EpiResidualLN
+// in gemm.hip.h): each keeps only its own row source
+// gamma or beta of the lane's chunks; zero beyond the row width D = 4 nchunk, so those chunks come out of the affine step as zeros
+template <int NV> __device__ __forceinline__ void ln_affine_load(f32x4 (&a)[NV], const float *p, int nchunk, int lane) {
+#pragma unroll
+    for (int v = 0; v < NV; ++v) {
+        const int c = lane + 64 * v;
+        a[v] = c < nchunk ? *reinterpret_cast<const f32x4 *>(p + 4 * c) : (f32x4){0, 0, 0, 0};
+    }
+}
+// xv <- LayerNorm(xv) for the wave's 4 rows; s[r]: the lane's share of row r's sum on entry, of the new row's on return (a second
+// LayerNorm can follow).  The rows are nnorm chunks wide for the statistics (inv_d = 1 / (4 nnorm)): the chunks from nnorm on hold exact
+// zeros (zero padding), so the sums need no mask, the centred squares do.
+template <int NV>
+__device__ __forceinline__ void ln_rows4(f32x4 (&xv)[4][NV], float (&s)[4], const f32x4 (&gam)[NV], const f32x4 (&bet)[NV], int lane, int nnorm, float inv_d,
+                                         float eps) {
+    float mean[4], q[4];
+#pragma unroll
+    for (int r = 0; r < 4; ++r) mean[r] = wave_sum(s[r]) * inv_d;
+#pragma unroll
+    for (int r = 0; r < 4; ++r) {
+        q[r] = 0.f;
+#pragma unroll
+        for (int v = 0; v < NV; ++v) {
+            const bool ok = lane + 64 * v < nnorm;
+#pragma unroll
+            for (int e = 0; e < 4; ++e) { const float d = ok ? xv[r][v][e] - mean[r] : 0.f; q[r] += d * d; }
+        }
+    }
+#pragma unroll
+    for (int r = 0; r < 4; ++r) {
+        const float rstd = 1.0f / sqrtf(wave_sum(q[r]) * inv_d + eps);
+        s[r] = 0.f;
+#pragma unroll
+        for (int v = 0; v < NV; ++v)
+#pragma unroll
+            for (int e = 0; e < 4; ++e) {
+                xv[r][v][e] = (xv[r][v][e] - mean[r]) * rstd * gam[v][e] + bet[v][e];
+                s[r] += xv[r][v][e];
+            }
+    }
+}
+// rows m0 .. m0+3 (those below M) of the wave's chunks -> out (M, D) as T
+template <typename T, int NV> __device__ __forceinline__ void ln_rows4_store(T *out, int m0, int M, int D, int lane, const f32x4 (&xv)[4][NV]) {
+#pragma unroll
+    for (int r = 0; r < 4; ++r)
+#pragma unroll
+        for (int v = 0; v < NV; ++v) {
+            const int c = lane + 64 * v;
+            if (m0 + r < M && c < (D >> 2)) {
+                T *p = out + (size_t)(m0 + r) * D + 4 * c;
+                if constexpr (sizeof(T) == 2) { bf16x4 o = {(T)xv[r][v][0], (T)xv[r][v][1], (T)xv[r][v][2], (T)xv[r][v][3]}; *reinterpret_cast<bf16x4 *>(p) = o; }
+                else { *reinterpret_cast<f32x4 *>(p) = xv[r][v]; }
+            }
+        }
+}
+
 template <typename T, int NV>
 __global__ __launch_bounds__(256) void layernorm_kernel(const float *x, int M, int D, int Dn, float eps,      // Dn: LayerNorm width (columns [Dn, D): zero padding)
                                                         const float *__restrict__ g1, const float *__restrict__ b1,
@@ -24,16 +81,11 @@ __global__ __launch_bounds__(256) void layernorm_kernel(const float *x, int M, i
     const float inv_d = 1.0f / (float)Dn;
     const int nchunk = D >> 2, nnorm = Dn >> 2;
     f32x4 ga[NV], ba[NV], gb[NV], bb[NV];
-#pragma unroll
-    for (int v = 0; v < NV; ++v) {
-        const int c = lane + 64 * v;
-        const bool ok = c < nchunk;
-        ga[v] = ok ? *reinterpret_cast<const f32x4 *>(g1 + 4 * c) : (f32x4){0, 0, 0, 0};
-        ba[v] = ok ? *reinterpret_cast<const f32x4 *>(b1 + 4 * c) : (f32x4){0, 0, 0, 0};
-        if (g2) {
-            gb[v] = ok ? *reinterpret_cast<const f32x4 *>(g2 + 4 * c) : (f32x4){0, 0, 0, 0};
-            bb[v] = ok ? *reinterpret_cast<const f32x4 *>(b2 + 4 * c) : (f32x4){0, 0, 0, 0};
-        }
+    ln_affine_load<NV>(ga, g1, nchunk, lane);
+    ln_affine_load<NV>(ba, b1, nchunk, lane);
+    if (g2) {
+        ln_affine_load<NV>(gb, g2, nchunk, lane);
+        ln_affine_load<NV>(bb, b2, nchunk, lane);
     }
     f32x4 xv[4][NV];
     float s[4];
@@ -48,67 +100,17 @@ __global__ __launch_bounds__(256) void layernorm_kernel(const float *x, int M, i
             s[r] += xv[r][v][0] + xv[r][v][1] + xv[r][v][2] + xv[r][v][3];
         }
     }
-    auto normalise = [&](const f32x4 *gam, const f32x4 *bet) {
-        float mean[4], q[4];
-#pragma unroll
-        for (int r = 0; r < 4; ++r) mean[r] = wave_sum(s[r]) * inv_d;
-#pragma unroll
-        for (int r = 0; r < 4; ++r) {
-            q[r] = 0.f;
-#pragma unroll
-            for (int v = 0; v < NV; ++v) {
-                const bool ok = lane + 64 * v < nnorm;
-#pragma unroll
-                for (int e = 0; e < 4; ++e) { const float d = ok ? xv[r][v][e] - mean[r] : 0.f; q[r] += d * d; }
-            }
-        }
-#pragma unroll
-        for (int r = 0; r < 4; ++r) {
-            const float rstd = 1.0f / sqrtf(wave_sum(q[r]) * inv_d + eps);
-            s[r] = 0.f;
-#pragma unroll
-            for (int v = 0; v < NV; ++v)
-#pragma unroll
-                for (int e = 0; e < 4; ++e) {
-                    xv[r][v][e] = (xv[r][v][e] - mean[r]) * rstd * gam[v][e] + bet[v][e];   // chunks beyond D: gamma = beta = 0
-                    s[r] += xv[r][v][e];
-                }
-        }
-    };
-    normalise(ga, ba);
-    if (out_f32) {
-#pragma unroll
-        for (int r = 0; r < 4; ++r) {
-            const int m = row0 + r;
-#pragma unroll
-            for (int v = 0; v < NV; ++v) {
-                const int c = lane + 64 * v;
-                if (m < M && c < nchunk) *reinterpret_cast<f32x4 *>(out_f32 + (size_t)m * D + 4 * c) = xv[r][v];
-            }
-        }
-    }
+    ln_rows4<NV>(xv, s, ga, ba, lane, nnorm, inv_d, eps);
+    if (out_f32) ln_rows4_store<float, NV>(out_f32, row0, M, D, lane, xv);
     if (!out_t) return;
-    if (g2) normalise(gb, bb);
-#pragma unroll
-    for (int r = 0; r < 4; ++r) {
-        const int m = row0 + r;
-#pragma unroll
-        for (int v = 0; v < NV; ++v) {
-            const int c = lane + 64 * v;
-            if (m < M && c < nchunk) {
-                T *p = out_t + (size_t)m * D + 4 * c;
-                if constexpr (sizeof(T) == 2) { bf16x4 o = {(T)xv[r][v][0], (T)xv[r][v][1], (T)xv[r][v][2], (T)xv[r][v][3]}; *reinterpret_cast<bf16x4 *>(p) = o; }
-                else { *reinterpret_cast<f32x4 *>(p) = xv[r][v]; }
-            }
-        }
-    }
+    if (g2) ln_rows4<NV>(xv, s, gb, bb, lane, nnorm, inv_d, eps);
+    ln_rows4_store<T, NV>(out_t, row0, M, D, lane, xv);
 }
 
 template <typename T>
-static inline void launch_layernorm(hipStream_t s, const float *x, int M, int D, const float *g1, const float *b1,
-                                    float *out_f32, const float *g2, const float *b2, T *out_t, int Dn = 0) {
+static inline void launch_layernorm(hipStream_t s, const float *x, int M, int D, int Dn, const float *g1, const float *b1, float *out_f32, const float *g2,
+                                    const float *b2, T *out_t) {
     dim3 grid(ceil_div(M, 16));
-    if (Dn <= 0) Dn = D;
     if (D <= 256) hipLaunchKernelGGL((layernorm_kernel<T, 1>), grid, dim3(256), 0, s, x, M, D, Dn, 1e-5f, g1, b1, out_f32, g2, b2, out_t);
     else if (D <= 512) hipLaunchKernelGGL((layernorm_kernel<T, 2>), grid, dim3(256), 0, s, x, M, D, Dn, 1e-5f, g1, b1, out_f32, g2, b2, out_t);
     else hipLaunchKernelGGL((layernorm_kernel<T, 4>), grid, dim3(256), 0, s, x, M, D, Dn, 1e-5f, g1, b1, out_f32, g2, b2, out_t);
@@ -123,10 +125,9 @@ __global__ __launch_bounds__(256) void splitk_reduce_ln_kernel(const float *__re
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     const int row0 = (blockIdx.x * 4 + wave) * 4;
     if (row0 >= M) return;
-    const int nchunk = D >> 2, nnorm = Dn >> 2, c = lane, cc = min(c, nchunk - 1);
-    const float inv_d = 1.0f / (float)Dn;
+    const int nchunk = D >> 2, c = lane, cc = min(c, nchunk - 1);
     const f32x4 bb = *reinterpret_cast<const f32x4 *>(bias + 4 * cc);
-    f32x4 v[4];
+    f32x4 v[4][1];
     float s[4];
 #pragma unroll
     for (int r = 0; r < 4; ++r) {
@@ -134,26 +135,13 @@ __global__ __launch_bounds__(256) void splitk_reduce_ln_kernel(const float *__re
         f32x4 t = bb;
         for (int z = 0; z < splits; ++z) t += *reinterpret_cast<const f32x4 *>(partial + z * zstride + off);
         if (c >= nchunk) t = (f32x4){0, 0, 0, 0};
-        v[r] = t;
+        v[r][0] = t;
         s[r] = t[0] + t[1] + t[2] + t[3];
-        if (row0 + r < M && c < nchunk) *reinterpret_cast<f32x4 *>(x + (size_t)(row0 + r) * D + 4 * c) = t;
     }
-    const f32x4 ga = c < nchunk ? *reinterpret_cast<const f32x4 *>(g1 + 4 * cc) : (f32x4){0, 0, 0, 0};
-    const f32x4 be = c < nchunk ? *reinterpret_cast<const f32x4 *>(b1 + 4 * cc) : (f32x4){0, 0, 0, 0};
-#pragma unroll
-    for (int r = 0; r < 4; ++r) {
-        const float mean = wave_sum(s[r]) * inv_d;
-        float q = 0.f;
-#pragma unroll
-        for (int e = 0; e < 4; ++e) { const float d = c < nnorm ? v[r][e] - mean : 0.f; q += d * d; }
-        const float rstd = 1.0f / sqrtf(wave_sum(q) * inv_d + 1e-5f);
-        if (row0 + r < M && c < nchunk) {
-            T *p = xn + (size_t)(row0 + r) * D + 4 * c;
-            float o[4];
-#pragma unroll
-            for (int e = 0; e < 4; ++e) o[e] = (v[r][e] - mean) * rstd * ga[e] + be[e];
-            if constexpr (sizeof(T) == 2) { bf16x4 w = {(T)o[0], (T)o[1], (T)o[2], (T)o[3]}; *reinterpret_cast<bf16x4 *>(p) = w; }
-            else { *reinterpret_cast<f32x4 *>(p) = (f32x4){o[0], o[1], o[2], o[3]}; }
-        }
-    }
+    ln_rows4_store<float, 1>(x, row0, M, D, lane, v);
+    f32x4 ga[1], be[1];
+    ln_affine_load<1>(ga, g1, nchunk, lane);
+    ln_affine_load<1>(be, b1, nchunk, lane);
+    ln_rows4<1>(v, s, ga, be, lane, Dn >> 2, 1.0f / (float)Dn, 1e-5f);
+    ln_rows4_store<T, 1>(xn, row0, M, D, lane, v);
 }

@@ -98,8 +98,8 @@ enum DropSite { DROP_FF_HIDDEN = 2, DROP_FF_OUT = 3, DROP_ATTN_WEIGHTS = 4, DROP
 constexpr unsigned DROP_SITE_INPUT = 1;                                            // after the frontend's output linear
 static unsigned drop_site(int l, DropSite k, int which = 0) { return (unsigned)(16 * l + k + 8 * which); }      // which: the block's first / second feed-forward module
 
-// weight gradients are tall-K products (K = rows): split-K partial sums [splits][out x in]
-static int train_wg_splits(int Nc, int Kr) { const int tiles = ceil_div(Nc, COCR_FO_BM) * ceil_div(Kr, COCR_FO_BN); return std::max(1, std::min(32, 512 / tiles)); }
+// weight gradients are tall-K products (K = rows): split-K partial sums [splits][out x in], in the tiles of launch_gemm_splitk (launch_gemm_tn's are as large)
+static int train_wg_splits(int Nc, int Kr) { const int tiles = ceil_div(Nc, SPLITK_BM) * ceil_div(Kr, SPLITK_BN); return std::max(1, std::min(32, 512 / tiles)); }
 // 'medium': does this Linear run on bf16 copies (and keep its input's for the backward)?
 static bool train_lin_bf16(const TrainState *t, int Nc, int Kr) { return t->matmul_bf16 && t->Wb.p && t->WTb.p && Nc % 8 == 0 && Kr % 8 == 0; }
 static dim3 grid1(size_t n) { return dim3((unsigned)std::min<size_t>((n + 255) / 256, 8192)); }

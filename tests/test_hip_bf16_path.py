@@ -345,6 +345,29 @@ def test_zero_padded_layouts_of_other_narrow_models(D, heads, ksz, C, monkeypatc
     assert da <= 0.15 and db <= 0.15 and d <= 0.15, (da, db, d)
 
 
+def test_zero_padded_narrow_model_on_the_per_product_kernels(monkeypatch):
+    """The zero-padded layout (encoder_dim 144 laid out at 256, feed-forward 576 at 768) outside the row chains (COCR_NO_CHAIN=1): the fused
+    feed-forward kernel and the row-complete products normalise over the model's 144 columns, not over the 256 of the layout.  Against the
+    fp32 oracle and against the chains on the same padded layout."""
+    from tests.hip_util import oracle_taps
+    hp = synth.hparams('cfg1', encoder_dim=144, num_attention_heads=4, conv_kernel_size=31, subsampling_conv_channels=32, num_encoder_layers=2,
+                       num_classes=40)
+    state = synth.make_state_dict(hp, seed=148, decoder_gain=4.0)
+    image, lens = synth.make_lines(3, hp.height, 332, seed=144, widths=[332, 201, 97])
+    ref, ref_lens, _ = oracle_taps(hp, state, image, lens)
+    x = torch.from_numpy(image[:, 0]).cuda()
+    a, ol_a = make_engine(hp, state, 'bf16').forward(x, lens)
+    monkeypatch.setenv('COCR_NO_CHAIN', '1')
+    b, ol_b = make_engine(hp, state, 'bf16').forward(x, lens)
+    torch.cuda.synchronize()
+    a, b = a.cpu().numpy(), b.cpu().numpy()
+    assert ol_a.tolist() == ref_lens.tolist() and ol_b.tolist() == ref_lens.tolist()
+    da, db, d = float(np.abs(a - ref).max()), float(np.abs(b - ref).max()), float(np.abs(a - b).max())
+    _log('pad_144_no_chain', {'chains_vs_oracle': da, 'per_product_vs_oracle': db, 'chains_vs_per_product': d})
+    assert d > 0.0 and np.isfinite(b).all()      # the flag did select other kernels
+    assert da <= 0.15 and db <= 0.15 and d <= 0.15, (da, db, d)
+
+
 def test_bucketed_loop_on_the_wide_model(text_case):
     """BASELINE configs[3] through the drop-in class: `evaluate.recognize` (fixed 200-px buckets, batches of 8, pipelined upload)
     on the D=512 / L=16 model, mixed widths 400..2400; strings equal to the reference's greedy strings of the same padded

@@ -292,7 +292,7 @@ MEDIUM_SHAPE_CASES = ('cfg1_1', 'd512k7', 'nohalf97ff2', 'widest')
 
 
 def train_wg_splits(Nc: int, Kr: int) -> int:
-    """train_step.hip.h `train_wg_splits`: `tiles = ceil_div(Nc, COCR_FO_BM) * ceil_div(Kr, COCR_FO_BN)` with 128 x 128 tiles,
+    """train_step.hip.h `train_wg_splits`: `tiles = ceil_div(Nc, SPLITK_BM) * ceil_div(Kr, SPLITK_BN)` with 128 x 128 tiles,
     `max(1, min(32, 512 / tiles))`."""
     tiles = -(-Nc // 128) * -(-Kr // 128)
     return max(1, min(32, 512 // tiles))
